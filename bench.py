@@ -4,6 +4,7 @@ synthetic shape set (scene S1).
 
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     (also writes the last timed frame as DIR/*.npy)
 
 A step is one pass of the hot path over one frame, starting from the raw edge list resident in HBM: binning on the device
 (band lists in painter's order, row chunks, scan-converter constants) -> per-row winding / cells -> launch order of the
@@ -34,6 +35,23 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is the measured ceiling
 DEFAULT_IN_FLIGHT = 4
 BATCH_FRAMES, BATCH_LAUNCHES = 8, 12     # roofline.batched: frames per kernel launch, timed launches
+DUMP_SAMPLE_PX = 1 << 20      # --dump-outputs: pixels of the fixed, seeded sample (16 MB as float32 RGBA + 8 MB of indices)
+
+
+def dump_outputs(dirpath, img):
+    """--dump-outputs: the frame of the timed path's last step (premultiplied RGBA8, what swfr_read_image hands a caller) as .npy
+    files under `dirpath`: a fixed sample of pixels (seeded, the same for every run with the same arguments) with their flat
+    indices, and the per-row and per-column sums of the whole frame, so that every pixel counts in some file (under 64 MB in all)."""
+    import numpy as np
+    img = np.ascontiguousarray(img)
+    H, W = img.shape[:2]
+    flat = img.reshape(H * W, 4)
+    idx = np.sort(np.random.default_rng(0x5EED).choice(H * W, size=min(DUMP_SAMPLE_PX, H * W), replace=False))
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "frame_sample_rgba.npy"), flat[idx].astype(np.float32))
+    np.save(os.path.join(dirpath, "frame_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirpath, "frame_row_sums.npy"), img.sum(axis=1, dtype=np.float64))
+    np.save(os.path.join(dirpath, "frame_col_sums.npy"), img.sum(axis=0, dtype=np.float64))
 
 
 def _oracle_args(fx, cols):
@@ -172,6 +190,9 @@ def main():
                          "all-to-all (every rank's links busy in both directions); root = every frame gathered to rank 0 (bound by rank 0's inbound links)")
     ap.add_argument("--workload", default="s1", choices=["s1", "s2"],
                     help="s1 = BASELINE.json's metric configuration (4K, 10k edges; the default and the judged line); s2 = 8K, 100k edges")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last timed step as DIR/<name>.npy (float32/float64; see dump_outputs); "
+                         "N>1, bands: rank 0's newest assembled frame")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -326,6 +347,10 @@ def main():
         dt = float(t.item())
 
     verified = None
+    if args.dump_outputs and rank == 0:
+        if bands and out is None:
+            raise SystemExit("--dump-outputs: rank 0 assembled no frame in the timed region")
+        dump_outputs(args.dump_outputs, out.cpu().numpy() if bands else r.read_image(premultiplied=True))
     if not args.no_verify and rank == 0:
         import hashlib
         img = out.cpu().numpy() if bands else r.read_image(premultiplied=True)
