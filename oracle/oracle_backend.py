@@ -58,6 +58,7 @@ def lib():
         sig("swfo_pixels", c.POINTER(c.c_uint32), P)
         sig("swfo_is_clear", I, P)
         sig("swfo_fill_polygons_fixed", None, P, P, P, P, I, I)
+        sig("swfo_fill_edges", I, P, P, I, I, I, I, I, I, c.c_uint32)
         _LIB = L
     return _LIB
 
@@ -177,6 +178,16 @@ class OracleBackend:
     def stroke(self):
         self._apply(self._stroke)
         self.unsupported |= self.L.swfo_stroke_preserve(self.ctx)
+
+    def fill_edges(self, edges, rect, even_odd: bool, argb: int):
+        """Scan-converts raw edges exactly as given (int32 records in swfr_edge's layout: x1, y1, x2, y2, top, bottom, dir,
+        reserved; 24.8) over the pixel rectangle rect = (x0, y0, x1, y1) with a solid premultiplied ARGB colour.  The directions
+        of the edges active in any sample row must sum to zero, as for closed polygons; otherwise ValueError."""
+        e = np.ascontiguousarray(edges)
+        e = e.view(np.int32).reshape(-1, 8) if e.dtype.names else np.ascontiguousarray(e.reshape(-1, 8), dtype=np.int32)
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        if self.L.swfo_fill_edges(self.ctx, e.ctypes.data, len(e), x0, y0, x1, y1, int(bool(even_odd)), int(argb) & 0xffffffff):
+            raise ValueError("edge directions do not balance along every sample row (no closed polygon): Cairo never scan-converts that")
 
     def premultiplied_rgba(self) -> np.ndarray:
         ptr = self.L.swfo_pixels(self.ctx)

@@ -2104,3 +2104,56 @@ EXPORT void swfo_fill_polygons_fixed(swfo_ctx *c, const int32_t *xy, const int32
         swfo_fill_preserve(c);
     }
 }
+
+/* Raw-edge entry (the checker of swfr_upload_edges / swfr_render_edges): `edges` holds n records in the layout of swfr_edge
+   (x1, y1, x2, y2, top, bottom, dir, reserved; 24.8), taken exactly as given -- no clipping, no polygon building -- and
+   scan-converted by tor_render over the pixel rectangle [x0, x1) x [y0, y1) with a solid premultiplied ARGB source.  The blend is
+   chosen as for every other operation: SOURCE lerp for an opaque colour or a still clear surface, OVER otherwise.
+   Cairo's scan converter only ever sees closed polygons: the directions of the edges active in a sample row of the rectangle sum
+   to zero, and its
+   full-row pass relies on that.  An edge list that breaks it is refused (-1, nothing painted); 0 otherwise. */
+typedef struct { int64_t y; int dir; } wev_t;
+static int cmp_wev(const void *a, const void *b) { int64_t x = ((const wev_t *)a)->y, y = ((const wev_t *)b)->y; return (x > y) - (x < y); }
+EXPORT int swfo_fill_edges(swfo_ctx *c, const int32_t *edges, int n, int x0, int y0, int x1, int y1, int even_odd, uint32_t argb)
+{
+    if (n < 0) return -1;
+    ensure_scratch(c);
+    c->last_unsupported = 0; c->last_poly_n = 0;
+    if (x0 < 0) x0 = 0; if (y0 < 0) y0 = 0; if (x1 > c->w) x1 = c->w; if (y1 > c->h) y1 = c->h;
+    if ((argb >> 24) == 0 || x0 >= x1 || y0 >= y1) return 0;
+    {   /* winding balance per sample row of the rectangle (rows as tor_render rounds and clamps top / bottom) */
+        wev_t *ev = malloc(sizeof(wev_t) * 2 * (size_t)(n ? n : 1));
+        int ne = 0, ok = 1;
+        for (int i = 0; i < n; i++) {
+            const int32_t *r = edges + 8 * i;
+            int64_t yt = ((int64_t)GRID_Y * r[4] + 128) >> 8, yb = ((int64_t)GRID_Y * r[5] + 128) >> 8;
+            if (yt < (int64_t)GRID_Y * y0) yt = (int64_t)GRID_Y * y0;
+            if (yb > (int64_t)GRID_Y * y1) yb = (int64_t)GRID_Y * y1;
+            if (yb <= yt) continue;
+            ev[ne].y = yt; ev[ne++].dir = r[6];
+            ev[ne].y = yb; ev[ne++].dir = -r[6];
+        }
+        qsort(ev, ne, sizeof(wev_t), cmp_wev);
+        int64_t sum = 0;
+        for (int i = 0; i < ne; i++) {
+            sum += ev[i].dir;
+            if ((i + 1 == ne || ev[i + 1].y != ev[i].y) && sum != 0) ok = 0;
+        }
+        free(ev);
+        if (!ok) return -1;
+    }
+    polygon_t g; memset(&g, 0, sizeof(g));
+    g.n = g.cap = n;
+    g.e = malloc(sizeof(pedge_t) * (size_t)(n ? n : 1));
+    for (int i = 0; i < n; i++) {
+        const int32_t *r = edges + 8 * i;
+        pedge_t *e = &g.e[i];
+        e->p1.x = r[0]; e->p1.y = r[1]; e->p2.x = r[2]; e->p2.y = r[3]; e->top = r[4]; e->bottom = r[5]; e->dir = r[6];
+    }
+    c->src.kind = SRC_SOLID; c->src.pixel = argb;
+    int lerp_mode = source_is_opaque_solid(&c->src) || c->is_clear;
+    tor_render(c, &g, even_odd, lerp_mode, x0, y0, x1, y1);
+    c->is_clear = 0;
+    free(g.e);
+    return 0;
+}

@@ -347,6 +347,20 @@ void FrameBuilder::emit_polygon(Polygon& poly, bool rectilinear, uint32_t style,
     if (rectilinear) {
         p.kind = SWFR_PATH_BOXES;
         rectilinear_to_boxes(poly, even_odd_, edges_);
+        // the box stroker's polygon is not clipped (see emit_stroke): a box may reach far past the frame, even past +-2^23 in 24.8
+        // (a path point near +-32768 px plus the half line width).  Only the converter rectangle is painted (Cairo's compositor clips
+        // the boxes to it), so the boxes are clamped to it and those that miss it are dropped
+        const fixed_t cx0 = fixed_t(p.x_min) * 256, cy0 = fixed_t(p.y_min) * 256, cx1 = fixed_t(p.x_max) * 256, cy1 = fixed_t(p.y_max) * 256;
+        size_t out = p.first_edge;
+        for (size_t k = p.first_edge; k < edges_.size(); ++k) {
+            swfr_edge b = edges_[k];
+            b.x1 = std::max(b.x1, cx0); b.x2 = std::min(b.x2, cx1);
+            b.y1 = std::max(b.y1, cy0); b.y2 = std::min(b.y2, cy1);
+            if (b.x1 >= b.x2 || b.y1 >= b.y2) continue;
+            b.top = b.y1; b.bottom = b.y2;
+            edges_[out++] = b;
+        }
+        edges_.resize(out);
     } else {
         p.kind = SWFR_PATH_TOR;
         edges_.insert(edges_.end(), poly.edges().begin(), poly.edges().end());
@@ -522,7 +536,8 @@ void FrameBuilder::emit_stroke(const StyledPath& p, bool morph, double ratio) {
         // Cairo's box stroker when it accepts the style: the union of one box per segment, painted like a rectilinear fill.  Its
         // boxes are NOT clipped against the frame first: a stroke whose boxes all lie outside is then "boxes that miss the operation's
         // rectangle" (nothing drawn, the surface keeps its clear state) and not "no boxes at all" (which counts as drawn) -- found by
-        // the soak (mixed 7100/2196: the next translucent fill is then still composited with the SOURCE rule)
+        // the soak (mixed 7100/2196: the next translucent fill is then still composited with the SOURCE rule).  emit_polygon decides
+        // on these unclipped boxes, then clamps them to the frame
         poly.reset(false, frame_lo, frame_hi);
         if (stroke_rectilinear_to_boxes(path_, sp, st.ctm, poly)) {
             emit_polygon(poly, true, push_solid(px), opaque, bx0, by0, bx1, by1);

@@ -983,6 +983,7 @@ void rectilinear_to_boxes(const Polygon& poly, bool even_odd, std::vector<swfr_e
     ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
     std::stable_sort(vs.begin(), vs.end(), [](const V& a, const V& b) { return a.x < b.x; });
     const unsigned mask = even_odd ? 1u : ~0u;
+    const size_t first = boxes.size();      // `boxes` may hold other paths' edges: only this polygon's own boxes are merged
     for (size_t s = 0; s + 1 < ys.size(); ++s) {
         const fixed_t ya = ys[s], yb = ys[s + 1];
         int winding = 0;
@@ -1000,7 +1001,7 @@ void rectilinear_to_boxes(const Polygon& poly, bool even_odd, std::vector<swfr_e
                 if (xs != v.x) {
                     // merge with the box directly above when it has the same x-range
                     bool merged = false;
-                    for (auto it = boxes.rbegin(); it != boxes.rend() && it->y2 >= ya; ++it) {
+                    for (auto it = boxes.rbegin(); it != boxes.rend() - first && it->y2 >= ya; ++it) {
                         if (it->y2 == ya && it->x1 == xs && it->x2 == v.x) {
                             it->y2 = yb;
                             it->bottom = yb;

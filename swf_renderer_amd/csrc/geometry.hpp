@@ -125,7 +125,8 @@ int stroke_pen_vertices(double line_width, const Affine& ctm);
 // left/right edges in `out`; the union (non-zero) is the stroke.  Returns false when Cairo would decline (the polygon
 // stroker is used then).
 bool stroke_rectilinear_to_boxes(const DevicePath& path, const StrokeParams& sp, const Affine& ctm, Polygon& out);
-// Rectilinear fill region -> disjoint boxes (x1,y1)-(x2,y2), stored in swfr_edge records.
+// Rectilinear fill region -> disjoint boxes (x1,y1)-(x2,y2), stored in swfr_edge records appended to `boxes` (what `boxes` held
+// before is left alone).
 void rectilinear_to_boxes(const Polygon& poly, bool even_odd, std::vector<swfr_edge>& boxes);
 
 }  // namespace swfr

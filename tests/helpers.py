@@ -349,3 +349,108 @@ def soak_scene(name, seed, index):
     for _ in range(index + 1):
         sc = gens[name](rng)
     return sc
+
+
+# ---- the limits of the 24.8 device range the product accepts (+-32768 px = +-2^23 in 24.8): vertices thousands of pixels off the
+#      frame, edges tens of thousands of pixels long, 1/256 px slopes across the whole range, end points exactly on the limit
+LARGE_MODES = ("far", "long_shallow", "long_steep", "boundary")
+LIMIT = 32768.0
+EPS = 1.0 / 256
+
+
+def large_pts(rng, W, H, n, mode):
+    """n vertices (device pixels) of a polygon in one of LARGE_MODES around a W x H frame."""
+    def inside():
+        return (float(rng.uniform(0, W)), float(rng.uniform(0, H)))
+    if mode == "far":               # uniform in +-32000 px; the first edge crosses the frame from far left to far right
+        pts = [(float(rng.uniform(-32000, -W)), float(rng.uniform(0, H))), (float(rng.uniform(W, 32000)), float(rng.uniform(0, H)))]
+        pts += [(float(rng.uniform(-32000, 32000)), float(rng.uniform(-32000, 32000))) for _ in range(n - 2)]
+    elif mode == "long_shallow":    # more than 60 000 px wide, less than 1 px tall, through the frame; the rest above or below it
+        y = float(rng.uniform(0, H))
+        pts = [(float(rng.uniform(-LIMIT, -30000)), y), (float(rng.uniform(30000, LIMIT)), y + float(rng.integers(1, 256)) * EPS * rng.choice([-1, 1]))]
+        side = rng.choice([-1, 1])
+        pts += [(float(rng.uniform(-LIMIT, LIMIT)), y + side * float(rng.uniform(1, LIMIT - H))) for _ in range(n - 2)]
+    elif mode == "long_steep":      # the mirror case; sometimes an edge 1/256 px wide over the whole y range
+        x = float(rng.uniform(0, W))
+        if rng.integers(0, 2):
+            pts = [(x, -LIMIT), (x + EPS * rng.choice([-1, 1]), LIMIT)]
+        else:
+            pts = [(x, float(rng.uniform(-LIMIT, -30000))), (x + float(rng.integers(1, 256)) * EPS * rng.choice([-1, 1]), float(rng.uniform(30000, LIMIT)))]
+        side = rng.choice([-1, 1])
+        pts += [(x + side * float(rng.uniform(1, LIMIT - W)), float(rng.uniform(-LIMIT, LIMIT))) for _ in range(n - 2)]
+    else:                           # "boundary": coordinates exactly at +-32768 px and +-(32768 - 1/256) px, the others in the frame
+        edge = [-LIMIT, -LIMIT + EPS, LIMIT - EPS, LIMIT]
+        pts = []
+        for _ in range(n):
+            x, y = inside()
+            if rng.integers(0, 3):
+                x = float(rng.choice(edge))
+            if rng.integers(0, 3):
+                y = float(rng.choice(edge))
+            pts.append((x, y))
+    return pts
+
+
+# Shapes of the extreme scenes are given in 1/256 twips (object matrix scale 1/256, exact in 16.16): every 24.8 device position up
+# to +-32768 px, the limit included, is then a whole number of shape units.
+FINE = 20 * 256
+
+
+def _fine_shape(pts_px, curves, fill, line=None, line_width_px=0.0, closed=True):
+    """DefineShape of one path through device-pixel points (a curve flag at i makes pts[i] the control point of pts[i + 1])."""
+    p = [(int(round(x * FINE)), int(round(y * FINE))) for x, y in pts_px]
+    sc = {"type": "style-change", "move_to": {"x": p[0][0], "y": p[0][1]}}
+    if fill is not None:
+        sc["left_fill"] = 1
+    if line is not None:
+        sc["line_style"] = 1
+    recs, cur, i = [sc], p[0], 1
+    seq = p[1:] + ([p[0]] if closed else [])
+    while i <= len(seq):
+        q = seq[i - 1]
+        if curves and i < len(seq) and curves[i]:
+            e = seq[i]
+            recs.append({"type": "edge", "control_delta": {"x": q[0] - cur[0], "y": q[1] - cur[1]}, "delta": {"x": e[0] - cur[0], "y": e[1] - cur[1]}})
+            cur, i = e, i + 2
+        else:
+            recs.append({"type": "edge", "delta": {"x": q[0] - cur[0], "y": q[1] - cur[1]}})
+            cur, i = q, i + 1
+    xs, ys = [q[0] for q in p], [q[1] for q in p]
+    lines = [] if line is None else [{"width": int(round(line_width_px * FINE)), "fill": {"type": "solid", "color": line}}]
+    return {"id": 1, "bounds": {"x_min": min(xs), "x_max": max(xs), "y_min": min(ys), "y_max": max(ys)},
+            "shape": {"initial_styles": {"fill": [] if fill is None else [fill], "line": lines}, "records": recs}}
+
+
+def extreme_scene(rng, W, H, mode, kinds=("fill", "curve", "stroke", "rect_stroke")):
+    """One frame of one to three shapes whose geometry reaches the limits of the device range (LARGE_MODES): solid fills (opaque and
+    translucent, both fill rules), quadratic curves, strokes of the same outlines, and rectilinear strokes whose corners lie near
+    +-32768 px."""
+    import scenarios
+    fine = scenarios._m(1 / 256, 1 / 256)
+    kids = []
+    for _ in range(int(rng.integers(1, 4))):
+        kind = kinds[int(rng.integers(0, len(kinds)))]
+        col = scenarios._rgba(*[int(v) for v in rng.integers(0, 256, 3)], int(rng.choice([255, 255, 200, 128, 31])))
+        n = int(rng.integers(3, 8))
+        pts = large_pts(rng, W, H, n, mode)
+        if kind == "fill":
+            tag = _fine_shape(pts, None, {"type": "solid", "color": col})
+        elif kind == "curve":
+            tag = _fine_shape(pts, [bool(rng.integers(0, 2)) for _ in range(n)], {"type": "solid", "color": col})
+        elif kind == "stroke":
+            # the outline of a polygon stroke keeps the end points of its lines when it is clipped: they must stay inside the
+            # range, so the path is pulled in by the miter reach (10 half widths); see test_polygon_stroke_beyond_the_limit_is_refused
+            w = float(rng.choice([0.5, 1.0, 3.0, 20.0, 300.0]))
+            f = (LIMIT - 5 * w - 1) / LIMIT
+            tag = _fine_shape([(x * f, y * f) for x, y in pts], None, None, line=col, line_width_px=w)
+        else:                              # axis-aligned outline: Cairo's box stroker, boxes reaching past the frame and the limit
+            x0, x1 = sorted(float(v) for v in rng.choice([-LIMIT, -LIMIT + EPS, -30000.0, LIMIT - 50, LIMIT - EPS, LIMIT], 2, replace=False))
+            y0, y1 = sorted(float(v) for v in rng.choice([-LIMIT, -LIMIT + EPS, -30000.0, LIMIT - 40, LIMIT - EPS, LIMIT], 2, replace=False))
+            if rng.integers(0, 2):         # one side inside the frame: a partly covered frame
+                if rng.integers(0, 2):
+                    x1 = float(rng.integers(1, W))
+                else:
+                    y0 = float(rng.integers(0, H - 1))
+            tag = _fine_shape([(x0, y0), (x1, y0), (x1, y1), (x0, y1)], None, None, line=col, line_width_px=float(rng.choice([1.0, 2.5, 20.0, 164.0])))
+        kids.append({"type": "shape", "definition": tag, "matrix": fine})
+    return dict(width=W, height=H, even_odd=bool(rng.integers(0, 2)), stage={"children": kids})

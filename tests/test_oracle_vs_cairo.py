@@ -5,6 +5,7 @@ import zlib
 import numpy as np
 import pytest
 
+from helpers import LARGE_MODES, LIMIT, large_pts
 from oracle import cairo_backend as cb, oracle_backend as ob
 
 pytestmark = pytest.mark.skipif(not cb.available(), reason="libcairo not installed")
@@ -40,6 +41,8 @@ def _draw(be, ops):
             be.stroke()
         else:                                  # "pen": strokes with every style knob (dict)
             o = op[1]
+            if o.get("matrix"):
+                be.transform(*o["matrix"])
             if o.get("scale"):
                 be.scale(*o["scale"])
             be.begin_path()
@@ -82,10 +85,12 @@ def _pts(rng, W, H, n, mode):
     if mode == "steep":
         x = rng.uniform(0, W)
         return [(float(x + rng.uniform(-2, 2)), float(rng.uniform(0, H))) for _ in range(n)]
+    if mode in LARGE_MODES:
+        return large_pts(rng, W, H, n, mode)
     return [(float(rng.uniform(0, W)), float(rng.uniform(0, H))) for _ in range(n)]
 
 
-@pytest.mark.parametrize("mode", ["uniform", "quarter", "integer", "offframe", "shallow", "steep"])
+@pytest.mark.parametrize("mode", ["uniform", "quarter", "integer", "offframe", "shallow", "steep"] + list(LARGE_MODES))
 def test_polygons_both_fill_rules(mode):
     rng = np.random.default_rng(zlib.crc32(mode.encode()) % 1000)
     for _ in range(250):
@@ -101,6 +106,22 @@ def test_quadratic_curves():
         n = int(rng.integers(4, 9))
         ops = [("poly", _pts(rng, 48, 40, n, "uniform"), (10, 200, 30, 255), False, [bool(rng.integers(0, 2)) for _ in range(n)])]
         assert _same(48, 40, ops), ops
+
+
+@pytest.mark.parametrize("mode", LARGE_MODES)
+def test_quadratic_curves_at_large_magnitudes(mode):
+    """Curves whose control and end points lie up to 32768 px away: flattening with long chords, clipped to the frame."""
+    rng = np.random.default_rng(zlib.crc32(("curves" + mode).encode()) % 1000)
+    painted = 0
+    for _ in range(150):
+        n = int(rng.integers(4, 9))
+        ops = [("poly", _pts(rng, 48, 40, n, mode), (10, 200, 30, int(rng.choice([255, 130]))), bool(rng.integers(0, 2)),
+                [bool(rng.integers(0, 2)) for _ in range(n)])]
+        a = cb.CairoBackend(48, 40); _draw(a, ops); ca = a.premultiplied_rgba(); a.close()
+        b = ob.OracleBackend(48, 40); _draw(b, ops); oa = b.premultiplied_rgba(); b.close()
+        assert (ca == oa).all(), ops
+        painted += int(((ca[..., 3] > 0) & (ca[..., 3] < 255)).sum())
+    assert painted > 500          # edges do cross the frame (partial coverage), not only empty or full frames
 
 
 def test_translucent_painters_order():
@@ -157,12 +178,37 @@ def _pen_case(rng, W, H, *, cap=None, join=None, closed=None, curves=False, rect
                         scale=(float(rng.choice([-1, 1]) * rng.uniform(0.5, 2)), float(rng.uniform(0.5, 2))) if scale and rng.integers(0, 2) else None))
 
 
-@pytest.mark.parametrize("kind", ["round_join", "bevel_join", "round_cap", "square_cap", "closed", "curves", "rectilinear", "hairline", "everything"])
+def _large_scale(rng, op, W, H):
+    """Places a pen case under a uniform stage scale up to the point where the path reaches +-32768 px (the limit of the product's
+    device range), translated so that some part of the stroke stays near the frame."""
+    o = op[1]
+    xs = [p[0] for sub in o["subs"] for p in sub[0]]
+    ys = [p[1] for sub in o["subs"] for p in sub[0]]
+    reach = max(max(map(abs, xs)), max(map(abs, ys)), 1.0)
+    k = float(rng.uniform(0.5, 1.0)) * (LIMIT - 2 * max(W, H)) / reach / (2 if rng.integers(0, 2) else 1)
+    cx, cy = xs[0], ys[0]                     # the first vertex lands inside the frame
+    # (a reflection or a non-uniform scale only without round joins and caps: see test_round_join_under_a_non_uniform_scale_known_difference)
+    round_pen = o["join"] == 1 or o["cap"] == 1
+    ky = k * float(rng.choice([1, -1, 0.5])) if not round_pen else k
+    o["matrix"] = (k, 0.0, 0.0, ky, float(rng.uniform(0, W)) - k * cx, float(rng.uniform(0, H)) - ky * cy)
+    o["scale"] = None
+    # 0.5 to 40 device pixels wide, or up to several thousand
+    o["w"] = float(rng.uniform(0.5, 40.0)) / k if rng.integers(0, 3) else float(rng.uniform(0.02, 4.0))
+    return op
+
+
+@pytest.mark.parametrize("kind", ["round_join", "bevel_join", "round_cap", "square_cap", "closed", "curves", "rectilinear", "hairline", "everything",
+                                  "large_scale", "large_scale_rectilinear"])
 def test_stroker_styles(kind):
     rng = np.random.default_rng(zlib.crc32(kind.encode()) % 997)
     W, H = 48, 40
+    varied = 0
     for _ in range(250):
-        if kind == "round_join":
+        if kind == "large_scale":
+            op = _large_scale(rng, _pen_case(rng, W, H, curves=True, margin=-12, subs=int(rng.integers(1, 3))), W, H)
+        elif kind == "large_scale_rectilinear":
+            op = _large_scale(rng, _pen_case(rng, W, H, rect=True, join=int(rng.choice([0, 0, 1, 2])), cap=int(rng.choice([0, 2]))), W, H)
+        elif kind == "round_join":
             op = _pen_case(rng, W, H, cap=0, join=1, closed=False)
         elif kind == "bevel_join":
             op = _pen_case(rng, W, H, cap=0, join=2, closed=False)
@@ -181,6 +227,25 @@ def test_stroker_styles(kind):
         else:
             op = _pen_case(rng, W, H, curves=True, margin=-12, scale=True, subs=int(rng.integers(1, 4)))
         assert _same(W, H, [op]), op
+        if kind.startswith("large_scale"):
+            a = cb.CairoBackend(W, H); _draw(a, [op]); img = a.premultiplied_rgba()[..., 3]; a.close()
+            varied += bool((img != img.flat[0]).any())
+    if kind.startswith("large_scale"):
+        assert varied > 150           # most frames show an outline's edge, not only an empty or uniformly covered frame
+
+
+@pytest.mark.xfail(strict=True, reason="known oracle difference: one pixel of a round join under a non-uniform scale, 2/255 off")
+def test_round_join_under_a_non_uniform_scale_known_difference():
+    """Found by the large-scale stroke fuzz, but independent of the magnitudes (the same device geometry drawn from user coordinates
+    near the origin differs the same way; a uniform scale or a 3 px shift does not): a closed four-point path with round joins,
+    a pen 33 x 16 device pixels wide.  One pixel of the oracle is 181 where libcairo gives 179.  Pinned here so that a fix of the
+    oracle's pen / fan restatement shows up.  Reflected large pens (y scale -k) differ in the same way; the large-scale fuzz keeps
+    reflections and non-uniform scales to miter and bevel joins until then."""
+    op = ("pen", dict(subs=[([(56.256924568088294, 10.381050109408882), (6.631615315619026, 8.70962727024363),
+                              (31.900229039925122, 39.502684441614086), (33.37925896304273, 39.51596599539821)], None, True)],
+                      w=0.17924089612921035, cap=0, join=1, col=(103, 20, 30, 255), scale=None,
+                      matrix=(184.16369457889198, 0.0, 0.0, 92.08184728944599, -10333.66549487574, -940.9449840521969)))
+    assert _same(48, 40, [op])
 
 
 # ---- bitmap fills: CAIRO_FILTER_GOOD = bilinear above scale 0.75, pixman's separable convolution below.  Tables and accumulation

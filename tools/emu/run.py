@@ -1,7 +1,8 @@
 """Runs the GPU parity tests (tests/test_gpu_parity.py) against tools/emu/libswfr_emu.so -- the kernels compiled as plain C++ and
 executed by the lock-step wavefront emulator -- instead of libswfr.so.  A development aid: it finds kernel bugs (divergent
 barriers, out-of-bounds indices, wrong pixels) without a GPU; it proves nothing about the GPU build, whose parity is tested
-on the GPU.   usage: python tools/emu/run.py [pytest args ...]      e.g.  python tools/emu/run.py -k scenario -x -q
+on the GPU.   usage: python tools/emu/run.py [test files] [pytest args ...]      e.g.  python tools/emu/run.py -k scenario -x -q,
+python tools/emu/run.py tests/test_gpu_extremes.py -x -q
 """
 import ctypes
 import os
@@ -33,4 +34,7 @@ if __name__ == "__main__":
     torch.cuda.is_available = lambda: True   # the `gpu` fixture of tests/conftest.py: the emulator plays the device
     os.environ["SWFR_EMULATOR"] = "1"        # (tests skip the cases that are only a matter of time on the emulator)
     args = sys.argv[1:] or ["-x", "-q"]
-    sys.exit(pytest.main([os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-p", "no:cacheprovider"] + args))
+    files = [a for a in args if a.endswith(".py") or ".py::" in a]       # test files given: those instead of test_gpu_parity.py
+    if not files:
+        args = [os.path.join(ROOT, "tests", "test_gpu_parity.py")] + args
+    sys.exit(pytest.main(["-m", "gpu", "-p", "no:cacheprovider"] + args))
