@@ -137,6 +137,9 @@ typedef struct {
 #define SWFR_DEVICE_HOST_ONLY (-1)       /* decode + geometry only; swfr_render fails with NO_DEVICE */
 #define SWFR_FLAG_EVEN_ODD 1u            /* fill rule override (the reference always uses nonzero) */
 #define SWFR_FLAG_BANDS_CONTIGUOUS 2u    /* multi-GPU: this handle's tile-rows are one contiguous block, see band_index below */
+#define SWFR_FLAG_ANTIALIAS_NONE 4u      /* aliased edges: cairo_set_antialias(cr, CAIRO_ANTIALIAS_NONE), node-canvas's
+                                            ctx.antialias = 'none' (the reference always antialiases): polygons are sampled at pixel
+                                            centres, rectilinear paths rounded to whole pixels; every render route honours it */
 
 typedef struct {
     int32_t device;                      /* HIP device ordinal, or SWFR_DEVICE_HOST_ONLY */

@@ -19,6 +19,8 @@ OK, ERR_INVALID, ERR_NOT_IMPLEMENTED, ERR_NOT_FOUND, ERR_NO_DEVICE, ERR_DEVICE, 
 DEVICE_HOST_ONLY = -1
 FLAG_EVEN_ODD = 1
 FLAG_BANDS_CONTIGUOUS = 2
+FLAG_ANTIALIAS_NONE = 4
+ANTIALIAS_MODES = ("default", "none")   # node-canvas's ctx.antialias values this renderer knows
 PATH_TOR, PATH_BOXES = 0, 1
 STYLE_SOLID, STYLE_RADIAL, STYLE_LINEAR, STYLE_BITMAP = 0, 1, 2, 3
 MAX_STOPS = 16
@@ -392,10 +394,15 @@ def decode_x_swf_bmp(data: bytes):
 class Renderer:
     """`new NodeCanvasRenderer(width, height)` + `Renderer{render, addBitmap}` over libswfr.so."""
 
-    def __init__(self, width, height, device=0, even_odd=False, band_index=0, band_count=0, contiguous_bands=False):
+    def __init__(self, width, height, device=0, even_odd=False, band_index=0, band_count=0, contiguous_bands=False, antialias="default"):
+        # antialias: "default" (Cairo's 15x256 antialiasing, the reference) or "none" (aliased edges: CAIRO_ANTIALIAS_NONE)
+        if antialias not in ANTIALIAS_MODES:
+            raise ValueError("antialias must be one of %r, not %r" % (ANTIALIAS_MODES, antialias))
         self.L = load_library()
         self.width, self.height = int(width), int(height)
-        cfg = Config(int(device), (FLAG_EVEN_ODD if even_odd else 0) | (FLAG_BANDS_CONTIGUOUS if contiguous_bands else 0), band_index, band_count)
+        self.antialias = antialias
+        flags = (FLAG_EVEN_ODD if even_odd else 0) | (FLAG_BANDS_CONTIGUOUS if contiguous_bands else 0) | (FLAG_ANTIALIAS_NONE if antialias == "none" else 0)
+        cfg = Config(int(device), flags, band_index, band_count)
         h = C.c_void_p()
         rc = self.L.swfr_create(self.width, self.height, C.byref(cfg), C.byref(h))
         if rc != OK:

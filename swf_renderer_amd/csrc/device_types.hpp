@@ -236,6 +236,7 @@ struct Frame2 {
     uint32_t n_strip_slots;             // launch list slots of the tile pass: XCDS * ceil(local tile-rows / XCDS) * strips per tile-row (strip_slots())
     uint32_t band_first, band_stride;   // the handle's tile-rows: band_first + l * band_stride, l < n_strips / (STRIPS_PER_TILE * tiles_x)
                                         // (interleaved over the ranks: stride = ranks; one contiguous block per rank: stride = 1)
+    uint32_t mono;           // 1: SWFR_FLAG_ANTIALIAS_NONE -- tor paths are converted at pixel centres by k2_rows_mono (mono.hip)
 };
 
 }  // namespace swfr

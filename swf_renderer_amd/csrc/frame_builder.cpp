@@ -122,7 +122,7 @@ struct FrameBuilder::Pool {
     }
 };
 
-FrameBuilder::FrameBuilder(uint32_t width, uint32_t height, bool even_odd) : w_(width), h_(height), even_odd_(even_odd) {}
+FrameBuilder::FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased) : w_(width), h_(height), even_odd_(even_odd), aliased_(aliased) {}
 
 FrameBuilder::~FrameBuilder() {
     if (pool_) {
@@ -187,7 +187,7 @@ void FrameBuilder::build(const swfr_stage& stage) {
     if (!pool_) pool_.reset(new Pool);
     Pool& P = *pool_;
     while (int(P.builders.size()) < pieces) {                 // (piece k is built by builders[k-1] for k >= 1; piece 0 needs a scratch builder, too)
-        P.builders.emplace_back(new FrameBuilder(w_, h_, even_odd_));
+        P.builders.emplace_back(new FrameBuilder(w_, h_, even_odd_, aliased_));
         P.builders.back()->parent_ = this;
         P.builders.back()->threads_ = 0;
     }
@@ -349,11 +349,13 @@ void FrameBuilder::emit_polygon(Polygon& poly, bool rectilinear, uint32_t style,
         rectilinear_to_boxes(poly, even_odd_, edges_);
         // the box stroker's polygon is not clipped (see emit_stroke): a box may reach far past the frame, even past +-2^23 in 24.8
         // (a path point near +-32768 px plus the half line width).  Only the converter rectangle is painted (Cairo's compositor clips
-        // the boxes to it), so the boxes are clamped to it and those that miss it are dropped
+        // the boxes to it), so the boxes are clamped to it and those that miss it are dropped.  Aliased: every box is rounded to whole
+        // pixels first (a path whose boxes all round away has drawn, like one without boxes: the surface is no longer clear)
         const fixed_t cx0 = fixed_t(p.x_min) * 256, cy0 = fixed_t(p.y_min) * 256, cx1 = fixed_t(p.x_max) * 256, cy1 = fixed_t(p.y_max) * 256;
         size_t out = p.first_edge;
         for (size_t k = p.first_edge; k < edges_.size(); ++k) {
             swfr_edge b = edges_[k];
+            if (aliased_) round_box_to_pixels(b);
             b.x1 = std::max(b.x1, cx0); b.x2 = std::min(b.x2, cx1);
             b.y1 = std::max(b.y1, cy0); b.y2 = std::min(b.y2, cy1);
             if (b.x1 >= b.x2 || b.y1 >= b.y2) continue;

@@ -34,7 +34,7 @@ struct StatusError {
 // paint into a SOURCE-rule lerp -- is marked in the paths (`lerp` = 2) and settled when the pieces are joined.
 class FrameBuilder {
 public:
-    FrameBuilder(uint32_t width, uint32_t height, bool even_odd);
+    FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased = false);   // aliased: SWFR_FLAG_ANTIALIAS_NONE
     ~FrameBuilder();
     FrameBuilder(const FrameBuilder&) = delete;
     FrameBuilder& operator=(const FrameBuilder&) = delete;
@@ -82,6 +82,7 @@ private:
 
     uint32_t w_, h_;
     bool even_odd_;
+    bool aliased_;
     std::vector<DecodedShape> shapes_, morphs_;
     std::map<uint32_t, BitmapInfo> bitmaps_;
     std::vector<State> stack_;

@@ -128,5 +128,12 @@ bool stroke_rectilinear_to_boxes(const DevicePath& path, const StrokeParams& sp,
 // Rectilinear fill region -> disjoint boxes (x1,y1)-(x2,y2), stored in swfr_edge records appended to `boxes` (what `boxes` held
 // before is left alone).
 void rectilinear_to_boxes(const Polygon& poly, bool even_odd, std::vector<swfr_edge>& boxes);
+// A box under CAIRO_ANTIALIAS_NONE (_cairo_boxes_add: _cairo_fixed_round_down of every coordinate, (v + 127) & ~255): it then
+// covers exactly the pixels whose centres it contains.  Rounding commutes with the union of boxes for that reason; a box that
+// rounds to nothing covers nothing.
+inline void round_box_to_pixels(swfr_edge& b) {
+    auto rd = [](fixed_t v) { return fixed_t((int64_t(v) + 127) & ~int64_t(255)); };
+    b.x1 = rd(b.x1); b.y1 = rd(b.y1); b.x2 = rd(b.x2); b.y2 = rd(b.y2);
+}
 
 }  // namespace swfr

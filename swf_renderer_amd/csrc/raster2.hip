@@ -320,7 +320,8 @@ __device__ __forceinline__ void bin_body(FramePtr F, uint32_t slow_kernels) {
     // the workgroups behind the tile-rows': first one thread per edge, then -- in workgroups of their own, so that the two run side by
     // side (round 4: the workgroup that did both was the kernel's long pole) -- one thread per path
     // (batched launches: a frame with fewer tile-rows, edges or paths leaves blocks idle)
-    const uint32_t rel = blockIdx.x - F->n_bands, edge_blocks = (F->n_edges + BIN_THREADS - 1) / BIN_THREADS;
+    // (an aliased frame has no edge workgroups: its row pass reads the raw edges)
+    const uint32_t rel = blockIdx.x - F->n_bands, edge_blocks = F->mono ? 0u : (F->n_edges + BIN_THREADS - 1) / BIN_THREADS;
     const bool path_block = rel >= edge_blocks;
     const uint32_t i = path_block ? ~0u : rel * BIN_THREADS + (uint32_t)tid;
     // ---- one thread per edge: scan converter constants
@@ -533,6 +534,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R2_WIDE_WAVE
     if (blockIdx.x >= FR->n_chunks) return;
     rows3_chunk_body<ROWS_STAGE_WIDE, ROWS_FAST_WIDE>(FR, blockIdx.x);
 }
+
+#include "mono.hip"
+
+__global__ __launch_bounds__(64) void k2_rows_mono_b(const Frame2* __restrict__ frames) {
+    FramePtr FR = FRAME_PTR(frames, blockIdx.y);
+    if (blockIdx.x >= FR->n_chunks) return;
+    mono_chunk_body(FR, blockIdx.x);
+}
+__global__ __launch_bounds__(HUGE_THREADS) void k2_rows_mono_huge_b(const Frame2* __restrict__ frames) { mono_huge_loop(FRAME_PTR(frames, blockIdx.y)); }
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1735,17 +1745,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_SHA
 // launchers: `frames` is a device array of n_frames descriptors, blockIdx.y picks one
 // ---------------------------------------------------------------------------------------------
 // slow_kernels: 0 when the queued-row kernels will not be launched behind this k2_bin (their DevEdge records are then not written)
-void launch2_bin(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_edges, uint32_t max_paths, uint32_t max_bands, uint32_t slow_kernels) {
+// mono: the frames are aliased (Frame2::mono) -- k2_bin has no edge workgroups, the row pass is k2_rows_mono (+ k2_rows_mono_huge)
+void launch2_bin(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_edges, uint32_t max_paths, uint32_t max_bands, uint32_t slow_kernels, bool mono) {
     // tile-rows' workgroups, edge workgroups, path workgroups (a frame's own follow its own edge workgroups), + the eight that order the strips
-    const uint32_t g = max_bands + (max_edges + BIN_THREADS - 1) / BIN_THREADS + (max_paths + BIN_THREADS - 1) / BIN_THREADS + XCDS;
+    const uint32_t g = max_bands + (mono ? 0u : (max_edges + BIN_THREADS - 1) / BIN_THREADS) + (max_paths + BIN_THREADS - 1) / BIN_THREADS + XCDS;
     hipLaunchKernelGGL(k2_bin_b, dim3(g, n_frames), dim3(BIN_THREADS), 0, st, frames, slow_kernels);
 }
-void launch2_rows(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_chunks, uint32_t max_path_edges) {
+void launch2_rows(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_chunks, uint32_t max_path_edges, bool mono) {
     if (!max_chunks) return;
+    if (mono) { hipLaunchKernelGGL(k2_rows_mono_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames); return; }
     if (max_path_edges > ROWS_STAGE) hipLaunchKernelGGL(k2_rows_wide_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames);
     else hipLaunchKernelGGL(k2_rows_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames);
 }
-void launch2_rows_slow(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t grid_slow, uint32_t grid_huge, uint32_t max_passes) {
+void launch2_rows_slow(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t grid_slow, uint32_t grid_huge, uint32_t max_passes, bool mono) {
+    // an aliased frame's queued rows need no order replay and no second pass (mono.hip): grid_huge workgroups, at least one
+    if (mono) { hipLaunchKernelGGL(k2_rows_mono_huge_b, dim3(grid_huge ? grid_huge : 64u, n_frames), dim3(HUGE_THREADS), 0, st, frames); return; }
     if (grid_slow) hipLaunchKernelGGL(k2_start_ranks_b, dim3(grid_slow / 4 + 1, n_frames), dim3(256), 0, st, frames);
     // a queued row whose edge-order history runs through another queued row is queued again for the next pass
     for (uint32_t pass = 0; pass < SLOW_PASSES; ++pass) {

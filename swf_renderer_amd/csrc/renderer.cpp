@@ -25,9 +25,9 @@
 #include "bitmap_decode.hpp"
 
 namespace swfr {
-void launch2_bin(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
-void launch2_rows(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t);
-void launch2_rows_slow(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t);
+void launch2_bin(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, bool);
+void launch2_rows(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, bool);
+void launch2_rows_slow(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, bool);
 void launch2_tiles(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, int, uint32_t*);
 void launch_unpremultiply(hipStream_t, const uint32_t*, uint32_t*, size_t);
 void launch_pack_band(hipStream_t, const uint32_t*, uint32_t*, int, int, uint32_t, uint32_t, uint32_t);
@@ -219,6 +219,7 @@ struct swfr_renderer {
     int strip_order = 1;                    // SWFR_STRIP_ORDER=0: launch the k2_tiles wavefronts in row-major order (per XCD class)
     int event_stride = 16;                  // SWFR_EVENT_STRIDE: per-kernel HIP events on every n-th resident frame
     bool event_stride_given = false;        // (set explicitly: short runs do not lower it)
+    bool mono = false;                      // SWFR_FLAG_ANTIALIAS_NONE: boxes rounded to pixels, tor paths by k2_rows_mono (Frame2::mono)
     int fast_limit = 16;                    // rows with more active edges go to k2_rows_slow; the row kernel's instance caps it at its 8 or 16 slots (SWFR_FAST_LIMIT: test knob)
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
@@ -734,6 +735,7 @@ void fill_frame_sizes(const swfr_renderer* r, const SceneLayout& L, size_t n_edg
     f.band_first = bs.first; f.band_stride = bs.stride;
     f.cell_main = uint32_t(L.cell_main);
     f.chunk_rows = L.chunk_rows; f.chunk_cap = uint32_t(L.n_chunks + 1); f.strip_order = r->strip_order ? 1u : 0u;
+    f.mono = r->mono ? 1u : 0u;
 }
 
 // Uploads a scene -- the raw edge list, the paths and the styles, plus the layout above -- and sizes the buffers the
@@ -758,6 +760,11 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
         tagged.assign(edges, edges + n_edges);
         for (size_t i = 0; i < n_paths; ++i)
             for (uint32_t k = 0; k < paths[i].n_edges; ++k) tagged[paths[i].first_edge + k].reserved = int32_t(i);
+        // an aliased handle paints a caller's boxes as the frame builder makes them: rounded to whole pixels (a box that rounds away covers nothing)
+        if (r->mono)
+            for (size_t i = 0; i < n_paths; ++i)
+                if (paths[i].kind == SWFR_PATH_BOXES)
+                    for (uint32_t k = 0; k < paths[i].n_edges; ++k) round_box_to_pixels(tagged[paths[i].first_edge + k]);
         edges = tagged.data();
     }
     static thread_local std::vector<swfr_edge> split_e;
@@ -862,11 +869,11 @@ void launch_frame(swfr_renderer* r, const swfr_renderer::Scene& sc, swfr_rendere
         // the frame's descriptor (scene arrays, this set's buffers, the framebuffer) was written with the scene
         const Frame2* fh = sc.frames_dev + (&F - r->fs);        // the set's descriptor, uploaded with the scene
         if (e) HIP_CHECK(hipEventRecord(e[0], st));
-        launch2_bin(st, fh, 1, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u);
+        launch2_bin(st, fh, 1, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
         if (e) HIP_CHECK(hipEventRecord(e[1], st));
-        launch2_rows(st, fh, 1, uint32_t(sc.n_chunks), sc.max_path_edges);
+        launch2_rows(st, fh, 1, uint32_t(sc.n_chunks), sc.max_path_edges, r->mono);
         // the queued rows (coincident edges, crowded rows): skipped once a frame of this resident scene has shown there are none
-        if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, 1, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes);
+        if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, 1, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes, r->mono);
         if (e) HIP_CHECK(hipEventRecord(e[2], st));
         const uint32_t grid = r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : (overlapped ? ~0u : 0x7fffffffu);   // (~0u: the default shape; any other value caps the wavefronts)
         launch2_tiles(st, fh, 1, uint32_t(sc.n_strip_slots), grid, sc.shader_level, fb);      // (fb: this frame's own target, else the descriptor's)
@@ -1008,9 +1015,9 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
             const uint32_t g = gi % groups, cnt = std::min(rb, frames - f);
             const hipStream_t st = r->fs[g * rb].stream;
             const Frame2* fh = sc.frames_dev + g * rb;
-            launch2_bin(st, fh, cnt, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u);
-            launch2_rows(st, fh, cnt, uint32_t(sc.n_chunks), sc.max_path_edges);
-            if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, cnt, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes);
+            launch2_bin(st, fh, cnt, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
+            launch2_rows(st, fh, cnt, uint32_t(sc.n_chunks), sc.max_path_edges, r->mono);
+            if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, cnt, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes, r->mono);
             launch2_tiles(st, fh, cnt, uint32_t(sc.n_strip_slots), r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : ~0u, sc.shader_level, nullptr);
             last_set = g * rb + cnt - 1;
             last_on[g * rb] = int64_t(gi);
@@ -1216,9 +1223,9 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
         t_stage += ms_since(t0); t0 = clk::now();
         if (!G.ev_begin) { HIP_CHECK(hipEventCreate(&G.ev_begin)); HIP_CHECK(hipEventCreate(&G.ev_end)); }
         HIP_CHECK(hipEventRecord(G.ev_begin, G.stream));
-        launch2_bin(G.stream, frames_dev, cnt, uint32_t(max_e), uint32_t(max_p), uint32_t(max_bands), 1u);
-        launch2_rows(G.stream, frames_dev, cnt, uint32_t(max_chunks), max_pe);
-        if (max_chunks) launch2_rows_slow(G.stream, frames_dev, cnt, 256u, 64u, SLOW_PASSES);
+        launch2_bin(G.stream, frames_dev, cnt, uint32_t(max_e), uint32_t(max_p), uint32_t(max_bands), 1u, r->mono);
+        launch2_rows(G.stream, frames_dev, cnt, uint32_t(max_chunks), max_pe, r->mono);
+        if (max_chunks) launch2_rows_slow(G.stream, frames_dev, cnt, 256u, 64u, SLOW_PASSES, r->mono);
         launch2_tiles(G.stream, frames_dev, cnt, uint32_t(max_strips), ~0u, shader_level, nullptr);
         HIP_CHECK(hipEventRecord(G.ev_end, G.stream));
         for (uint32_t k = 0; k < cnt; ++k)
@@ -1292,9 +1299,9 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     HIP_CHECK(hipStreamSynchronize(st));                       // (fr is a local)
     if (!r->rb_ev[0]) { HIP_CHECK(hipEventCreate(&r->rb_ev[0])); HIP_CHECK(hipEventCreate(&r->rb_ev[1])); }
     auto one_launch = [&]() {
-        launch2_bin(st, r->rb_frames.ptr, B, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u);
-        launch2_rows(st, r->rb_frames.ptr, B, uint32_t(sc.n_chunks), sc.max_path_edges);
-        if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, r->rb_frames.ptr, B, 256u, sc.slow_state == 2 ? 0u : 64u, sc.slow_passes);
+        launch2_bin(st, r->rb_frames.ptr, B, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
+        launch2_rows(st, r->rb_frames.ptr, B, uint32_t(sc.n_chunks), sc.max_path_edges, r->mono);
+        if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, r->rb_frames.ptr, B, 256u, sc.slow_state == 2 ? 0u : 64u, sc.slow_passes, r->mono);
         launch2_tiles(st, r->rb_frames.ptr, B, uint32_t(sc.n_strip_slots), ~0u, sc.shader_level, nullptr);
     };
     one_launch();                                              // warm-up: leaves a cost history for the strip order
@@ -1420,7 +1427,8 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->height = height;
     if (cfg) r->cfg = *cfg;
     if (r->cfg.band_count > 1 && r->cfg.band_index >= r->cfg.band_count) return SWFR_ERR_INVALID;
-    r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0));
+    r->mono = (r->cfg.flags & SWFR_FLAG_ANTIALIAS_NONE) != 0;
+    r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
     if (const char* bf = std::getenv("SWFR_BATCH_FRAMES")) r->batch_frames = std::max(1, std::atoi(bf));
