@@ -116,7 +116,10 @@ typedef struct {                         /* tags::DefineShape / tags::DefineMorp
 } swfr_define_shape;
 
 /* ---- stage ------------------------------------------------------------------------------- */
-enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER = 2 };
+enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER = 2,
+       SWFR_OBJECT_COLOR_TRANSFORM = 3   /* a container (matrix + children) whose `id` names a colour-transform slot (swfr_set_color_transform):
+                                            the slot's value at the time of the render call applies to everything below it.  Beyond the
+                                            reference, whose display objects carry a matrix and a ratio only */ };
 
 typedef struct swfr_display_object {
     uint32_t type;                       /* SWFR_OBJECT_* (ts/src/lib/display/display-object-type.ts) */
@@ -132,6 +135,17 @@ typedef struct {
     swfr_rgba8 background_color;         /* not painted by the reference (canvas-renderer.ts:72) */
     uint32_t n_children; const swfr_display_object *children;
 } swfr_stage;
+
+/* ---- colour transforms (swf-tree ColorTransformWithAlpha, PlaceObject2/3's CXFORMWITHALPHA) -------------------------------
+   Channels r, g, b, a.  mult in Sfixed8P8 epsilons (256 = 1.0); all eight values in the int16 range.  One channel maps as
+   c' = clamp(((c * mult) >> 8) + add, 0, 255) in int32 with an arithmetic shift; nested transforms apply innermost first, each one
+   clamping.  What is transformed is the straight colour a definition holds: solid fill and line colours, gradient stops, both
+   colours of a morph shape (the ratio interpolation comes after), and every straight texel of a bitmap fill as registered (before
+   the putImageData premultiply and any filtering).  The stage background is not.  DESIGN.md, "Colour transforms". */
+typedef struct { int32_t mult[4], add[4]; } swfr_color_transform;
+/* Sets slot `slot` (< 65536) of the handle, or clears it (ct == NULL).  Out-of-range values: SWFR_ERR_INVALID.  A display object of
+   type SWFR_OBJECT_COLOR_TRANSFORM naming an unset slot makes the render call fail with SWFR_ERR_NOT_FOUND ("ColorTransformNotFound"). */
+int swfr_set_color_transform(swfr_renderer *r, uint32_t slot, const swfr_color_transform *ct);
 
 /* ---- configuration ------------------------------------------------------------------------ */
 #define SWFR_DEVICE_HOST_ONLY (-1)       /* decode + geometry only; swfr_render fails with NO_DEVICE */
@@ -219,7 +233,8 @@ typedef struct {
     uint32_t n_stops;
     float stop_offset[SWFR_MAX_STOPS];
     float stop_rgba[SWFR_MAX_STOPS][4];  /* straight, 0..1 */
-    uint32_t bitmap;                     /* registered bitmap id */
+    uint32_t bitmap;                     /* registered bitmap id; 65536 + k: texture k of the colour-transformed bitmaps of the frame the
+                                            handle's last scene walk built (swfr_build_frame), valid on that handle until its next walk */
     uint32_t extend;                     /* 0 none, 1 repeat */
 } swfr_style;
 
@@ -328,6 +343,10 @@ int  swfr_wait(swfr_renderer *r);
    1: cells (4 bytes each: column relative to the path's x_min << 19 | covered height (5 bits signed) << 14 | uncovered area (14 bits signed)).
    Returns the number of bytes copied (at most `bytes`), or a negative SWFR_ERR_*. */
 long swfr_debug_copy(swfr_renderer *r, int what, void *dst, size_t bytes);
+/* Measurement (tools/cxform_bench.py): the texel pass of colour transforms (cxform.hip) over registered bitmap `bitmap_id` under
+   `ct`, `reps` times back to back into a scratch texture, then `reps` device-to-device copies of the same bytes; HIP-event time per
+   pass and per copy in *pass_ms / *copy_ms.  Touches no frame and no cache. */
+int  swfr_debug_time_cxform(swfr_renderer *r, uint32_t bitmap_id, const swfr_color_transform *ct, uint32_t reps, float *pass_ms, float *copy_ms);
 /* Device pointer of the premultiplied RGBA8 framebuffer (width*height*4 bytes, tight rows). */
 void *swfr_device_framebuffer(swfr_renderer *r);
 

@@ -33,7 +33,10 @@ EXPORTS = [
     "swfr_render_sequence", "swfr_set_targets", "swfr_render_resident_async", "swfr_stream_handle", "swfr_wait",
     "swfr_render_resident_batched", "swfr_read_image_async", "swfr_read_image_wait", "swfr_render_sequence_readback",
     "swfr_register_bitmap_tag", "swfr_decode_x_swf_bmp", "swfr_render_resident_async_to", "swfr_render_resident_group_to",
+    "swfr_set_color_transform", "swfr_debug_time_cxform",
 ]
+OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
+VARIANT_BASE = 65536                    # a bitmap style's `bitmap` at or above it names a colour-transformed texture of the frame
 
 
 class SwfrError(RuntimeError):
@@ -98,6 +101,10 @@ class DisplayObject(C.Structure):
 
 DisplayObject._fields_ = [("type", C.c_uint32), ("id", C.c_uint32), ("has_matrix", C.c_uint8), ("matrix", Matrix),
                           ("ratio", C.c_double), ("n_children", C.c_uint32), ("children", C.POINTER(DisplayObject))]
+
+
+class ColorTransform(C.Structure):
+    _fields_ = [("mult", C.c_int32 * 4), ("add", C.c_int32 * 4)]
 
 
 class Stage(C.Structure):
@@ -231,6 +238,10 @@ def load_library():
     L.swfr_last_path_timing.argtypes = [P, C.POINTER(PathTiming)]
     L.swfr_render_sequence.restype = I
     L.swfr_render_sequence.argtypes = [P, C.POINTER(Stage), U, U, C.POINTER(C.c_double), C.POINTER(PathTiming)]
+    L.swfr_set_color_transform.restype = I
+    L.swfr_set_color_transform.argtypes = [P, U, C.POINTER(ColorTransform)]
+    L.swfr_debug_time_cxform.restype = I
+    L.swfr_debug_time_cxform.argtypes = [P, U, C.POINTER(ColorTransform), U, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     if L.swfr_abi_version() != 1:
         raise ImportError("libswfr.so ABI mismatch")
     _LIB = L
@@ -242,10 +253,11 @@ _FILL_TYPES = {"solid": 0, "linear-gradient": 1, "radial-gradient": 2, "focal-gr
 
 
 class _Arena:
-    """Keeps every ctypes object referenced by pointer alive for the duration of one call."""
+    """Keeps every ctypes object referenced by pointer alive for the duration of one call; collects the call's colour transforms."""
 
     def __init__(self):
         self.keep = []
+        self.cxforms = {}     # the eight values -> slot: one slot per distinct transform of the call (all of its stages)
 
     def array(self, ctype, items):
         arr = (ctype * max(len(items), 1))(*items)
@@ -259,6 +271,19 @@ def _rgba(c):
 
 def _matrix(m):
     return Matrix(m["scale_x"], m["scale_y"], m["rotate_skew0"], m["rotate_skew1"], m["translate_x"], m["translate_y"])
+
+
+_CX_CHANNELS = ("red", "green", "blue", "alpha")
+
+
+def color_transform_values(ct):
+    """swf-tree ColorTransformWithAlpha (snake_case keys red_mult .. alpha_mult, red_add .. alpha_add) -> the eight integers of
+    swfr_color_transform: mult in Sfixed8P8 epsilons ({"epsilons": n}, or a number read as its value like focal_point: 1 -> 256),
+    add as is.  A missing mult is 1.0, a missing add 0."""
+    def mult(v):
+        return int(v["epsilons"]) if isinstance(v, dict) else int(round(float(v) * 256))
+    return (tuple(mult(ct[c + "_mult"]) if c + "_mult" in ct else 256 for c in _CX_CHANNELS) +
+            tuple(int(ct.get(c + "_add", 0)) for c in _CX_CHANNELS))
 
 
 def _fill(arena, s):
@@ -448,23 +473,57 @@ class Renderer:
         buf = (C.c_uint8 * len(rgba_straight)).from_buffer_copy(rgba_straight)
         self._check(self.L.swfr_register_bitmap(self.h, bitmap_id, width, height, C.cast(buf, C.c_void_p), width * 4))
 
+    def set_color_transform(self, slot, ct):
+        """swfr_set_color_transform: `ct` a swf-tree ColorTransformWithAlpha dict, or None to clear the slot.  (render() and the
+        other stage calls assign slots 0.. to the transforms of their own stages and set them; this is for callers that build
+        type-3 display objects themselves.)"""
+        if ct is None:
+            self._check(self.L.swfr_set_color_transform(self.h, slot, None))
+            return
+        v = color_transform_values(ct)
+        c = ColorTransform((C.c_int32 * 4)(*v[:4]), (C.c_int32 * 4)(*v[4:]))
+        self._check(self.L.swfr_set_color_transform(self.h, slot, C.byref(c)))
+
     def shape_json(self, shape_id, morph=False) -> str:
         out = C.c_char_p()
         self._check(self.L.swfr_shape_json(self.h, shape_id, 1 if morph else 0, C.byref(out)))
         return out.value.decode("utf-8")
 
     # -- stage
+    @staticmethod
+    def _cx_slot(arena, ct):
+        v = color_transform_values(ct)
+        return arena.cxforms.setdefault(v, len(arena.cxforms))
+
+    def _apply_cxforms(self, arena):
+        """Sets the handle's colour-transform slots to this call's transforms (slots 0..n-1, by first appearance)."""
+        for v, slot in arena.cxforms.items():
+            ct = ColorTransform((C.c_int32 * 4)(*v[:4]), (C.c_int32 * 4)(*v[4:]))
+            self._check(self.L.swfr_set_color_transform(self.h, slot, C.byref(ct)))
+
     def _object(self, arena, obj):
         d = DisplayObject()
         t = obj["type"]
         if obj.get("matrix") is not None:
             d.has_matrix = 1
             d.matrix = _matrix(obj["matrix"])
+        ct = obj.get("color_transform")
         if t == "container":
-            d.type = 2
+            d.type = OBJECT_CONTAINER if ct is None else OBJECT_COLOR_TRANSFORM
+            if ct is not None:
+                d.id = self._cx_slot(arena, ct)
             kids = arena.array(DisplayObject, [self._object(arena, c) for c in obj["children"]])
             d.n_children, d.children = len(obj["children"]), C.cast(kids, C.POINTER(DisplayObject))
             return d
+        if ct is not None and t in ("shape", "morph-shape"):
+            # a shape or morph shape with a colour transform: the same object inside a type-3 wrapper naming the transform's slot
+            w = DisplayObject()
+            w.type, w.id = OBJECT_COLOR_TRANSFORM, self._cx_slot(arena, ct)
+            inner = dict(obj)
+            del inner["color_transform"]
+            kids = arena.array(DisplayObject, [self._object(arena, inner)])
+            w.n_children, w.children = 1, C.cast(kids, C.POINTER(DisplayObject))
+            return w
         if t not in ("shape", "morph-shape"):
             raise SwfrError(ERR_INVALID, "UnexpectedDisplayObjectType")
         morph = t == "morph-shape"
@@ -494,6 +553,7 @@ class Renderer:
         """Renderer.render(stage): blocking; the image stays in HBM until read_image()."""
         arena = _Arena()
         s = self._stage(arena, stage)
+        self._apply_cxforms(arena)
         self._check(self.L.swfr_render(self.h, C.byref(s)))
 
     def render_sequence(self, stages, repeat=1):
@@ -501,6 +561,7 @@ class Renderer:
         Returns (seconds, dict of the per-frame times added up)."""
         arena = _Arena()
         arr = (Stage * max(len(stages), 1))(*[self._stage(arena, st) for st in stages])
+        self._apply_cxforms(arena)
         secs, acc = C.c_double(), PathTiming()
         self._check(self.L.swfr_render_sequence(self.h, arr, len(stages), int(repeat), C.byref(secs), C.byref(acc)))
         return secs.value, {n: getattr(acc, n) for n, _ in PathTiming._fields_}
@@ -528,7 +589,8 @@ class Renderer:
         are rendered in groups, one launch per kernel and group, the host building one group while the GPU renders the other.
         Frame i lands at device_ptr + i * frame_stride (device memory: pass tensor.data_ptr()); without a destination only the
         last frame is kept for read_image().  `stages`: a list of stage dicts, or the result of marshal_stages().  Blocking."""
-        _, arr, n = stages if isinstance(stages, tuple) else self.marshal_stages(stages)
+        arena, arr, n = stages if isinstance(stages, tuple) else self.marshal_stages(stages)
+        self._apply_cxforms(arena)
         self._check(self.L.swfr_render_batch(self.h, arr, n, C.c_void_p(device_ptr) if device_ptr else None,
                                              int(frame_stride) if device_ptr else 0))
 
@@ -536,6 +598,7 @@ class Renderer:
         """Host half only: (edges, paths, styles) exactly as render() would upload them."""
         arena = _Arena()
         s = self._stage(arena, stage)
+        self._apply_cxforms(arena)
         pe, pp, ps = C.c_void_p(), C.c_void_p(), C.c_void_p()
         ne, npth, ns = C.c_size_t(), C.c_size_t(), C.c_size_t()
         self._check(self.L.swfr_build_frame(self.h, C.byref(s), C.byref(pe), C.byref(ne), C.byref(pp), C.byref(npth),
@@ -609,7 +672,8 @@ class Renderer:
 
     def render_sequence_readback(self, stages, repeat=1, premultiplied=False, overlap=True):
         """render + mapped read-back of every frame (the reference's test loop), timed below the C-ABI; returns seconds."""
-        _, arr, n = stages if isinstance(stages, tuple) else self.marshal_stages(stages)
+        arena, arr, n = stages if isinstance(stages, tuple) else self.marshal_stages(stages)
+        self._apply_cxforms(arena)
         secs, chk = C.c_double(), C.c_uint64()
         self._check(self.L.swfr_render_sequence_readback(self.h, arr, n, int(repeat), 1 if premultiplied else 0, 1 if overlap else 0, C.byref(secs), C.byref(chk)))
         return secs.value

@@ -42,6 +42,60 @@ Css morph_color(const swfr_rgba8& s, const swfr_rgba8& e, bool morph, double rat
 
 }  // namespace
 
+bool color_transform_valid(const swfr_color_transform& ct) {
+    for (int k = 0; k < 4; ++k)
+        if (ct.mult[k] < INT16_MIN || ct.mult[k] > INT16_MAX || ct.add[k] < INT16_MIN || ct.add[k] > INT16_MAX) return false;
+    return true;
+}
+
+swfr_rgba8 FrameBuilder::cx(const swfr_rgba8& c) const {
+    const int32_t li = stack_.back().lut;
+    if (li < 0) return c;
+    const ColorLut& L = luts_[size_t(li)];
+    return swfr_rgba8{L.t[0][c.r], L.t[1][c.g], L.t[2][c.b], L.t[3][c.a]};
+}
+
+// c' = clamp(((c * mult) >> 8) + add, 0, 255) per channel (int32, arithmetic shift), then the outer chain: nested transforms apply
+// innermost first and each one clamps, so a chain is a table per channel and nothing less.  Chains are kept once per content and
+// an all-identity chain is -1, so that an identity wrapper changes nothing at all.
+int32_t FrameBuilder::compose(int32_t outer, const swfr_color_transform& inner) {
+    const auto memo_key = std::make_pair(outer, std::string(reinterpret_cast<const char*>(&inner), sizeof inner));
+    const auto hit = compose_memo_.find(memo_key);
+    if (hit != compose_memo_.end()) return hit->second;
+    ColorLut L;
+    bool identity = true;
+    for (int ch = 0; ch < 4; ++ch)
+        for (int c = 0; c < 256; ++c) {
+            const int32_t v = std::clamp(((c * inner.mult[ch]) >> 8) + inner.add[ch], 0, 255);
+            const uint8_t out = outer < 0 ? uint8_t(v) : luts_[size_t(outer)].t[ch][v];
+            L.t[ch][c] = out;
+            identity = identity && out == c;
+        }
+    int32_t index = -1;
+    if (!identity) {
+        std::string bytes(reinterpret_cast<const char*>(&L), sizeof L);
+        const auto it = lut_index_.find(bytes);
+        if (it != lut_index_.end()) index = it->second;
+        else {
+            index = int32_t(luts_.size());
+            luts_.push_back(L);
+            lut_index_.emplace(std::move(bytes), index);
+        }
+    }
+    compose_memo_.emplace(memo_key, index);
+    return index;
+}
+
+uint32_t FrameBuilder::variant_of(uint32_t bitmap, int32_t lut) {
+    const auto key = std::make_pair(bitmap, lut);
+    const auto it = variant_index_.find(key);
+    if (it != variant_index_.end()) return it->second;
+    const uint32_t k = uint32_t(variants_.size());
+    variants_.push_back(TextureVariant{bitmap, luts_[size_t(lut)]});
+    variant_index_.emplace(key, k);
+    return k;
+}
+
 Affine FrameBuilder::matrix_of(const swfr_matrix& m) {
     // applyMatrix (canvas-renderer.ts:179-188): transform(scaleX, rotateSkew0, rotateSkew1, scaleY, tx, ty)
     Affine a;
@@ -133,11 +187,12 @@ FrameBuilder::~FrameBuilder() {
     }
 }
 
-void FrameBuilder::build_range(const swfr_stage& stage, uint32_t lo, uint32_t hi) {
+void FrameBuilder::build_range(const std::vector<const swfr_display_object*>& wraps, const swfr_display_object* kids, uint32_t lo, uint32_t hi) {
     edges_.clear();
     paths_.clear();
     styles_.clear();
     stack_.clear();
+    luts_.clear(); lut_index_.clear(); compose_memo_.clear(); variant_index_.clear(); variants_.clear();
     failed_ = false;
     surface_clear_ = true;  // clearRect over the whole canvas (canvas-renderer.ts:70-71); a later piece learns the truth when joined
     State s;
@@ -145,7 +200,17 @@ void FrameBuilder::build_range(const swfr_stage& stage, uint32_t lo, uint32_t hi
     s.inv = Affine::scale(1.0 / (1.0 / 20.0), 1.0 / (1.0 / 20.0));  // cairo_scale: ctm_inverse *= scale(1/sx, 1/sy)
     stack_.push_back(s);
     try {
-        for (uint32_t i = lo; i < hi; ++i) draw(stage.children[i], 0);
+        // the wrappers the children sit in (see build): their matrices and colour transforms, as draw() applies them
+        for (const swfr_display_object* w : wraps) {
+            stack_.push_back(stack_.back());
+            if (w->has_matrix) transform(matrix_of(w->matrix));
+            if (w->type == SWFR_OBJECT_COLOR_TRANSFORM) {
+                const auto it = store()->cxforms_.find(w->id);
+                if (it == store()->cxforms_.end()) throw StatusError{SWFR_ERR_NOT_FOUND, "ColorTransformNotFound"};
+                stack_.back().lut = compose(stack_.back().lut, it->second);
+            }
+        }
+        for (uint32_t i = lo; i < hi; ++i) draw(kids[i], int(wraps.size()));
     } catch (const StatusError& e) {
         failed_ = true;
         failure_ = e;
@@ -153,7 +218,8 @@ void FrameBuilder::build_range(const swfr_stage& stage, uint32_t lo, uint32_t hi
 }
 
 // this piece's arrays into their place in the joined frame: indices shifted, the "still clear?" lerps settled
-void FrameBuilder::copy_piece(FrameBuilder& dst, size_t edge_off, size_t path_off, size_t style_off, bool clear_at_start) const {
+void FrameBuilder::copy_piece(FrameBuilder& dst, size_t edge_off, size_t path_off, size_t style_off, bool clear_at_start,
+                              const std::vector<uint32_t>& variant_map) const {
     for (size_t i = 0; i < edges_.size(); ++i) {
         swfr_edge e = edges_[i];
         e.reserved += int32_t(path_off);
@@ -167,6 +233,11 @@ void FrameBuilder::copy_piece(FrameBuilder& dst, size_t edge_off, size_t path_of
         dst.paths_[path_off + i] = p;
     }
     if (!styles_.empty()) std::memcpy(&dst.styles_[style_off], styles_.data(), styles_.size() * sizeof(swfr_style));
+    if (!variants_.empty())                                     // the piece's textures renumbered to the joined frame's
+        for (size_t i = 0; i < styles_.size(); ++i) {
+            swfr_style& st = dst.styles_[style_off + i];
+            if (st.kind == SWFR_STYLE_BITMAP && st.bitmap >= VARIANT_BASE) st.bitmap = VARIANT_BASE + variant_map[st.bitmap - VARIANT_BASE];
+        }
 }
 
 void FrameBuilder::build(const swfr_stage& stage) {
@@ -176,10 +247,21 @@ void FrameBuilder::build(const swfr_stage& stage) {
         want = env ? std::atoi(env) : int(std::min(8u, std::max(1u, std::thread::hardware_concurrency())));
         threads_ = want;
     }
-    // pieces of at least 64 top-level display objects each
-    const int pieces = int(std::min<uint32_t>(uint32_t(std::max(want, 1)), stage.n_children / 64));
+    // The objects that are cut into pieces: the stage's children -- or, when the stage holds one container or colour-transform wrapper
+    // (a whole clip under one fade), that wrapper's children, through up to 16 such single wrappers.  A piece then walks its share of them
+    // inside the wrappers' state, which is what a single walk does: the wrappers draw nothing themselves.
+    std::vector<const swfr_display_object*> wraps;
+    const swfr_display_object* kids = stage.children;
+    uint32_t n_kids = stage.n_children;
+    while (n_kids == 1 && wraps.size() < 16 && (kids[0].type == SWFR_OBJECT_CONTAINER || kids[0].type == SWFR_OBJECT_COLOR_TRANSFORM)) {
+        wraps.push_back(&kids[0]);
+        n_kids = kids[0].n_children;
+        kids = kids[0].children;
+    }
+    // pieces of at least 64 display objects each
+    const int pieces = int(std::min<uint32_t>(uint32_t(std::max(want, 1)), n_kids / 64));
     if (pieces < 2) {
-        build_range(stage, 0, stage.n_children);
+        build_range({}, stage.children, 0, stage.n_children);
         if (failed_) throw failure_;
         for (swfr_path& p : paths_) if (p.lerp == 2) p.lerp = 1;
         return;
@@ -195,9 +277,9 @@ void FrameBuilder::build(const swfr_stage& stage) {
         const int index = int(P.threads.size()) + 1;
         P.threads.emplace_back([&P, index] { P.worker(index); });
     }
-    auto lo_of = [&](int k) { return uint32_t(uint64_t(stage.n_children) * uint64_t(k) / uint64_t(pieces)); };
+    auto lo_of = [&](int k) { return uint32_t(uint64_t(n_kids) * uint64_t(k) / uint64_t(pieces)); };
     // ---- phase A: every piece into its own builder
-    P.run(pieces, [&](int k) { P.builders[k]->build_range(stage, lo_of(k), lo_of(k + 1)); });
+    P.run(pieces, [&](int k) { P.builders[k]->build_range(wraps, kids, lo_of(k), lo_of(k + 1)); });
     size_t ne = 0, np = 0, ns = 0;
     std::vector<size_t> eo(pieces), po(pieces), so(pieces);
     std::vector<char> clear_at(pieces);
@@ -211,8 +293,24 @@ void FrameBuilder::build(const swfr_stage& stage) {
     }
     edges_.resize(ne); paths_.resize(np); styles_.resize(ns);
     surface_clear_ = clear;
+    // the pieces' texture variants in painter's order, each (bitmap, chain) once: the numbering a single walk gives them
+    variants_.clear();
+    std::vector<std::vector<uint32_t>> vmap(pieces);
+    {
+        std::map<std::pair<uint32_t, std::string>, uint32_t> seen;
+        for (int k = 0; k < pieces; ++k)
+            for (const TextureVariant& v : P.builders[k]->variants_) {
+                auto key = std::make_pair(v.bitmap, std::string(reinterpret_cast<const char*>(&v.lut), sizeof v.lut));
+                auto it = seen.find(key);
+                if (it == seen.end()) {
+                    it = seen.emplace(std::move(key), uint32_t(variants_.size())).first;
+                    variants_.push_back(v);
+                }
+                vmap[k].push_back(it->second);
+            }
+    }
     // ---- phase B: the pieces copied to their places, in parallel
-    P.run(pieces, [&](int k) { P.builders[k]->copy_piece(*this, eo[k], po[k], so[k], clear_at[k] != 0); });
+    P.run(pieces, [&](int k) { P.builders[k]->copy_piece(*this, eo[k], po[k], so[k], clear_at[k] != 0, vmap[k]); });
 }
 
 void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
@@ -227,6 +325,14 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
         case SWFR_OBJECT_CONTAINER:
             for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
             break;
+        case SWFR_OBJECT_COLOR_TRANSFORM: {
+            const auto& slots = store()->cxforms_;
+            const auto it = slots.find(obj.id);
+            if (it == slots.end()) throw StatusError{SWFR_ERR_NOT_FOUND, "ColorTransformNotFound"};
+            stack_.back().lut = compose(stack_.back().lut, it->second);
+            for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
+            break;
+        }
         case SWFR_OBJECT_SHAPE: {
             const DecodedShape* sh = shape(obj.id, false);
             if (!sh) throw StatusError{SWFR_ERR_NOT_FOUND, "unknown shape id"};
@@ -380,7 +486,7 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
     bool opaque_solid = false;
     // context.save(); <source>; fill(); context.restore()  (canvas-renderer.ts:292-336)
     if (s.type == SWFR_FILL_SOLID) {
-        const uint32_t px = premultiplied_pixel(morph_color(s.color, s.morph_color, morph, ratio));
+        const uint32_t px = premultiplied_pixel(morph_color(cx(s.color), cx(s.morph_color), morph, ratio));
         if ((px >> 24) == 0) return;  // Cairo: OVER with a clear source is a no-op
         opaque_solid = (px >> 24) == 0xff;
         style_index = push_solid(px);
@@ -396,7 +502,8 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         const Affine inv = stack_.back().inv.then(fm);
         const double m[6] = {inv.xx, inv.yx, inv.xy, inv.yy, inv.x0, inv.y0};
         std::memcpy(st.inv, m, sizeof m);
-        st.bitmap = s.bitmap_id;
+        const int32_t lut = stack_.back().lut;
+        st.bitmap = lut < 0 ? s.bitmap_id : VARIANT_BASE + variant_of(s.bitmap_id, lut);
         st.extend = s.repeating ? 1 : 0;
         styles_.push_back(st);
         style_index = uint32_t(styles_.size() - 1);
@@ -425,6 +532,7 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         }
         // stops sorted by offset, stable (cairo_pattern_add_color_stop keeps them ordered)
         std::vector<swfr_color_stop> stops = f.stops;
+        for (swfr_color_stop& c : stops) { c.color = cx(c.color); c.morph_color = cx(c.morph_color); }
         std::stable_sort(stops.begin(), stops.end(), [](const swfr_color_stop& a, const swfr_color_stop& b) { return a.ratio < b.ratio; });
         st.n_stops = uint32_t(stops.size());
         for (size_t i = 0; i < stops.size(); ++i) {
@@ -497,7 +605,7 @@ void FrameBuilder::emit_stroke(const StyledPath& p, bool morph, double ratio) {
     State& st = stack_.back();
     const double width = morph ? lerp(p.width, p.morph_width, ratio) : double(p.width);
     if (width > 0) st.line_width = width;  // node-canvas ignores non-positive widths
-    const uint32_t px = premultiplied_pixel(morph_color(p.fill.style.color, p.fill.style.morph_color, morph, ratio));
+    const uint32_t px = premultiplied_pixel(morph_color(cx(p.fill.style.color), cx(p.fill.style.morph_color), morph, ratio));
     if (morph) st.cap = st.join = 1;  // lineCap = lineJoin = "round" (canvas-renderer.ts:263-264)
     if ((px >> 24) == 0) return;
     if (path_.empty_extents()) return;

@@ -28,6 +28,20 @@ struct StatusError {
     std::string message;
 };
 
+// A chain of colour transforms as four 256-entry tables, channel-major (r, g, b, a): the value a straight channel c takes is lut[ch][c].
+struct ColorLut {
+    uint8_t t[4][256];
+};
+// A bitmap fill under a non-identity chain: the frame's bitmap style then names texture VARIANT_BASE + k of the frame's variants().
+struct TextureVariant {
+    uint32_t bitmap;
+    ColorLut lut;
+};
+constexpr uint32_t VARIANT_BASE = 65536;         // (registered bitmap ids are below it)
+
+// swfr_set_color_transform's check: eight values in the int16 range
+bool color_transform_valid(const swfr_color_transform& ct);
+
 // Frames with many top-level display objects are built by several threads: the children are cut into contiguous ranges, every range
 // is walked by a worker builder of its own (same code, its own output arrays), and the pieces are joined in painter's order.  The one
 // thing a display object's output depends on besides itself -- whether the surface is still clear, which turns the first translucent
@@ -43,6 +57,7 @@ public:
     uint32_t add_shape(DecodedShape s) { shapes_.push_back(std::move(s)); return uint32_t(shapes_.size() - 1); }
     uint32_t add_morph_shape(DecodedShape s) { morphs_.push_back(std::move(s)); return uint32_t(morphs_.size() - 1); }
     void add_bitmap(uint32_t id, BitmapInfo info) { bitmaps_[id] = info; }
+    void set_color_transform(uint32_t slot, const swfr_color_transform* ct) { if (ct) cxforms_[slot] = *ct; else cxforms_.erase(slot); }
     const DecodedShape* shape(uint32_t id, bool morph) const;
 
     // Throws StatusError.  Results stay valid until the next build().
@@ -50,6 +65,7 @@ public:
     const std::vector<swfr_edge>& edges() const { return edges_; }
     const std::vector<swfr_path>& paths() const { return paths_; }
     const std::vector<swfr_style>& styles() const { return styles_; }
+    const std::vector<TextureVariant>& variants() const { return variants_; }   // textures VARIANT_BASE + k of the bitmap styles, first-use order
 
 private:
     struct State {
@@ -57,6 +73,7 @@ private:
         Affine inv;               // Cairo keeps the inverse beside the CTM and updates it factor by factor (_cairo_gstate_transform)
         double line_width = 1.0;  // node-canvas creates its context with line width 1
         int cap = 0, join = 0;
+        int32_t lut = -1;         // colour-transform chain: index into luts_, -1 identity
     };
     void draw(const swfr_display_object& obj, int depth);
     void draw_path(const StyledPath& p, bool morph, double ratio);
@@ -65,14 +82,18 @@ private:
     void emit_stroke(const StyledPath& p, bool morph, double ratio);
     void emit_polygon(Polygon& poly, bool rectilinear, uint32_t style, bool opaque_solid, int bx0 = 0, int by0 = 0, int bx1 = INT32_MAX, int by1 = INT32_MAX);
     uint32_t push_solid(uint32_t pixel);
+    swfr_rgba8 cx(const swfr_rgba8& c) const;                  // the current chain applied to a straight colour
+    int32_t compose(int32_t outer, const swfr_color_transform& inner);   // chain `outer` after `inner`: an index into luts_ (-1: identity)
+    uint32_t variant_of(uint32_t bitmap, int32_t lut);         // this builder's texture index of (bitmap, chain)
     bool frame_bounds(Pt lo, Pt hi, bool& needs_clip) const;
     bool transform(const Affine& m);  // context.transform(m); false: singular
     static Affine matrix_of(const swfr_matrix& m);
 
     // ---- multi-threaded build
     struct Pool;                                         // the worker threads (created on first use)
-    void build_range(const swfr_stage& stage, uint32_t lo, uint32_t hi);    // worker: children [lo, hi) into this builder's arrays
-    void copy_piece(FrameBuilder& dst, size_t edge_off, size_t path_off, size_t style_off, bool clear_at_start) const;
+    // worker: kids [lo, hi), inside the single wrappers `wraps` (outermost first), into this builder's arrays
+    void build_range(const std::vector<const swfr_display_object*>& wraps, const swfr_display_object* kids, uint32_t lo, uint32_t hi);
+    void copy_piece(FrameBuilder& dst, size_t edge_off, size_t path_off, size_t style_off, bool clear_at_start, const std::vector<uint32_t>& variant_map) const;
     const FrameBuilder* store() const { return parent_ ? parent_ : this; }  // where shapes and bitmaps are registered
     const FrameBuilder* parent_ = nullptr;
     std::unique_ptr<Pool> pool_;
@@ -92,6 +113,14 @@ private:
     std::vector<swfr_edge> edges_;
     std::vector<swfr_path> paths_;
     std::vector<swfr_style> styles_;
+    // colour transforms: the slots (set on the handle's builder), the chains of this walk (deduplicated by content) and the
+    // textures its bitmap styles ask for (deduplicated by (bitmap, chain))
+    std::map<uint32_t, swfr_color_transform> cxforms_;
+    std::vector<ColorLut> luts_;
+    std::map<std::string, int32_t> lut_index_;                 // table bytes -> index into luts_
+    std::map<std::pair<int32_t, std::string>, int32_t> compose_memo_;   // (outer chain, inner transform bytes) -> chain
+    std::map<std::pair<uint32_t, int32_t>, uint32_t> variant_index_;
+    std::vector<TextureVariant> variants_;
 };
 
 }  // namespace swfr

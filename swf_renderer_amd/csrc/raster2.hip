@@ -1782,6 +1782,8 @@ void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint
     else hipLaunchKernelGGL(k2_tiles_solid_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
 }
 
+#include "cxform.hip"
+
 }  // namespace swfr
 
 #if defined(SWFR_TRACE) || defined(SWFR_TSTATS)

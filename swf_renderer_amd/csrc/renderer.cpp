@@ -12,10 +12,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/swfr.h"
@@ -31,6 +33,7 @@ void launch2_rows_slow(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t,
 void launch2_tiles(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, int, uint32_t*);
 void launch_unpremultiply(hipStream_t, const uint32_t*, uint32_t*, size_t);
 void launch_pack_band(hipStream_t, const uint32_t*, uint32_t*, int, int, uint32_t, uint32_t, uint32_t);
+void launch_cxform_texels(hipStream_t, const uint8_t*, uint32_t*, size_t, const uint32_t*);
 }  // namespace swfr
 
 using namespace swfr;
@@ -131,6 +134,29 @@ struct SceneArena {
 struct DeviceBitmap {
     uint32_t* pixels = nullptr;
     uint32_t width = 0, height = 0;
+    uint64_t gen = 0;                        // registration generation: a colour-transformed texture is made from one generation
+    std::vector<uint8_t> straight;           // the straight RGBA8 texels as registered (tight rows), for the texel pass
+    uint8_t* d_straight = nullptr;           // ... on the device: uploaded the first time a colour transform uses the bitmap (kept until the
+                                             // bitmap is registered again; not counted against SWFR_CXFORM_CACHE_MB)
+    hipEvent_t straight_ready = nullptr;     // recorded behind that upload, on straight_stream
+    hipStream_t straight_stream = nullptr;
+    bool straight_done = false;              // the upload is known to have completed
+};
+
+// A colour-transformed texture (cxform.hip): premultiplied ARGB of one (bitmap, generation, chain), made by the texel pass on `stream`
+// (`ready` recorded behind it).  Kept in the handle's cache under a byte budget (SWFR_CXFORM_CACHE_MB); never evicted while the call
+// that uses it runs (used_epoch) or while it belongs to the resident scene (pinned).
+struct CxVariant {
+    uint32_t* pixels = nullptr;
+    size_t bytes = 0;
+    uint32_t bitmap = 0;
+    uint64_t gen = 0;
+    hipEvent_t ready = nullptr;
+    hipStream_t stream = nullptr;
+    bool done = false;                       // `ready` known to have completed
+    bool pinned = false;
+    uint64_t used_epoch = 0, last_use = 0;
+    std::shared_ptr<uint32_t> table;         // the chain's packed table as copied behind the texels (kept: the copy is queued on `stream`)
 };
 
 }  // namespace
@@ -211,6 +237,13 @@ struct swfr_renderer {
     uint32_t* fb_cur = nullptr;             // framebuffer of the last completed frame
     std::map<uint32_t, DeviceBitmap> bitmaps;
     std::vector<DevBitmap> bitmap_table;   // indexed by bitmap id
+    uint64_t bitmap_gen = 0;
+    // colour-transformed textures: key = bitmap id | generation | the chain's 1 024 table bytes
+    std::unordered_map<std::string, CxVariant> cx_cache;
+    size_t cx_bytes = 0, cx_budget = size_t(512) << 20;   // SWFR_CXFORM_CACHE_MB
+    uint64_t cx_epoch = 0, cx_tick = 0, cx_synced_epoch = ~uint64_t(0);
+    std::vector<std::string> cx_pins;      // the resident scene's textures
+    std::vector<DevBitmap> variant_table;  // textures VARIANT_BASE + k of the scene being laid out
     bool bitmap_table_dirty = false, bitmap_table_dirty_copied = false;
     bool scene_ready = false, fb_valid = false;
     swfr_timing timing{};
@@ -273,7 +306,15 @@ struct swfr_renderer {
                 if (g.h_counters) (void)hipHostFree(g.h_counters);
                 if (g.ev_begin) { (void)hipEventDestroy(g.ev_begin); (void)hipEventDestroy(g.ev_end); }
             }
-            for (auto& kv : bitmaps) if (kv.second.pixels) (void)hipFree(kv.second.pixels);
+            for (auto& kv : bitmaps) {
+                if (kv.second.pixels) (void)hipFree(kv.second.pixels);
+                if (kv.second.d_straight) (void)hipFree(kv.second.d_straight);
+                if (kv.second.straight_ready) (void)hipEventDestroy(kv.second.straight_ready);
+            }
+            for (auto& kv : cx_cache) {
+                if (kv.second.pixels) (void)hipFree(kv.second.pixels);
+                if (kv.second.ready) (void)hipEventDestroy(kv.second.ready);
+            }
             for (auto& e : ev) if (e) (void)hipEventDestroy(e);
             if (stream) (void)hipStreamDestroy(stream);
         }
@@ -369,7 +410,12 @@ void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edg
         const swfr_style& s = styles[i];
         if (s.kind > SWFR_STYLE_BITMAP) throw StatusError{SWFR_ERR_INVALID, "unknown style kind"};
         if (s.n_stops > SWFR_MAX_STOPS) throw StatusError{SWFR_ERR_INVALID, "too many gradient stops"};
-        if (s.kind == SWFR_STYLE_BITMAP && !r->bitmaps.count(s.bitmap)) throw StatusError{SWFR_ERR_NOT_FOUND, "BitmapNotFound"};
+        if (s.kind == SWFR_STYLE_BITMAP) {
+            const auto& V = r->builder->variants();
+            const bool known = s.bitmap >= VARIANT_BASE ? (s.bitmap - VARIANT_BASE < V.size() && r->bitmaps.count(V[s.bitmap - VARIANT_BASE].bitmap))
+                                                        : r->bitmaps.count(s.bitmap) != 0;
+            if (!known) throw StatusError{SWFR_ERR_NOT_FOUND, "BitmapNotFound"};
+        }
     }
 }
 
@@ -546,7 +592,8 @@ DevFilter good_filter(const swfr_style& st, const int rect[4], std::vector<int32
 
 // pixman's view of every bitmap / radial-gradient style of a scene (sample positions, filter tables, colour ramps)
 void prepare_sources(const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles, std::vector<DevFilter>& filters,
-                     std::vector<DevGradient>& gradients, std::vector<int32_t>& fparams, const std::vector<DevBitmap>& bitmap_table) {
+                     std::vector<DevGradient>& gradients, std::vector<int32_t>& fparams, const std::vector<DevBitmap>& bitmap_table,
+                     const std::vector<DevBitmap>& variant_table) {
     filters.assign(n_styles, DevFilter{});
     // a bitmap style belongs to one drawing operation: pixman's transform is anchored at the centre of that operation's rectangle
     std::vector<int> rect(4 * n_styles, 0);
@@ -563,9 +610,12 @@ void prepare_sources(const swfr_path* paths, size_t n_paths, const swfr_style* s
     for (size_t i = 0; i < n_styles; ++i) {
         filters[i] = good_filter(styles[i], &rect[4 * i], fparams);
         filters[i].kind = styles[i].kind; filters[i].extend = styles[i].extend;
-        if (styles[i].kind == SWFR_STYLE_BITMAP && styles[i].bitmap < bitmap_table.size()) {
-            const DevBitmap& bm = bitmap_table[styles[i].bitmap];
-            filters[i].pixels = bm.pixels; filters[i].width = bm.width; filters[i].height = bm.height;
+        if (styles[i].kind == SWFR_STYLE_BITMAP) {
+            // (a colour-transformed bitmap samples its texture from the texel pass: resolve_variants)
+            const uint32_t b = styles[i].bitmap;
+            const DevBitmap* bm = b >= VARIANT_BASE ? (b - VARIANT_BASE < variant_table.size() ? &variant_table[b - VARIANT_BASE] : nullptr)
+                                                    : (b < bitmap_table.size() ? &bitmap_table[b] : nullptr);
+            if (bm) { filters[i].pixels = bm->pixels; filters[i].width = bm->width; filters[i].height = bm->height; }
         }
         if (styles[i].kind == SWFR_STYLE_RADIAL) {
             gradients.push_back(radial_of(styles[i], &rect[4 * i]));
@@ -657,8 +707,8 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
     L.n_strips = size_t(local_tile_rows(r)) * tiles_x * STRIPS_PER_TILE;
     L.n_strip_slots = strip_slots(local_tile_rows(r), uint32_t(tiles_x * STRIPS_PER_TILE));
     L.filters.clear(); L.gradients.clear(); L.fparams.clear();
-    if (src_paths) prepare_sources(src_paths, n_src_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table);
-    else prepare_sources(paths, n_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table);
+    if (src_paths) prepare_sources(src_paths, n_src_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
+    else prepare_sources(paths, n_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
 }
 // A tor path wider than the 13-bit column field of a cell (only possible in frames wider than 8192 px) is rasterized as several
 // paths over the SAME edges, one per block of 8192 pixel columns: the scan converter clips a path's cells to its column range
@@ -738,6 +788,147 @@ void fill_frame_sizes(const swfr_renderer* r, const SceneLayout& L, size_t n_edg
     f.mono = r->mono ? 1u : 0u;
 }
 
+// ---- colour-transformed textures ("Colour transforms")
+constexpr size_t CX_TABLE_BYTES = 256 * sizeof(uint32_t);
+// Waits for every stream of the handle once per call before the first texture of the cache is freed or reused: a texture outside the
+// call and outside the resident scene can only be read by frames that were queued before the call.
+void cx_quiesce(swfr_renderer* r) {
+    if (r->cx_synced_epoch == r->cx_epoch) return;
+    for (auto& x : r->fs) if (x.stream) HIP_CHECK(hipStreamSynchronize(x.stream));
+    for (auto& g : r->groups) if (g.stream) HIP_CHECK(hipStreamSynchronize(g.stream));
+    r->cx_synced_epoch = r->cx_epoch;
+}
+bool cx_stale(const swfr_renderer* r, const CxVariant& v) {
+    const auto it = r->bitmaps.find(v.bitmap);
+    return it == r->bitmaps.end() || it->second.gen != v.gen;
+}
+// The bitmap's straight texels on the device, ordered before whatever is queued on `st` next.  The first use uploads them on `st` (a
+// hipMemcpy from pageable memory may return before its DMA has landed, and the frame streams are not ordered behind the null stream)
+// and records an event behind the copy; a later use on another stream -- the next frame set of swfr_render_batch, the other batch group
+// -- waits for that event on the device until it is known to have completed.  bm.straight stays until the bitmap is registered again.
+void cx_straight_on(DeviceBitmap& bm, hipStream_t st) {
+    if (!bm.d_straight) {
+        const size_t bytes = size_t(bm.width) * bm.height * 4;
+        if (!bm.straight_ready) HIP_CHECK(hipEventCreateWithFlags(&bm.straight_ready, hipEventDisableTiming));
+        uint8_t* d = nullptr;
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), bytes));
+        try {
+            HIP_CHECK(hipMemcpyAsync(d, bm.straight.data(), bytes, hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipEventRecord(bm.straight_ready, st));
+        } catch (...) {                                           // (never left half uploaded: the next use uploads again)
+            (void)hipFree(d);
+            throw;
+        }
+        bm.d_straight = d;
+        bm.straight_stream = st;
+        bm.straight_done = false;
+        return;
+    }
+    if (!bm.straight_done && bm.straight_stream != st) {
+        if (hipEventQuery(bm.straight_ready) == hipSuccess) bm.straight_done = true;
+        else HIP_CHECK(hipStreamWaitEvent(st, bm.straight_ready, 0));
+    }
+}
+// Evicts textures (stale generations first, then the least recently used) until `bytes` more fit the budget or nothing else may go;
+// a texture of exactly `bytes` is handed back for reuse (its buffer and event) instead of being freed.
+CxVariant cx_make_room(swfr_renderer* r, size_t bytes) {
+    CxVariant reuse;
+    while (r->cx_bytes + bytes > r->cx_budget) {
+        auto victim = r->cx_cache.end();
+        bool victim_stale = false;
+        for (auto it = r->cx_cache.begin(); it != r->cx_cache.end(); ++it) {
+            const CxVariant& v = it->second;
+            if (v.pinned || v.used_epoch == r->cx_epoch) continue;
+            const bool st = cx_stale(r, v);
+            if (victim == r->cx_cache.end() || (st && !victim_stale) || (st == victim_stale && v.last_use < victim->second.last_use)) {
+                victim = it;
+                victim_stale = st;
+            }
+        }
+        if (victim == r->cx_cache.end()) break;                // the rest is in use: this call goes over the budget
+        cx_quiesce(r);
+        CxVariant& v = victim->second;
+        if (!reuse.pixels && v.bytes == bytes) reuse = v;
+        else {
+            HIP_CHECK(hipFree(v.pixels));
+            if (v.ready) HIP_CHECK(hipEventDestroy(v.ready));
+        }
+        r->cx_bytes -= v.bytes;
+        r->cx_cache.erase(victim);
+    }
+    return reuse;
+}
+// The textures a scene's colour-transformed bitmap styles sample (swfr_style::bitmap = VARIANT_BASE + k, k into the builder's
+// variants()): from the cache, or made by the texel pass queued on `st` ahead of the frame.  Fills r->variant_table for
+// prepare_sources.  pin: the scene goes to the resident slot -- its textures stay until the next scene replaces it there.
+void resolve_variants(swfr_renderer* r, const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles, hipStream_t st, bool pin) {
+    r->variant_table.clear();
+    if (pin) {
+        for (const std::string& key : r->cx_pins) {
+            const auto it = r->cx_cache.find(key);
+            if (it != r->cx_cache.end()) it->second.pinned = false;
+        }
+        r->cx_pins.clear();
+    }
+    bool any = false;
+    for (size_t i = 0; i < n_styles && !any; ++i) any = styles[i].kind == SWFR_STYLE_BITMAP && styles[i].bitmap >= VARIANT_BASE;
+    if (!any) return;                                             // (a scene without colour-transformed bitmaps: nothing at all)
+    const auto& V = r->builder->variants();
+    r->variant_table.assign(V.size(), DevBitmap{nullptr, 0, 0});
+    for (size_t i = 0; i < n_paths; ++i) {
+        const swfr_style& s = styles[paths[i].style];
+        if (s.kind != SWFR_STYLE_BITMAP || s.bitmap < VARIANT_BASE) continue;
+        const uint32_t k = s.bitmap - VARIANT_BASE;               // (validate_scene: k < V.size(), the bitmap is registered)
+        if (r->variant_table[k].pixels) continue;
+        const TextureVariant& tv = V[k];
+        DeviceBitmap& bm = r->bitmaps.at(tv.bitmap);
+        std::string key(sizeof(uint32_t) + sizeof(uint64_t) + sizeof(ColorLut), '\0');
+        std::memcpy(&key[0], &tv.bitmap, sizeof(uint32_t));
+        std::memcpy(&key[sizeof(uint32_t)], &bm.gen, sizeof(uint64_t));
+        std::memcpy(&key[sizeof(uint32_t) + sizeof(uint64_t)], &tv.lut, sizeof(ColorLut));
+        auto it = r->cx_cache.find(key);
+        if (it == r->cx_cache.end()) {
+            const size_t n = size_t(bm.width) * bm.height, bytes = n * 4;
+            cx_straight_on(bm, st);
+            CxVariant v = cx_make_room(r, bytes);
+            if (!v.pixels) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v.pixels), bytes + CX_TABLE_BYTES));   // (the chain's table behind the texels)
+            r->cx_bytes += bytes;
+            v.bytes = bytes;
+            it = r->cx_cache.emplace(key, v).first;
+            CxVariant& e = it->second;
+            try {
+                if (!e.ready) HIP_CHECK(hipEventCreateWithFlags(&e.ready, hipEventDisableTiming));
+                e.bitmap = tv.bitmap; e.gen = bm.gen; e.stream = st; e.done = false; e.pinned = false;
+                e.table.reset(new uint32_t[256], std::default_delete<uint32_t[]>());
+                for (int c = 0; c < 256; ++c)
+                    e.table.get()[c] = uint32_t(tv.lut.t[0][c]) | uint32_t(tv.lut.t[1][c]) << 8 | uint32_t(tv.lut.t[2][c]) << 16 | uint32_t(tv.lut.t[3][c]) << 24;
+                HIP_CHECK(hipMemcpyAsync(e.pixels + n, e.table.get(), CX_TABLE_BYTES, hipMemcpyHostToDevice, st));
+                launch_cxform_texels(st, bm.d_straight, e.pixels, n, e.pixels + n);
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipEventRecord(e.ready, st));
+            } catch (...) {                                       // a texture that was not made never stays in the cache
+                (void)hipFree(e.pixels);
+                if (e.ready) (void)hipEventDestroy(e.ready);
+                r->cx_bytes -= bytes;
+                r->cx_cache.erase(it);
+                throw;
+            }
+        } else {
+            CxVariant& e = it->second;
+            // made on another stream and maybe still running: this frame's stream waits for it on the device
+            if (!e.done && e.stream != st) {
+                if (hipEventQuery(e.ready) == hipSuccess) e.done = true;
+                else HIP_CHECK(hipStreamWaitEvent(st, e.ready, 0));
+            }
+        }
+        CxVariant& e = it->second;
+        e.used_epoch = r->cx_epoch;
+        e.last_use = ++r->cx_tick;
+        if (pin && !e.pinned) { e.pinned = true; r->cx_pins.push_back(key); }
+        r->variant_table[k] = DevBitmap{e.pixels, bm.width, bm.height};
+    }
+}
+
 // Uploads a scene -- the raw edge list, the paths and the styles, plus the layout above -- and sizes the buffers the
 // kernels write.
 int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
@@ -776,6 +967,8 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
     }
     static thread_local SceneLayout layout_scratch;        // (vectors keep their capacity from frame to frame)
     SceneLayout& L = layout_scratch;
+    if (src_paths) resolve_variants(r, src_paths, n_src_paths, styles, n_styles, up_stream, si == 0);
+    else resolve_variants(r, paths, n_paths, styles, n_styles, up_stream, si == 0);
     layout_scene(r, edges, n_edges, paths, n_paths, styles, n_styles, L, src_paths, n_src_paths);
     sc.n_edges = n_edges; sc.n_paths = n_paths; sc.n_styles = n_styles; sc.any_shader = L.any_shader; sc.shader_level = L.shader_level;
     sc.n_chunks = L.n_chunks; sc.chunk_rows = L.chunk_rows; sc.n_bands = L.n_bands; sc.n_rows = L.n_rows;
@@ -1154,6 +1347,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             r->builder->build(stages[first + k]);
             F.e = r->builder->edges(); F.p = r->builder->paths(); F.s = r->builder->styles();
             validate_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size());
+            resolve_variants(r, F.p.data(), F.p.size(), F.s.data(), F.s.size(), G.stream, false);
             {
                 std::vector<swfr_edge> se; std::vector<swfr_path> sp;
                 if (split_wide_paths(F.e.data(), F.p.data(), F.p.size(), se, sp)) {
@@ -1441,6 +1635,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->use_graphs = 0;                                              // (the emulator's runtime has no graphs)
 #endif
     if (const char* rb = std::getenv("SWFR_RESIDENT_BATCH")) r->resident_batch = std::atoi(rb);
+    if (const char* cm = std::getenv("SWFR_CXFORM_CACHE_MB")) r->cx_budget = size_t(std::max(0, std::atoi(cm))) << 20;
     if (r->cfg.device == SWFR_DEVICE_HOST_ONLY) {
         *out = r.release();
         return SWFR_OK;
@@ -1532,7 +1727,21 @@ int swfr_register_bitmap(swfr_renderer* r, uint32_t id, uint32_t width, uint32_t
         }
         DeviceBitmap& slot = r->bitmaps[id];
         if (slot.pixels) HIP_CHECK(hipFree(slot.pixels));
+        if (slot.d_straight) HIP_CHECK(hipFree(slot.d_straight));
+        if (slot.straight_ready) HIP_CHECK(hipEventDestroy(slot.straight_ready));
         slot = DeviceBitmap{};
+        slot.gen = ++r->bitmap_gen;                             // (the colour-transformed textures of the previous generation are stale)
+        slot.straight.resize(size_t(width) * height * 4);
+        for (uint32_t y = 0; y < height; ++y) std::memcpy(&slot.straight[size_t(y) * width * 4], rgba + size_t(y) * stride, size_t(width) * 4);
+        for (auto it = r->cx_cache.begin(); it != r->cx_cache.end();) {
+            if (it->second.bitmap == id && !it->second.pinned) {
+                cx_quiesce(r);
+                (void)hipFree(it->second.pixels);
+                if (it->second.ready) (void)hipEventDestroy(it->second.ready);
+                r->cx_bytes -= it->second.bytes;
+                it = r->cx_cache.erase(it);
+            } else ++it;
+        }
         HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&slot.pixels), argb.size() * 4));
         HIP_CHECK(hipMemcpy(slot.pixels, argb.data(), argb.size() * 4, hipMemcpyHostToDevice));
         slot.width = width;
@@ -1540,6 +1749,62 @@ int swfr_register_bitmap(swfr_renderer* r, uint32_t id, uint32_t width, uint32_t
         if (r->bitmap_table.size() <= id) r->bitmap_table.resize(id + 1, DevBitmap{nullptr, 0, 0});
         r->bitmap_table[id] = DevBitmap{slot.pixels, width, height};
         r->bitmap_table_dirty = true;
+        return int(SWFR_OK);
+    });
+}
+
+int swfr_set_color_transform(swfr_renderer* r, uint32_t slot, const swfr_color_transform* ct) {
+    if (!r) return SWFR_ERR_INVALID;
+    if (slot > 65535) return fail(r, SWFR_ERR_INVALID, "colour transform slot out of range (0..65535)");
+    if (ct && !color_transform_valid(*ct)) return fail(r, SWFR_ERR_INVALID, "colour transform value outside the int16 range");
+    r->builder->set_color_transform(slot, ct);
+    return SWFR_OK;
+}
+
+int swfr_debug_time_cxform(swfr_renderer* r, uint32_t bitmap_id, const swfr_color_transform* ct, uint32_t reps, float* pass_ms, float* copy_ms) {
+    if (!r || !ct || !pass_ms || !copy_ms || reps == 0) return fail(r, SWFR_ERR_INVALID, "null argument");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    if (!color_transform_valid(*ct)) return fail(r, SWFR_ERR_INVALID, "colour transform value outside the int16 range");
+    return guarded(r, [&]() {
+        const auto bit = r->bitmaps.find(bitmap_id);
+        if (bit == r->bitmaps.end()) return fail(r, SWFR_ERR_NOT_FOUND, "BitmapNotFound");
+        DeviceBitmap& bm = bit->second;
+        const size_t n = size_t(bm.width) * bm.height, bytes = n * 4;
+        cx_straight_on(bm, r->stream);
+        uint32_t chain[256];
+        for (int c = 0; c < 256; ++c) {
+            uint32_t w = 0;
+            for (int k = 0; k < 4; ++k) w |= uint32_t(std::clamp(((c * ct->mult[k]) >> 8) + ct->add[k], 0, 255)) << (8 * k);
+            chain[c] = w;
+        }
+        uint32_t* out = nullptr;
+        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+        std::exception_ptr failure;
+        try {
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&out), bytes + CX_TABLE_BYTES));
+            HIP_CHECK(hipMemcpyAsync(out + n, chain, CX_TABLE_BYTES, hipMemcpyHostToDevice, r->stream));
+            HIP_CHECK(hipStreamSynchronize(r->stream));                                             // (`chain` is a local)
+            for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
+            launch_cxform_texels(r->stream, bm.d_straight, out, n, out + n);                       // (warm-up)
+            HIP_CHECK(hipMemcpyAsync(out, bm.d_straight, bytes, hipMemcpyDeviceToDevice, r->stream));
+            HIP_CHECK(hipEventRecord(e[0], r->stream));
+            for (uint32_t i = 0; i < reps; ++i) launch_cxform_texels(r->stream, bm.d_straight, out, n, out + n);
+            HIP_CHECK(hipEventRecord(e[1], r->stream));
+            for (uint32_t i = 0; i < reps; ++i) HIP_CHECK(hipMemcpyAsync(out, bm.d_straight, bytes, hipMemcpyDeviceToDevice, r->stream));
+            HIP_CHECK(hipEventRecord(e[2], r->stream));
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipEventSynchronize(e[2]));
+            HIP_CHECK(hipEventElapsedTime(pass_ms, e[0], e[1]));
+            HIP_CHECK(hipEventElapsedTime(copy_ms, e[1], e[2]));
+            *pass_ms /= float(reps);
+            *copy_ms /= float(reps);
+        } catch (...) {
+            failure = std::current_exception();
+        }
+        (void)hipStreamSynchronize(r->stream);
+        if (out) (void)hipFree(out);
+        for (auto& x : e) if (x) (void)hipEventDestroy(x);
+        if (failure) std::rethrow_exception(failure);
         return int(SWFR_OK);
     });
 }
@@ -1563,6 +1828,7 @@ int swfr_build_frame(swfr_renderer* r, const swfr_stage* stage, const swfr_edge*
 int swfr_upload_edges(swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
                       const swfr_style* styles, size_t n_styles) {
     if (!r || (n_edges && !edges) || (n_paths && !paths) || (n_styles && !styles)) return fail(r, SWFR_ERR_INVALID, "null argument");
+    ++r->cx_epoch;
     return guarded(r, [&]() { return upload(r, 0, true, edges, n_edges, paths, n_paths, styles, n_styles); });
 }
 
@@ -1581,6 +1847,7 @@ int swfr_render_edges(swfr_renderer* r, const swfr_edge* edges, size_t n_edges, 
 int swfr_render(swfr_renderer* r, const swfr_stage* stage) {
     if (!r || !stage) return fail(r, SWFR_ERR_INVALID, "null argument");
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    ++r->cx_epoch;
     return guarded(r, [&]() {
         using clk = std::chrono::steady_clock;
         auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -1662,6 +1929,7 @@ int swfr_render_sequence_readback(swfr_renderer* r, const swfr_stage* stages, ui
 int swfr_render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n_stages, void* device_dst, size_t frame_stride) {
     if (!r || (!stages && n_stages)) return fail(r, SWFR_ERR_INVALID, "null argument");
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    ++r->cx_epoch;
     return guarded(r, [&]() { return render_batch(r, stages, n_stages, device_dst, frame_stride); });
 }
 
