@@ -130,6 +130,9 @@ def test_goldens_regenerate_byte_for_byte():
     rnd = np.load(os.path.join(GOLD, "cairo_aliased_random.npz"))
     for s in list(G.RANDOM_SEEDS)[:8]:
         assert (G.cairo_aliased(G.random_scene(s)) == rnd["mixed_%d" % s]).all(), s
+    ext = np.load(os.path.join(GOLD, "cairo_aliased_extreme.npz"))
+    for k, sc in list(G.extreme_scenes().items())[::2]:
+        assert (G.cairo_aliased(sc) == ext[k]).all(), k
 
 
 # ---------------------------------------------------------------------------------------------------------- on the GPU

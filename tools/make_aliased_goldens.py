@@ -9,12 +9,15 @@ functions below (tests/test_aliased.py imports this module), so a golden file ho
   cairo_aliased_combs.npz        rows with 2 200 and 6 000 active edges of one path, both fill rules (key comb_<teeth>_<rule>)
   cairo_aliased_wide.npz         a frame wider than 8 192 px, a few rows tall (key wide_<k>)
   cairo_aliased_s1.npz           S1 at 4K: sha256 of the premultiplied frame (key sha256) and five 256 x 256 crops (key x_y)
+  cairo_aliased_extreme.npz      tests/helpers.extreme_scene frames, geometry at the +-2^23 limits, three per LARGE_MODES entry (key <mode>_<k>)
 
-usage: python tools/make_aliased_goldens.py [--check]    (--check: regenerate in memory and compare with the committed files)
+usage: python tools/make_aliased_goldens.py [--check] [--only NAME ...]    (--check: regenerate in memory and compare with the committed
+       files; --only: just the named files, e.g. --only cairo_aliased_extreme)
 """
 import hashlib
 import os
 import sys
+import zlib
 
 import numpy as np
 
@@ -149,14 +152,27 @@ def wide_scenes():
             for k, kids in enumerate(([wide], [wide, sliver, far]))}
 
 
+def extreme_scenes():
+    """three seeded extreme_scene frames of each LARGE_MODES entry, 64 x 48 and 333 x 97 in turn"""
+    from helpers import LARGE_MODES, extreme_scene
+    out = {}
+    for mode in LARGE_MODES:
+        rng = np.random.default_rng(zlib.crc32(("aliased golden " + mode).encode()) % 1000)
+        for k in range(3):
+            out["%s_%d" % (mode, k)] = extreme_scene(rng, *[(64, 48), (333, 97)][k % 2], mode)
+    return out
+
+
 def s1_image():
     pts, cols = synth.scene(**synth.S1)
     from swf_renderer_amd import api
     return cairo_aliased(dict(width=synth.S1["width"], height=synth.S1["height"], stage=api.stars_to_stage(pts, cols)))
 
 
-def generate():
-    """name -> {key: array} of every golden file"""
+def generate(only=None):
+    """name -> {key: array} of every golden file (of the named ones only)"""
+    if only:
+        return {name: _extreme() if name == "cairo_aliased_extreme" else generate()[name] for name in only}
     files = {}
     for name, sc in scenarios.scenarios().items():
         files["cairo_aliased_" + name] = {"rgba_premul": cairo_aliased(sc)}
@@ -170,14 +186,20 @@ def generate():
     for (x, y) in S1_CROPS:
         s1["%d_%d" % (x, y)] = img[y:y + 256, x:x + 256].copy()
     files["cairo_aliased_s1"] = s1
+    files["cairo_aliased_extreme"] = _extreme()
     return files
+
+
+def _extreme():
+    return {k: cairo_aliased(sc) for k, sc in extreme_scenes().items()}
 
 
 def main():
     assert cb.available(), "libcairo is required to generate goldens"
     check = "--check" in sys.argv
+    only = sys.argv[sys.argv.index("--only") + 1:] if "--only" in sys.argv else None
     bad = []
-    for name, arrays in generate().items():
+    for name, arrays in generate(only).items():
         path = os.path.join(OUT, name + ".npz")
         if check:
             old = np.load(path)
