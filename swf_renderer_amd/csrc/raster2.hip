@@ -1751,10 +1751,11 @@ void launch2_bin(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32
     const uint32_t g = max_bands + (mono ? 0u : (max_edges + BIN_THREADS - 1) / BIN_THREADS) + (max_paths + BIN_THREADS - 1) / BIN_THREADS + XCDS;
     hipLaunchKernelGGL(k2_bin_b, dim3(g, n_frames), dim3(BIN_THREADS), 0, st, frames, slow_kernels);
 }
-void launch2_rows(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_chunks, uint32_t max_path_edges, bool mono) {
+// wide: k2_rows_wide even when no path has more than ROWS_STAGE edges (the SWFR_ROWS_WIDE test knob)
+void launch2_rows(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_chunks, uint32_t max_path_edges, bool wide, bool mono) {
     if (!max_chunks) return;
     if (mono) { hipLaunchKernelGGL(k2_rows_mono_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames); return; }
-    if (max_path_edges > ROWS_STAGE) hipLaunchKernelGGL(k2_rows_wide_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames);
+    if (wide || max_path_edges > ROWS_STAGE) hipLaunchKernelGGL(k2_rows_wide_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames);
     else hipLaunchKernelGGL(k2_rows_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames);
 }
 void launch2_rows_slow(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t grid_slow, uint32_t grid_huge, uint32_t max_passes, bool mono) {

@@ -28,7 +28,7 @@
 
 namespace swfr {
 void launch2_bin(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, bool);
-void launch2_rows(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, bool);
+void launch2_rows(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, bool, bool);
 void launch2_rows_slow(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, bool);
 void launch2_tiles(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, int, uint32_t*);
 void launch_unpremultiply(hipStream_t, const uint32_t*, uint32_t*, size_t);
@@ -185,6 +185,7 @@ struct swfr_renderer {
         size_t n_incidences = 0, n_strips = 0, n_strip_slots = 0;   // (edge, pixel row) pairs: bounds the cells of a frame; k2_tiles wavefronts / launch list slots
         size_t n_slots = 0, cell_total = 0;
         uint32_t max_path_edges = 0;              // picks the row kernel's instance (edges staged in LDS per chunk)
+        bool rows_wide = false;                   // SWFR_ROWS_WIDE: k2_rows_wide whatever max_path_edges says
         Frame2 proto{};                           // the scene fields and sizes of a frame descriptor (per-frame buffers not filled in)
         Frame2* frames_dev = nullptr;            // one descriptor per frame set (contiguous, in the arena)
         uint32_t slow_passes = SLOW_PASSES;      // passes of the slow-row kernels the scene needs (known after a frame of a resident scene)
@@ -255,6 +256,8 @@ struct swfr_renderer {
     bool mono = false;                      // SWFR_FLAG_ANTIALIAS_NONE: boxes rounded to pixels, tor paths by k2_rows_mono (Frame2::mono)
     int fast_limit = 16;                    // rows with more active edges go to k2_rows_slow; the row kernel's instance caps it at its 8 or 16 slots (SWFR_FAST_LIMIT: test knob)
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
+    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded; test knob)
+    bool rows_wide = false;                 // SWFR_ROWS_WIDE=1: every frame with tor paths runs k2_rows_wide (test knob; aliased frames keep k2_rows_mono)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
     // the host builds one while the GPU works on the other
     struct BatchGroup {
@@ -632,6 +635,7 @@ struct SceneLayout {
     size_t n_chunks = 0, n_slots = 0, n_rows = 0, n_bands = 0, n_strips = 0, n_strip_slots = 0, incidences = 0, cell_main = 0, cell_total = 0;
     bool any_shader = false;
     uint32_t max_path_edges = 0;
+    bool rows_wide = false;     // the row kernel's wide instance although no path has more than ROWS_STAGE edges (SWFR_ROWS_WIDE)
     int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients: picks the tile kernel's instance
     std::vector<uint32_t> chunk_base, slot_base, inc_base, band_off;
     std::vector<uint32_t> band_span;     // per path: first tile-row | last tile-row << 16 of its rectangle (0xffff | 0 << 16: none); padded to a multiple of 16 paths
@@ -668,6 +672,9 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
         L.any_shader = L.any_shader || styles[i].kind != SWFR_STYLE_SOLID;
         L.shader_level = std::max(L.shader_level, styles[i].kind == SWFR_STYLE_SOLID ? 0 : (styles[i].kind == SWFR_STYLE_BITMAP ? 1 : 2));
     }
+    // (the test knobs: a higher instance than the frame needs -- with the style table in its full format -- and the wide row kernel)
+    L.shader_level = std::max(L.shader_level, r->tiles_shaders);
+    L.rows_wide = r->rows_wide;
     // exclusive prefixes over the paths (first chunk, first band slot) and over the tile-rows (band list offsets, by a difference
     // array over the paths' tile-row ranges)
     L.n_chunks = L.n_slots = L.n_rows = 0; L.max_path_edges = 0;
@@ -973,7 +980,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
     sc.n_edges = n_edges; sc.n_paths = n_paths; sc.n_styles = n_styles; sc.any_shader = L.any_shader; sc.shader_level = L.shader_level;
     sc.n_chunks = L.n_chunks; sc.chunk_rows = L.chunk_rows; sc.n_bands = L.n_bands; sc.n_rows = L.n_rows;
     sc.n_strips = L.n_strips; sc.n_strip_slots = L.n_strip_slots; sc.n_incidences = L.incidences;
-    sc.n_slots = L.n_slots; sc.cell_total = L.cell_total; sc.max_path_edges = L.max_path_edges;
+    sc.n_slots = L.n_slots; sc.cell_total = L.cell_total; sc.max_path_edges = L.max_path_edges; sc.rows_wide = L.rows_wide;
     SceneArena& A = sc.arena;
     A.begin(scene_arena_bytes(L, n_edges, n_paths, n_styles) + SceneArena::padded(4 * sizeof(Frame2)) + 4096);
     Frame2 proto;
@@ -1064,7 +1071,7 @@ void launch_frame(swfr_renderer* r, const swfr_renderer::Scene& sc, swfr_rendere
         if (e) HIP_CHECK(hipEventRecord(e[0], st));
         launch2_bin(st, fh, 1, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
         if (e) HIP_CHECK(hipEventRecord(e[1], st));
-        launch2_rows(st, fh, 1, uint32_t(sc.n_chunks), sc.max_path_edges, r->mono);
+        launch2_rows(st, fh, 1, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
         // the queued rows (coincident edges, crowded rows): skipped once a frame of this resident scene has shown there are none
         if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, 1, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes, r->mono);
         if (e) HIP_CHECK(hipEventRecord(e[2], st));
@@ -1209,7 +1216,7 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
             const hipStream_t st = r->fs[g * rb].stream;
             const Frame2* fh = sc.frames_dev + g * rb;
             launch2_bin(st, fh, cnt, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
-            launch2_rows(st, fh, cnt, uint32_t(sc.n_chunks), sc.max_path_edges, r->mono);
+            launch2_rows(st, fh, cnt, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
             if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, cnt, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes, r->mono);
             launch2_tiles(st, fh, cnt, uint32_t(sc.n_strip_slots), r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : ~0u, sc.shader_level, nullptr);
             last_set = g * rb + cnt - 1;
@@ -1341,6 +1348,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
         size_t max_e = 0, max_p = 0, max_bands = 0, max_chunks = 0, max_strips = 0;
         int shader_level = 0;
         uint32_t max_pe = 0;
+        bool rows_wide = false;
         auto t0 = clk::now();
         for (uint32_t k = 0; k < cnt; ++k) {
             FrameData& F = fd[k];
@@ -1367,6 +1375,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             max_chunks = std::max(max_chunks, L.n_chunks); max_strips = std::max(max_strips, L.n_strip_slots);
             shader_level = std::max(shader_level, L.shader_level);
             max_pe = std::max(max_pe, L.max_path_edges);
+            rows_wide = rows_wide || L.rows_wide;
         }
         t_build += ms_since(t0); t0 = clk::now();
         // ---- this group's previous use must be over before its staging and device buffers are rewritten
@@ -1418,7 +1427,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
         if (!G.ev_begin) { HIP_CHECK(hipEventCreate(&G.ev_begin)); HIP_CHECK(hipEventCreate(&G.ev_end)); }
         HIP_CHECK(hipEventRecord(G.ev_begin, G.stream));
         launch2_bin(G.stream, frames_dev, cnt, uint32_t(max_e), uint32_t(max_p), uint32_t(max_bands), 1u, r->mono);
-        launch2_rows(G.stream, frames_dev, cnt, uint32_t(max_chunks), max_pe, r->mono);
+        launch2_rows(G.stream, frames_dev, cnt, uint32_t(max_chunks), max_pe, rows_wide, r->mono);
         if (max_chunks) launch2_rows_slow(G.stream, frames_dev, cnt, 256u, 64u, SLOW_PASSES, r->mono);
         launch2_tiles(G.stream, frames_dev, cnt, uint32_t(max_strips), ~0u, shader_level, nullptr);
         HIP_CHECK(hipEventRecord(G.ev_end, G.stream));
@@ -1494,7 +1503,7 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     if (!r->rb_ev[0]) { HIP_CHECK(hipEventCreate(&r->rb_ev[0])); HIP_CHECK(hipEventCreate(&r->rb_ev[1])); }
     auto one_launch = [&]() {
         launch2_bin(st, r->rb_frames.ptr, B, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
-        launch2_rows(st, r->rb_frames.ptr, B, uint32_t(sc.n_chunks), sc.max_path_edges, r->mono);
+        launch2_rows(st, r->rb_frames.ptr, B, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
         if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, r->rb_frames.ptr, B, 256u, sc.slow_state == 2 ? 0u : 64u, sc.slow_passes, r->mono);
         launch2_tiles(st, r->rb_frames.ptr, B, uint32_t(sc.n_strip_slots), ~0u, sc.shader_level, nullptr);
     };
@@ -1625,6 +1634,8 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
+    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 2);
+    if (const char* rw = std::getenv("SWFR_ROWS_WIDE")) r->rows_wide = std::atoi(rw) != 0;
     if (const char* bf = std::getenv("SWFR_BATCH_FRAMES")) r->batch_frames = std::max(1, std::atoi(bf));
     if (const char* cr = std::getenv("SWFR_CHUNK_ROWS")) r->force_chunk_rows = std::atoi(cr);
     if (const char* so = std::getenv("SWFR_STRIP_ORDER")) r->strip_order = std::atoi(so);

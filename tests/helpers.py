@@ -342,6 +342,14 @@ def rand_long_scene(rng):
     return dict(width=W, height=H, even_odd=bool(rng.integers(0, 2)), stage={"children": kids})
 
 
+# scenes of the soak whose tied edges once came out wrong (tests/test_gpu_parity.py::test_soak_regressions_tied_edges)
+SOAK_TIE_CASES = [("radial", 1000, 940), ("mixed", 1000, 445), ("mixed", 1000, 607), ("mixed", 1000, 688), ("bitmap", 1000, 820),
+                  ("mixed", 2000, 755), ("mixed", 2000, 1130), ("mixed", 2000, 1265), ("mixed", 4000, 241), ("mixed", 4000, 1424),
+                  ("mixed", 5000, 507), ("radial", 7000, 670), ("bitmap", 7000, 816), ("mixed", 7000, 101), ("mixed", 7000, 388),
+                  ("mixed", 8000, 995), ("mixed", 8000, 1018), ("mixed", 23000, 196), ("big", 300, 146), ("big", 300, 9), ("big", 5000, 854),
+                  ("long", 300, 171), ("mixed", 777777, 722)]
+
+
 def soak_scene(name, seed, index):
     """Scene `index` of generator `name` in tools/soak.py's numbering (the generators are seeded per name)."""
     gens = {"mixed": rand_mixed_scene, "bitmap": rand_bitmap_scene, "radial": rand_radial_scene, "big": rand_big_scene, "long": rand_long_scene}
@@ -454,3 +462,406 @@ def extreme_scene(rng, W, H, mode, kinds=("fill", "curve", "stroke", "rect_strok
             tag = _fine_shape([(x0, y0), (x1, y0), (x1, y1), (x0, y1)], None, None, line=col, line_width_px=float(rng.choice([1.0, 2.5, 20.0, 164.0])))
         kids.append({"type": "shape", "definition": tag, "matrix": fine})
     return dict(width=W, height=H, even_odd=bool(rng.integers(0, 2)), stage={"children": kids})
+
+
+# ---- scene builders shared by the GPU parity tests and tests/test_gpu_instances.py (the same frames under every kernel instance)
+def oracle_polys(fx, cols, W, H, even_odd=False):
+    """The oracle's frame of polygons given in 24.8 fixed point (synth.scene / synth.twips_to_fixed) with straight RGBA colours."""
+    L = ob.lib()
+    ctx = L.swfo_create(W, H)
+    argb = ((cols[:, 3].astype(np.uint32) << 24) | (cols[:, 0].astype(np.uint32) << 16) |
+            (cols[:, 1].astype(np.uint32) << 8) | cols[:, 2]).astype(np.uint32)
+    counts = np.full(len(fx), fx.shape[1], dtype=np.int32)
+    xy = np.ascontiguousarray(fx.reshape(-1))
+    L.swfo_fill_polygons_fixed(ctx, xy.ctypes.data, counts.ctypes.data, argb.ctypes.data, len(fx), 1 if even_odd else 0)
+    px = np.ctypeslib.as_array(L.swfo_pixels(ctx), shape=(H, W)).copy()
+    L.swfo_destroy(ctx)
+    return np.stack([(px >> 16) & 255, (px >> 8) & 255, px & 255, px >> 24], -1).astype(np.uint8)
+
+
+def synth_scene(cfg):
+    """(W, H, fixed-point polygons, colours, (edges, paths, styles)) of a swf_renderer_amd.synth configuration (S1, S2, ...)."""
+    from swf_renderer_amd import api, synth
+    pts, cols = synth.scene(**cfg)
+    W, H = cfg["width"], cfg["height"]
+    fx = synth.twips_to_fixed(pts)
+    return W, H, fx, cols, api.polygons_to_scene(fx, cols, W, H)
+
+
+TWENTY_THOUSAND_PATHS = dict(seed=77, n_shapes=20000, width=640, height=48, rmin=2.0, rmax=9.0)
+
+
+def rand_polygon_scene(rng, it):
+    """One frame of the polygon fuzz: a random polygon (mode it % 4: uniform, quarter-pixel ties, pixel corners, leaving the frame),
+    either fill rule.  Returns (scene, (mode, even_odd, points))."""
+    import scenarios
+    W, H = int(rng.integers(16, 200)), int(rng.integers(16, 120))
+    n = int(rng.integers(3, 9))
+    mode = it % 4
+    if mode == 0:
+        pts = rng.uniform(0, 1, (n, 2)) * [W, H]
+    elif mode == 1:
+        pts = rng.integers(0, 4 * min(W, H), (n, 2)) / 4.0          # tie-heavy quarter pixels
+    elif mode == 2:
+        pts = rng.integers(0, min(W, H), (n, 2)).astype(float)      # vertices on pixel corners
+    else:
+        pts = rng.uniform(-30, 30 + max(W, H), (n, 2))              # leaves the frame
+    eo = bool(rng.integers(0, 2))
+    col = scenarios._rgba(int(rng.integers(0, 256)), 9, 200, int(rng.choice([255, 255, 120])))
+    tag = scenarios._poly_shape(np.rint(pts * 20), {"type": "solid", "color": col})
+    return dict(width=W, height=H, even_odd=eo, stage={"children": [{"type": "shape", "definition": tag}]}), (mode, eo, pts.tolist())
+
+
+def rand_layered_translucent_scene(rng):
+    """2-6 random polygons of alpha 255 ... 1 over each other in a 150x90 frame."""
+    import scenarios
+    W, H = 150, 90
+    kids = []
+    for _ in range(int(rng.integers(2, 7))):
+        n = int(rng.integers(3, 8))
+        pts = rng.uniform(-10, 1, (n, 2)) * 0 + rng.uniform(0, 1, (n, 2)) * [W, H]
+        col = scenarios._rgba(*[int(v) for v in rng.integers(0, 256, 3)], int(rng.choice([255, 200, 128, 31, 1])))
+        kids.append({"type": "shape", "definition": scenarios._poly_shape(np.rint(pts * 20), {"type": "solid", "color": col})})
+    return dict(width=W, height=H, stage={"children": kids})
+
+
+def rand_stroked_scene(rng):
+    """1-3 random stroked (morph) shapes in a 120x100 frame: curves, rectilinear box strokes, round caps / joins, hairlines,
+    reflected and off-frame placements."""
+    import scenarios
+    from test_host import _rand_path_shape
+    W, H = 120, 100
+    kids = []
+    for _ in range(int(rng.integers(1, 4))):
+        morph = bool(rng.integers(0, 3) == 0)
+        tag = _rand_path_shape(rng, int(rng.choice([1, 2, 5, 20, 45, 90, 200])), morph)
+        sx, sy = float(rng.choice([1, 1, 0.6, 1.7, -1])), float(rng.choice([1, 1, 0.8, 1.3]))
+        mat = scenarios._m(sx, sy, int(rng.integers(-300, 900)) + (2000 if sx < 0 else 0), int(rng.integers(-300, 500)),
+                           float(rng.choice([0, 0, 0.2])), float(rng.choice([0, 0, -0.15])))
+        kids.append({"type": "morph-shape", "definition": tag, "ratio": float(rng.uniform(0, 1)), "matrix": mat} if morph else
+                    {"type": "shape", "definition": tag, "matrix": mat})
+    return dict(width=W, height=H, stage={"children": kids})
+
+
+def comb_shape(teeth, width_twips):
+    """One path of `teeth` narrow teeth over a bar: 2 * teeth edges active in most rows."""
+    import scenarios
+    pts = []
+    step = width_twips / teeth
+    for k in range(teeth):
+        pts += [(100 + step * k, 100), (100 + step * k + step / 2, 1900)]
+    pts += [(100 + width_twips + 100, 1950), (50, 1950)]
+    return scenarios._poly_shape(pts, {"type": "solid", "color": scenarios._rgba(1, 2, 3)})
+
+
+def crowded_rows_scene(teeth, even_odd):
+    """The frame of test_crowded_rows_vs_oracle: a comb of `teeth` teeth (24 ... 6000 active edges per row)."""
+    tag = comb_shape(teeth, 2000 if teeth <= 140 else 6000)
+    return dict(width=120 if teeth <= 140 else 320, height=100, even_odd=even_odd, stage={"children": [{"type": "shape", "definition": tag}]})
+
+
+def comb_points(teeth, width_twips, x0, y_top, y_bottom):
+    pts = []
+    step = width_twips / teeth
+    for k in range(teeth):
+        pts += [(x0 + step * k, y_top), (x0 + step * k + step / 2, y_bottom)]
+    pts += [(x0 + width_twips + 100, y_bottom + 50), (x0 - 50, y_bottom + 50)]
+    return pts
+
+
+def frame_top_scene(teeth, y_top, even_odd):
+    """The frame of test_edges_arriving_together_at_the_frame_top_vs_oracle: 2 * teeth edges of one translucent path that become
+    active together at sample row 0 (the frame's top edge clips them)."""
+    import scenarios
+    tag = scenarios._poly_shape(comb_points(teeth, 2200, 60, y_top, 1700), {"type": "solid", "color": scenarios._rgba(200, 30, 90, 180)})
+    return dict(width=128, height=96, even_odd=even_odd, stage={"children": [{"type": "shape", "definition": tag}]})
+
+
+def uncovered_path_row_scenes():
+    """The frames of test_tile_with_an_uncovered_path_row_is_not_a_full_cover: a triangle whose last pixel row has no active sample
+    row, opaque and translucent, at three bottoms; then the two soak scenes that found it.  [(key, scene)]"""
+    import scenarios
+    out = []
+    for sy in (1.0001, 1.0, 1.002):                                  # bottom at y = 242.026 (the case), 242.0, 242.48
+        pts = np.array([(9.75, 213.40), (350.65, 242.0), (155.5, 242.0)])
+        for col in (scenarios._rgba(200, 80, 40, 255), scenarios._rgba(200, 80, 40, 140)):
+            tag = scenarios._poly_shape(np.rint(pts * 20), {"type": "solid", "color": col})
+            out.append(((sy, col["a"]), dict(width=512, height=300, stage={"children": [{"type": "shape", "definition": tag, "matrix": scenarios._m(1.0, sy)}]})))
+    for case in (("big", 200, 551), ("big", 200, 572)):
+        out.append((case, soak_scene(*case)))
+    return out
+
+
+def wide_frame_parts():
+    """Shapes of test_frames_wider_than_a_cell_column_field (a 9600x48 frame): a translucent triangle beyond column 9000 (`far`), an
+    opaque one near the left (`near`), a solid path wider than 8192 px opaque and translucent (`wide`, `wide_t`), a shallow sliver
+    crossing a block boundary inside an anti-aliased span, and the wide path with a radial gradient (`wide_grad`)."""
+    import scenarios
+    far = scenarios._poly_shape([(9000 * 20 + 7, 100), (9500 * 20 + 3, 300), (9200 * 20, 900)], {"type": "solid", "color": scenarios._rgba(200, 100, 50, 160)})
+    near = scenarios._poly_shape([(50, 60), (4000, 130), (900, 880)], {"type": "solid", "color": scenarios._rgba(20, 200, 50)})
+    pts = [(100, 100), (9400 * 20, 200), (9400 * 20, 700), (100, 600), (3000 * 20, 350)]
+    wide = scenarios._poly_shape(pts, {"type": "solid", "color": scenarios._rgba(1, 2, 3)})
+    wide_t = scenarios._poly_shape(pts, {"type": "solid", "color": scenarios._rgba(200, 30, 90, 140)})
+    # a shallow edge crossing column 5 + 8192 (the block boundary of a path that starts at x = 5) inside an anti-aliased span
+    sliver = scenarios._poly_shape([(100, 400), (9590 * 20, 470), (9590 * 20, 520), (100, 430)], {"type": "solid", "color": scenarios._rgba(10, 90, 250, 200)})
+    grad = {"type": "radial-gradient", "matrix": scenarios._m(4.0, 0.02, 4800 * 20, 400),
+            "gradient": scenarios._grad([(0, (255, 0, 0)), (128, (0, 255, 0, 90)), (255, (0, 0, 255))])}
+    return dict(far=far, near=near, wide=wide, wide_t=wide_t, sliver=sliver, wide_grad=scenarios._poly_shape(pts, grad))
+
+
+WIDE_FRAME = (9600, 48)
+
+
+def wide_frame_scenes():
+    """Every frame of test_frames_wider_than_a_cell_column_field: {key: scene}."""
+    w, h = WIDE_FRAME
+    p = wide_frame_parts()
+    combos = {"near_far": ["near", "far"], "wide": ["wide"], "near_wide_t_far": ["near", "wide_t", "far"],
+              "wide_sliver_wide_t": ["wide", "sliver", "wide_t"], "wide_sliver": ["wide", "sliver"], "near_wide_grad": ["near", "wide_grad"]}
+    return {k: dict(width=w, height=h, stage={"children": [{"type": "shape", "definition": p[n]} for n in v]}) for k, v in combos.items()}
+
+
+# ---- raw edge lists (Renderer.render_edges / the oracle's swfo_fill_edges)
+RAW_LIMIT = 1 << 23                     # +-32768 px in 24.8
+
+
+def random_raw_pair(rng, W, H):
+    """Two random lines anywhere in +-2^23 active over the same [top, bottom) with opposite directions (the edges active in a row
+    then balance, as the edges of a closed polygon do): top / bottom inside both lines, now and then strictly inside them; half of
+    the lines have an end point near the frame.  Now and then both are never active (top == bottom)."""
+    L = RAW_LIMIT
+    top, bottom = sorted(int(v) for v in rng.integers(-L, L + 1, 2))
+    if rng.integers(0, 2):
+        top, bottom = sorted(int(v) for v in rng.integers(-2 * H * 256, 3 * H * 256, 2))
+    if top == bottom:
+        bottom += 1
+    out = []
+    for d in (1, -1):
+        y1 = top if rng.integers(0, 2) else int(rng.integers(-L, top + 1))
+        y2 = bottom if rng.integers(0, 2) else int(rng.integers(bottom, L + 1))
+        near = rng.integers(0, 2)
+        x1 = int(rng.integers(-2 * W * 256, 3 * W * 256)) if near else int(rng.integers(-L, L + 1))
+        x2 = int(rng.integers(-L, L + 1))
+        out.append((x1, y1, x2, y2, top, bottom, d))
+    if rng.integers(0, 6) == 0:                       # never active, both
+        out = [(x1, y1, x2, y2, t, t, d) for x1, y1, x2, y2, t, b, d in out]
+    return out
+
+
+def rand_raw_frame(rng, it):
+    """One frame of the raw-edge fuzz: (W, H, groups), 1-3 paths of random edge pairs, both fill rules, opaque and translucent."""
+    W, H = [(64, 48), (333, 97), (97, 333)][it % 3]
+    groups = []
+    for _ in range(int(rng.integers(1, 4))):
+        edges = []
+        for _ in range(int(rng.integers(1, 12))):
+            edges += random_raw_pair(rng, W, H)
+        argb = int(rng.choice([0xff000000 | int(rng.integers(0, 1 << 24)), 0x80402010, 0x20101000]))
+        groups.append((edges, bool(rng.integers(0, 2)), argb))
+    return W, H, groups
+
+
+def raw_scene(W, H, groups):
+    """groups: [(edge rows (x1, y1, x2, y2, top, bottom, dir), even_odd, premultiplied ARGB)], one path each with the frame as its
+    rectangle, painted in order.  Returns (edges, paths, styles) for Renderer.render_edges."""
+    from swf_renderer_amd import api
+    rows, paths, styles = [], np.zeros(len(groups), api.PATH_DTYPE), []
+    clear = True
+    for i, (edges, eo, argb) in enumerate(groups):
+        e = np.zeros(len(edges), api.EDGE_DTYPE)
+        for k, name in enumerate(("x1", "y1", "x2", "y2", "top", "bottom", "dir")):
+            e[name] = [r[k] for r in edges]
+        e["reserved"] = i
+        paths[i] = (sum(len(r) for r in rows), len(e), api.PATH_TOR, int(eo), i, int((argb >> 24) == 255 or clear), 0, 0, W, H)
+        rows.append(e)
+        styles.append(api.solid_style(argb))
+        clear = False
+    return np.concatenate(rows), paths, styles
+
+
+def raw_oracle(W, H, groups):
+    """The oracle's frame of raw_scene(W, H, groups)."""
+    edges, _, _ = raw_scene(W, H, groups)
+    be = ob.OracleBackend(W, H)
+    at = 0
+    for edge_rows, eo, argb in groups:
+        be.fill_edges(edges[at:at + len(edge_rows)], (0, 0, W, H), eo, argb)
+        at += len(edge_rows)
+    want = be.premultiplied_rgba()
+    be.close()
+    return want
+
+
+def raw_product(W, H, groups):
+    import swf_renderer_amd as S
+    r = S.Renderer(W, H)
+    try:
+        r.render_edges(*raw_scene(W, H, groups))
+        return r.read_image(premultiplied=True)
+    finally:
+        r.close()
+
+
+# ---- dense mixed-fill frames: every kind of path and style layered deep enough that the strips of the shaded tile instances see
+#      dozens of entries (staging rounds, the StripTop cull, cell fetches beyond 16 per row, box paths, the compacted edge-pixel blend)
+def _dense_gradient(rng, W, H, kind):
+    import scenarios
+    n = int(rng.integers(1, 9))
+    ratios = sorted(int(v) for v in rng.integers(0, 256, n))
+    if n > 2 and rng.integers(0, 3) == 0:
+        ratios[1] = ratios[0]
+    colors = [(ratios[i], (int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.choice([255, 255, 128, 0, 37]))))
+              for i in range(n)]
+    # the gradient circle is at least 0.6 frame diagonals wide and centred in the frame: every sample stays within two radii
+    ky = float(rng.uniform(0.5, 1.0))
+    sc = float(rng.uniform(0.6, 3.0)) * 20 / 16384 * float(np.hypot(W, H)) / ky
+    t = float(rng.uniform(-3.2, 3.2))
+    c, sn = np.cos(t), np.sin(t)
+    fill = {"type": kind, "gradient": scenarios._grad(colors),
+            "matrix": scenarios._m(sc * c, sc * ky * c, int(rng.integers(0, W * 20)), int(rng.integers(0, H * 20)), sc * sn, -sc * ky * sn)}
+    if kind == "focal-gradient":
+        fill["focal_point"] = {"epsilons": int(rng.integers(-240, 241))}
+    return fill
+
+
+def _dense_bitmap(rng, W, H, bitmap_id, magnified):
+    import scenarios
+    k = float(rng.uniform(1.6, 9.0)) if magnified else float(rng.uniform(0.15, 0.7))
+    t = float(rng.uniform(-3.2, 3.2)) if rng.integers(0, 2) else 0.0
+    c, sn = np.cos(t), np.sin(t)
+    return {"type": "bitmap", "bitmap_id": bitmap_id, "repeating": bool(rng.integers(0, 2)), "smoothed": True,
+            "matrix": scenarios._m(20 * k * c, 20 * k * c, int(rng.integers(-200, W * 20)), int(rng.integers(-200, H * 20)), 20 * k * sn, -20 * k * sn)}
+
+
+DENSE_KINDS = ("solid", "rect_fill", "rect_stroke", "bitmap_mag", "bitmap_min", "radial", "focal", "stroke", "linear")
+
+
+def rand_dense_scene(rng, linear=False, width=None, height=None, shapes=None):
+    """One frame of many layered shapes of every kind -- opaque and translucent solids (alpha 1 ... 254), rectilinear fills and strokes
+    (box paths), repeating and clamped bitmap fills magnified (bilinear, also across the texture's border) and minified (convolution),
+    radial and focal gradients, strokes of polygons -- with opaque covers of the whole frame in the middle of the stack (the StripTop
+    cull), a translucent first shape on the clear surface (the lerp route), a width that is not a multiple of 64 and a tile-row count
+    that is not a multiple of 8.  linear=True adds ONE shape with a linear gradient (the +-1 LSB extension: two of them overlapping
+    could differ by 2)."""
+    import scenarios
+    if width is None:
+        W = int(rng.integers(2, 5)) * 64 + int(rng.integers(1, 64))
+    else:
+        W = width
+    if height is None:
+        tile_rows = int(rng.choice([3, 4, 5, 6, 7]))
+        H = (tile_rows - 1) * 16 + int(rng.integers(1, 17))
+    else:
+        H = height
+    bitmaps = [make_bitmap_tag(3, int(rng.integers(2, 12)), int(rng.integers(2, 12)), rng),
+               make_bitmap_tag(4, int(rng.integers(24, 64)), int(rng.integers(24, 64)), rng)]
+    kinds = [k for k in DENSE_KINDS if k != "linear"]
+    n = shapes if shapes is not None else int(rng.integers(45, 70))
+    cover_at = sorted(int(v) for v in rng.choice(np.arange(n // 3, 2 * n // 3), 2, replace=False))
+    linear_at = int(rng.integers(cover_at[1] + 1, n)) if linear else -1
+    kids = []
+
+    def shape(tag, mat=None):
+        kids.append({"type": "shape", "definition": tag} if mat is None else {"type": "shape", "definition": tag, "matrix": mat})
+
+    def polygon(big):
+        m = int(rng.integers(3, 8))
+        if big:
+            return rng.uniform(-0.15, 1.15, (m, 2)) * [W, H]
+        cx, cy, r = rng.uniform(0, W), rng.uniform(0, H), rng.uniform(6, 0.5 * max(W, H))
+        a = np.sort(rng.uniform(0, 2 * np.pi, m))
+        return np.stack([cx + r * np.cos(a), cy + r * rng.uniform(0.3, 1.0) * np.sin(a)], -1)
+
+    def color(alpha=None):
+        a = alpha if alpha is not None else int(rng.choice([255, 255, int(rng.integers(1, 255)), int(rng.integers(1, 255)), 1, 254]))
+        return scenarios._rgba(*[int(v) for v in rng.integers(0, 256, 3)], a)
+
+    # the first shape lands on the clear surface: translucent (SOURCE-lerp)
+    shape(scenarios._poly_shape(np.rint(polygon(True) * 20), {"type": "solid", "color": color(int(rng.integers(1, 255)))}))
+    for i in range(n):
+        if i in cover_at:
+            # an opaque cover of the whole frame: a rectangle (box path) or a polygon reaching past every side (tor path)
+            if i == cover_at[0]:
+                pts = np.array([(-1.5, -2.25), (W + 3.0, -2.25), (W + 3.0, H + 1.75), (-1.5, H + 1.75)])
+            else:
+                pts = np.array([(-0.4 * W, -0.3 * H), (1.7 * W, -0.2 * H), (0.5 * W, 2.2 * H)])
+            shape(scenarios._poly_shape(np.rint(pts * 20), {"type": "solid", "color": color(255)}))
+            continue
+        kind = "linear" if i == linear_at else kinds[int(rng.integers(0, len(kinds)))]
+        big = bool(rng.integers(0, 3))
+        if kind == "solid":
+            shape(scenarios._poly_shape(np.rint(polygon(big) * 20), {"type": "solid", "color": color()}))
+        elif kind in ("rect_fill", "rect_stroke"):
+            x0, y0 = rng.uniform(-0.1 * W, 0.8 * W), rng.uniform(-0.1 * H, 0.8 * H)
+            x1, y1 = x0 + rng.uniform(2, W), y0 + rng.uniform(2, H)
+            q = (lambda v: float(np.round(v))) if rng.integers(0, 2) else (lambda v: float(v))       # on pixel edges or anywhere
+            pts = np.array([(q(x0), q(y0)), (q(x1), q(y0)), (q(x1), q(y1)), (q(x0), q(y1))])
+            mat = scenarios._m(float(rng.choice([1, 1, 0.75, 1.5])), float(rng.choice([1, 1, 1.25])))
+            if kind == "rect_fill":
+                shape(scenarios._poly_shape(np.rint(pts / [mat["scale_x"] / 65536, mat["scale_y"] / 65536] * 20), {"type": "solid", "color": color()}), mat)
+            else:
+                shape(scenarios._poly_shape(np.rint(pts * 20), None, line=color(), line_width=int(rng.choice([20, 30, 50, 90, 170]))))
+        elif kind in ("bitmap_mag", "bitmap_min"):
+            mag = kind == "bitmap_mag"
+            fill = _dense_bitmap(rng, W, H, 3 if mag else 4, mag)
+            shape(scenarios._poly_shape(np.rint(polygon(big) * 20), fill))
+        elif kind in ("radial", "focal", "linear"):
+            fill = _dense_gradient(rng, W, H, {"radial": "radial-gradient", "focal": "focal-gradient", "linear": "linear-gradient"}[kind])
+            shape(scenarios._poly_shape(np.rint(polygon(big) * 20), fill))
+        else:                                   # a stroked polygon, sometimes filled too (two paths)
+            fill = {"type": "solid", "color": color()} if rng.integers(0, 2) else None
+            shape(scenarios._poly_shape(np.rint(polygon(big) * 20), fill, line=color(), line_width=int(rng.choice([10, 25, 60, 140]))))
+    return dict(width=W, height=H, bitmaps=bitmaps, stage={"children": kids})
+
+
+def strip_path_counts(width, height, paths):
+    """Paths whose pixel rectangle meets each 64x8 strip of a frame: an int array of (tile-rows * 2, tile columns)."""
+    sw, sh = (width + 63) // 64, (height + 7) // 8
+    cnt = np.zeros((sh, sw), int)
+    for p in paths:
+        if p["x_max"] <= p["x_min"] or p["y_max"] <= p["y_min"]:
+            continue
+        cnt[p["y_min"] // 8:(p["y_max"] - 1) // 8 + 1, p["x_min"] // 64:(p["x_max"] - 1) // 64 + 1] += 1
+    return cnt
+
+
+# ---- gradient edges: focal points on and beyond the circle (|focal| >= 1: the a == 0 branch of the walker, cones with transparent
+#      regions), and 1, 2 and SWFR_MAX_STOPS stops
+GRADIENT_EDGE_FOCALS = (256, -256, 257, -257, 384, -384, 1024, -1024, 32767, -32768)     # Sfixed8P8 epsilons: +-1, +-1.004, ..., 128, -128
+
+
+def gradient_edge_stops(n, rng):
+    """n stops with translucent colours; from 4 stops on, duplicate ratios (a hard step) and a transparent stop."""
+    ratios = sorted(int(v) for v in rng.integers(0, 256, n))
+    if n >= 4:
+        ratios[2] = ratios[1]
+        ratios[-1] = ratios[-2]
+    alphas = [255, 128, 37, 0, 200, 255]
+    return [(ratios[i], (int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 256)), alphas[(i * 5 + n) % len(alphas)])) for i in range(n)]
+
+
+def gradient_edge_scenes():
+    """{key: scene}: a focal gradient for every epsilon of GRADIENT_EDGE_FOCALS with 1, 2 and 16 stops, on a clear frame and over an
+    opaque backdrop, plus a radial gradient with 16 stops.  The gradient circle is centred in the frame and at least as large as the
+    frame's diagonal, and the shape lies inside the frame: every sample stays within one radius of the centre (pixman's 16.16 range
+    is never left)."""
+    import scenarios
+    W, H = 90, 70
+    out = {}
+    rng = np.random.default_rng(1616)
+    back = scenarios._poly_shape([(-100, -60), (W * 20 + 80, 40), (W * 20 + 40, H * 20 + 90), (60, H * 20 + 50)], {"type": "solid", "color": scenarios._rgba(30, 90, 160)})
+    shape_pts = np.array(scenarios._circleish(W * 10, H * 10, 0.46 * H * 20, 20)) * [W / H, 1.0] + [-(W / H - 1) * W * 10, 0]
+    cases = [(f, n) for f in GRADIENT_EDGE_FOCALS for n in (1, 2, 16)] + [(None, 16)]
+    for i, (focal, n) in enumerate(cases):
+        r = float(np.hypot(W, H)) * (1.0 + 0.15 * (i % 3))              # radius in pixels
+        sc = r * 20 / 16384
+        t = 0.37 * i
+        c, sn = np.cos(t), np.sin(t)
+        fill = {"type": "radial-gradient" if focal is None else "focal-gradient", "gradient": scenarios._grad(gradient_edge_stops(n, rng)),
+                "matrix": scenarios._m(sc * c, sc * c, W * 10 + i % 5, H * 10 - i % 7, sc * sn, -sc * sn)}
+        if focal is not None:
+            fill["focal_point"] = {"epsilons": focal}
+        for backdrop in (False, True):
+            kids = ([{"type": "shape", "definition": back}] if backdrop else []) + [{"type": "shape", "definition": scenarios._poly_shape(np.rint(shape_pts), fill)}]
+            out["%s_%d_%s" % ("radial" if focal is None else "focal%d" % focal, n, "over" if backdrop else "clear")] = dict(width=W, height=H, stage={"children": kids})
+    return out

@@ -20,7 +20,8 @@ import numpy as np
 import pytest
 
 import scenarios
-from helpers import LARGE_MODES, diff_stats, extreme_scene, oracle_render, product_render
+from helpers import LARGE_MODES, diff_stats, extreme_scene, oracle_render, product_render, rand_raw_frame, raw_oracle, raw_product
+from helpers import random_raw_pair as _random_pair  # noqa: F401  (tests/test_mono_gpu.py draws its raw edges with it)
 from oracle import oracle_backend as ob
 
 pytestmark = pytest.mark.gpu
@@ -87,30 +88,7 @@ def test_rectilinear_stroke_near_the_limit_renders():
 def _render_raw(W, H, groups):
     """groups: [(edge rows (x1, y1, x2, y2, top, bottom, dir), even_odd, premultiplied ARGB)], one path each with the frame as its
     rectangle.  Returns (HIP image, oracle image)."""
-    import swf_renderer_amd as S
-    from swf_renderer_amd import api
-    rows, paths, styles = [], np.zeros(len(groups), api.PATH_DTYPE), []
-    be = ob.OracleBackend(W, H)
-    clear = True
-    for i, (edges, eo, argb) in enumerate(groups):
-        e = np.zeros(len(edges), api.EDGE_DTYPE)
-        for k, name in enumerate(("x1", "y1", "x2", "y2", "top", "bottom", "dir")):
-            e[name] = [r[k] for r in edges]
-        e["reserved"] = i
-        paths[i] = (sum(len(r) for r in rows), len(e), api.PATH_TOR, int(eo), i, int((argb >> 24) == 255 or clear), 0, 0, W, H)
-        rows.append(e)
-        styles.append(api.solid_style(argb))
-        be.fill_edges(e, (0, 0, W, H), eo, argb)
-        clear = False
-    want = be.premultiplied_rgba()
-    be.close()
-    r = S.Renderer(W, H)
-    try:
-        r.render_edges(np.concatenate(rows), paths, styles)
-        got = r.read_image(premultiplied=True)
-    finally:
-        r.close()
-    return got, want
+    return raw_product(W, H, groups), raw_oracle(W, H, groups)
 
 
 FLAT_S = 14 + 15 * 10                         # sample rows s = 14 (mod 15) are centred 7/15 of a unit below an integer y (24.8)
@@ -196,28 +174,6 @@ def test_raw_edges_at_the_limits(name, env, monkeypatch):
             assert row[x - 2] != row[x + 2], (name, row)
 
 
-def _random_pair(rng, W, H):
-    """Two random lines anywhere in +-2^23 active over the same [top, bottom) with opposite directions (the edges active in a row
-    then balance, as the edges of a closed polygon do): top / bottom inside both lines, now and then strictly inside them; half of
-    the lines have an end point near the frame.  Now and then both are never active (top == bottom)."""
-    top, bottom = sorted(int(v) for v in rng.integers(-L, L + 1, 2))
-    if rng.integers(0, 2):
-        top, bottom = sorted(int(v) for v in rng.integers(-2 * H * 256, 3 * H * 256, 2))
-    if top == bottom:
-        bottom += 1
-    out = []
-    for d in (1, -1):
-        y1 = top if rng.integers(0, 2) else int(rng.integers(-L, top + 1))
-        y2 = bottom if rng.integers(0, 2) else int(rng.integers(bottom, L + 1))
-        near = rng.integers(0, 2)
-        x1 = int(rng.integers(-2 * W * 256, 3 * W * 256)) if near else int(rng.integers(-L, L + 1))
-        x2 = int(rng.integers(-L, L + 1))
-        out.append((x1, y1, x2, y2, top, bottom, d))
-    if rng.integers(0, 6) == 0:                       # never active, both
-        out = [(x1, y1, x2, y2, t, t, d) for x1, y1, x2, y2, t, b, d in out]
-    return out
-
-
 @pytest.mark.parametrize("env", ROUTES, ids=ROUTE_IDS)
 def test_random_raw_edges_anywhere_in_the_range(env, monkeypatch):
     """Seeded fuzz of raw edge lists that meet the validation rule (y1 < y2, y1 <= top < bottom <= y2, or never active) with end
@@ -226,14 +182,7 @@ def test_random_raw_edges_anywhere_in_the_range(env, monkeypatch):
     rng = np.random.default_rng(2 ** 23)
     partial = 0
     for it in range(20 if EMU else 40):
-        W, H = [(64, 48), (333, 97), (97, 333)][it % 3]
-        groups = []
-        for _ in range(int(rng.integers(1, 4))):
-            edges = []
-            for _ in range(int(rng.integers(1, 12))):
-                edges += _random_pair(rng, W, H)
-            argb = int(rng.choice([0xff000000 | int(rng.integers(0, 1 << 24)), 0x80402010, 0x20101000]))
-            groups.append((edges, bool(rng.integers(0, 2)), argb))
+        W, H, groups = rand_raw_frame(rng, it)
         got, want = _render_raw(W, H, groups)
         assert diff_stats(got, want) == (0, 0), (env, it)
         partial += _kind(want) == "partial"

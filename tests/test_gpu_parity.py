@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 import scenarios
+import helpers
 from helpers import GOLD, diff_stats, fixture, golden, oracle_render, product_render
-from oracle import canvas_replay as cr, oracle_backend as ob
+from oracle import canvas_replay as cr
 
 pytestmark = pytest.mark.gpu
 SC = scenarios.scenarios()
@@ -21,17 +22,7 @@ def _need_gpu(gpu):
     assert os.path.exists(S.library_path()), "libswfr.so must be built: the product has no fallback"
 
 
-def _oracle_polys(fx, cols, W, H, even_odd=False):
-    L = ob.lib()
-    ctx = L.swfo_create(W, H)
-    argb = ((cols[:, 3].astype(np.uint32) << 24) | (cols[:, 0].astype(np.uint32) << 16) |
-            (cols[:, 1].astype(np.uint32) << 8) | cols[:, 2]).astype(np.uint32)
-    counts = np.full(len(fx), fx.shape[1], dtype=np.int32)
-    xy = np.ascontiguousarray(fx.reshape(-1))
-    L.swfo_fill_polygons_fixed(ctx, xy.ctypes.data, counts.ctypes.data, argb.ctypes.data, len(fx), 1 if even_odd else 0)
-    px = np.ctypeslib.as_array(L.swfo_pixels(ctx), shape=(H, W)).copy()
-    L.swfo_destroy(ctx)
-    return np.stack([(px >> 16) & 255, (px >> 8) & 255, px & 255, px >> 24], -1).astype(np.uint8)
+_oracle_polys = helpers.oracle_polys
 
 
 # ---- every scenario: HIP vs oracle and vs the committed libcairo golden
@@ -245,58 +236,25 @@ def test_morph_256_ratios_vs_oracle():
 
 # ---- fuzz: random polygons through the whole host+device path
 def test_fuzz_polygons_vs_oracle():
-    import swf_renderer_amd as S
     rng = np.random.default_rng(5)
     for it in range(160):
-        W, H = int(rng.integers(16, 200)), int(rng.integers(16, 120))
-        n = int(rng.integers(3, 9))
-        mode = it % 4
-        if mode == 0:
-            pts = rng.uniform(0, 1, (n, 2)) * [W, H]
-        elif mode == 1:
-            pts = rng.integers(0, 4 * min(W, H), (n, 2)) / 4.0          # tie-heavy quarter pixels
-        elif mode == 2:
-            pts = rng.integers(0, min(W, H), (n, 2)).astype(float)      # vertices on pixel corners
-        else:
-            pts = rng.uniform(-30, 30 + max(W, H), (n, 2))              # leaves the frame
-        eo = bool(rng.integers(0, 2))
-        col = scenarios._rgba(int(rng.integers(0, 256)), 9, 200, int(rng.choice([255, 255, 120])))
-        tag = scenarios._poly_shape(np.rint(pts * 20), {"type": "solid", "color": col})
-        sc = dict(width=W, height=H, even_odd=eo, stage={"children": [{"type": "shape", "definition": tag}]})
-        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), (it, mode, eo, pts.tolist())
+        sc, (mode, eo, pts) = helpers.rand_polygon_scene(rng, it)
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), (it, mode, eo, pts)
 
 
 def test_fuzz_layered_translucent_vs_oracle():
     rng = np.random.default_rng(11)
     for it in range(40):
-        W, H = 150, 90
-        kids = []
-        for _ in range(int(rng.integers(2, 7))):
-            n = int(rng.integers(3, 8))
-            pts = rng.uniform(-10, 1, (n, 2)) * 0 + rng.uniform(0, 1, (n, 2)) * [W, H]
-            col = scenarios._rgba(*[int(v) for v in rng.integers(0, 256, 3)], int(rng.choice([255, 200, 128, 31, 1])))
-            kids.append({"type": "shape", "definition": scenarios._poly_shape(np.rint(pts * 20), {"type": "solid", "color": col})})
-        sc = dict(width=W, height=H, stage={"children": kids})
+        sc = helpers.rand_layered_translucent_scene(rng)
         assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), it
 
 
 def test_fuzz_stroked_shapes_vs_oracle():
     """Random stroked (morph) shapes -- curves, rectilinear box strokes, round caps / joins, hairlines, reflected and off-frame
     placements -- through the whole product path against the oracle's pixels."""
-    from test_host import _rand_path_shape
     rng = np.random.default_rng(78)
-    W, H = 120, 100
     for it in range(120):
-        kids = []
-        for _ in range(int(rng.integers(1, 4))):
-            morph = bool(rng.integers(0, 3) == 0)
-            tag = _rand_path_shape(rng, int(rng.choice([1, 2, 5, 20, 45, 90, 200])), morph)
-            sx, sy = float(rng.choice([1, 1, 0.6, 1.7, -1])), float(rng.choice([1, 1, 0.8, 1.3]))
-            mat = scenarios._m(sx, sy, int(rng.integers(-300, 900)) + (2000 if sx < 0 else 0), int(rng.integers(-300, 500)),
-                               float(rng.choice([0, 0, 0.2])), float(rng.choice([0, 0, -0.15])))
-            kids.append({"type": "morph-shape", "definition": tag, "ratio": float(rng.uniform(0, 1)), "matrix": mat} if morph else
-                        {"type": "shape", "definition": tag, "matrix": mat})
-        sc = dict(width=W, height=H, stage={"children": kids})
+        sc = helpers.rand_stroked_scene(rng)
         assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), it
 
 
@@ -330,10 +288,7 @@ def test_fuzz_radial_gradients_vs_oracle():
     assert painted > 50000
 
 
-@pytest.mark.parametrize("case", [("radial", 1000, 940), ("mixed", 1000, 445), ("mixed", 1000, 607), ("mixed", 1000, 688), ("bitmap", 1000, 820),
-                                  ("mixed", 2000, 755), ("mixed", 2000, 1130), ("mixed", 2000, 1265), ("mixed", 4000, 241), ("mixed", 4000, 1424),
-                                  ("mixed", 5000, 507), ("radial", 7000, 670), ("bitmap", 7000, 816), ("mixed", 7000, 101), ("mixed", 7000, 388),
-                                  ("mixed", 8000, 995), ("mixed", 8000, 1018), ("mixed", 23000, 196), ("big", 300, 146), ("big", 300, 9), ("big", 5000, 854), ("long", 300, 171), ("mixed", 777777, 722)])
+@pytest.mark.parametrize("case", helpers.SOAK_TIE_CASES)
 def test_soak_regressions_tied_edges(case):
     """Scenes soak runs (tools/soak.py gpu) found: edges whose cells coincide at a pixel row's first sample row.  Their order in
     Cairo's list decides whether the row is converted analytically: two active edges keep the order of the last time the list was
@@ -381,16 +336,10 @@ def test_tile_with_an_uncovered_path_row_is_not_a_full_cover():
     """Soak finding (large frames): a path whose bottom lies less than a sample row below a pixel boundary has a last pixel row with
     no active sample row at all.  A tile that the path covers completely in its other rows is then neither empty nor full although
     no single pixel of it is partial: it must take the accumulate-and-scan route, not the full-cover shortcut."""
-    for sy in (1.0001, 1.0, 1.002):                                  # bottom at y = 242.026 (the case), 242.0, 242.48
-        pts = np.array([(9.75, 213.40), (350.65, 242.0), (155.5, 242.0)])
-        for col in (scenarios._rgba(200, 80, 40, 255), scenarios._rgba(200, 80, 40, 140)):
-            tag = scenarios._poly_shape(np.rint(pts * 20), {"type": "solid", "color": col})
-            sc = dict(width=512, height=300, stage={"children": [{"type": "shape", "definition": tag, "matrix": scenarios._m(1.0, sy)}]})
-            assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), (sy, col)
-    for case in (("big", 200, 551), ("big", 200, 572)):
-        from helpers import soak_scene
-        sc = soak_scene(*case)
-        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), case
+    scenes = helpers.uncovered_path_row_scenes()
+    assert len(scenes) == 8
+    for key, sc in scenes:                  # bottoms at y = 242.026 (the case), 242.0, 242.48, opaque and translucent; two soak scenes
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), key
 
 
 # ---- every internal route of the row/tile kernels gives the same pixels
@@ -500,12 +449,7 @@ def test_config4_large_texture_4k_vs_oracle():
 
 
 # ---- full BASELINE sizes
-def _s_scene(cfg):
-    from swf_renderer_amd import api, synth
-    pts, cols = synth.scene(**cfg)
-    W, H = cfg["width"], cfg["height"]
-    fx = synth.twips_to_fixed(pts)
-    return W, H, fx, cols, api.polygons_to_scene(fx, cols, W, H)
+_s_scene = helpers.synth_scene
 
 
 def test_s1_4k_10k_edges_known_answer_and_properties():
@@ -561,7 +505,7 @@ def test_twenty_thousand_paths_in_three_tile_rows_vs_oracle():
     """k2_bin builds a tile-row's list in rounds of 16 384 paths and windows of 4 096 hits: here 20 000 small stars crowd a 640x48
     frame, so every tile-row's list takes two rounds and more than one window (S2's 10 000 paths: one round, one window)."""
     import swf_renderer_amd as S
-    cfg = dict(seed=77, n_shapes=20000, width=640, height=48, rmin=2.0, rmax=9.0)
+    cfg = helpers.TWENTY_THOUSAND_PATHS
     W, H, fx, cols, (edges, paths, styles) = _s_scene(cfg)
     assert len(paths) > 16384
     r = S.Renderer(W, H)
@@ -707,13 +651,7 @@ def test_empty_ragged_and_tiny_frames():
         r.close()
 
 
-def _comb(teeth, width_twips):
-    pts = []
-    step = width_twips / teeth
-    for k in range(teeth):
-        pts += [(100 + step * k, 100), (100 + step * k + step / 2, 1900)]
-    pts += [(100 + width_twips + 100, 1950), (50, 1950)]
-    return scenarios._poly_shape(pts, {"type": "solid", "color": scenarios._rgba(1, 2, 3)})
+_comb = helpers.comb_shape
 
 
 @pytest.mark.parametrize("teeth", [12, 40, 100, 140, 500, 1000, 1100, 3000])
@@ -724,19 +662,12 @@ def test_crowded_rows_vs_oracle(teeth):
     of them starting at one sample row) were refused until round 3 raised the per-row capacity from 2048 to 8192."""
     if teeth > 1100 and os.environ.get("SWFR_EMULATOR"):
         pytest.skip("thousands of edges per row: quadratic work per row, hours on the emulator")
-    tag = _comb(teeth, 2000 if teeth <= 140 else 6000)
     for eo in (False, True):
-        sc = dict(width=120 if teeth <= 140 else 320, height=100, even_odd=eo, stage={"children": [{"type": "shape", "definition": tag}]})
+        sc = helpers.crowded_rows_scene(teeth, eo)
         assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), (teeth, eo)
 
 
-def _comb_points(teeth, width_twips, x0, y_top, y_bottom):
-    pts = []
-    step = width_twips / teeth
-    for k in range(teeth):
-        pts += [(x0 + step * k, y_top), (x0 + step * k + step / 2, y_bottom)]
-    pts += [(x0 + width_twips + 100, y_bottom + 50), (x0 - 50, y_bottom + 50)]
-    return pts
+_comb_points = helpers.comb_points
 
 
 def _multi_poly_shape(polys, fill):
@@ -764,9 +695,8 @@ def test_edges_arriving_together_at_the_frame_top_vs_oracle(teeth, y_top):
     ordered at most sixteen such edges and silently fell back to path order beyond): the start ranks of k2_start_ranks replay
     Cairo's merge sort for any group size.  y_top = 0 puts the teeth's shared vertices exactly on the first sample row (pairs of
     edges coincide there), -7 twips a fraction of a pixel above it, -300 well outside."""
-    tag = scenarios._poly_shape(_comb_points(teeth, 2200, 60, y_top, 1700), {"type": "solid", "color": scenarios._rgba(200, 30, 90, 180)})
     for eo in (False, True):
-        sc = dict(width=128, height=96, even_odd=eo, stage={"children": [{"type": "shape", "definition": tag}]})
+        sc = helpers.frame_top_scene(teeth, y_top, eo)
         stats = {}
         assert diff_stats(product_render(sc, stats=stats), oracle_render(sc)) == (0, 0), (teeth, y_top, eo)
         assert stats["pairtest_limit"] == stats["start_group_limit"] == stats["history_limit"] == 0
@@ -836,16 +766,13 @@ def test_frames_wider_than_a_cell_column_field():
     import torch
     import swf_renderer_amd as S
     from swf_renderer_amd import api
-    w, h = 9600, 48
-    far = scenarios._poly_shape([(9000 * 20 + 7, 100), (9500 * 20 + 3, 300), (9200 * 20, 900)], {"type": "solid", "color": scenarios._rgba(200, 100, 50, 160)})
-    near = scenarios._poly_shape([(50, 60), (4000, 130), (900, 880)], {"type": "solid", "color": scenarios._rgba(20, 200, 50)})
+    w, h = helpers.WIDE_FRAME
+    parts = helpers.wide_frame_parts()
+    far, near, wide, wide_t, sliver = (parts[k] for k in ("far", "near", "wide", "wide_t", "sliver"))
     sc = dict(width=w, height=h, stage={"children": [{"type": "shape", "definition": near}, {"type": "shape", "definition": far}]})
     assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0)
-    pts = [(100, 100), (9400 * 20, 200), (9400 * 20, 700), (100, 600), (3000 * 20, 350)]
-    wide = scenarios._poly_shape(pts, {"type": "solid", "color": scenarios._rgba(1, 2, 3)})
-    wide_t = scenarios._poly_shape(pts, {"type": "solid", "color": scenarios._rgba(200, 30, 90, 140)})
-    # a shallow edge crossing column 5 + 8192 (the block boundary of a path that starts at x = 5) inside an anti-aliased span
-    sliver = scenarios._poly_shape([(100, 400), (9590 * 20, 470), (9590 * 20, 520), (100, 430)], {"type": "solid", "color": scenarios._rgba(10, 90, 250, 200)})
+    # a solid path wider than 8192 px, and a shallow edge crossing column 5 + 8192 (the block boundary of a path that starts at
+    # x = 5) inside an anti-aliased span
     for kids in ([wide], [near, wide_t, far], [wide, sliver, wide_t]):
         sc = dict(width=w, height=h, stage={"children": [{"type": "shape", "definition": k} for k in kids]})
         assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), len(kids)
@@ -860,9 +787,7 @@ def test_frames_wider_than_a_cell_column_field():
         r.render_batch([stage, stage])                           # (the per-frame route)
         assert diff_stats(r.read_image(premultiplied=True), want) == (0, 0)
         # a wide path with a radial gradient: the blocks share the style, which stays anchored at the unsplit path's rectangle
-        grad = {"type": "radial-gradient", "matrix": scenarios._m(4.0, 0.02, 4800 * 20, 400),
-                "gradient": scenarios._grad([(0, (255, 0, 0)), (128, (0, 255, 0, 90)), (255, (0, 0, 255))])}
-        gstage = {"children": [{"type": "shape", "definition": near}, {"type": "shape", "definition": scenarios._poly_shape(pts, grad)}]}
+        gstage = {"children": [{"type": "shape", "definition": near}, {"type": "shape", "definition": parts["wide_grad"]}]}
         r.render(gstage)
         assert diff_stats(r.read_image(premultiplied=True), oracle_render(dict(width=w, height=h, stage=gstage))) == (0, 0)
     finally:

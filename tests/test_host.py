@@ -589,3 +589,65 @@ def test_oracle_raw_edge_entry_equals_its_polygon_fill():
         assert b.premultiplied_rgba()[..., 3].any()
     finally:
         b.close()
+
+
+def test_dense_generator_covers_every_kind():
+    """tests/helpers.py rand_dense_scene is what pins the shaded tile instances' crowded strips (tests/test_gpu_instances.py): its
+    frames must keep having strips of more than 16 and of more than 32 entries, every kind of path and of style, opaque covers
+    of the whole frame, a translucent first draw, a width that is not a multiple of 64 and a tile-row count that is not a
+    multiple of 8 -- checked on the frames the product builds, so that a change to the generator cannot quietly test less."""
+    from helpers import rand_dense_scene, strip_path_counts
+    rng = np.random.default_rng(4040)                  # (test_gpu_instances.py DENSE_SEED: the same frames)
+    painted = crowded = over32 = 0
+    path_kinds, style_kinds, fills = set(), set(), set()
+    for it in range(40):
+        sc = rand_dense_scene(rng)
+        W, H = sc["width"], sc["height"]
+        assert W % 64 != 0 and ((H + 15) // 16) % 8 != 0, (it, W, H)
+        r = S.Renderer(W, H, device=api.DEVICE_HOST_ONLY)
+        try:
+            for b in sc["bitmaps"]:
+                r.add_bitmap(b)
+            edges, paths, styles = r.build_frame(sc["stage"])
+        finally:
+            r.close()
+        cnt = strip_path_counts(W, H, paths)
+        painted += int((cnt > 0).sum())
+        crowded += int((cnt > 16).sum())
+        over32 += int((cnt > 32).sum())
+        path_kinds |= set(int(k) for k in paths["kind"])
+        style_kinds |= set(s.kind for s in styles)
+        for p in paths:
+            s = styles[p["style"]]
+            a = s.pixel >> 24
+            full = p["x_min"] == 0 and p["y_min"] == 0 and p["x_max"] == W and p["y_max"] == H
+            if s.kind == api.STYLE_SOLID:
+                fills.add("opaque" if a == 255 else "translucent")
+                fills.add("alpha1" if a == 1 else ("alpha254" if a == 254 else "other"))
+                if a == 255 and full:
+                    fills.add("box cover" if p["kind"] == api.PATH_BOXES else "tor cover")
+            if s.kind == api.STYLE_BITMAP:
+                fills.add("repeat" if s.extend else "clamped")
+                k = float(np.hypot(s.inv[0], s.inv[1]))   # texels per pixel along x
+                fills.add("magnified" if k < 0.75 else ("minified" if k > 1.4 else "near 1"))
+            if s.kind == api.STYLE_RADIAL:
+                fills.add("focal" if s.c0x != 0 else "radial")
+        first = paths[0]
+        assert first["lerp"] == 1 and styles[first["style"]].pixel >> 24 < 255, it      # translucent onto the clear surface
+    assert crowded * 4 >= painted and over32 > 0, (painted, crowded, over32)
+    assert path_kinds == {api.PATH_TOR, api.PATH_BOXES}
+    assert style_kinds == {api.STYLE_SOLID, api.STYLE_BITMAP, api.STYLE_RADIAL}      # (no linear gradient in the bit-exact corpus)
+    assert {"opaque", "translucent", "alpha1", "alpha254", "box cover", "tor cover", "repeat", "clamped", "magnified", "minified",
+            "focal", "radial"} <= fills, fills
+    rng = np.random.default_rng(4041)
+    assert any(s.kind == api.STYLE_LINEAR for _ in range(3) for s in _dense_styles(rand_dense_scene(rng, linear=True)))
+
+
+def _dense_styles(sc):
+    r = S.Renderer(sc["width"], sc["height"], device=api.DEVICE_HOST_ONLY)
+    try:
+        for b in sc["bitmaps"]:
+            r.add_bitmap(b)
+        return r.build_frame(sc["stage"])[2]
+    finally:
+        r.close()

@@ -481,3 +481,34 @@ def test_gradient_with_only_transparent_stops_is_a_clear_source():
     sc["stage"] = {"children": [kids[3], kids[11]]}
     ref, got = _replay_both(sc)
     assert (ref[..., 3] > 0).sum() > 1000 and np.array_equal(ref, got)
+
+
+@pytest.mark.parametrize("linear", [False, True], ids=["exact", "linear"])
+def test_dense_scenes_through_the_canvas_replay(linear):
+    """The dense mixed-fill frames of tests/helpers.py rand_dense_scene (the GPU instance tests' corpus: dozens of layered solids,
+    box paths, bitmap fills magnified and minified, radial and focal gradients, strokes, opaque covers) rendered by libcairo and by
+    the oracle: identical; with linear gradients (the documented extension) within +-1 LSB."""
+    from helpers import rand_dense_scene
+    rng = np.random.default_rng(4040 if not linear else 4041)
+    for it in range(12):
+        ref, got = _replay_both(rand_dense_scene(rng, linear=linear))
+        assert (ref[..., 3] > 0).mean() > 0.9
+        if linear:
+            assert np.abs(ref - got).max() <= 1, it
+        else:
+            assert np.array_equal(ref, got), (it, int((ref != got).any(-1).sum()))
+
+
+def test_gradient_edges_through_the_canvas_replay():
+    """Focal points at +-1 and beyond (epsilons +-256 ... 32767, -32768: the a == 0 branch, cones with transparent regions) and 1, 2
+    and 16 stops with translucent and duplicate ratios, on a clear frame and over a backdrop (tests/helpers.py
+    gradient_edge_scenes; the gradient circle covers the frame): libcairo and the oracle agree byte for byte."""
+    from helpers import gradient_edge_scenes
+    scenes = gradient_edge_scenes()
+    cones = 0
+    for key, sc in sorted(scenes.items()):
+        ref, got = _replay_both(sc)
+        assert np.array_equal(ref, got), key
+        assert (ref[..., 3] > 0).sum() > 500, key
+        cones += "clear" in key and "focal" in key and bool((ref[..., 3] == 0).any() and (ref[..., 3] > 0).any())
+    assert cones > 10
