@@ -268,7 +268,11 @@ int  swfr_shape_json(swfr_renderer *r, uint32_t id, int morph, const char **json
    in groups of up to SWFR_BATCH_FRAMES (default 64) by ONE launch per kernel and group, two groups alternating so that the host
    builds one while the GPU renders the other; frame i lands, premultiplied RGBA8 with tight rows, at device_dst + i * frame_stride
    (DEVICE memory, e.g. a torch tensor).  With device_dst == NULL the frames are rendered one after the other and only the last is
-   kept for swfr_read_image.  Blocking: returns when every frame is finished. */
+   kept for swfr_read_image.  Blocking: returns when every frame is finished.
+   A refused frame (e.g. SWFR_ERR_NOT_FOUND for an unknown shape or bitmap) ends the batch with its error code, returned only after
+   everything the call queued has finished: no frame is still being written.  The frames before it are complete, except that with
+   a device destination the frames of the refused frame's own group (launched together) are not written either; no later slot is
+   written.  The handle renders correctly afterwards; swfr_read_image returns SWFR_ERR_INVALID until the next frame is rendered. */
 int  swfr_render_batch(swfr_renderer *r, const swfr_stage *stages, uint32_t n_stages, void *device_dst, size_t frame_stride);
 
 /* Timing of the last swfr_render / swfr_render_resident, from HIP events on the handle's stream. */

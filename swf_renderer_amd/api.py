@@ -671,11 +671,13 @@ class Renderer:
         return np.ctypeslib.as_array(data, shape=(self.height, self.width, 4))
 
     def render_sequence_readback(self, stages, repeat=1, premultiplied=False, overlap=True):
-        """render + mapped read-back of every frame (the reference's test loop), timed below the C-ABI; returns seconds."""
+        """render + mapped read-back of every frame (the reference's test loop), timed below the C-ABI; returns seconds.  The call's
+        checksum (bytes 0 and 3 of every frame's middle pixel, summed) is kept in self.readback_checksum."""
         arena, arr, n = stages if isinstance(stages, tuple) else self.marshal_stages(stages)
         self._apply_cxforms(arena)
         secs, chk = C.c_double(), C.c_uint64()
         self._check(self.L.swfr_render_sequence_readback(self.h, arr, n, int(repeat), 1 if premultiplied else 0, 1 if overlap else 0, C.byref(secs), C.byref(chk)))
+        self.readback_checksum = int(chk.value)
         return secs.value
 
     def band_slab_bytes(self) -> int:

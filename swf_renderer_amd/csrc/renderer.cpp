@@ -1337,106 +1337,120 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
         for (uint32_t k = 0; k < pend[g].count && rc == SWFR_OK; ++k) rc = check_counters(r, G.h_counters + size_t(k) * COUNTER_WORDS);
         pend[g].count = 0;
     };
-    for (uint32_t first = 0; first < n && rc == SWFR_OK; first += B, ++gi) {
-        const uint32_t cnt = std::min(B, n - first);
-        const int g = int(gi & 1);
-        auto& G = r->groups[g];
-        if (!G.stream) HIP_CHECK(hipStreamCreateWithFlags(&G.stream, hipStreamNonBlocking));
-        // ---- host: build the group's frames (the other group is being rasterized meanwhile)
-        if (fd.size() < cnt) fd.resize(cnt);
-        size_t arena_bytes = pad(cnt * sizeof(Frame2)) + 4096, work_bytes = 0, cls_bytes = 0;
-        size_t max_e = 0, max_p = 0, max_bands = 0, max_chunks = 0, max_strips = 0;
-        int shader_level = 0;
-        uint32_t max_pe = 0;
-        bool rows_wide = false;
-        auto t0 = clk::now();
-        for (uint32_t k = 0; k < cnt; ++k) {
-            FrameData& F = fd[k];
-            r->builder->build(stages[first + k]);
-            F.e = r->builder->edges(); F.p = r->builder->paths(); F.s = r->builder->styles();
-            validate_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size());
-            resolve_variants(r, F.p.data(), F.p.size(), F.s.data(), F.s.size(), G.stream, false);
-            {
-                std::vector<swfr_edge> se; std::vector<swfr_path> sp;
-                if (split_wide_paths(F.e.data(), F.p.data(), F.p.size(), se, sp)) {
-                    const std::vector<swfr_path> orig = F.p;
-                    F.e.swap(se); F.p.swap(sp);
-                    layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L, orig.data(), orig.size());
-                } else layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L);
+    try {
+        for (uint32_t first = 0; first < n && rc == SWFR_OK; first += B, ++gi) {
+            const uint32_t cnt = std::min(B, n - first);
+            const int g = int(gi & 1);
+            auto& G = r->groups[g];
+            if (!G.stream) HIP_CHECK(hipStreamCreateWithFlags(&G.stream, hipStreamNonBlocking));
+            // ---- host: build the group's frames (the other group is being rasterized meanwhile)
+            if (fd.size() < cnt) fd.resize(cnt);
+            size_t arena_bytes = pad(cnt * sizeof(Frame2)) + 4096, work_bytes = 0, cls_bytes = 0;
+            size_t max_e = 0, max_p = 0, max_bands = 0, max_chunks = 0, max_strips = 0;
+            int shader_level = 0;
+            uint32_t max_pe = 0;
+            bool rows_wide = false;
+            auto t0 = clk::now();
+            for (uint32_t k = 0; k < cnt; ++k) {
+                FrameData& F = fd[k];
+                r->builder->build(stages[first + k]);
+                F.e = r->builder->edges(); F.p = r->builder->paths(); F.s = r->builder->styles();
+                validate_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size());
+                resolve_variants(r, F.p.data(), F.p.size(), F.s.data(), F.s.size(), G.stream, false);
+                {
+                    std::vector<swfr_edge> se; std::vector<swfr_path> sp;
+                    if (split_wide_paths(F.e.data(), F.p.data(), F.p.size(), se, sp)) {
+                        const std::vector<swfr_path> orig = F.p;
+                        F.e.swap(se); F.p.swap(sp);
+                        layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L, orig.data(), orig.size());
+                    } else layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L);
+                }
+                arena_bytes += scene_arena_bytes(F.L, F.e.size(), F.p.size(), F.s.size());
+                const SceneLayout& L = F.L;
+                work_bytes += pad((2 * F.e.size() + 1) * sizeof(DevEdge)) + pad(L.n_slots * sizeof(BandEntry2)) + pad((L.n_slots * TILE_H + 64) * sizeof(RowInfo2)) +
+                              pad(L.cell_total * sizeof(Cell)) + 2 * pad(2 * (L.n_rows + 64) * sizeof(SlowRow)) + 2 * pad((F.p.size() + 64) * sizeof(uint32_t)) +
+                              pad((L.n_chunks + 1) * sizeof(ChunkInfo)) + pad((L.n_slots + 8) * sizeof(BandSlot)) + pad((L.n_strip_slots + 1) * sizeof(StripDesc)) +
+                              pad((L.n_strips + 1) * sizeof(uint32_t)) + pad(COUNTER_WORDS * sizeof(uint32_t));
+                cls_bytes += pad(cls_region_bytes(L.n_slots, tiles_x, L.n_strips));
+                max_e = std::max(max_e, F.e.size()); max_p = std::max(max_p, F.p.size()); max_bands = std::max(max_bands, L.n_bands);
+                max_chunks = std::max(max_chunks, L.n_chunks); max_strips = std::max(max_strips, L.n_strip_slots);
+                shader_level = std::max(shader_level, L.shader_level);
+                max_pe = std::max(max_pe, L.max_path_edges);
+                rows_wide = rows_wide || L.rows_wide;
             }
-            arena_bytes += scene_arena_bytes(F.L, F.e.size(), F.p.size(), F.s.size());
-            const SceneLayout& L = F.L;
-            work_bytes += pad((2 * F.e.size() + 1) * sizeof(DevEdge)) + pad(L.n_slots * sizeof(BandEntry2)) + pad((L.n_slots * TILE_H + 64) * sizeof(RowInfo2)) +
-                          pad(L.cell_total * sizeof(Cell)) + 2 * pad(2 * (L.n_rows + 64) * sizeof(SlowRow)) + 2 * pad((F.p.size() + 64) * sizeof(uint32_t)) +
-                          pad((L.n_chunks + 1) * sizeof(ChunkInfo)) + pad((L.n_slots + 8) * sizeof(BandSlot)) + pad((L.n_strip_slots + 1) * sizeof(StripDesc)) +
-                          pad((L.n_strips + 1) * sizeof(uint32_t)) + pad(COUNTER_WORDS * sizeof(uint32_t));
-            cls_bytes += pad(cls_region_bytes(L.n_slots, tiles_x, L.n_strips));
-            max_e = std::max(max_e, F.e.size()); max_p = std::max(max_p, F.p.size()); max_bands = std::max(max_bands, L.n_bands);
-            max_chunks = std::max(max_chunks, L.n_chunks); max_strips = std::max(max_strips, L.n_strip_slots);
-            shader_level = std::max(shader_level, L.shader_level);
-            max_pe = std::max(max_pe, L.max_path_edges);
-            rows_wide = rows_wide || L.rows_wide;
+            t_build += ms_since(t0); t0 = clk::now();
+            // ---- this group's previous use must be over before its staging and device buffers are rewritten
+            finish_group(g);
+            t_wait += ms_since(t0); t0 = clk::now();
+            if (rc != SWFR_OK) break;
+            G.arena.begin(arena_bytes);
+            const uint8_t* work_before = G.work.ptr;
+            G.work.reserve(work_bytes + 4096); G.cls.reserve(cls_bytes + 4096);
+            if (G.work.ptr != work_before) HIP_CHECK(hipMemsetAsync(G.work.ptr, 0, G.work.cap, G.stream));      // (fresh memory: the strip costs start at zero)
+            HIP_CHECK(hipMemsetAsync(G.cls.ptr, 0, cls_bytes, G.stream));                                        // class bytes outside the paths' rectangles
+            if (G.h_counters_cap < cnt) {
+                if (G.h_counters) (void)hipHostFree(G.h_counters);
+                HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&G.h_counters), size_t(B) * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+                G.h_counters_cap = B;
+            }
+            std::vector<Frame2> fr(cnt);
+            uint8_t* w = G.work.ptr;
+            uint8_t* c = G.cls.ptr;
+            auto carve = [&](size_t bytes) { uint8_t* q = w; w += pad(bytes); return q; };
+            for (uint32_t k = 0; k < cnt; ++k) {
+                FrameData& F = fd[k];
+                const SceneLayout& L = F.L;
+                Frame2& f = fr[k];
+                std::memset(&f, 0, sizeof f);
+                push_scene(G.arena, L, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), f);
+                fill_frame_sizes(r, L, F.e.size(), F.p.size(), f);
+                f.src.bitmaps = r->d_bitmap_table.ptr;
+                f.edges = reinterpret_cast<DevEdge*>(carve((2 * F.e.size() + 1) * sizeof(DevEdge)));
+                f.band_list = reinterpret_cast<BandEntry2*>(carve(L.n_slots * sizeof(BandEntry2)));
+                f.rows = reinterpret_cast<RowInfo2*>(carve((L.n_slots * TILE_H + 64) * sizeof(RowInfo2)));
+                f.cells = reinterpret_cast<Cell*>(carve(L.cell_total * sizeof(Cell)));
+                f.slow = reinterpret_cast<SlowRow*>(carve(2 * (L.n_rows + 64) * sizeof(SlowRow)));
+                f.huge = reinterpret_cast<SlowRow*>(carve(2 * (L.n_rows + 64) * sizeof(SlowRow)));
+                f.path_flag = reinterpret_cast<uint32_t*>(carve((F.p.size() + 64) * sizeof(uint32_t)));
+                f.path_queue = reinterpret_cast<uint32_t*>(carve((F.p.size() + 64) * sizeof(uint32_t)));
+                f.chunks = reinterpret_cast<ChunkInfo*>(carve((L.n_chunks + 1) * sizeof(ChunkInfo)));
+                f.band_slots = reinterpret_cast<BandSlot*>(carve((L.n_slots + 8) * sizeof(BandSlot)));
+                f.strips = reinterpret_cast<StripDesc*>(carve((L.n_strip_slots + 1) * sizeof(StripDesc)));
+                f.strip_cost = reinterpret_cast<uint32_t*>(carve((L.n_strips + 1) * sizeof(uint32_t)));
+                f.counters = reinterpret_cast<uint32_t*>(carve(COUNTER_WORDS * sizeof(uint32_t)));
+                f.cls = c; f.strip_top = reinterpret_cast<StripTop*>(c + cls_bytes_of(L.n_slots, tiles_x)); c += pad(cls_region_bytes(L.n_slots, tiles_x, L.n_strips));
+                f.strip_order = 0;                              // (a frame's buffers held another frame before: no cost history to order by)
+                f.fb = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(device_dst) + size_t(first + k) * frame_stride);
+            }
+            const Frame2* frames_dev = static_cast<Frame2*>(G.arena.push(fr.data(), cnt * sizeof(Frame2)));
+            G.arena.flush(G.stream);
+            t_stage += ms_since(t0); t0 = clk::now();
+            if (!G.ev_begin) { HIP_CHECK(hipEventCreate(&G.ev_begin)); HIP_CHECK(hipEventCreate(&G.ev_end)); }
+            HIP_CHECK(hipEventRecord(G.ev_begin, G.stream));
+            launch2_bin(G.stream, frames_dev, cnt, uint32_t(max_e), uint32_t(max_p), uint32_t(max_bands), 1u, r->mono);
+            launch2_rows(G.stream, frames_dev, cnt, uint32_t(max_chunks), max_pe, rows_wide, r->mono);
+            if (max_chunks) launch2_rows_slow(G.stream, frames_dev, cnt, 256u, 64u, SLOW_PASSES, r->mono);
+            launch2_tiles(G.stream, frames_dev, cnt, uint32_t(max_strips), ~0u, shader_level, nullptr);
+            HIP_CHECK(hipEventRecord(G.ev_end, G.stream));
+            for (uint32_t k = 0; k < cnt; ++k)
+                HIP_CHECK(hipMemcpyAsync(G.h_counters + size_t(k) * COUNTER_WORDS, fr[k].counters, COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, G.stream));
+            HIP_CHECK(hipGetLastError());
+            pend[g] = Pending{first, cnt};
+            r->fb_cur = fr[cnt - 1].fb;
+            t_launch += ms_since(t0);
         }
-        t_build += ms_since(t0); t0 = clk::now();
-        // ---- this group's previous use must be over before its staging and device buffers are rewritten
-        finish_group(g);
-        t_wait += ms_since(t0); t0 = clk::now();
-        if (rc != SWFR_OK) break;
-        G.arena.begin(arena_bytes);
-        const uint8_t* work_before = G.work.ptr;
-        G.work.reserve(work_bytes + 4096); G.cls.reserve(cls_bytes + 4096);
-        if (G.work.ptr != work_before) HIP_CHECK(hipMemsetAsync(G.work.ptr, 0, G.work.cap, G.stream));      // (fresh memory: the strip costs start at zero)
-        HIP_CHECK(hipMemsetAsync(G.cls.ptr, 0, cls_bytes, G.stream));                                        // class bytes outside the paths' rectangles
-        if (G.h_counters_cap < cnt) {
-            if (G.h_counters) (void)hipHostFree(G.h_counters);
-            HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&G.h_counters), size_t(B) * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
-            G.h_counters_cap = B;
-        }
-        std::vector<Frame2> fr(cnt);
-        uint8_t* w = G.work.ptr;
-        uint8_t* c = G.cls.ptr;
-        auto carve = [&](size_t bytes) { uint8_t* q = w; w += pad(bytes); return q; };
-        for (uint32_t k = 0; k < cnt; ++k) {
-            FrameData& F = fd[k];
-            const SceneLayout& L = F.L;
-            Frame2& f = fr[k];
-            std::memset(&f, 0, sizeof f);
-            push_scene(G.arena, L, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), f);
-            fill_frame_sizes(r, L, F.e.size(), F.p.size(), f);
-            f.src.bitmaps = r->d_bitmap_table.ptr;
-            f.edges = reinterpret_cast<DevEdge*>(carve((2 * F.e.size() + 1) * sizeof(DevEdge)));
-            f.band_list = reinterpret_cast<BandEntry2*>(carve(L.n_slots * sizeof(BandEntry2)));
-            f.rows = reinterpret_cast<RowInfo2*>(carve((L.n_slots * TILE_H + 64) * sizeof(RowInfo2)));
-            f.cells = reinterpret_cast<Cell*>(carve(L.cell_total * sizeof(Cell)));
-            f.slow = reinterpret_cast<SlowRow*>(carve(2 * (L.n_rows + 64) * sizeof(SlowRow)));
-            f.huge = reinterpret_cast<SlowRow*>(carve(2 * (L.n_rows + 64) * sizeof(SlowRow)));
-            f.path_flag = reinterpret_cast<uint32_t*>(carve((F.p.size() + 64) * sizeof(uint32_t)));
-            f.path_queue = reinterpret_cast<uint32_t*>(carve((F.p.size() + 64) * sizeof(uint32_t)));
-            f.chunks = reinterpret_cast<ChunkInfo*>(carve((L.n_chunks + 1) * sizeof(ChunkInfo)));
-            f.band_slots = reinterpret_cast<BandSlot*>(carve((L.n_slots + 8) * sizeof(BandSlot)));
-            f.strips = reinterpret_cast<StripDesc*>(carve((L.n_strip_slots + 1) * sizeof(StripDesc)));
-            f.strip_cost = reinterpret_cast<uint32_t*>(carve((L.n_strips + 1) * sizeof(uint32_t)));
-            f.counters = reinterpret_cast<uint32_t*>(carve(COUNTER_WORDS * sizeof(uint32_t)));
-            f.cls = c; f.strip_top = reinterpret_cast<StripTop*>(c + cls_bytes_of(L.n_slots, tiles_x)); c += pad(cls_region_bytes(L.n_slots, tiles_x, L.n_strips));
-            f.strip_order = 0;                              // (a frame's buffers held another frame before: no cost history to order by)
-            f.fb = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(device_dst) + size_t(first + k) * frame_stride);
-        }
-        const Frame2* frames_dev = static_cast<Frame2*>(G.arena.push(fr.data(), cnt * sizeof(Frame2)));
-        G.arena.flush(G.stream);
-        t_stage += ms_since(t0); t0 = clk::now();
-        if (!G.ev_begin) { HIP_CHECK(hipEventCreate(&G.ev_begin)); HIP_CHECK(hipEventCreate(&G.ev_end)); }
-        HIP_CHECK(hipEventRecord(G.ev_begin, G.stream));
-        launch2_bin(G.stream, frames_dev, cnt, uint32_t(max_e), uint32_t(max_p), uint32_t(max_bands), 1u, r->mono);
-        launch2_rows(G.stream, frames_dev, cnt, uint32_t(max_chunks), max_pe, rows_wide, r->mono);
-        if (max_chunks) launch2_rows_slow(G.stream, frames_dev, cnt, 256u, 64u, SLOW_PASSES, r->mono);
-        launch2_tiles(G.stream, frames_dev, cnt, uint32_t(max_strips), ~0u, shader_level, nullptr);
-        HIP_CHECK(hipEventRecord(G.ev_end, G.stream));
-        for (uint32_t k = 0; k < cnt; ++k)
-            HIP_CHECK(hipMemcpyAsync(G.h_counters + size_t(k) * COUNTER_WORDS, fr[k].counters, COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, G.stream));
-        HIP_CHECK(hipGetLastError());
-        pend[g] = Pending{first, cnt};
-        r->fb_cur = fr[cnt - 1].fb;
-        t_launch += ms_since(t0);
+    } catch (...) {
+        // a refused frame (a StatusError of the frame builder or the layout) or a failed HIP call while up to two groups still
+        // write the caller's frames: they finish, and their counters are read, before the error reaches the caller (swfr.h)
+        try {
+            for (int g = 0; g < 2; ++g)
+                if (r->groups[g].stream) HIP_CHECK(hipStreamSynchronize(r->groups[g].stream));   // (also a texel pass of the group being built)
+            finish_group(0);
+            finish_group(1);
+        } catch (...) {}
+        r->scene_ready = false;
+        r->fb_valid = false; r->fb_cur = nullptr;
+        throw;
     }
     auto t_end = clk::now();
     finish_group(0);
@@ -1568,7 +1582,14 @@ int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* d
         for (uint32_t k = 0; k < n_sets; ++k)
             if (r->fs[k].stream) HIP_CHECK(hipStreamSynchronize(r->fs[k].stream));
     } catch (...) {
+        // a refused frame: the frames queued before it, and their counter copies into hc, finish before hc is freed and the error
+        // reaches the caller (swfr.h); none of them is the handle's image
+        for (uint32_t k = 0; k < 4; ++k)
+            if (r->fs[k].stream) (void)hipStreamSynchronize(r->fs[k].stream);
+        (void)hipStreamSynchronize(r->stream);
         (void)hipHostFree(hc);
+        r->scene_ready = false;
+        r->fb_valid = false; r->fb_cur = nullptr;
         throw;
     }
     r->scene_ready = false;                 // scene 0 now holds some frame of the batch, not a scene the caller uploaded

@@ -865,3 +865,63 @@ def gradient_edge_scenes():
             kids = ([{"type": "shape", "definition": back}] if backdrop else []) + [{"type": "shape", "definition": scenarios._poly_shape(np.rint(shape_pts), fill)}]
             out["%s_%d_%s" % ("radial" if focal is None else "focal%d" % focal, n, "over" if backdrop else "clear")] = dict(width=W, height=H, stage={"children": kids})
     return out
+
+
+# ---- a batch corpus: frames of one size, one kind of frame per code path a group of swfr_render_batch frames can mix
+#      (tests/test_gpu_batches.py; tests/test_host.py checks that every kind keeps what it is in the corpus for)
+BATCH_W, BATCH_H = 160, 120
+BATCH_TIE_CASE = ("mixed", 2000, 1265)            # a SOAK_TIE_CASES scene whose tied rows lie inside BATCH_W x BATCH_H
+
+
+def _placed(stage, sx, sy, tx, ty):
+    """a stage's objects inside one container placed by scale (sx, sy) and translation (tx, ty) twips"""
+    import scenarios
+    return {"type": "container", "matrix": scenarios._m(sx, sy, tx, ty), "children": stage["children"]}
+
+
+def batch_corpus(W=BATCH_W, H=BATCH_H):
+    """{kind: scene} re-framed to W x H: the empty stage; box paths only; solid polygons only (the compact style table); a translucent
+    stack; bitmap fills (magnified, minified, repeat, no-repeat); radial and focal gradients; a linear gradient (the +-1 LSB
+    extension); round-joined strokes (queued rows); a soak scene with tied edges (the list-order replay); a crowded comb (k2_rows_huge);
+    one path of more than ROWS_STAGE edges; a colour-transformed bitmap scene (the texel pass); morph shapes at several ratios.
+    Every scene's bitmaps use the ids of tests/scenarios.py's fixture bitmap (3) only."""
+    import scenarios
+    SC = scenarios.scenarios()
+    rgba = scenarios._rgba
+
+    def poly(pts_px, fill, line=None, line_width=0):
+        return {"type": "shape", "definition": scenarios._poly_shape(np.rint(np.asarray(pts_px, float) * 20), fill, line=line, line_width=line_width)}
+
+    def rect(x0, y0, x1, y1):
+        return [(x0, y0), (x1, y0), (x1, y1), (x0, y1)]
+
+    out = {"empty": {"children": []}}
+    out["boxes"] = {"children": [
+        poly(rect(8, 6, 60, 40), {"type": "solid", "color": rgba(200, 40, 30)}),                        # whole pixels
+        poly(rect(30.35, 22.6, 97.15, 71.05), {"type": "solid", "color": rgba(20, 90, 220, 140)}),      # fractional
+        poly(rect(101.5, 9.25, 155.75, 30.5), {"type": "solid", "color": rgba(250, 250, 20, 255)}),
+        poly(rect(70, 50, 150, 110), None, line=rgba(10, 140, 60, 200), line_width=50),                   # rectilinear strokes
+        poly(rect(12.3, 60.45, 55.1, 113.7), None, line=rgba(0, 0, 0), line_width=23)]}
+    out["solid"] = {"children": [
+        poly([(5, 3), (150, 20), (90, 115)], {"type": "solid", "color": rgba(30, 160, 220)}),
+        poly([(120, 5), (158, 60), (130, 117), (60, 100), (70, 40)], {"type": "solid", "color": rgba(230, 120, 10, 200)}),
+        poly([(-20, 70), (80, 50), (40, 140)], {"type": "solid", "color": rgba(90, 20, 120, 37)})]}
+    out["translucent"] = SC["translucent_stack"]["stage"]
+    out["bitmaps"] = {"children": SC["bitmap_no_repeat_magnified"]["stage"]["children"] + SC["bitmap_no_repeat_minified"]["stage"]["children"][:1] +
+                      SC["bitmap_repeat_over_solid"]["stage"]["children"][1:] + SC["bitmap_minified_rotated"]["stage"]["children"]}
+    out["radial_focal"] = {"children": [_placed(SC["gradient_radial"]["stage"], 0.7, 0.7, 0, 0),
+                                        _placed(SC["gradient_focal"]["stage"], 0.8, 0.7, 1300, 700),
+                                        _placed(SC["gradient_alpha_over"]["stage"], 0.5, 0.5, 1500, 0)]}
+    out["linear"] = SC["gradient_linear_ext"]["stage"]
+    out["round_strokes"] = SC["morph_round_stroke_090"]["stage"]
+    out["tie"] = soak_scene(*BATCH_TIE_CASE)["stage"]
+    out["comb"] = crowded_rows_scene(60, False)["stage"]
+    out["long_path"] = {"children": [poly(scenarios._circleish(80, 60, 55, n=50), {"type": "solid", "color": rgba(40, 200, 120, 180)}),
+                                     poly([(10, 10), (50, 12), (30, 40)], {"type": "solid", "color": rgba(200, 0, 0)})]}
+    ct = {"red_mult": {"epsilons": 256}, "green_mult": {"epsilons": 160}, "blue_mult": {"epsilons": 90}, "alpha_mult": {"epsilons": 220},
+          "red_add": 20, "green_add": -10, "blue_add": 40, "alpha_add": 0}
+    out["cxform"] = {"children": [{"type": "container", "color_transform": ct, "children": SC["bitmap_minified_rotated"]["stage"]["children"]}]}
+    out["morph"] = {"children": [_placed(SC["morph_000"]["stage"], 0.55, 0.55, 0, 0), _placed(SC["morph_128"]["stage"], 0.55, 0.6, 1500, 100),
+                                 _placed(SC["morph_color_030"]["stage"], 0.6, 0.55, 300, 1150), _placed(SC["morph_255"]["stage"], 0.5, 0.5, 1700, 1300)]}
+    bitmaps = SC["bitmap_minified_rotated"]["bitmaps"]
+    return {k: dict(width=W, height=H, stage=st, bitmaps=bitmaps if k in ("bitmaps", "cxform") else []) for k, st in out.items()}

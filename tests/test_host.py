@@ -651,3 +651,65 @@ def _dense_styles(sc):
         return r.build_frame(sc["stage"])[2]
     finally:
         r.close()
+
+
+def test_batch_corpus_kinds_keep_their_properties():
+    """tests/helpers.py batch_corpus is what mixes unlike frames in one batch group (tests/test_gpu_batches.py): every kind must keep
+    the property it is in the corpus for -- checked on the frames the product builds, so that a change to a generator or a scenario
+    cannot quietly empty a kind.  (Queued, crowded and tied rows are counted by the GPU test itself.)"""
+    from helpers import BATCH_H, BATCH_W, batch_corpus
+    corpus = batch_corpus()
+    assert list(corpus) == ["empty", "boxes", "solid", "translucent", "bitmaps", "radial_focal", "linear", "round_strokes", "tie", "comb",
+                            "long_path", "cxform", "morph"]
+    built = {}
+    for kind, sc in corpus.items():
+        assert (sc["width"], sc["height"]) == (BATCH_W, BATCH_H), kind
+        r = S.Renderer(sc["width"], sc["height"], device=api.DEVICE_HOST_ONLY)
+        try:
+            for b in sc["bitmaps"]:
+                r.add_bitmap(b)
+            built[kind] = r.build_frame(sc["stage"])
+        finally:
+            r.close()
+    ids = {}
+    for sc in corpus.values():
+        for b in sc["bitmaps"]:
+            assert ids.setdefault(b["id"], b) is b, "one bitmap per id across the corpus"
+
+    def kinds_of(kind):
+        _, p, s = built[kind]
+        return set(int(k) for k in p["kind"]), set(x.kind for x in s)
+
+    e, p, s = built["empty"]
+    assert len(e) == len(p) == 0
+    # boxes only (no tor chunks): fills at whole and fractional pixels, and rectilinear strokes
+    e, p, s = built["boxes"]
+    assert kinds_of("boxes") == ({api.PATH_BOXES}, {api.STYLE_SOLID}) and len(p) >= 5
+    xy = np.stack([e["x1"], e["y1"], e["x2"], e["y2"]], -1)
+    assert (xy % 256 != 0).any() and (xy % 256 == 0).all(-1).any()
+    # solid styles only (the compact style table) and tor paths
+    for kind in ("solid", "translucent", "long_path", "round_strokes", "tie", "comb", "morph"):
+        assert kinds_of(kind)[1] == {api.STYLE_SOLID}, kind
+        assert api.PATH_TOR in kinds_of(kind)[0], kind
+    alphas = [x.pixel >> 24 for x in built["translucent"][2]]
+    assert sum(a < 255 for a in alphas) >= 2, alphas
+    # bitmap fills: repeat and clamped, magnified and minified
+    fills = set()
+    for x in built["bitmaps"][2]:
+        if x.kind == api.STYLE_BITMAP:
+            fills.add("repeat" if x.extend else "clamped")
+            k = float(np.hypot(x.inv[0], x.inv[1]))
+            fills.add("magnified" if k < 0.75 else ("minified" if k > 1.4 else "near 1"))
+    assert {"repeat", "clamped", "magnified", "minified"} <= fills, fills
+    # radial and focal gradients; a linear gradient
+    grads = [x for x in built["radial_focal"][2] if x.kind == api.STYLE_RADIAL]
+    assert any(x.c0x != 0 for x in grads) and any(x.c0x == 0 for x in grads)
+    assert api.STYLE_LINEAR in kinds_of("linear")[1]
+    # a path of more than ROWS_STAGE (32) edges in a solid-only frame; a comb of more than 64 edges active in one row
+    assert int(built["long_path"][1]["n_edges"].max()) > 32
+    assert int(built["comb"][1]["n_edges"].max()) >= 120
+    assert int(built["round_strokes"][1]["n_edges"].max()) > 32
+    # the colour-transformed bitmap: a texture variant of the texel pass
+    assert any(x.kind == api.STYLE_BITMAP and x.bitmap >= api.VARIANT_BASE for x in built["cxform"][2])
+    # morph shapes: four placements at several ratios; the soak scene's shapes
+    assert len(built["morph"][1]) >= 4 and len(built["tie"][1]) >= 2
