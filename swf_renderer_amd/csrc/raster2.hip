@@ -1403,7 +1403,9 @@ __device__ __forceinline__ void blend8(uint32_t (&px)[8], const uint32_t (&al)[8
 
 template <int SHADERS>
 __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
-    __shared__ __attribute__((aligned(16))) int acc[STRIP_H][T3_ACC_STRIDE];     // per pixel: covered height << 20 | uncovered area (20 bits, signed)
+    // per pixel: deltas whose prefix sum along the row is 17 * N(x), N = Cairo's coverage numerator 512 * H(x) - ua(x) (H: the heights
+    // of the cells at columns <= x, ua: the uncovered areas of the cells at x); all zero while no path uses them
+    __shared__ __attribute__((aligned(16))) int acc[STRIP_H][T3_ACC_STRIDE];
     __shared__ __attribute__((aligned(16))) uint32_t ent[T3_LIST][12];         // BandEntry2 as dwords, [8] = its class byte for this strip
     __shared__ __attribute__((aligned(16))) uint32_t hdr[T3_LIST][2 * STRIP_H]; // the strip's eight RowInfo2 of a partial tor entry
     __shared__ __attribute__((aligned(16))) uint32_t bq[8 * T3_UNITS];         // the compacted blend's queue: per unit {coverage[4], pixel[4]}
@@ -1599,7 +1601,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                             lds_barrier();
                         }
                         uint32_t off = 0; int n_c = 0;
-                        if (ty0 + cr < height) {
+                        if (cr >= row_lo && cr < row_hi) {                   // (a row outside the path's rows gets no cells: alpha 0)
                             const uint2 hq = *reinterpret_cast<const uint2*>(&hdr[li][2 * cr]);
                             off = hq.x; n_c = (int)(hq.y & 0xffffu);
                             if (off > FR->cell_slice - min((uint32_t)n_c, FR->cell_slice)) { atomicOr(&FR->counters[C2_ERROR], E2_CELL_RANGE); n_c = 0; }   // off + n_c > cell_slice
@@ -1615,10 +1617,15 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                         auto add_cell = [&](Cell c, bool valid) {
                             const int i = cell_col(c) + xrel;                 // (columns are stored relative to the path's x_min)
                             const int v = (int)(c.w << 13) >> 13;             // covered height * 16384 + uncovered area
-                            const int ua = (v << 18) >> 18;
-                            const int hgt = (v - ua) << 6;                    // height << 20
-                            // a cell left of the tile only adds its height to everything right of it: to column 0, without an area
-                            if (valid && i < TILE_W) atomicAdd(&arow[max(i, 0)], i < 0 ? hgt : hgt + ua);
+                            const int ua = (int)(c.w << 18) >> 18;
+                            const int h512 = (v - ua) >> 5;                   // height * 512
+                            // N gains 512 h - ua at column i and ua back at i + 1; a cell left of the tile only adds its height to
+                            // everything right of it: 512 h to column 0  (|d|, |ua| < 2^14: the products are full-rate 24-bit multiplies)
+                            const int d = i < 0 ? h512 : h512 - ua;
+                            if (valid && i < TILE_W) {
+                                atomicAdd(&arow[max(i, 0)], 17 * d);
+                                if (i >= 0 && i + 1 < TILE_W) atomicAdd(&arow[i + 1], 17 * ua);   // (never into the padding columns)
+                            }
                         };
 #ifndef ABL_T_NOACC
                         add_cell(c0c, ck < n_c);
@@ -1638,37 +1645,30 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                             const int4 v0 = *a0, v1 = *a1;
                             *a0 = make_int4(0, 0, 0, 0); *a1 = make_int4(0, 0, 0, 0);
                             const int v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                            int ua[8], ch[8];
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) { ua[j] = (int)((uint32_t)v[j] << 12) >> 12; ch[j] = (v[j] - ua[j]) >> 20; }
 #pragma unroll
                             for (int h = 0; h < 2; ++h) {
-                                ch[4 * h + 1] += ch[4 * h]; ch[4 * h + 2] += ch[4 * h + 1]; ch[4 * h + 3] += ch[4 * h + 2];
-                                int t = ch[4 * h + 3];                       // this lane's four columns; inclusive scan over the DPP row = the pixel row
-#ifdef ABL_T_NOSCAN
-                                const int ex = 0;
-#else
+                                const int* d = v + 4 * h;
+                                int t = d[0] + d[1] + d[2] + d[3];           // this lane's four columns; inclusive scan over the DPP row = the pixel row
+#ifndef ABL_T_NOSCAN
                                 t += __builtin_amdgcn_update_dpp(0, t, 0x111, 0xf, 0xf, false);   // row_shr:1
                                 t += __builtin_amdgcn_update_dpp(0, t, 0x112, 0xf, 0xf, false);   // row_shr:2
                                 t += __builtin_amdgcn_update_dpp(0, t, 0x114, 0xf, 0xf, false);   // row_shr:4
                                 t += __builtin_amdgcn_update_dpp(0, t, 0x118, 0xf, 0xf, false);   // row_shr:8
-                                const int ex = t - ch[4 * h + 3];
 #endif
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) {
-                                    const int j = 4 * h + i;
-                                    al[j] = (uint32_t)((__mul24(ch[j] + ex, 512 * 17) - __mul24(ua[j], 17) + 256) >> 9) & 255u;
-                                }
+                                // P = 17 N + 256 at the lane's four columns, right to left (the 256 added once, after the scan: a constant in
+                                // column 0 of acc would hold a register across the strip loop); alpha = bits 9 .. 16 of P, one bit-field
+                                // extract whatever the sign: the same bits as Cairo's ((17 N + 256) >> 9) & 255
+                                const int p3 = t + 256;
+                                const int p2 = p3 - d[3], p1 = p2 - d[2], p0 = p1 - d[1];
+                                al[4 * h] = ((uint32_t)p0 >> 9) & 255u; al[4 * h + 1] = ((uint32_t)p1 >> 9) & 255u;
+                                al[4 * h + 2] = ((uint32_t)p2 >> 9) & 255u; al[4 * h + 3] = ((uint32_t)p3 >> 9) & 255u;
                             }
-                            // the converter's rectangle bounds what is painted (a cell at or beyond x_max is never emitted, so the coverage
-                            // may not return to zero there); wave-uniform tests: most pairs lie inside
-                            if (tx0 < e_xmin || tx0 + TILE_W > e_xmax) {
+                            // the converter's rectangle bounds what is painted: no cell lies left of the path's x_min (a cell's column is
+                            // unsigned and relative to it), but a cell at or beyond x_max is never emitted, so the coverage may not return
+                            // to zero there; wave-uniform test: most pairs lie inside
+                            if (tx0 + TILE_W > e_xmax) {
 #pragma unroll
-                                for (int j = 0; j < 8; ++j) { const int cx = cx0 + (j & 3); if (cx < e_xmin || cx >= e_xmax) al[j] = 0u; }
-                            }
-                            if (row_lo > 0 || row_hi < STRIP_H) {
-#pragma unroll
-                                for (int j = 0; j < 8; ++j) { const int rr = g + 4 * (j >> 2); if (rr < row_lo || rr >= row_hi) al[j] = 0u; }
+                                for (int i = 0; i < 4; ++i) if (cx0 >= e_xmax - i) { al[i] = 0u; al[4 + i] = 0u; }   // (column cx0 + i)
                             }
                         }
                     } else {
