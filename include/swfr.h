@@ -119,7 +119,21 @@ typedef struct {                         /* tags::DefineShape / tags::DefineMorp
 enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER = 2,
        SWFR_OBJECT_COLOR_TRANSFORM = 3   /* a container (matrix + children) whose `id` names a colour-transform slot (swfr_set_color_transform):
                                             the slot's value at the time of the render call applies to everything below it.  Beyond the
-                                            reference, whose display objects carry a matrix and a ratio only */ };
+                                            reference, whose display objects carry a matrix and a ratio only */,
+       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as is 6 and above) */
+       SWFR_OBJECT_BLEND_MODE = 5        /* a container (matrix + children) whose `id` is an SWF blend-mode number (SWFR_BLEND_*): every path
+                                            drawn below it is composited, each on its own, with the mode's Cairo operator -- what
+                                            CanvasRenderer would do if it set ctx.globalCompositeOperation before drawing the object.  It
+                                            draws nothing itself; the innermost mode wins, an inner SWFR_BLEND_NORMAL restores OVER.  There
+                                            is NO group isolation (Flash Player composites a blended clip as one layer: where paths of one
+                                            blended object overlap each other the result differs).  DESIGN.md, "Blend modes" */ };
+
+/* SWF blend-mode numbers (PlaceObject3, swf-tree BlendMode).  0, 1: OVER.  3..8, 13, 14: the Cairo operator of the same name
+   (CAIRO_OPERATOR_MULTIPLY, SCREEN, LIGHTEN, DARKEN, DIFFERENCE, ADD, OVERLAY, HARD_LIGHT).  LAYER, SUBTRACT, INVERT, ALPHA, ERASE have
+   no Cairo operator or need an isolated group: SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode".  Above 14: SWFR_ERR_INVALID. */
+enum { SWFR_BLEND_NORMAL0 = 0, SWFR_BLEND_NORMAL = 1, SWFR_BLEND_LAYER = 2, SWFR_BLEND_MULTIPLY = 3, SWFR_BLEND_SCREEN = 4,
+       SWFR_BLEND_LIGHTEN = 5, SWFR_BLEND_DARKEN = 6, SWFR_BLEND_DIFFERENCE = 7, SWFR_BLEND_ADD = 8, SWFR_BLEND_SUBTRACT = 9,
+       SWFR_BLEND_INVERT = 10, SWFR_BLEND_ALPHA = 11, SWFR_BLEND_ERASE = 12, SWFR_BLEND_OVERLAY = 13, SWFR_BLEND_HARDLIGHT = 14 };
 
 typedef struct swfr_display_object {
     uint32_t type;                       /* SWFR_OBJECT_* (ts/src/lib/display/display-object-type.ts) */
@@ -216,9 +230,15 @@ typedef struct {
     uint32_t kind;                       /* SWFR_PATH_* */
     uint32_t fill_rule;                  /* 0 nonzero, 1 even-odd */
     uint32_t style;                      /* index into styles */
-    uint32_t lerp;                       /* 1: SOURCE-lerp blend (opaque source or clear surface), 0: OVER */
+    uint32_t lerp;                       /* bits 0..7: 1: SOURCE-lerp blend (opaque source or clear surface), 0: OVER;
+                                            bits 8..15: operator (SWFR_OP_*), 0: what bits 0..7 say.  An operator needs lerp bits 0
+                                            (SWFR_ERR_INVALID at upload otherwise); the rest of the word must be 0 */
     int32_t x_min, y_min, x_max, y_max;  /* pixel rectangle of the converter (polygon extents ∩ frame) */
 } swfr_path;
+
+/* The operator of a path (swfr_path::lerp >> 8): pixman's unified combiner of that name applied to mul_un8(source pixel, coverage). */
+enum { SWFR_OP_OVER = 0, SWFR_OP_MULTIPLY = 1, SWFR_OP_SCREEN = 2, SWFR_OP_LIGHTEN = 3, SWFR_OP_DARKEN = 4, SWFR_OP_DIFFERENCE = 5,
+       SWFR_OP_ADD = 6, SWFR_OP_OVERLAY = 7, SWFR_OP_HARDLIGHT = 8 };
 
 enum { SWFR_STYLE_SOLID = 0, SWFR_STYLE_RADIAL = 1, SWFR_STYLE_LINEAR = 2, SWFR_STYLE_BITMAP = 3 };
 #define SWFR_MAX_STOPS 16

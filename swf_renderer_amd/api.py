@@ -36,6 +36,24 @@ EXPORTS = [
     "swfr_set_color_transform", "swfr_debug_time_cxform",
 ]
 OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
+OBJECT_BLEND_MODE = 5
+# SWF blend-mode numbers under swf-tree's names (BlendMode); what the library does with each is swfr.h's SWFR_BLEND_* comment
+BLEND_MODES = {"normal": 1, "layer": 2, "multiply": 3, "screen": 4, "lighten": 5, "darken": 6, "difference": 7, "add": 8,
+               "subtract": 9, "invert": 10, "alpha": 11, "erase": 12, "overlay": 13, "hardlight": 14}
+# operators of a low-level path (swfr_path::lerp >> 8, swfr.h SWFR_OP_*)
+PATH_OPERATORS = {"over": 0, "multiply": 1, "screen": 2, "lighten": 3, "darken": 4, "difference": 5, "add": 6, "overlay": 7, "hardlight": 8}
+
+
+def blend_mode_number(mode) -> int:
+    """the SWF number of a "blend_mode" value: one of swf-tree's names (any case; "hard-light" / "hard_light" too), or the number"""
+    if isinstance(mode, str):
+        key = mode.lower().replace("-", "").replace("_", "")
+        if key not in BLEND_MODES:
+            raise SwfrError(ERR_INVALID, "InvalidBlendMode: %r" % (mode,))
+        return BLEND_MODES[key]
+    if isinstance(mode, bool) or int(mode) != mode or not 0 <= int(mode) < 2 ** 32:
+        raise SwfrError(ERR_INVALID, "InvalidBlendMode: %r" % (mode,))
+    return int(mode)
 VARIANT_BASE = 65536                    # a bitmap style's `bitmap` at or above it names a colour-transformed texture of the frame
 
 
@@ -507,6 +525,15 @@ class Renderer:
         if obj.get("matrix") is not None:
             d.has_matrix = 1
             d.matrix = _matrix(obj["matrix"])
+        if obj.get("blend_mode") is not None:
+            # the object inside a type-5 wrapper (outside its colour-transform wrapper, if any: the two commute); the matrix stays inside
+            w = DisplayObject()
+            w.type, w.id = OBJECT_BLEND_MODE, blend_mode_number(obj["blend_mode"])
+            inner = dict(obj)
+            del inner["blend_mode"]
+            kids = arena.array(DisplayObject, [self._object(arena, inner)])
+            w.n_children, w.children = 1, C.cast(kids, C.POINTER(DisplayObject))
+            return w
         ct = obj.get("color_transform")
         if t == "container":
             d.type = OBJECT_CONTAINER if ct is None else OBJECT_COLOR_TRANSFORM

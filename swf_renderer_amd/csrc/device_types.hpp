@@ -237,6 +237,9 @@ struct Frame2 {
     uint32_t band_first, band_stride;   // the handle's tile-rows: band_first + l * band_stride, l < n_strips / (STRIPS_PER_TILE * tiles_x)
                                         // (interleaved over the ranks: stride = ranks; one contiguous block per rank: stride = 1)
     uint32_t mono;           // 1: SWFR_FLAG_ANTIALIAS_NONE -- tor paths are converted at pixel centres by k2_rows_mono (mono.hip)
+    const uint8_t* path_op;  // per path: its operator (SWFR_OP_*), read by k2_tiles<3> alone; nullptr in a frame without a blended path.
+                             // The path records themselves carry lerp & 1 only -- 0 for every blended path -- so that nothing k2_bin and
+                             // the row kernels derive from "lerp is not zero" (BE_LERP, opaque covers, culling) can fire for one
 };
 
 }  // namespace swfr

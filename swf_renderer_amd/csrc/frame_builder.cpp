@@ -40,6 +40,28 @@ Css morph_color(const swfr_rgba8& s, const swfr_rgba8& e, bool morph, double rat
                      lerp(s.b / 255.0, e.b / 255.0, ratio), lerp(s.a / 255.0, e.a / 255.0, ratio));
 }
 
+// SWF blend-mode number -> path operator ("Blend modes"): the eight modes Cairo has an operator for; the others need an
+// isolated group (layer, alpha, erase) or have no Cairo operator (subtract, invert)
+uint32_t blend_operator(uint32_t mode) {
+    switch (mode) {
+        case SWFR_BLEND_NORMAL0: case SWFR_BLEND_NORMAL: return SWFR_OP_OVER;
+        case SWFR_BLEND_MULTIPLY: return SWFR_OP_MULTIPLY;
+        case SWFR_BLEND_SCREEN: return SWFR_OP_SCREEN;
+        case SWFR_BLEND_LIGHTEN: return SWFR_OP_LIGHTEN;
+        case SWFR_BLEND_DARKEN: return SWFR_OP_DARKEN;
+        case SWFR_BLEND_DIFFERENCE: return SWFR_OP_DIFFERENCE;
+        case SWFR_BLEND_ADD: return SWFR_OP_ADD;
+        case SWFR_BLEND_OVERLAY: return SWFR_OP_OVERLAY;
+        case SWFR_BLEND_HARDLIGHT: return SWFR_OP_HARDLIGHT;
+        default: break;
+    }
+    if (mode <= SWFR_BLEND_HARDLIGHT) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode"};
+    throw StatusError{SWFR_ERR_INVALID, "InvalidBlendMode"};
+}
+// a path's blend field once it is known whether the surface was still clear when it was drawn: "2" (a lerp only because nothing was
+// painted yet -- an OVER or an ADD path) becomes the SOURCE lerp, or what the path is otherwise: OVER, or its operator
+inline uint32_t settle_lerp(uint32_t lerp, bool clear) { return (lerp & 0xffu) == 2u ? (clear ? 1u : (lerp & ~0xffu)) : lerp; }
+
 }  // namespace
 
 bool color_transform_valid(const swfr_color_transform& ct) {
@@ -209,6 +231,7 @@ void FrameBuilder::build_range(const std::vector<const swfr_display_object*>& wr
                 if (it == store()->cxforms_.end()) throw StatusError{SWFR_ERR_NOT_FOUND, "ColorTransformNotFound"};
                 stack_.back().lut = compose(stack_.back().lut, it->second);
             }
+            if (w->type == SWFR_OBJECT_BLEND_MODE) stack_.back().op = blend_operator(w->id);
         }
         for (uint32_t i = lo; i < hi; ++i) draw(kids[i], int(wraps.size()));
     } catch (const StatusError& e) {
@@ -229,7 +252,7 @@ void FrameBuilder::copy_piece(FrameBuilder& dst, size_t edge_off, size_t path_of
         swfr_path p = paths_[i];
         p.first_edge += uint32_t(edge_off);
         p.style += uint32_t(style_off);
-        if (p.lerp == 2) p.lerp = clear_at_start ? 1 : 0;       // (inside the piece the flag is only ever 2 while nothing was painted)
+        p.lerp = settle_lerp(p.lerp, clear_at_start);           // (inside the piece the flag is only ever 2 while nothing was painted)
         dst.paths_[path_off + i] = p;
     }
     if (!styles_.empty()) std::memcpy(&dst.styles_[style_off], styles_.data(), styles_.size() * sizeof(swfr_style));
@@ -247,13 +270,13 @@ void FrameBuilder::build(const swfr_stage& stage) {
         want = env ? std::atoi(env) : int(std::min(8u, std::max(1u, std::thread::hardware_concurrency())));
         threads_ = want;
     }
-    // The objects that are cut into pieces: the stage's children -- or, when the stage holds one container or colour-transform wrapper
-    // (a whole clip under one fade), that wrapper's children, through up to 16 such single wrappers.  A piece then walks its share of them
+    // The objects that are cut into pieces: the stage's children -- or, when the stage holds one container, colour-transform or
+    // blend-mode wrapper (a whole clip under one fade), that wrapper's children, through up to 16 such single wrappers.  A piece then walks its share of them
     // inside the wrappers' state, which is what a single walk does: the wrappers draw nothing themselves.
     std::vector<const swfr_display_object*> wraps;
     const swfr_display_object* kids = stage.children;
     uint32_t n_kids = stage.n_children;
-    while (n_kids == 1 && wraps.size() < 16 && (kids[0].type == SWFR_OBJECT_CONTAINER || kids[0].type == SWFR_OBJECT_COLOR_TRANSFORM)) {
+    while (n_kids == 1 && wraps.size() < 16 && (kids[0].type == SWFR_OBJECT_CONTAINER || kids[0].type == SWFR_OBJECT_COLOR_TRANSFORM || kids[0].type == SWFR_OBJECT_BLEND_MODE)) {
         wraps.push_back(&kids[0]);
         n_kids = kids[0].n_children;
         kids = kids[0].children;
@@ -263,7 +286,7 @@ void FrameBuilder::build(const swfr_stage& stage) {
     if (pieces < 2) {
         build_range({}, stage.children, 0, stage.n_children);
         if (failed_) throw failure_;
-        for (swfr_path& p : paths_) if (p.lerp == 2) p.lerp = 1;
+        for (swfr_path& p : paths_) p.lerp = settle_lerp(p.lerp, true);
         return;
     }
     if (!pool_) pool_.reset(new Pool);
@@ -333,6 +356,10 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
             for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
             break;
         }
+        case SWFR_OBJECT_BLEND_MODE:
+            stack_.back().op = blend_operator(obj.id);
+            for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
+            break;
         case SWFR_OBJECT_SHAPE: {
             const DecodedShape* sh = shape(obj.id, false);
             if (!sh) throw StatusError{SWFR_ERR_NOT_FOUND, "unknown shape id"};
@@ -441,7 +468,12 @@ void FrameBuilder::emit_polygon(Polygon& poly, bool rectilinear, uint32_t style,
     p.first_edge = uint32_t(edges_.size());
     p.fill_rule = even_odd_ ? 1 : 0;
     p.style = style;
-    p.lerp = opaque_solid ? 1 : (surface_clear_ ? 2 : 0);      // 2: a lerp only because the surface is still clear (settled by build())
+    // 2: a lerp only because the surface is still clear (settled by build()).  A blended path is never a lerp -- an opaque colour under
+    // MULTIPLY is not "opaque" for any shortcut -- except that Cairo turns ADD on a still-clear surface into SOURCE, as it does OVER
+    const uint32_t op = stack_.back().op;
+    if (op == SWFR_OP_OVER) p.lerp = opaque_solid ? 1 : (surface_clear_ ? 2 : 0);
+    else if (op == SWFR_OP_ADD) p.lerp = (op << 8) | (surface_clear_ ? 2u : 0u);
+    else p.lerp = op << 8;
     (void)lerp_blend;
     // converter rectangle: the polygon's extents inside the operation's bounded rectangle (the frame for fills)
     p.x_min = std::max(floor_px(poly.ext_min().x), std::max(bx0, 0));
@@ -487,7 +519,7 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
     // context.save(); <source>; fill(); context.restore()  (canvas-renderer.ts:292-336)
     if (s.type == SWFR_FILL_SOLID) {
         const uint32_t px = premultiplied_pixel(morph_color(cx(s.color), cx(s.morph_color), morph, ratio));
-        if ((px >> 24) == 0) return;  // Cairo: OVER with a clear source is a no-op
+        if ((px >> 24) == 0 && clear_source_is_noop()) return;  // Cairo: OVER (and ADD) with a clear source is a no-op
         opaque_solid = (px >> 24) == 0xff;
         style_index = push_solid(px);
     } else if (s.type == SWFR_FILL_BITMAP) {
@@ -545,7 +577,7 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         }
         // a gradient whose stops are all transparent is a clear source (_cairo_pattern_is_clear -> _gradient_is_clear): OVER with
         // it is a no-op that leaves the surface's "clear" state alone, like the transparent solid above
-        if (std::all_of(stops.begin(), stops.end(), [](const swfr_color_stop& c) { return c.color.a == 0; })) return;
+        if (clear_source_is_noop() && std::all_of(stops.begin(), stops.end(), [](const swfr_color_stop& c) { return c.color.a == 0; })) return;
         styles_.push_back(st);
         style_index = uint32_t(styles_.size() - 1);
     }
@@ -607,7 +639,7 @@ void FrameBuilder::emit_stroke(const StyledPath& p, bool morph, double ratio) {
     if (width > 0) st.line_width = width;  // node-canvas ignores non-positive widths
     const uint32_t px = premultiplied_pixel(morph_color(cx(p.fill.style.color), cx(p.fill.style.morph_color), morph, ratio));
     if (morph) st.cap = st.join = 1;  // lineCap = lineJoin = "round" (canvas-renderer.ts:263-264)
-    if ((px >> 24) == 0) return;
+    if ((px >> 24) == 0 && clear_source_is_noop()) return;
     if (path_.empty_extents()) return;
     // _cairo_compositor_stroke: a pen that degenerates to one vertex (line width <= tolerance/2 = 0.05 device pixels under the CTM)
     // paints nothing, whatever the stroker; the surface stays untouched

@@ -74,6 +74,7 @@ private:
         double line_width = 1.0;  // node-canvas creates its context with line width 1
         int cap = 0, join = 0;
         int32_t lut = -1;         // colour-transform chain: index into luts_, -1 identity
+        uint32_t op = 0;          // blend mode of the innermost SWFR_OBJECT_BLEND_MODE wrapper as a path operator (SWFR_OP_*), 0: OVER
     };
     void draw(const swfr_display_object& obj, int depth);
     void draw_path(const StyledPath& p, bool morph, double ratio);
@@ -82,6 +83,9 @@ private:
     void emit_stroke(const StyledPath& p, bool morph, double ratio);
     void emit_polygon(Polygon& poly, bool rectilinear, uint32_t style, bool opaque_solid, int bx0 = 0, int by0 = 0, int bx1 = INT32_MAX, int by1 = INT32_MAX);
     uint32_t push_solid(uint32_t pixel);
+    // Cairo drops a drawing operation with a clear source only under OVER and ADD; under the other operators it changes no pixel
+    // either but is an operation like any other: the surface no longer counts as clear behind it
+    bool clear_source_is_noop() const { return stack_.back().op == SWFR_OP_OVER || stack_.back().op == SWFR_OP_ADD; }
     swfr_rgba8 cx(const swfr_rgba8& c) const;                  // the current chain applied to a straight colour
     int32_t compose(int32_t outer, const swfr_color_transform& inner);   // chain `outer` after `inner`: an index into luts_ (-1: identity)
     uint32_t variant_of(uint32_t bitmap, int32_t lut);         // this builder's texture index of (bitmap, chain)

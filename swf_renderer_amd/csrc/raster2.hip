@@ -1216,7 +1216,7 @@ __device__ __forceinline__ uint32_t shade_bitmap(uint32_t style_index, const Sou
     bilinear_taps(flt, px, py, t);
     return bilinear_mix(t, flt.pixels + t.o[0][0], flt.pixels + t.o[1][0], flt.pixels + t.o[0][1], flt.pixels + t.o[1][1]);
 }
-// SHADERS: 0 solid colours only, 1 + bitmaps, 2 + gradients
+// SHADERS: 0 solid colours only, 1 + bitmaps, 2 + gradients, 3 + blend operators (what an unblended entry gets is instance 2's)
 template <int SHADERS>
 __device__ __forceinline__ uint32_t blend2(uint32_t dst, uint32_t a, uint32_t eflags, uint32_t solid, const swfr_style* __restrict__ styles,
                                            uint32_t style, const Sources& src, int cx, int cy) {
@@ -1401,6 +1401,107 @@ __device__ __forceinline__ void blend8(uint32_t (&px)[8], const uint32_t (&al)[8
     for (int j = 0; j < 8; ++j) if (al[j]) px[j] = blend2<SHADERS>(px[j], al[j], eflags, solid, styles, style, src, cx0 + (j & 3), cy0 + 4 * (j >> 2));
 }
 
+#ifndef T2_WAVES_BLEND
+#define T2_WAVES_BLEND 3              // the blend instance of k2_tiles: 160 VGPRs, no scratch; at four wavefronts per SIMD (128 VGPRs) it spills 46
+#endif
+// ---------------------------------------------------------------------------------------------
+// blend operators (k2_tiles<3>; DESIGN.md, "Blend modes"): pixman's unified combiners on premultiplied 0xAARRGGBB pixels, s = the
+// source pixel times the coverage, d = the destination.  At s = 0 every one of them returns d.  Integers only, no division:
+// DIV1(x) = (x + 0x80 + ((x + 0x80) >> 8)) >> 8; every product is a full-rate 24-bit multiply (all factors < 2^17)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t mul8x2_80_24(uint32_t x, uint32_t a) {       // two channels (0x00ff00ff layout) times an 8-bit factor, 0x80 rounding
+    uint32_t t = __umul24(x, a) + 0x800080u;
+    return ((t + ((t >> 8) & 0xff00ffu)) >> 8) & 0xff00ffu;
+}
+__device__ __forceinline__ uint32_t mul8x2_8x2_80_24(uint32_t a, uint32_t b) {   // two channels times two channels (UN8x4_MUL_UN8x4, one half)
+    uint32_t t = __umul24(a & 0xffu, b & 0xffu) + (__umul24(a >> 16, b >> 16) << 16) + 0x800080u;
+    return ((t + ((t >> 8) & 0xff00ffu)) >> 8) & 0xff00ffu;
+}
+__device__ __forceinline__ uint32_t op_add(uint32_t s, uint32_t d) {
+    return add8x2_sat(d & 0xff00ffu, s & 0xff00ffu) | (add8x2_sat((d >> 8) & 0xff00ffu, (s >> 8) & 0xff00ffu) << 8);
+}
+// combine_multiply_u: d * s + (s * (255 - da) (+) d * (255 - sa)), (+) and + saturating, alpha channel included
+__device__ __forceinline__ uint32_t op_multiply(uint32_t s, uint32_t d) {
+    const uint32_t isa = 255u - (s >> 24), ida = 255u - (d >> 24);
+    const uint32_t s0 = s & 0xff00ffu, s1 = (s >> 8) & 0xff00ffu, d0 = d & 0xff00ffu, d1 = (d >> 8) & 0xff00ffu;
+    const uint32_t q0 = add8x2_sat(mul8x2_80_24(s0, ida), mul8x2_80_24(d0, isa));
+    const uint32_t q1 = add8x2_sat(mul8x2_80_24(s1, ida), mul8x2_80_24(d1, isa));
+    return add8x2_sat(mul8x2_8x2_80_24(d0, s0), q0) | (add8x2_sat(mul8x2_8x2_80_24(d1, s1), q1) << 8);
+}
+__device__ __forceinline__ uint32_t div1_un8(uint32_t x) { x += 0x80u; return (x + (x >> 8)) >> 8; }
+// pixman's separable PDF modes: B(d, da, s, sa) of one colour channel; sada = sa * da
+template <int OP>
+__device__ __forceinline__ int pdf_term(int d, int da, int s, int sa, int sada) {
+    if (OP == SWFR_OP_SCREEN) return mul_i24(s, da) + mul_i24(d, sa) - mul_i24(s, d);
+    if (OP == SWFR_OP_DARKEN) return min(mul_i24(s, da), mul_i24(d, sa));
+    if (OP == SWFR_OP_LIGHTEN) return max(mul_i24(s, da), mul_i24(d, sa));
+    if (OP == SWFR_OP_DIFFERENCE) return abs(mul_i24(d, sa) - mul_i24(s, da));
+    const bool low = OP == SWFR_OP_OVERLAY ? 2 * d < da : 2 * s < sa;              // overlay tests the destination, hard light the source
+    return low ? 2 * mul_i24(s, d) : sada - 2 * mul_i24(da - d, sa - s);
+}
+template <int OP>
+__device__ __forceinline__ uint32_t op_pdf(uint32_t s, uint32_t d) {
+    const int sa = (int)(s >> 24), da = (int)(d >> 24);
+    const int isa = 255 - sa, ida = 255 - da, sada = mul_i24(sa, da);                // shared by the three colour channels
+    uint32_t out = div1_un8((uint32_t)min(max(255 * (sa + da) - sada, 0), 65025)) << 24;
+#pragma unroll
+    for (int sh = 0; sh < 24; sh += 8) {
+        const int sc = (int)((s >> sh) & 255u), dc = (int)((d >> sh) & 255u);
+        const int x = mul_i24(isa, dc) + mul_i24(ida, sc) + pdf_term<OP>(dc, da, sc, sa, sada);      // < 3 * 65025
+        out |= div1_un8((uint32_t)min(max(x, 0), 65025)) << sh;
+    }
+    return out;
+}
+template <int OP>
+__device__ __forceinline__ uint32_t op_pixel(uint32_t s, uint32_t d) {
+    if (OP == SWFR_OP_ADD) return op_add(s, d);
+    if (OP == SWFR_OP_MULTIPLY) return op_multiply(s, d);
+    return op_pdf<OP>(s, d);
+}
+template <int OP>
+__device__ __forceinline__ void op_pixels4(uint32_t (&px)[4], const uint32_t (&sp)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) px[i] = op_pixel<OP>(sp[i], px[i]);
+}
+// The strip's eight pixels of one lane under a blended entry, one row half (a lane's four pixels of a row) at a time: the source
+// pixels (the colour, or the bitmap / gradient sample of the pixels with coverage) times the coverage, then ONE operator's code for
+// the four -- `op` is wave-uniform, the switch is a scalar branch.  No coverage-255 shortcut and no queue: an operator needs the
+// destination at every pixel of the path.  A pixel without coverage (s = 0) is left as it is by every operator, so a row half in which
+// no lane of the wavefront has coverage (rows outside the path's rectangle, the empty rows of a partial pair) is skipped as a whole.
+__device__ __forceinline__ void blend8_op(uint32_t (&px)[8], const uint32_t (&al)[8], uint32_t op, uint32_t eflags, uint32_t solid,
+                                          const swfr_style* __restrict__ styles, uint32_t style, const Sources& src, int cx0, int cy0) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (__ballot((al[4 * h] | al[4 * h + 1] | al[4 * h + 2] | al[4 * h + 3]) != 0u) == 0ull) continue;      // (wave-uniform)
+        uint32_t sp[4], p4[4] = {px[4 * h], px[4 * h + 1], px[4 * h + 2], px[4 * h + 3]};
+        if (eflags & BE_SOLID) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sp[i] = mul_un8_24(solid, al[4 * h + i]);
+        } else {
+            const bool bitmap = src.filters[style].kind == SWFR_STYLE_BITMAP;         // (wave-uniform)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t a = al[4 * h + i];
+                uint32_t c = 0u;
+                if (a) c = bitmap ? shade_bitmap(style, src, cx0 + i, cy0 + 4 * h) : shade(styles[style], style, src, cx0 + i, cy0 + 4 * h);
+                sp[i] = mul_un8_24(c, a);
+            }
+        }
+        switch (op) {
+            case SWFR_OP_MULTIPLY: op_pixels4<SWFR_OP_MULTIPLY>(p4, sp); break;
+            case SWFR_OP_SCREEN: op_pixels4<SWFR_OP_SCREEN>(p4, sp); break;
+            case SWFR_OP_LIGHTEN: op_pixels4<SWFR_OP_LIGHTEN>(p4, sp); break;
+            case SWFR_OP_DARKEN: op_pixels4<SWFR_OP_DARKEN>(p4, sp); break;
+            case SWFR_OP_DIFFERENCE: op_pixels4<SWFR_OP_DIFFERENCE>(p4, sp); break;
+            case SWFR_OP_ADD: op_pixels4<SWFR_OP_ADD>(p4, sp); break;
+            case SWFR_OP_OVERLAY: op_pixels4<SWFR_OP_OVERLAY>(p4, sp); break;
+            default: op_pixels4<SWFR_OP_HARDLIGHT>(p4, sp); break;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) px[4 * h + i] = p4[i];
+    }
+}
+
 template <int SHADERS>
 __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     // per pixel: deltas whose prefix sum along the row is 17 * N(x), N = Cairo's coverage numerator 512 * H(x) - ua(x) (H: the heights
@@ -1540,6 +1641,9 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     }
                     uint4* e4 = reinterpret_cast<uint4*>(&ent[rank][0]);
                     e4[0] = q0; e4[1] = q1; ent[rank][8] = f;
+                    // (instance 3: the path's operator beside its entry; a frame without a blended path -- in a batch that has one, or
+                    //  forced through this instance -- has no table)
+                    if constexpr (SHADERS == 3) ent[rank][9] = FR->path_op ? (uint32_t)FR->path_op[q1.w] : 0u;
                     if (part) { uint4* d4 = reinterpret_cast<uint4*>(&hdr[rank][0]); d4[0] = h0; d4[1] = h1; d4[2] = h2; d4[3] = h3; }
                 }
                 lds_barrier();
@@ -1558,6 +1662,8 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     const int e_ymin = (int)(int16_t)(yw & 0xffffu), e_ymax = (int)(int16_t)(yw >> 16);
                     const uint32_t eflags = (uint32_t)__builtin_amdgcn_readfirstlane((int)ea.z), solid = (uint32_t)__builtin_amdgcn_readfirstlane((int)ea.w);
                     const uint32_t style = (uint32_t)__builtin_amdgcn_readfirstlane((int)eb.x);
+                    uint32_t op = 0u;                                    // the entry's blend operator (wave-uniform; instance 3 only)
+                    if constexpr (SHADERS == 3) op = (uint32_t)__builtin_amdgcn_readfirstlane((int)ent[li][9]);
                     const int row_lo = max(e_ymin, ty0) - ty0, row_hi = min(min(e_ymax, ty0 + STRIP_H), height) - ty0;
                     if (row_hi <= row_lo) continue;                    // the path misses this strip of the tile
                     STAT(2, 1);
@@ -1674,7 +1780,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     } else {
                         // full cover: every in-frame pixel of the path's rows in this tile has coverage 255
                         const bool in0 = g >= row_lo && g < row_hi, in1 = g + 4 >= row_lo && g + 4 < row_hi;
-                        if ((SHADERS == 0 || (eflags & BE_SOLID)) && ((eflags & BE_LERP) || (solid >> 24) == 0xffu)) {     // (wave-uniform) the colour itself
+                        if ((SHADERS < 3 || op == 0u) && (SHADERS == 0 || (eflags & BE_SOLID)) && ((eflags & BE_LERP) || (solid >> 24) == 0xffu)) {     // (wave-uniform) the colour itself
 #pragma unroll
                             for (int j = 0; j < 4; ++j) { px[j] = in0 ? solid : px[j]; px[4 + j] = in1 ? solid : px[4 + j]; }
                             continue;
@@ -1685,6 +1791,9 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
 #ifdef ABL_T_NOBLEND
                     for (int j = 0; j < 8; ++j) px[j] = al[j] == 255u ? solid : px[j];
 #else
+                    if constexpr (SHADERS == 3) {
+                        if (op) { blend8_op(px, al, op, eflags, solid, styles, style, bitmaps, cx0, cy0); continue; }   // (wave-uniform)
+                    }
                     blend8<SHADERS>(px, al, eflags, solid, styles, style, bitmaps, cx0, cy0, bq, lane);
 #endif
                 }
@@ -1740,6 +1849,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES))) 
 #endif
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_SHADED))) void k2_tiles_bitmap_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<1>(FRAME_PTR(frames, blockIdx.y), fb_to); }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_SHADED))) void k2_tiles_shaded_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<2>(FRAME_PTR(frames, blockIdx.y), fb_to); }
+// frames with a blended path (swfr_path::lerp >> 8): everything the shaded instance does, plus the eight blend operators
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_BLEND))) void k2_tiles_blend_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<3>(FRAME_PTR(frames, blockIdx.y), fb_to); }
 
 // ---------------------------------------------------------------------------------------------
 // launchers: `frames` is a device array of n_frames descriptors, blockIdx.y picks one
@@ -1778,7 +1889,8 @@ void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint
     // smaller frames do not fill the GPU and keep one wavefront per strip.
     uint32_t g = max_strips < grid_cap ? max_strips : grid_cap;
     if (grid_cap == ~0u && max_strips > T3_PAIR_FROM) g = (max_strips + 1u) / 2u;
-    if (shader_level >= 2) hipLaunchKernelGGL(k2_tiles_shaded_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    if (shader_level >= 3) hipLaunchKernelGGL(k2_tiles_blend_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    else if (shader_level >= 2) hipLaunchKernelGGL(k2_tiles_shaded_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 1) hipLaunchKernelGGL(k2_tiles_bitmap_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else hipLaunchKernelGGL(k2_tiles_solid_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
 }

@@ -256,7 +256,7 @@ struct swfr_renderer {
     bool mono = false;                      // SWFR_FLAG_ANTIALIAS_NONE: boxes rounded to pixels, tor paths by k2_rows_mono (Frame2::mono)
     int fast_limit = 16;                    // rows with more active edges go to k2_rows_slow; the row kernel's instance caps it at its 8 or 16 slots (SWFR_FAST_LIMIT: test knob)
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
-    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded; test knob)
+    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators; test knob)
     bool rows_wide = false;                 // SWFR_ROWS_WIDE=1: every frame with tor paths runs k2_rows_wide (test knob; aliased frames keep k2_rows_mono)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
     // the host builds one while the GPU works on the other
@@ -366,6 +366,15 @@ uint32_t local_tile_rows(const swfr_renderer* r) { return band_share(r).count; }
 // scene is uploaded (the tile pass clears a strip's record again when it has read it).
 inline size_t cls_bytes_of(size_t n_slots, size_t tiles_x) { return (size_t(STRIPS_PER_TILE) * n_slots * tiles_x + 64 + 15) & ~size_t(15); }
 inline size_t cls_region_bytes(size_t n_slots, size_t tiles_x, size_t n_strips) { return cls_bytes_of(n_slots, tiles_x) + (n_strips + 1) * sizeof(StripTop); }
+
+// swfr_path::lerp is lerp | operator << 8: an operator is never a SOURCE lerp
+void validate_blend_fields(const swfr_path* paths, size_t n_paths) {
+    for (size_t i = 0; i < n_paths; ++i) {
+        const uint32_t v = paths[i].lerp;
+        if ((v & 0xffu) > 1u || (v >> 8) > SWFR_OP_HARDLIGHT || ((v >> 8) != 0u && (v & 0xffu) != 0u))
+            throw StatusError{SWFR_ERR_INVALID, "path blend field: lerp must be 0 or 1, the operator at most 8, and lerp 0 with an operator"};
+    }
+}
 
 void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
                     const swfr_style* styles, size_t n_styles) {
@@ -636,7 +645,8 @@ struct SceneLayout {
     bool any_shader = false;
     uint32_t max_path_edges = 0;
     bool rows_wide = false;     // the row kernel's wide instance although no path has more than ROWS_STAGE edges (SWFR_ROWS_WIDE)
-    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients: picks the tile kernel's instance
+    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators: picks the tile kernel's instance
+    bool any_blend = false;     // some path carries an operator (swfr_path::lerp >> 8): the arena gets the path_op table
     std::vector<uint32_t> chunk_base, slot_base, inc_base, band_off;
     std::vector<uint32_t> band_span;     // per path: first tile-row | last tile-row << 16 of its rectangle (0xffff | 0 << 16: none); padded to a multiple of 16 paths
     std::vector<DevFilter> filters;
@@ -672,6 +682,10 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
         L.any_shader = L.any_shader || styles[i].kind != SWFR_STYLE_SOLID;
         L.shader_level = std::max(L.shader_level, styles[i].kind == SWFR_STYLE_SOLID ? 0 : (styles[i].kind == SWFR_STYLE_BITMAP ? 1 : 2));
     }
+    uint32_t blend_bits = 0;
+    for (size_t i = 0; i < n_paths; ++i) blend_bits |= paths[i].lerp;
+    L.any_blend = (blend_bits >> 8) != 0u;
+    if (L.any_blend) L.shader_level = 3;
     // (the test knobs: a higher instance than the frame needs -- with the style table in its full format -- and the wide row kernel)
     L.shader_level = std::max(L.shader_level, r->tiles_shaders);
     L.rows_wide = r->rows_wide;
@@ -753,7 +767,7 @@ size_t scene_arena_bytes(const SceneLayout& L, size_t n_edges, size_t n_paths, s
     // (a scene of solid colours only: the styles' {kind, pixel} heads, no filter records)
     return P(n_edges * sizeof(swfr_edge)) + P(n_paths * sizeof(swfr_path)) + (L.shader_level == 0 ? P(n_styles * 8) : P(n_styles * sizeof(swfr_style)) + P(n_styles * sizeof(DevFilter))) +
            P(L.fparams.size() * sizeof(int32_t)) + P(L.gradients.size() * sizeof(DevGradient)) + 3 * P((n_paths + 1) * sizeof(uint32_t)) +
-           P((L.n_bands + 2) * sizeof(uint32_t)) + P(L.band_span.size() * sizeof(uint32_t));
+           P((L.n_bands + 2) * sizeof(uint32_t)) + P(L.band_span.size() * sizeof(uint32_t)) + (L.any_blend ? P(n_paths + 64) : 0);
 }
 // pushes that part and fills the descriptor's scene fields; the edge array's host staging copy is returned (for tagging)
 swfr_edge* push_scene(SceneArena& A, const SceneLayout& L, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
@@ -781,6 +795,16 @@ swfr_edge* push_scene(SceneArena& A, const SceneLayout& L, const swfr_edge* edge
     f.path_inc = static_cast<uint32_t*>(A.push(L.inc_base.data(), (n_paths + 1) * sizeof(uint32_t)));
     f.band_off = static_cast<uint32_t*>(A.push(L.band_off.data(), (L.n_bands + 2) * sizeof(uint32_t)));
     f.path_bands = static_cast<uint32_t*>(A.push(L.band_span.data(), L.band_span.size() * sizeof(uint32_t)));
+    f.path_op = nullptr;
+    if (L.any_blend) {
+        // the ABI's blend field split: the device's path record keeps lerp & 1 (0 for a blended path: no kernel may take one for a lerp
+        // or a cover), the operator goes to a table of its own that only k2_tiles<3> reads
+        swfr_path* staged_paths = reinterpret_cast<swfr_path*>(A.host + (reinterpret_cast<const uint8_t*>(f.paths) - A.dev));
+        uint8_t* ops = A.host + A.used;
+        for (size_t i = 0; i < n_paths; ++i) { ops[i] = uint8_t(staged_paths[i].lerp >> 8); staged_paths[i].lerp &= 1u; }
+        std::memset(ops + n_paths, 0, 64);
+        f.path_op = static_cast<const uint8_t*>(A.push(nullptr, n_paths + 64));
+    }
     return staged;
 }
 void fill_frame_sizes(const swfr_renderer* r, const SceneLayout& L, size_t n_edges, size_t n_paths, Frame2& f) {
@@ -1054,6 +1078,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
 // Uploads a caller-supplied scene (validated first) into scene slot `si`; see upload2.
 int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
            const swfr_style* styles, size_t n_styles, uint32_t* fb_override = nullptr) {
+    validate_blend_fields(paths, n_paths);                       // (a malformed blend field is refused as such even by a host-only handle)
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
     validate_scene(r, edges, n_edges, paths, n_paths, styles, n_styles);
     return upload2(r, si, all_sets, edges, n_edges, paths, n_paths, styles, n_styles, fb_override, false);
@@ -1655,7 +1680,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
-    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 2);
+    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 3);
     if (const char* rw = std::getenv("SWFR_ROWS_WIDE")) r->rows_wide = std::atoi(rw) != 0;
     if (const char* bf = std::getenv("SWFR_BATCH_FRAMES")) r->batch_frames = std::max(1, std::atoi(bf));
     if (const char* cr = std::getenv("SWFR_CHUNK_ROWS")) r->force_chunk_rows = std::atoi(cr);
