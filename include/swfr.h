@@ -120,17 +120,28 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
        SWFR_OBJECT_COLOR_TRANSFORM = 3   /* a container (matrix + children) whose `id` names a colour-transform slot (swfr_set_color_transform):
                                             the slot's value at the time of the render call applies to everything below it.  Beyond the
                                             reference, whose display objects carry a matrix and a ratio only */,
-       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as is 6 and above) */
-       SWFR_OBJECT_BLEND_MODE = 5        /* a container (matrix + children) whose `id` is an SWF blend-mode number (SWFR_BLEND_*): every path
+       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7 and 9 and above) */
+       SWFR_OBJECT_BLEND_MODE = 5,       /* a container (matrix + children) whose `id` is an SWF blend-mode number (SWFR_BLEND_*): every path
                                             drawn below it is composited, each on its own, with the mode's Cairo operator -- what
                                             CanvasRenderer would do if it set ctx.globalCompositeOperation before drawing the object.  It
-                                            draws nothing itself; the innermost mode wins, an inner SWFR_BLEND_NORMAL restores OVER.  There
-                                            is NO group isolation (Flash Player composites a blended clip as one layer: where paths of one
-                                            blended object overlap each other the result differs).  DESIGN.md, "Blend modes" */ };
+                                            draws nothing itself; the innermost mode wins, an inner SWFR_BLEND_NORMAL restores OVER.  The
+                                            paths are NOT composited as one layer: that is SWFR_OBJECT_LAYER.  DESIGN.md, "Blend modes" */
+       SWFR_OBJECT_LAYER = 8             /* an isolated group: a container (matrix + children) whose children are drawn onto a transparent
+                                            surface of the frame's size, which is then composited onto the parent as ONE layer with the
+                                            operator of the SWF blend-mode number in `id` -- cairo_push_group; the children;
+                                            cairo_pop_group_to_source; cairo_set_operator; cairo_paint.  0, 1, 2 (normal, layer): OVER;
+                                            3..8, 13, 14: the mode's operator; 9..12: SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode";
+                                            above 14: SWFR_ERR_INVALID.  A SWFR_OBJECT_BLEND_MODE in force around the layer still applies
+                                            per path inside it, against the layer's own pixels.  Layers nest up to SWFR_MAX_LAYER_DEPTH
+                                            deep: deeper is SWFR_ERR_CAPACITY, "LayerDepth".  No layer opacity, no masks; a colour
+                                            transform around a layer recolours the definitions below it, it does not fade the layer as
+                                            a whole.  DESIGN.md, "Isolated layers" */ };
+#define SWFR_MAX_LAYER_DEPTH 4
 
 /* SWF blend-mode numbers (PlaceObject3, swf-tree BlendMode).  0, 1: OVER.  3..8, 13, 14: the Cairo operator of the same name
-   (CAIRO_OPERATOR_MULTIPLY, SCREEN, LIGHTEN, DARKEN, DIFFERENCE, ADD, OVERLAY, HARD_LIGHT).  LAYER, SUBTRACT, INVERT, ALPHA, ERASE have
-   no Cairo operator or need an isolated group: SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode".  Above 14: SWFR_ERR_INVALID. */
+   (CAIRO_OPERATOR_MULTIPLY, SCREEN, LIGHTEN, DARKEN, DIFFERENCE, ADD, OVERLAY, HARD_LIGHT).  SUBTRACT, INVERT, ALPHA, ERASE have no
+   Cairo operator or act on a parent layer's alpha, and LAYER means nothing for a SWFR_OBJECT_BLEND_MODE (it is SWFR_OBJECT_LAYER's
+   OVER): SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode".  Above 14: SWFR_ERR_INVALID. */
 enum { SWFR_BLEND_NORMAL0 = 0, SWFR_BLEND_NORMAL = 1, SWFR_BLEND_LAYER = 2, SWFR_BLEND_MULTIPLY = 3, SWFR_BLEND_SCREEN = 4,
        SWFR_BLEND_LIGHTEN = 5, SWFR_BLEND_DARKEN = 6, SWFR_BLEND_DIFFERENCE = 7, SWFR_BLEND_ADD = 8, SWFR_BLEND_SUBTRACT = 9,
        SWFR_BLEND_INVERT = 10, SWFR_BLEND_ALPHA = 11, SWFR_BLEND_ERASE = 12, SWFR_BLEND_OVERLAY = 13, SWFR_BLEND_HARDLIGHT = 14 };
@@ -223,7 +234,13 @@ int  swfr_render_sequence_readback(swfr_renderer *r, const swfr_stage *stages, u
 typedef struct { int32_t x1, y1, x2, y2, top, bottom, dir, reserved; } swfr_edge;
 
 enum { SWFR_PATH_TOR = 0,   /* general polygon: Cairo "tor" 15x256 scan conversion */
-       SWFR_PATH_BOXES = 1  /* rectilinear: `edges` hold disjoint boxes (x1,y1)-(x2,y2) */ };
+       SWFR_PATH_BOXES = 1, /* rectilinear: `edges` hold disjoint boxes (x1,y1)-(x2,y2) */
+       /* the two markers of an isolated group (SWFR_OBJECT_LAYER): the paths between them are drawn onto a transparent surface, which
+          GROUP_END composites onto what was there at GROUP_BEGIN.  Both have n_edges 0 and the same rectangle: the union of the
+          rectangles of the paths between them (those lie inside it).  BEGIN's `lerp` is 0; END's holds the composite's operator in bits
+          8..15 and 0 in bits 0..7.  Markers are balanced and nest at most SWFR_MAX_LAYER_DEPTH deep; their `style` is ignored.  Inside a
+          group "the surface" of the lerp rule is the group's: its first paint is a SOURCE lerp.  SWFR_ERR_INVALID at upload otherwise */
+       SWFR_PATH_GROUP_BEGIN = 2, SWFR_PATH_GROUP_END = 3 };
 
 typedef struct {
     uint32_t first_edge, n_edges;
@@ -236,7 +253,8 @@ typedef struct {
     int32_t x_min, y_min, x_max, y_max;  /* pixel rectangle of the converter (polygon extents ∩ frame) */
 } swfr_path;
 
-/* The operator of a path (swfr_path::lerp >> 8): pixman's unified combiner of that name applied to mul_un8(source pixel, coverage). */
+/* The operator of a path (swfr_path::lerp >> 8): pixman's unified combiner of that name applied to mul_un8(source pixel, coverage).
+   Of a SWFR_PATH_GROUP_END: the same combiner applied to the group's pixel itself (no coverage). */
 enum { SWFR_OP_OVER = 0, SWFR_OP_MULTIPLY = 1, SWFR_OP_SCREEN = 2, SWFR_OP_LIGHTEN = 3, SWFR_OP_DARKEN = 4, SWFR_OP_DIFFERENCE = 5,
        SWFR_OP_ADD = 6, SWFR_OP_OVERLAY = 7, SWFR_OP_HARDLIGHT = 8 };
 

@@ -37,6 +37,9 @@ EXPORTS = [
 ]
 OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
 OBJECT_BLEND_MODE = 5
+OBJECT_LAYER = 8                        # an isolated group (swfr.h SWFR_OBJECT_LAYER); `id` is the blend mode it is composited with
+MAX_LAYER_DEPTH = 4
+PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END = 0, 1, 2, 3
 # SWF blend-mode numbers under swf-tree's names (BlendMode); what the library does with each is swfr.h's SWFR_BLEND_* comment
 BLEND_MODES = {"normal": 1, "layer": 2, "multiply": 3, "screen": 4, "lighten": 5, "darken": 6, "difference": 7, "add": 8,
                "subtract": 9, "invert": 10, "alpha": 11, "erase": 12, "overlay": 13, "hardlight": 14}
@@ -54,6 +57,11 @@ def blend_mode_number(mode) -> int:
     if isinstance(mode, bool) or int(mode) != mode or not 0 <= int(mode) < 2 ** 32:
         raise SwfrError(ERR_INVALID, "InvalidBlendMode: %r" % (mode,))
     return int(mode)
+
+
+def layer_mode_number(layer) -> int:
+    """the SWF number of a "layer" value: True (an isolated group composited with OVER), a mode name or a number (blend_mode_number)"""
+    return BLEND_MODES["normal"] if layer is True else blend_mode_number(layer)
 VARIANT_BASE = 65536                    # a bitmap style's `bitmap` at or above it names a colour-transformed texture of the frame
 
 
@@ -525,6 +533,16 @@ class Renderer:
         if obj.get("matrix") is not None:
             d.has_matrix = 1
             d.matrix = _matrix(obj["matrix"])
+        if obj.get("layer") is not None and obj.get("layer") is not False:
+            # the object inside a type-8 wrapper, outside its blend-mode and colour-transform wrappers: the object is drawn as an
+            # isolated group and composited as one layer ("layer": True / "normal" / "layer": OVER; a mode name or number: its operator)
+            w = DisplayObject()
+            w.type, w.id = OBJECT_LAYER, layer_mode_number(obj["layer"])
+            inner = dict(obj)
+            del inner["layer"]
+            kids = arena.array(DisplayObject, [self._object(arena, inner)])
+            w.n_children, w.children = 1, C.cast(kids, C.POINTER(DisplayObject))
+            return w
         if obj.get("blend_mode") is not None:
             # the object inside a type-5 wrapper (outside its colour-transform wrapper, if any: the two commute); the matrix stays inside
             w = DisplayObject()

@@ -59,6 +59,9 @@ constexpr uint32_t REC_CELLS = 0x40000000u;    // (net height in bits 8..15)
 constexpr int ROWS_CHUNK = 64;       // most pixel rows per k2_rows wavefront (one lane per row)
 
 // flags of a band list entry (BandEntry2)
+// a path's byte of Frame2::path_op: bits 0..3 the operator (SWFR_OP_*); what isolated groups add (renderer.cpp, lower_groups; a frame
+// with any of the two marker bits runs k2_tiles<4>): the path is a group marker, or -- inside a group -- blends by the lerp rule
+enum : uint32_t { PATH_OP_MASK = 0x0fu, PATH_OP_LERP = 0x10u, PATH_OP_GROUP_BEGIN = 0x20u, PATH_OP_GROUP_END = 0x40u };
 enum : uint32_t { BE_BOXES = 1u, BE_LERP = 2u, BE_SOLID = 4u, BE_OPAQUE_COVER = 8u /* solid, alpha 255, lerp blend */ };
 
 // One k2_rows wavefront: `rows` (<= 64) consecutive pixel rows of one path.  rec_base is the path's first (edge, row) incidence
@@ -237,7 +240,7 @@ struct Frame2 {
     uint32_t band_first, band_stride;   // the handle's tile-rows: band_first + l * band_stride, l < n_strips / (STRIPS_PER_TILE * tiles_x)
                                         // (interleaved over the ranks: stride = ranks; one contiguous block per rank: stride = 1)
     uint32_t mono;           // 1: SWFR_FLAG_ANTIALIAS_NONE -- tor paths are converted at pixel centres by k2_rows_mono (mono.hip)
-    const uint8_t* path_op;  // per path: its operator (SWFR_OP_*), read by k2_tiles<3> alone; nullptr in a frame without a blended path.
+    const uint8_t* path_op;  // per path: its operator (SWFR_OP_*) | PATH_OP_* bits, read by k2_tiles<3> and <4> alone; nullptr in a frame without a blended path.
                              // The path records themselves carry lerp & 1 only -- 0 for every blended path -- so that nothing k2_bin and
                              // the row kernels derive from "lerp is not zero" (BE_LERP, opaque covers, culling) can fire for one
 };

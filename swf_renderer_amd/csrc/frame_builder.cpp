@@ -58,6 +58,8 @@ uint32_t blend_operator(uint32_t mode) {
     if (mode <= SWFR_BLEND_HARDLIGHT) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode"};
     throw StatusError{SWFR_ERR_INVALID, "InvalidBlendMode"};
 }
+// the operator an isolated layer (SWFR_OBJECT_LAYER) is composited with: OVER also for "layer", the mode whose whole meaning is the group
+uint32_t layer_operator(uint32_t mode) { return mode == SWFR_BLEND_LAYER ? uint32_t(SWFR_OP_OVER) : blend_operator(mode); }
 // a path's blend field once it is known whether the surface was still clear when it was drawn: "2" (a lerp only because nothing was
 // painted yet -- an OVER or an ADD path) becomes the SOURCE lerp, or what the path is otherwise: OVER, or its operator
 inline uint32_t settle_lerp(uint32_t lerp, bool clear) { return (lerp & 0xffu) == 2u ? (clear ? 1u : (lerp & ~0xffu)) : lerp; }
@@ -216,6 +218,7 @@ void FrameBuilder::build_range(const std::vector<const swfr_display_object*>& wr
     stack_.clear();
     luts_.clear(); lut_index_.clear(); compose_memo_.clear(); variant_index_.clear(); variants_.clear();
     failed_ = false;
+    group_depth_ = 0;
     surface_clear_ = true;  // clearRect over the whole canvas (canvas-renderer.ts:70-71); a later piece learns the truth when joined
     State s;
     s.ctm = Affine::scale(1.0 / 20.0, 1.0 / 20.0);  // twips -> px (:74)
@@ -251,7 +254,7 @@ void FrameBuilder::copy_piece(FrameBuilder& dst, size_t edge_off, size_t path_of
     for (size_t i = 0; i < paths_.size(); ++i) {
         swfr_path p = paths_[i];
         p.first_edge += uint32_t(edge_off);
-        p.style += uint32_t(style_off);
+        if (p.kind < SWFR_PATH_GROUP_BEGIN) p.style += uint32_t(style_off);      // (a group marker has no style: its field stays 0)
         p.lerp = settle_lerp(p.lerp, clear_at_start);           // (inside the piece the flag is only ever 2 while nothing was painted)
         dst.paths_[path_off + i] = p;
     }
@@ -360,6 +363,9 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
             stack_.back().op = blend_operator(obj.id);
             for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
             break;
+        case SWFR_OBJECT_LAYER:
+            draw_layer(obj, depth);
+            break;
         case SWFR_OBJECT_SHAPE: {
             const DecodedShape* sh = shape(obj.id, false);
             if (!sh) throw StatusError{SWFR_ERR_NOT_FOUND, "unknown shape id"};
@@ -375,6 +381,46 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
         default:
             throw StatusError{SWFR_ERR_INVALID, "UnexpectedDisplayObjectType"};
     }
+}
+
+// An isolated group ("Isolated layers"): cairo_push_group; the children; cairo_pop_group_to_source; cairo_set_operator;
+// cairo_paint.  The children's paths go between a GROUP_BEGIN and a GROUP_END marker whose rectangle is the union of theirs; inside,
+// "the surface" is the group's and starts clear -- known here, so a first paint is settled to a SOURCE lerp at once (a group is never
+// cut across build pieces: only the single container, colour-transform and blend-mode wrappers around the pieces are).
+void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth) {
+    const uint32_t op = layer_operator(obj.id);
+    if (group_depth_ >= SWFR_MAX_LAYER_DEPTH) throw StatusError{SWFR_ERR_CAPACITY, "LayerDepth"};
+    const bool parent_clear = surface_clear_;
+    const size_t begin = paths_.size();
+    swfr_path m;
+    std::memset(&m, 0, sizeof m);
+    m.kind = SWFR_PATH_GROUP_BEGIN;
+    m.first_edge = uint32_t(edges_.size());
+    paths_.push_back(m);
+    surface_clear_ = true;
+    ++group_depth_;
+    for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);      // (a throw ends the whole build: nothing to unwind)
+    --group_depth_;
+    const bool group_clear = surface_clear_;
+    // libcairo: painting a still-clear group with OVER or ADD is NOTHING_TO_DO and leaves the parent's "still clear" state alone; under
+    // any other operator, and whenever the group was drawn on (even if every pixel of it is zero), the parent counts as drawn
+    surface_clear_ = parent_clear && group_clear && (op == SWFR_OP_OVER || op == SWFR_OP_ADD);
+    if (paths_.size() == begin + 1) {                         // no path survived: a transparent group changes no pixel under any operator
+        paths_.pop_back();
+        return;
+    }
+    swfr_path& b = paths_[begin];
+    b.x_min = b.y_min = INT32_MAX; b.x_max = b.y_max = INT32_MIN;
+    for (size_t i = begin + 1; i < paths_.size(); ++i) {
+        const swfr_path& p = paths_[i];
+        b.x_min = std::min(b.x_min, p.x_min); b.y_min = std::min(b.y_min, p.y_min);
+        b.x_max = std::max(b.x_max, p.x_max); b.y_max = std::max(b.y_max, p.y_max);
+    }
+    m = b;
+    m.kind = SWFR_PATH_GROUP_END;
+    m.first_edge = uint32_t(edges_.size());
+    m.lerp = op << 8;
+    paths_.push_back(m);
 }
 
 bool FrameBuilder::transform(const Affine& m) {
@@ -470,9 +516,11 @@ void FrameBuilder::emit_polygon(Polygon& poly, bool rectilinear, uint32_t style,
     p.style = style;
     // 2: a lerp only because the surface is still clear (settled by build()).  A blended path is never a lerp -- an opaque colour under
     // MULTIPLY is not "opaque" for any shortcut -- except that Cairo turns ADD on a still-clear surface into SOURCE, as it does OVER
+    // (inside a layer the surface is the group's, whose state this walk knows: settled here)
     const uint32_t op = stack_.back().op;
-    if (op == SWFR_OP_OVER) p.lerp = opaque_solid ? 1 : (surface_clear_ ? 2 : 0);
-    else if (op == SWFR_OP_ADD) p.lerp = (op << 8) | (surface_clear_ ? 2u : 0u);
+    const uint32_t first = group_depth_ ? 1u : 2u;
+    if (op == SWFR_OP_OVER) p.lerp = opaque_solid ? 1 : (surface_clear_ ? first : 0);
+    else if (op == SWFR_OP_ADD) p.lerp = surface_clear_ ? (group_depth_ ? 1u : ((op << 8) | 2u)) : (op << 8);
     else p.lerp = op << 8;
     (void)lerp_blend;
     // converter rectangle: the polygon's extents inside the operation's bounded rectangle (the frame for fills)

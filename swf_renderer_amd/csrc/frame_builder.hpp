@@ -77,6 +77,7 @@ private:
         uint32_t op = 0;          // blend mode of the innermost SWFR_OBJECT_BLEND_MODE wrapper as a path operator (SWFR_OP_*), 0: OVER
     };
     void draw(const swfr_display_object& obj, int depth);
+    void draw_layer(const swfr_display_object& obj, int depth);
     void draw_path(const StyledPath& p, bool morph, double ratio);
     void trace(const StyledPath& p, bool morph, double ratio);
     void emit_fill(const OwnedFill& f, bool morph, double ratio);
@@ -113,7 +114,8 @@ private:
     std::vector<State> stack_;
     DevicePath path_;
     Polygon poly_;
-    bool surface_clear_ = true;
+    bool surface_clear_ = true;   // of the surface being drawn on: the frame's, or inside a SWFR_OBJECT_LAYER the innermost group's
+    int group_depth_ = 0;         // open layers (at most SWFR_MAX_LAYER_DEPTH)
     std::vector<swfr_edge> edges_;
     std::vector<swfr_path> paths_;
     std::vector<swfr_style> styles_;

@@ -1216,7 +1216,8 @@ __device__ __forceinline__ uint32_t shade_bitmap(uint32_t style_index, const Sou
     bilinear_taps(flt, px, py, t);
     return bilinear_mix(t, flt.pixels + t.o[0][0], flt.pixels + t.o[1][0], flt.pixels + t.o[0][1], flt.pixels + t.o[1][1]);
 }
-// SHADERS: 0 solid colours only, 1 + bitmaps, 2 + gradients, 3 + blend operators (what an unblended entry gets is instance 2's)
+// SHADERS: 0 solid colours only, 1 + bitmaps, 2 + gradients, 3 + blend operators (what an unblended entry gets is instance 2's),
+// 4 + isolated groups (what an entry that is no group marker gets is instance 3's)
 template <int SHADERS>
 __device__ __forceinline__ uint32_t blend2(uint32_t dst, uint32_t a, uint32_t eflags, uint32_t solid, const swfr_style* __restrict__ styles,
                                            uint32_t style, const Sources& src, int cx, int cy) {
@@ -1502,6 +1503,46 @@ __device__ __forceinline__ void blend8_op(uint32_t (&px)[8], const uint32_t (&al
     }
 }
 
+#ifndef T2_WAVES_LAYER
+#define T2_WAVES_LAYER 3              // the layer instance of k2_tiles: the blend instance's registers; 13 KB of LDS a wavefront, twelve wavefronts in a CU's 160 KB
+#endif
+// ---------------------------------------------------------------------------------------------
+// isolated groups (k2_tiles<4>; DESIGN.md, "Isolated layers").  A strip's pixels live in the lanes' px[8]; a group is "set them aside,
+// start from clear, later composite onto what was set aside": a stack of up to SWFR_MAX_LAYER_DEPTH saved strips in LDS, 2 KB a level,
+// every lane reading back only what it wrote itself (no barrier), and only in the strips a path of the group reaches.  In registers
+// the four levels would cost 32 VGPRs on top of the blend instance's 160 and spill.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t* layer_stack() {
+    __shared__ uint32_t saved[SWFR_MAX_LAYER_DEPTH * 8 * 64];            // [level][pixel slot j][lane]
+    return saved;
+}
+// GROUP_END: the group's pixels `px` composited onto the strip as it was at GROUP_BEGIN (`d`), pixman's UNMASKED combiner -- the source
+// is the group pixel itself, no coverage.  A transparent group pixel leaves the destination as it is under every operator.
+__device__ __forceinline__ void composite_group(uint32_t (&px)[8], const uint32_t* __restrict__ d, uint32_t op) {
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+        uint32_t sp[4], p4[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { sp[i] = h ? px[4 + i] : px[i]; p4[i] = d[(4 * h + i) * 64]; }
+        switch (op) {
+            case SWFR_OP_OVER:
+#pragma unroll
+                for (int i = 0; i < 4; ++i) p4[i] = over_pixel(sp[i], p4[i]);
+                break;
+            case SWFR_OP_MULTIPLY: op_pixels4<SWFR_OP_MULTIPLY>(p4, sp); break;
+            case SWFR_OP_SCREEN: op_pixels4<SWFR_OP_SCREEN>(p4, sp); break;
+            case SWFR_OP_LIGHTEN: op_pixels4<SWFR_OP_LIGHTEN>(p4, sp); break;
+            case SWFR_OP_DARKEN: op_pixels4<SWFR_OP_DARKEN>(p4, sp); break;
+            case SWFR_OP_DIFFERENCE: op_pixels4<SWFR_OP_DIFFERENCE>(p4, sp); break;
+            case SWFR_OP_ADD: op_pixels4<SWFR_OP_ADD>(p4, sp); break;
+            case SWFR_OP_OVERLAY: op_pixels4<SWFR_OP_OVERLAY>(p4, sp); break;
+            default: op_pixels4<SWFR_OP_HARDLIGHT>(p4, sp); break;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { if (h) px[4 + i] = p4[i]; else px[i] = p4[i]; }
+    }
+}
+
 template <int SHADERS>
 __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     // per pixel: deltas whose prefix sum along the row is 17 * N(x), N = Cairo's coverage numerator 512 * H(x) - ua(x) (H: the heights
@@ -1579,6 +1620,8 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         uint32_t px[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) px[j] = 0u;
+        [[maybe_unused]] int sp = 0, mat = 0;                             // open groups of this strip's walk, and how many of them have had the
+                                                                         // strip's pixels set aside for them (wave-uniform; instance 4 only)
 
         const uint8_t* mycls = FR->cls + (size_t)STRIPS_PER_TILE * tiles_x * band_begin + (size_t)(tcol * STRIPS_PER_TILE + strip) * n_b;   // this strip's class byte per band entry
         auto cls_chunk = [&](uint32_t c0) -> uint32_t {               // the class bytes of entries c0 .. c0 + 63 (c0 a multiple of 64, wave-uniform)
@@ -1642,8 +1685,8 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     uint4* e4 = reinterpret_cast<uint4*>(&ent[rank][0]);
                     e4[0] = q0; e4[1] = q1; ent[rank][8] = f;
                     // (instance 3: the path's operator beside its entry; a frame without a blended path -- in a batch that has one, or
-                    //  forced through this instance -- has no table)
-                    if constexpr (SHADERS == 3) ent[rank][9] = FR->path_op ? (uint32_t)FR->path_op[q1.w] : 0u;
+                    //  forced through this instance -- has no table; instance 4: the byte also says what isolated groups need, PATH_OP_*)
+                    if constexpr (SHADERS >= 3) ent[rank][9] = FR->path_op ? (uint32_t)FR->path_op[q1.w] : 0u;
                     if (part) { uint4* d4 = reinterpret_cast<uint4*>(&hdr[rank][0]); d4[0] = h0; d4[1] = h1; d4[2] = h2; d4[3] = h3; }
                 }
                 lds_barrier();
@@ -1660,12 +1703,45 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     const uint32_t xw = (uint32_t)__builtin_amdgcn_readfirstlane((int)ea.x), yw = (uint32_t)__builtin_amdgcn_readfirstlane((int)ea.y);
                     const int e_xmin = (int)(int16_t)(xw & 0xffffu), e_xmax = (int)(int16_t)(xw >> 16);
                     const int e_ymin = (int)(int16_t)(yw & 0xffffu), e_ymax = (int)(int16_t)(yw >> 16);
-                    const uint32_t eflags = (uint32_t)__builtin_amdgcn_readfirstlane((int)ea.z), solid = (uint32_t)__builtin_amdgcn_readfirstlane((int)ea.w);
+                    uint32_t eflags = (uint32_t)__builtin_amdgcn_readfirstlane((int)ea.z);
+                    const uint32_t solid = (uint32_t)__builtin_amdgcn_readfirstlane((int)ea.w);
                     const uint32_t style = (uint32_t)__builtin_amdgcn_readfirstlane((int)eb.x);
-                    uint32_t op = 0u;                                    // the entry's blend operator (wave-uniform; instance 3 only)
-                    if constexpr (SHADERS == 3) op = (uint32_t)__builtin_amdgcn_readfirstlane((int)ent[li][9]);
+                    uint32_t op = 0u;                                    // the entry's blend operator (wave-uniform; instances 3 and 4 only)
+                    if constexpr (SHADERS >= 3) op = (uint32_t)__builtin_amdgcn_readfirstlane((int)ent[li][9]);
                     const int row_lo = max(e_ymin, ty0) - ty0, row_hi = min(min(e_ymax, ty0 + STRIP_H), height) - ty0;
                     if (row_hi <= row_lo) continue;                    // the path misses this strip of the tile
+                    if constexpr (SHADERS == 4) {
+                        // ---- isolated groups: a marker acts on the whole strip, whatever its own coverage (its two markers share a
+                        //      rectangle: both reach this strip or neither does, and every path between them lies inside it)
+                        if (op & (PATH_OP_GROUP_BEGIN | PATH_OP_GROUP_END)) {                      // (wave-uniform)
+                            // BEGIN only counts: the strip's pixels are set aside when the first path of the group reaches this strip
+                            // (below).  A group none of whose paths does -- its rectangle is the union of theirs, most of its strips
+                            // may be such -- costs two scalar additions: a transparent group changes no pixel under any operator
+                            if (op & PATH_OP_GROUP_BEGIN) ++sp;
+                            else if (sp > 0) {
+                                if (mat == sp) {
+                                    --mat;
+                                    if (mat < SWFR_MAX_LAYER_DEPTH) composite_group(px, layer_stack() + mat * (8 * 64) + lane, op & PATH_OP_MASK);
+                                }
+                                --sp;
+                            }
+                            continue;
+                        }
+                        if (mat < sp) {
+                            // the first path inside the open groups: px goes to the outermost group not yet set aside, the groups
+                            // opened inside it since start clear below a clear parent (upload refuses nesting beyond the stack)
+                            uint32_t* sv = layer_stack() + lane;
+                            for (; mat < sp; ++mat) {
+                                if (mat >= SWFR_MAX_LAYER_DEPTH) continue;
+#pragma unroll
+                                for (int j = 0; j < 8; ++j) { sv[(mat * 8 + j) * 64] = px[j]; px[j] = 0u; }
+                            }
+                        }
+                        // a path inside a group: its lerp flag travels in the operator byte (the path record's is 0: nothing outside
+                        // the group may be culled for it); on the group's surface the lerp rule and its shortcuts are what they are on the frame's
+                        if (op & PATH_OP_LERP) eflags |= BE_LERP;
+                        op &= PATH_OP_MASK;
+                    }
                     STAT(2, 1);
 #ifdef ABL_T_NOPARTIAL
                     if ((fe & (CLS_PARTIAL | CLS_BOX)) == CLS_PARTIAL) continue;
@@ -1791,7 +1867,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
 #ifdef ABL_T_NOBLEND
                     for (int j = 0; j < 8; ++j) px[j] = al[j] == 255u ? solid : px[j];
 #else
-                    if constexpr (SHADERS == 3) {
+                    if constexpr (SHADERS >= 3) {
                         if (op) { blend8_op(px, al, op, eflags, solid, styles, style, bitmaps, cx0, cy0); continue; }   // (wave-uniform)
                     }
                     blend8<SHADERS>(px, al, eflags, solid, styles, style, bitmaps, cx0, cy0, bq, lane);
@@ -1851,6 +1927,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_SHA
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_SHADED))) void k2_tiles_shaded_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<2>(FRAME_PTR(frames, blockIdx.y), fb_to); }
 // frames with a blended path (swfr_path::lerp >> 8): everything the shaded instance does, plus the eight blend operators
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_BLEND))) void k2_tiles_blend_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<3>(FRAME_PTR(frames, blockIdx.y), fb_to); }
+// frames with an isolated group (SWFR_PATH_GROUP_BEGIN / _END): everything the blend instance does, plus the stack of set-aside strips
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAYER))) void k2_tiles_layer_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<4>(FRAME_PTR(frames, blockIdx.y), fb_to); }
 
 // ---------------------------------------------------------------------------------------------
 // launchers: `frames` is a device array of n_frames descriptors, blockIdx.y picks one
@@ -1889,7 +1967,8 @@ void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint
     // smaller frames do not fill the GPU and keep one wavefront per strip.
     uint32_t g = max_strips < grid_cap ? max_strips : grid_cap;
     if (grid_cap == ~0u && max_strips > T3_PAIR_FROM) g = (max_strips + 1u) / 2u;
-    if (shader_level >= 3) hipLaunchKernelGGL(k2_tiles_blend_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    if (shader_level >= 4) hipLaunchKernelGGL(k2_tiles_layer_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    else if (shader_level == 3) hipLaunchKernelGGL(k2_tiles_blend_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level >= 2) hipLaunchKernelGGL(k2_tiles_shaded_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 1) hipLaunchKernelGGL(k2_tiles_bitmap_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else hipLaunchKernelGGL(k2_tiles_solid_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);

@@ -256,7 +256,7 @@ struct swfr_renderer {
     bool mono = false;                      // SWFR_FLAG_ANTIALIAS_NONE: boxes rounded to pixels, tor paths by k2_rows_mono (Frame2::mono)
     int fast_limit = 16;                    // rows with more active edges go to k2_rows_slow; the row kernel's instance caps it at its 8 or 16 slots (SWFR_FAST_LIMIT: test knob)
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
-    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators; test knob)
+    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups; test knob)
     bool rows_wide = false;                 // SWFR_ROWS_WIDE=1: every frame with tor paths runs k2_rows_wide (test knob; aliased frames keep k2_rows_mono)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
     // the host builds one while the GPU works on the other
@@ -371,9 +371,75 @@ inline size_t cls_region_bytes(size_t n_slots, size_t tiles_x, size_t n_strips) 
 void validate_blend_fields(const swfr_path* paths, size_t n_paths) {
     for (size_t i = 0; i < n_paths; ++i) {
         const uint32_t v = paths[i].lerp;
+        if (paths[i].kind == SWFR_PATH_GROUP_BEGIN || paths[i].kind == SWFR_PATH_GROUP_END) continue;      // (validate_groups)
         if ((v & 0xffu) > 1u || (v >> 8) > SWFR_OP_HARDLIGHT || ((v >> 8) != 0u && (v & 0xffu) != 0u))
             throw StatusError{SWFR_ERR_INVALID, "path blend field: lerp must be 0 or 1, the operator at most 8, and lerp 0 with an operator"};
     }
+}
+
+// the markers of isolated groups (swfr.h, SWFR_PATH_GROUP_BEGIN / _END): balanced, at most SWFR_MAX_LAYER_DEPTH deep, no edges, BEGIN's
+// and END's rectangles equal, every path between them inside that rectangle, the lerp bits zero, END's operator one of SWFR_OP_*
+void validate_groups(const swfr_path* paths, size_t n_paths) {
+    size_t open[SWFR_MAX_LAYER_DEPTH];
+    int depth = 0;
+    auto bad = [](const char* what) { throw StatusError{SWFR_ERR_INVALID, what}; };
+    for (size_t i = 0; i < n_paths; ++i) {
+        const swfr_path& p = paths[i];
+        if (depth) {
+            const swfr_path& g = paths[open[depth - 1]];
+            if (p.x_min < g.x_min || p.y_min < g.y_min || p.x_max > g.x_max || p.y_max > g.y_max)
+                bad(p.kind == SWFR_PATH_GROUP_END ? "group markers: the rectangles of GROUP_BEGIN and GROUP_END differ" : "a path lies outside the rectangle of its group");
+        }
+        if (p.kind == SWFR_PATH_GROUP_BEGIN) {
+            if (p.n_edges != 0u || p.lerp != 0u) bad("GROUP_BEGIN: n_edges and lerp must be 0");
+            if (depth == SWFR_MAX_LAYER_DEPTH) bad("group markers nest deeper than SWFR_MAX_LAYER_DEPTH");
+            open[depth++] = i;
+        } else if (p.kind == SWFR_PATH_GROUP_END) {
+            if (!depth) bad("GROUP_END without a GROUP_BEGIN");
+            const swfr_path& g = paths[open[--depth]];
+            if (p.n_edges != 0u || (p.lerp & 0xffu) != 0u || (p.lerp >> 8) > SWFR_OP_HARDLIGHT) bad("GROUP_END: n_edges and lerp bits 0..7 must be 0, the operator at most 8");
+            if (p.x_min != g.x_min || p.y_min != g.y_min || p.x_max != g.x_max || p.y_max != g.y_max) bad("group markers: the rectangles of GROUP_BEGIN and GROUP_END differ");
+        }
+    }
+    if (depth) bad("GROUP_BEGIN without a GROUP_END");
+}
+
+// What the device sees of isolated groups ("Isolated layers").  A marker becomes a box path of ONE box, its rectangle, with
+// a transparent solid style and lerp 0: to k2_bin and the row kernels an ordinary path that reaches exactly the strips of the
+// rectangle, in painter's order, and paints nothing.  What it means travels in the path's operator byte (bits 8..15 of `lerp`, split off
+// into Frame2::path_op by push_scene), which only k2_tiles<3> and <4> read: PATH_OP_GROUP_BEGIN, or PATH_OP_GROUP_END | operator.  A
+// path INSIDE a group loses its lerp bit (so that no kernel derives an opaque cover or a culling record from it: a cover inside a group
+// hides nothing outside) and carries it in PATH_OP_LERP instead, where k2_tiles<4> reads it back for the pixel arithmetic.
+// Returns false when the scene has no marker (nothing is copied).
+bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles,
+                  std::vector<swfr_edge>& out_e, std::vector<swfr_path>& out_p, std::vector<swfr_style>& out_s) {
+    bool any = false;
+    for (size_t i = 0; i < n_paths && !any; ++i) any = paths[i].kind >= SWFR_PATH_GROUP_BEGIN;
+    if (!any) return false;
+    out_e.assign(edges, edges + n_edges); out_p.assign(paths, paths + n_paths); out_s.assign(styles, styles + n_styles);
+    swfr_style clear;
+    std::memset(&clear, 0, sizeof clear);
+    clear.kind = SWFR_STYLE_SOLID;
+    out_s.push_back(clear);
+    int depth = 0;
+    for (size_t i = 0; i < n_paths; ++i) {
+        swfr_path& p = out_p[i];
+        if (p.kind < SWFR_PATH_GROUP_BEGIN) {
+            if (depth) p.lerp = ((p.lerp >> 8) | ((p.lerp & 1u) ? PATH_OP_LERP : 0u)) << 8;
+            continue;
+        }
+        const bool end = p.kind == SWFR_PATH_GROUP_END;
+        depth += end ? -1 : 1;
+        p.lerp = (end ? (PATH_OP_GROUP_END | (p.lerp >> 8)) : PATH_OP_GROUP_BEGIN) << 8;
+        p.kind = SWFR_PATH_BOXES; p.fill_rule = 0; p.style = uint32_t(n_styles);
+        p.first_edge = uint32_t(out_e.size()); p.n_edges = 1;
+        swfr_edge b;
+        std::memset(&b, 0, sizeof b);
+        b.x1 = p.x_min * 256; b.y1 = p.y_min * 256; b.x2 = p.x_max * 256; b.y2 = p.y_max * 256;
+        b.top = b.y1; b.bottom = b.y2; b.dir = 1; b.reserved = int32_t(i);
+        out_e.push_back(b);
+    }
+    return true;
 }
 
 void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
@@ -404,8 +470,8 @@ void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edg
     for (size_t i = 0; i < n_paths; ++i) {
         const swfr_path& p = paths[i];
         if (size_t(p.first_edge) + p.n_edges > n_edges) throw StatusError{SWFR_ERR_INVALID, "path edge range out of bounds"};
-        if (p.style >= n_styles) throw StatusError{SWFR_ERR_INVALID, "path style index out of bounds"};
-        if (p.kind > SWFR_PATH_BOXES) throw StatusError{SWFR_ERR_INVALID, "unknown path kind"};
+        if (p.style >= n_styles && p.kind < SWFR_PATH_GROUP_BEGIN) throw StatusError{SWFR_ERR_INVALID, "path style index out of bounds"};
+        if (p.kind > SWFR_PATH_GROUP_END) throw StatusError{SWFR_ERR_INVALID, "unknown path kind"};
         if (p.kind == SWFR_PATH_TOR)
             // an edge of the scan converter: a line (x1, y1)-(x2, y2) running downwards, active over [top, bottom) INSIDE its own extent
             // (what the frame builder and Cairo's clipper produce); the per-row stepping of k2_rows is exact only there
@@ -645,8 +711,8 @@ struct SceneLayout {
     bool any_shader = false;
     uint32_t max_path_edges = 0;
     bool rows_wide = false;     // the row kernel's wide instance although no path has more than ROWS_STAGE edges (SWFR_ROWS_WIDE)
-    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators: picks the tile kernel's instance
-    bool any_blend = false;     // some path carries an operator (swfr_path::lerp >> 8): the arena gets the path_op table
+    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators, 4 + isolated groups: picks the tile kernel's instance
+    bool any_blend = false;     // some path carries an operator byte (swfr_path::lerp >> 8; lower_groups): the arena gets the path_op table
     std::vector<uint32_t> chunk_base, slot_base, inc_base, band_off;
     std::vector<uint32_t> band_span;     // per path: first tile-row | last tile-row << 16 of its rectangle (0xffff | 0 << 16: none); padded to a multiple of 16 paths
     std::vector<DevFilter> filters;
@@ -685,7 +751,7 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
     uint32_t blend_bits = 0;
     for (size_t i = 0; i < n_paths; ++i) blend_bits |= paths[i].lerp;
     L.any_blend = (blend_bits >> 8) != 0u;
-    if (L.any_blend) L.shader_level = 3;
+    if (L.any_blend) L.shader_level = (blend_bits >> 8) & (PATH_OP_GROUP_BEGIN | PATH_OP_GROUP_END) ? 4 : 3;
     // (the test knobs: a higher instance than the frame needs -- with the style table in its full format -- and the wide row kernel)
     L.shader_level = std::max(L.shader_level, r->tiles_shaders);
     L.rows_wide = r->rows_wide;
@@ -798,7 +864,7 @@ swfr_edge* push_scene(SceneArena& A, const SceneLayout& L, const swfr_edge* edge
     f.path_op = nullptr;
     if (L.any_blend) {
         // the ABI's blend field split: the device's path record keeps lerp & 1 (0 for a blended path: no kernel may take one for a lerp
-        // or a cover), the operator goes to a table of its own that only k2_tiles<3> reads
+        // or a cover), the operator byte goes to a table of its own that only k2_tiles<3> and <4> read
         swfr_path* staged_paths = reinterpret_cast<swfr_path*>(A.host + (reinterpret_cast<const uint8_t*>(f.paths) - A.dev));
         uint8_t* ops = A.host + A.used;
         for (size_t i = 0; i < n_paths; ++i) { ops[i] = uint8_t(staged_paths[i].lerp >> 8); staged_paths[i].lerp &= 1u; }
@@ -989,6 +1055,12 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
                     for (uint32_t k = 0; k < paths[i].n_edges; ++k) round_box_to_pixels(tagged[paths[i].first_edge + k]);
         edges = tagged.data();
     }
+    static thread_local std::vector<swfr_edge> group_e;
+    static thread_local std::vector<swfr_path> group_p;
+    static thread_local std::vector<swfr_style> group_s;
+    if (lower_groups(edges, n_edges, paths, n_paths, styles, n_styles, group_e, group_p, group_s)) {   // (frames with an isolated group only)
+        edges = group_e.data(); n_edges = group_e.size(); paths = group_p.data(); n_paths = group_p.size(); styles = group_s.data(); n_styles = group_s.size();
+    }
     static thread_local std::vector<swfr_edge> split_e;
     static thread_local std::vector<swfr_path> split_p;
     const swfr_path* src_paths = nullptr; size_t n_src_paths = 0;
@@ -1078,6 +1150,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
 // Uploads a caller-supplied scene (validated first) into scene slot `si`; see upload2.
 int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
            const swfr_style* styles, size_t n_styles, uint32_t* fb_override = nullptr) {
+    validate_groups(paths, n_paths);
     validate_blend_fields(paths, n_paths);                       // (a malformed blend field is refused as such even by a host-only handle)
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
     validate_scene(r, edges, n_edges, paths, n_paths, styles, n_styles);
@@ -1381,6 +1454,10 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
                 r->builder->build(stages[first + k]);
                 F.e = r->builder->edges(); F.p = r->builder->paths(); F.s = r->builder->styles();
                 validate_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size());
+                {
+                    std::vector<swfr_edge> ge; std::vector<swfr_path> gp; std::vector<swfr_style> gs;
+                    if (lower_groups(F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), ge, gp, gs)) { F.e.swap(ge); F.p.swap(gp); F.s.swap(gs); }
+                }
                 resolve_variants(r, F.p.data(), F.p.size(), F.s.data(), F.s.size(), G.stream, false);
                 {
                     std::vector<swfr_edge> se; std::vector<swfr_path> sp;
@@ -1680,7 +1757,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
-    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 3);
+    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 4);
     if (const char* rw = std::getenv("SWFR_ROWS_WIDE")) r->rows_wide = std::atoi(rw) != 0;
     if (const char* bf = std::getenv("SWFR_BATCH_FRAMES")) r->batch_frames = std::max(1, std::atoi(bf));
     if (const char* cr = std::getenv("SWFR_CHUNK_ROWS")) r->force_chunk_rows = std::atoi(cr);

@@ -1,5 +1,5 @@
 // ThreadSanitizer harness for the multi-threaded frame builder (CPU only; the device half comes from tools/emu's stand-in runtime):
-//   g++ -std=c++17 -O1 -g -fsanitize=thread -DSWFR_BUILD -I tools/emu/include -x c++ tools/tsan_frame_builder.cpp swf_renderer_amd/csrc/{renderer,frame_builder,geometry,shape_decoder}.cpp swf_renderer_amd/csrc/raster2.hip tools/emu/emu_rt.cpp -o build/tsan_harness -ldl -lpthread && SWFR_BUILD_THREADS=8 build/tsan_harness
+//   g++ -std=c++17 -O1 -g -fsanitize=thread -DSWFR_BUILD -I tools/emu/include -x c++ tools/tsan_frame_builder.cpp swf_renderer_amd/csrc/{renderer,frame_builder,geometry,shape_decoder,bitmap_decode}.cpp swf_renderer_amd/csrc/raster2.hip tools/emu/emu_rt.cpp -o build/tsan_harness -ldl -lpthread && SWFR_BUILD_THREADS=8 build/tsan_harness
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -20,7 +20,7 @@ int main() {
     tag.initial_styles.n_fill = 1; tag.initial_styles.fill = &fs; tag.n_records = 4; tag.records = rec;
     uint32_t id = 0;
     if (swfr_register_shape(r, &tag, &id) != 0) { std::printf("register: %s\n", swfr_last_error(r)); return 1; }
-    std::vector<swfr_display_object> kids;
+    std::vector<swfr_display_object> kids, inner;
     for (int frame = 0; frame < 300; ++frame) {
         // the child count -- and with it the number of pieces the pool builds -- changes from frame to frame
         static const size_t counts[5] = {1000, 130, 400, 70, 1000};
@@ -30,6 +30,13 @@ int main() {
             kids[i].type = SWFR_OBJECT_SHAPE; kids[i].id = id; kids[i].has_matrix = 1;
             kids[i].matrix.scale_x = 65536; kids[i].matrix.scale_y = 65536;
             kids[i].matrix.translate_x = int((i * 37 + frame * 11) % 11000) - (i < 100 ? 40000 : 0); kids[i].matrix.translate_y = int((i * 53) % 8000);
+        }
+        // every seventh child inside an isolated layer (SWFR_OBJECT_LAYER): group markers and the group's own "still clear" state in every piece
+        inner = kids;
+        for (size_t i = 3; i < kids.size(); i += 7) {
+            std::memset(&kids[i], 0, sizeof kids[i]);
+            kids[i].type = SWFR_OBJECT_LAYER; kids[i].id = (i / 7) % 2 ? SWFR_BLEND_MULTIPLY : SWFR_BLEND_NORMAL;
+            kids[i].n_children = 1; kids[i].children = &inner[i];
         }
         swfr_stage st; std::memset(&st, 0, sizeof st); st.n_children = uint32_t(kids.size()); st.children = kids.data();
         const swfr_edge* e; const swfr_path* p; const swfr_style* s; size_t ne, np, ns;
