@@ -1,0 +1,149 @@
+"""The compositing rule of a whole frame in numpy: what a frame in swfr_upload_edges form (include/swfr.h) leaves in every pixel.
+
+    render(edges, paths, styles, W, H, even_odd_from_paths=True, aliased=False) -> H x W x 4 premultiplied RGBA
+
+`edges` / `paths` are EDGE_DTYPE / PATH_DTYPE arrays and `styles` Style structs: what Renderer.build_frame returns and what
+Renderer.render_edges takes, in the PUBLIC form of swfr_path -- `lerp` is lerp | operator << 8, groups are SWFR_PATH_GROUP_BEGIN / _END
+marker paths, END carrying the composite's operator.  Paths are painted in order onto a clear frame.
+
+- Coverage of a path, 0..255 per pixel of its rectangle (nothing is painted outside it):
+  antialiased tor paths -- the oracle's scan converter (OracleBackend.fill_edges) over the path's rectangle, opaque white on a clear
+  scratch surface of the rectangle's size, alpha channel (the edges are moved by the rectangle's corner, whole pixels: the sample
+  grid moves with them); box paths -- Cairo's exact area of the disjoint boxes in 16.16, alpha = (c >> 8) - (c >> 16); aliased --
+  the spans and boxes of tests/mono_model.py, every covered pixel at 255.
+- A path whose lerp bit is set is a SOURCE lerp (blend_model.lerp_source); otherwise its operator's combiner on mul_un8(colour,
+  coverage) (blend_model.blend; operator 0 is OVER).
+- GROUP_BEGIN sets the pixels of its rectangle aside and starts them clear; GROUP_END composites what was drawn since onto what was set
+  aside with layer_model.composite(operator).  Members lie inside the rectangle and a transparent group pixel leaves its destination
+  as it is under all nine operators (tests/layer_model.py), so working inside the rectangle is the rule on a surface of the frame's size.
+- Solid styles only: bitmap and gradient sources under operators stay pinned by the libcairo goldens.
+
+The model states the rule; it shares no code with the kernels (swf_renderer_amd/csrc) and knows nothing of strips, staging rounds,
+class bytes or culling.  All work is cropped to a path's rectangle: a 4K frame of thousands of small paths stays affordable.
+tests/test_frame_model.py pins it against the committed libcairo goldens, live libcairo and the oracle.
+"""
+import numpy as np
+
+import blend_model as bm
+import layer_model as lm
+import mono_model as mm
+from oracle import oracle_backend as ob
+
+PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END = 0, 1, 2, 3
+STYLE_SOLID = 0
+OPERATOR_NAMES = {v: ("normal" if k == "over" else k) for k, v in bm.OPERATORS.items()}      # SWFR_OP_* -> blend_model's mode names
+
+
+def _rect(p, W, H):
+    x0, y0, x1, y1 = (int(p[k]) for k in ("x_min", "y_min", "x_max", "y_max"))
+    return max(x0, 0), max(y0, 0), min(x1, W), min(y1, H)
+
+
+def tor_coverage(e, rect, even_odd):
+    """(y1 - y0) x (x1 - x0) uint8: Cairo's antialiased coverage of the edges `e` over the pixel rectangle rect = (x0, y0, x1, y1)"""
+    x0, y0, x1, y1 = rect
+    w, h = x1 - x0, y1 - y0
+    if len(e) == 0:
+        return np.zeros((h, w), np.uint8)
+    m = np.array(e, copy=True)
+    for k in ("x1", "x2"):
+        m[k] -= x0 * 256
+    for k in ("y1", "y2", "top", "bottom"):
+        m[k] -= y0 * 256
+    be = ob.OracleBackend(w, h)
+    try:
+        be.fill_edges(m, (0, 0, w, h), even_odd, 0xffffffff)
+        return be.premultiplied_rgba()[..., 3].copy()
+    finally:
+        be.close()
+
+
+def box_coverage(e, rect):
+    """Cairo's exact-area rule for disjoint boxes (x1, y1)-(x2, y2) in 24.8: the covered area of a pixel in 16.16, c, gives alpha
+    (c >> 8) - (c >> 16)"""
+    x0, y0, x1, y1 = rect
+    area = np.zeros((y1 - y0, x1 - x0), np.int64)
+    px = np.arange(x0, x1, dtype=np.int64) * 256
+    py = np.arange(y0, y1, dtype=np.int64) * 256
+    for b in e:
+        wx = np.minimum(int(b["x2"]), px + 256) - np.maximum(int(b["x1"]), px)
+        wy = np.minimum(int(b["y2"]), py + 256) - np.maximum(int(b["y1"]), py)
+        area += np.maximum(wy, 0)[:, None] * np.maximum(wx, 0)[None, :]
+    assert int(area.max(initial=0)) <= 65536, "boxes of one path overlap"
+    return (((area >> 8) - (area >> 16)) & 255).astype(np.uint8)
+
+
+def aliased_coverage(e, p, rect, even_odd, W, H):
+    """tests/mono_model.py's spans (tor) and rounded boxes, as 0 / 255 over the rectangle"""
+    x0, y0, x1, y1 = rect
+    cov = np.zeros((y1 - y0, x1 - x0), bool)
+    if int(p["kind"]) == PATH_TOR:
+        rows, xs, xe = mm.tor_spans(e, y0, y1, x0, x1, even_odd, H, W)
+        diff = np.zeros((y1 - y0, x1 - x0 + 1), np.int64)
+        np.add.at(diff, (rows - y0, xs - x0), 1)
+        np.add.at(diff, (rows - y0, xe - x0), -1)
+        cov = np.cumsum(diff[:, :-1], 1) > 0
+    else:
+        for b in e:
+            a0, a1 = max(mm._round(int(b["x1"])), x0), min(mm._round(int(b["x2"])), x1)
+            c0, c1 = max(mm._round(int(b["y1"])), y0), min(mm._round(int(b["y2"])), y1)
+            if a0 < a1 and c0 < c1:
+                cov[c0 - y0:c1 - y0, a0 - x0:a1 - x0] = True
+    return np.where(cov, 255, 0).astype(np.uint8)
+
+
+def path_coverage(edges, p, W, H, even_odd_from_paths=True, aliased=False):
+    """(rectangle, coverage over it) of one tor or box path"""
+    rect = _rect(p, W, H)
+    e = edges[int(p["first_edge"]):int(p["first_edge"]) + int(p["n_edges"])]
+    even_odd = bool(p["fill_rule"]) and even_odd_from_paths
+    kind = int(p["kind"])
+    assert kind in (PATH_TOR, PATH_BOXES), "unknown path kind"
+    if aliased:
+        return rect, aliased_coverage(e, p, rect, even_odd, W, H)
+    return rect, (tor_coverage(e, rect, even_odd) if kind == PATH_TOR else box_coverage(e, rect))
+
+
+def render(edges, paths, styles, W, H, even_odd_from_paths=True, aliased=False):
+    """premultiplied RGBA (H x W x 4 uint8) of a frame in swfr_upload_edges form"""
+    edges, paths = np.asarray(edges), np.asarray(paths)
+    img = np.zeros((H, W, 4), np.uint8)
+    stack = []                                                   # open groups: (rectangle, the pixels set aside)
+    for p in paths:
+        kind, field = int(p["kind"]), int(p["lerp"])
+        lerp, op = field & 0xff, field >> 8
+        if op not in OPERATOR_NAMES or lerp > 1:
+            raise ValueError("swfr_path::lerp %#x: no such operator or lerp value" % field)
+        x0, y0, x1, y1 = rect = _rect(p, W, H)
+        if kind == PATH_GROUP_BEGIN:
+            if field or len(stack) == lm.MAX_DEPTH:
+                raise ValueError("GROUP_BEGIN with a lerp field, or deeper than SWFR_MAX_LAYER_DEPTH")
+            stack.append((rect, img[y0:y1, x0:x1].copy()))
+            img[y0:y1, x0:x1] = 0
+            continue
+        if kind == PATH_GROUP_END:
+            if not stack or stack[-1][0] != rect or lerp:
+                raise ValueError("GROUP_END without its GROUP_BEGIN, or with lerp bits")
+            _, below = stack.pop()
+            img[y0:y1, x0:x1] = lm.composite(OPERATOR_NAMES[op], img[y0:y1, x0:x1], below)
+            continue
+        if stack:
+            g = stack[-1][0]
+            if x0 < g[0] or y0 < g[1] or x1 > g[2] or y1 > g[3]:
+                raise ValueError("a path lies outside the rectangle of its group")
+        if lerp and op:
+            raise ValueError("an operator needs lerp bits 0")
+        st = styles[int(p["style"])]
+        if int(st.kind) != STYLE_SOLID:
+            raise NotImplementedError("the model draws solid styles only")
+        if x0 >= x1 or y0 >= y1:
+            continue
+        pix = int(st.pixel) & 0xffffffff
+        c = np.array([(pix >> 16) & 255, (pix >> 8) & 255, pix & 255, pix >> 24], np.uint8)
+        _, cov = path_coverage(edges, p, W, H, even_odd_from_paths, aliased)
+        d = img[y0:y1, x0:x1]
+        cc = np.broadcast_to(c, d.shape)
+        img[y0:y1, x0:x1] = bm.lerp_source(cc, cov, d) if lerp else bm.blend(OPERATOR_NAMES[op], cc, cov, d)
+    if stack:
+        raise ValueError("GROUP_BEGIN without a GROUP_END")
+    return img

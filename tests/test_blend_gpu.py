@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import blend_scenes as bs  # noqa: E402
+import frame_model  # noqa: E402
 import helpers  # noqa: E402
 import scenarios  # noqa: E402
 from helpers import diff_stats, golden, oracle_render, product_render  # noqa: E402
@@ -146,9 +147,9 @@ def test_goldens_through_render_batch_with_unlike_frames(fname):
     for w, h in sizes:
         group = [(name, sc) for name, sc in items if (sc["width"], sc["height"]) == (w, h)]
         plain = dict(width=w, height=h, exact=True, stage={"children": bs._with_ground(dict(width=w, height=h))})
-        # (the plain frame's expected pixels: the oracle's; aliased, where there is no oracle, what `render` gives -- that frame then
-        #  checks the batch route against the render route, not against libcairo; the blended frames are checked against libcairo)
-        plain_want = product_render(plain, antialias="none") if aliased else oracle_render(plain)
+        # (the plain frame's expected pixels: the oracle's; aliased, where there is no oracle, tests/frame_model.py's -- the exact
+        #  model of the aliased rule over the frame builder's arrays; the blended frames are checked against libcairo)
+        plain_want = frame_model.render(*_built_on_a_host_handle(plain, True), w, h, aliased=True) if aliased else oracle_render(plain)
         frames = []                                               # (message, scenario, expected pixels)
         for k, (name, sc) in enumerate(group):
             frames.append((name, sc, gold[name]))

@@ -1,6 +1,7 @@
 """Isolated layers on the device: every libcairo golden of tests/layer_scenes.py -- every file, every scene -- through render,
 swfr_render_edges (+ resident frames), SWFR_GRAPHS=1, two-band handles (contiguous and interleaved) and render_batch with layered and
-plain frames in one group, zero differing bytes (linear-gradient scenes: LINEAR_BOUND, see layer_scenes.py).  Under the emulator the
+plain frames in one group, zero differing bytes (linear-gradient scenes: LINEAR_BOUND, see layer_scenes.py); the plain frames of a
+batch are held against the oracle, the aliased ones against tests/frame_model.py's render(..., aliased=True).  Under the emulator the
 routes other than render take every fourth scene of a file.  One 4K frame, S1 with its stars in layers.  And the existing corpus through
 the layer instance of the tile kernel (SWFR_TILES_SHADERS=4), byte-identical to what instances 0-2 give.  Runs on an MI355X (-m gpu) and
 under tools/emu/run.py.
@@ -17,6 +18,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import frame_model  # noqa: E402
 import layer_scenes as bs  # noqa: E402
 import helpers  # noqa: E402
 import scenarios  # noqa: E402
@@ -151,9 +153,10 @@ def test_goldens_through_render_batch_with_unlike_frames(fname):
     for w, h in sizes:
         group = [(name, sc) for name, sc in items if (sc["width"], sc["height"]) == (w, h)]
         plain = dict(width=w, height=h, exact=True, stage={"children": bs._with_ground(dict(width=w, height=h))})
-        # (the plain frame's expected pixels: the oracle's; aliased, where there is no oracle, what `render` gives -- that frame then
-        #  checks the batch route against the render route, not against libcairo; the layered frames are checked against libcairo)
-        plain_want = product_render(plain, antialias="none") if aliased else oracle_render(plain)
+        # (the plain frame's expected pixels: the oracle's; aliased, where there is no oracle, tests/frame_model.py's -- the exact
+        #  model of the aliased rule over the frame builder's arrays, pinned against libcairo by tests/test_frame_model.py; the layered
+        #  frames are checked against libcairo)
+        plain_want = frame_model.render(*_built_on_a_host_handle(plain, True), w, h, aliased=True) if aliased else oracle_render(plain)
         frames = []                                               # (message, scenario, expected pixels)
         for k, (name, sc) in enumerate(group):
             frames.append((name, sc, gold[name]))
