@@ -141,7 +141,8 @@ constexpr Cell make_cell(int col_rel, int ch, int ua) { return make_cell_v(col_r
 constexpr int cell_col(Cell c) { return (int)(c.w >> 19); }                  // relative to the path's x_min
 constexpr int cell_ua(Cell c) { return (int)(c.w << 18) >> 18; }
 constexpr int cell_ch(Cell c) { return (((int)(c.w << 13) >> 13) - cell_ua(c)) >> 14; }
-constexpr int MAX_CELLS_PER_EDGE_ROW = 17;   // a FULL-row edge has at most 15 + 2 cells with a non-zero height, a sampled one 15
+constexpr int MAX_CELLS_PER_EDGE_ROW = 17;   // a FULL-row edge has at most 15 + 2 cells with a non-zero height; a sampled one at most 15 (one per sample row: the room
+                                             // its row gets) and as few as one -- k2_rows adds the cells of neighbouring sample rows in one pixel column together (rows3.hip)
 
 // per (band entry, pixel row of its tile-row): indexed entry * TILE_H + (y % TILE_H), so a tile finds it from the band list position
 struct RowInfo2 {

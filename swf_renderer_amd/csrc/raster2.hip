@@ -1811,9 +1811,11 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                         };
 #ifndef ABL_T_NOACC
                         add_cell(c0c, ck < n_c);
-                        add_cell(c1c, ck + 8 < n_c);
+                        if (__ballot(ck + 8 < n_c) != 0ull) add_cell(c1c, ck + 8 < n_c);   // (wave-uniform) few rows have more than eight cells
 #endif
+                        STAT(6, __ballot(16 < n_c) != 0ull);                 // pairs that need a round beyond the first
                         for (int kb = 16; __ballot(kb < n_c) != 0ull; kb += 8) {   // wave-uniform
+                            STAT(5, 1);                                      // cell rounds beyond the first
                             Cell cc; cc.w = 0;
                             if (kb + ck < n_c) cc = cp[kb + ck];
                             add_cell(cc, kb + ck < n_c);

@@ -107,7 +107,7 @@ template <int STAGE, int NS>
 __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
     typedef typename R3Mask<STAGE>::type amask_t;
     __shared__ __attribute__((aligned(16))) FastEdge staged[STAGE];
-    __shared__ uint32_t sub_cells[4][NS * 15];        // the cells of the four rows of a sample pass, before they are copied out coalesced
+    __shared__ __attribute__((aligned(16))) uint32_t sub_cells[4][NS * 15];        // the merged cells of the four rows of a sample pass, summed there before they are copied out coalesced (all zero between passes)
     __shared__ uint32_t sub_masks[4][4];                       // ... and the rows' tile-column masks: cells, covered in all / in some sample rows
     __shared__ uint8_t slot_role[NS][64];             // role per edge slot, scattered there from the sorted order (column = lane: private)
     __shared__ uint8_t slot_edge[NS][64];             // staged edge per slot (the tie check looks edges up by sorted position)
@@ -343,7 +343,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
     }
     R3MARK(6);
     // ---- room for the rows' cells inside the wavefront's region: a FULL row takes the exact number of its cells, a SUB row room for
-    //      one cell per (active edge, sample row) -- its cells are counted while they are made, so the row uses a prefix of its room
+    //      one cell per (active edge, sample row) -- its cells are merged and counted while they are made, so the row uses a prefix of its room
     int n_cells = 0;
     if (mode == ROW_FULL && ri != ~0u) {
 #pragma unroll
@@ -396,12 +396,14 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         }
     };
     if (mode == ROW_FULL) { uint32_t iv, cv; full_row_masks(tc0, iv, cv); m_inter = iv; m_and = cv; m_or = cv; }
+    if (__ballot(is_sub) != 0ull)                                        // (wave-uniform) the sample passes sum into their staging: cleared once, each pass clears what it used
+        for (int i = lane; i < NS * 15; i += 64) reinterpret_cast<uint4*>(&sub_cells[0][0])[i] = make_uint4(0u, 0u, 0u, 0u);
     lds_barrier();
     TRACE(4);                                                            // sorted, roles, FULL cells and masks
     R3MARK(9);
     // ---- the wave's SUB rows, 4 rows per pass: lanes 16g .. 16g + 14 are the fifteen sample rows of the pass's g-th row (lane 16g + 15
-    //      idles): a lane sorts its sample row's cells, walks them once and emits Cairo's cells (A.5 add_subspan); a row's lanes are one
-    //      DPP row, so the cell counts and the classification masks combine by row shifts / rotations: no LDS atomics
+    //      idles): a lane sorts its sample row's cells, walks them once and makes Cairo's cells (A.5 add_subspan); a row's lanes are one
+    //      DPP row, so the cell counts and the classification masks combine by row shifts / rotations
     unsigned long long pending = __ballot(is_sub);
 #ifdef ABL3_NOSUB
     pending = 0ull;
@@ -475,21 +477,56 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
             }
         }
         if (ntc > 32) s_inter = ~0u;                            // (a path wider than 32 tile columns: its sampled rows count as partial everywhere)
-        // cells of this lane, of the row's lanes before it, of the row
+        // ---- merge before staging.  k2_tiles adds every cell of a row into one accumulator per pixel column, and what it adds is
+        //      linear in the cell's V = height * CELL_H + uncovered area (a cell left of the tile adds 512 h: linear as well), so any two
+        //      cells of one row and column may be added, whatever their edges and signs, and the order of a row's cells is free.  An
+        //      edge's x is monotonic in the sample row, so at walk position p the cells of neighbouring sample lanes with the same
+        //      CLAMPED column (the packed one: after pack_sub_cell's x_min / x_max rule) form runs, and a run becomes ONE cell whose V
+        //      is the sum of the run's: a steep edge gives one cell of height +-15 instead of fifteen of +-1.  Exact: a run has at most
+        //      fifteen cells of height +-1 and |area| <= 510, so |height| <= 15 and |area| <= 7650 < 2^13: V stays inside its signed
+        //      19 bits and the area inside the 14 bits k2_tiles sign-extends.  A run whose sum is zero stays, as a cell that adds
+        //      nothing.  The masks s_inter / s_cov above were made from the unmerged cells: classes, StripTop records and strip costs
+        //      do not change.
+        //      A run's head is the lane whose row_shr:1 neighbour has no cell at p or one of another column.  The head flags of the
+        //      walk positions travel as 4-bit counters, eight positions per word: one inclusive scan over the row's sixteen lanes gives
+        //      every lane the number of its run at each p, lane 15 (idle) the row's totals.  Cells come out p-major: position p's runs
+        //      follow those of the positions before it.  Every lane of a run adds its V into the run's staged word (no-return LDS
+        //      atomic), the head adds the column: the word is column * 2^19 + sum(V) in plain 32-bit arithmetic until it is copied out.
         const bool keep = riR != ~0u;
-        const int cnt = keep ? __popc(em) : 0;
-        int sc = cnt;
-        sc += __builtin_amdgcn_update_dpp(0, sc, 0x111, 0xf, 0xf, false);   // row_shr:1 .. 8: inclusive scan over the row's sixteen lanes
-        sc += __builtin_amdgcn_update_dpp(0, sc, 0x112, 0xf, 0xf, false);
-        sc += __builtin_amdgcn_update_dpp(0, sc, 0x114, 0xf, 0xf, false);
-        sc += __builtin_amdgcn_update_dpp(0, sc, 0x118, 0xf, 0xf, false);
-        {
-            uint32_t at = (uint32_t)(sc - cnt);
+        const unsigned emk = keep ? em : 0u;
+        const unsigned em_prev = (unsigned)__builtin_amdgcn_update_dpp(0, (int)emk, 0x111, 0xf, 0xf, false);   // row_shr:1 (a row's first lane: 0)
+        constexpr int NW = NS / 8;
+        uint32_t hn[NW], sc[NW], tot[NW];
 #pragma unroll
-            for (int p = 0; p < NS; ++p) {
-                if (p >= nmaxp) continue;
-                if (keep && ((em >> p) & 1u)) sub_cells[g][at++] = cw[p];
+        for (int j = 0; j < NW; ++j) hn[j] = 0u;
+#pragma unroll
+        for (int p = 0; p < NS; ++p) {
+            if (p >= nmaxp) continue;                            // wave-uniform
+            const uint32_t pw = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cw[p], 0x111, 0xf, 0xf, false);
+            const bool run = ((em_prev >> p) & 1u) != 0u && ((pw ^ cw[p]) >> 19) == 0u;
+            if (((emk >> p) & 1u) != 0u && !run) hn[p >> 3] |= 1u << (4 * (p & 7));
+        }
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            uint32_t t = hn[j];                                  // (at most fifteen heads per position: no carry between the counters)
+            t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x111, 0xf, 0xf, false);   // row_shr:1 .. 8: inclusive scan over the row's sixteen lanes
+            t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x112, 0xf, 0xf, false);
+            t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x114, 0xf, 0xf, false);
+            t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x118, 0xf, 0xf, false);
+            sc[j] = t;
+            tot[j] = (uint32_t)__shfl((int)t, lane | 15);
+        }
+        uint32_t n_merged = 0;                                   // the runs of the positions before p; in the end the row's cells
+#pragma unroll
+        for (int p = 0; p < NS; ++p) {
+            if (p >= nmaxp) continue;
+            const int q = 4 * (p & 7);
+            if ((emk >> p) & 1u) {
+                const uint32_t v = (uint32_t)((int)(cw[p] << 13) >> 13);
+                const uint32_t head = ((hn[p >> 3] >> q) & 1u) ? (cw[p] & 0xfff80000u) : 0u;
+                atomicAdd(&sub_cells[g][n_merged + ((sc[p >> 3] >> q) & 15u) - 1u], head + v);
             }
+            n_merged += (tot[p >> 3] >> q) & 15u;
         }
         // all-reduce of the masks over the row's sixteen lanes (four rotations each); the idle lanes hold the identities
         uint32_t a_and = sampling ? s_cov : ~0u, a_or = sampling ? s_cov : 0u, a_int = sampling ? s_inter : 0u;
@@ -513,8 +550,8 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         }
         // ---- copy out (coalesced) into the rows' room, row headers
         {
-            const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane(sc, 15), c1r = (uint32_t)__builtin_amdgcn_readlane(sc, 31);
-            const uint32_t c2 = (uint32_t)__builtin_amdgcn_readlane(sc, 47), c3 = (uint32_t)__builtin_amdgcn_readlane(sc, 63);
+            const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)n_merged, 15), c1r = (uint32_t)__builtin_amdgcn_readlane((int)n_merged, 31);
+            const uint32_t c2 = (uint32_t)__builtin_amdgcn_readlane((int)n_merged, 47), c3 = (uint32_t)__builtin_amdgcn_readlane((int)n_merged, 63);
             const uint32_t total = c0 + c1r + c2 + c3;
             // where the rooms of the pass's rows start: the row lanes know (exclusive prefix of the rooms), every lane asks
             int Rg[4];
@@ -525,13 +562,15 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
             }
             const uint32_t b0 = (uint32_t)__shfl((int)my_room, Rg[0]), b1 = (uint32_t)__shfl((int)my_room, Rg[1]);
             const uint32_t b2 = (uint32_t)__shfl((int)my_room, Rg[2]), b3 = (uint32_t)__shfl((int)my_room, Rg[3]);
-            if (wave_base != ~0u) {
-                for (uint32_t t = (uint32_t)lane; t < total; t += 64) {
-                    const int gg = t < c0 ? 0 : (t < c0 + c1r ? 1 : (t < c0 + c1r + c2 ? 2 : 3));
-                    const uint32_t pre = gg == 0 ? 0u : (gg == 1 ? c0 : (gg == 2 ? c0 + c1r : c0 + c1r + c2));
-                    const uint32_t bb = gg == 0 ? b0 : (gg == 1 ? b1 : (gg == 2 ? b2 : b3));
-                    FR->cells[bb + (t - pre)] = Cell{sub_cells[gg][t - pre]};
-                }
+            // (the staged word becomes the cell: its low 19 bits are sum(V), what is left the column; the staging is left cleared)
+            for (uint32_t t = (uint32_t)lane; t < total; t += 64) {
+                const int gg = t < c0 ? 0 : (t < c0 + c1r ? 1 : (t < c0 + c1r + c2 ? 2 : 3));
+                const uint32_t pre = gg == 0 ? 0u : (gg == 1 ? c0 : (gg == 2 ? c0 + c1r : c0 + c1r + c2));
+                const uint32_t bb = gg == 0 ? b0 : (gg == 1 ? b1 : (gg == 2 ? b2 : b3));
+                const uint32_t w = sub_cells[gg][t - pre];
+                sub_cells[gg][t - pre] = 0u;
+                const uint32_t v = (uint32_t)((int)(w << 13) >> 13);
+                if (wave_base != ~0u) FR->cells[bb + (t - pre)] = Cell{(w - v) | (v & 0x7ffffu)};
             }
             if (sub == 0 && R >= 0 && riR != ~0u) {          // the first sample lane of each of the pass's rows writes its header
                 const uint32_t bb = g == 0 ? b0 : (g == 1 ? b1 : (g == 2 ? b2 : b3));

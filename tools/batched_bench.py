@@ -1,5 +1,6 @@
 """The saturated-GPU measurements of bench.py on their own (for rocprofv3): the resident S1 scene, or S0 (one full-frame opaque
-rectangle), as 8 frames per kernel launch.   usage (GPU box): python tools/batched_bench.py s1|s0 [launches]"""
+rectangle), as 8 frames per kernel launch.   usage (GPU box): python tools/batched_bench.py s1|s0 [launches [library]]
+(library: another build of libswfr.so, e.g. build/<name>/libswfr.so from tools/build_variant.sh)"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -7,6 +8,9 @@ os.environ["SWFR_FRAMES_IN_FLIGHT"] = "1"
 import numpy as np
 import swf_renderer_amd as S
 from swf_renderer_amd import api, synth
+if len(sys.argv) > 3:
+    _lib = os.path.join(ROOT, sys.argv[3])
+    api.library_path = lambda: _lib
 which = sys.argv[1] if len(sys.argv) > 1 else "s1"
 launches = int(sys.argv[2]) if len(sys.argv) > 2 else 12
 cfg = synth.S1
