@@ -1246,18 +1246,18 @@ __device__ __forceinline__ uint32_t blend2(uint32_t dst, uint32_t a, uint32_t ef
 #define T3_PAIR_FROM 8192u            // strips per frame from which a frame's wavefronts paint two strips each
 #define T3_CLS_PRE 2                   // x 64 class bytes of a strip fetched up front
 
-// 24-bit multiplies (v_mul_u32_u24 / v_mad_u32_u24 issue at full rate, v_mul_lo_u32 at a quarter): two 8-bit channels in the
-// 0x00ff00ff layout times an 8-bit factor fit
+// The rounded products of the compacted blends: two 8-bit channels in the 0x00ff00ff layout times an 8-bit factor, in packed 16-bit
+// arithmetic (raster_common.hip): multiply-add, shift, add, shift -- four full-rate instructions and no mask between them, because
+// every intermediate of either half fits sixteen bits: 255 * 255 + 0x80 = 65 153, and + (that >> 8 = 254) = 65 407
+// (tests/test_tile_walk.py checks all 65 536 pairs of both roundings against the masked 32-bit form)
 __device__ __forceinline__ uint32_t mul8x2_7f_24(uint32_t a, uint32_t b) {
-    uint32_t t = __umul24(a & 0xff00ffu, b) + 0x7f007fu;
-    return ((t + ((t >> 8) & 0xff00ffu)) >> 8) & 0xff00ffu;
+    const uint32_t t = pk_mad_u16(a & 0xff00ffu, pk_both(b), 0x7f007fu);
+    return pk_lshr_u16<8>(pk_add_u16(t, pk_lshr_u16<8>(t)));
 }
 __device__ __forceinline__ uint32_t mul_un8_24(uint32_t x, uint32_t a) {
-    uint32_t rb = __umul24(x & 0xff00ffu, a) + 0x800080u;
-    rb = ((rb + ((rb >> 8) & 0xff00ffu)) >> 8) & 0xff00ffu;
-    uint32_t ag = __umul24((x >> 8) & 0xff00ffu, a) + 0x800080u;
-    ag = ((ag + ((ag >> 8) & 0xff00ffu)) >> 8) & 0xff00ffu;
-    return rb | (ag << 8);
+    const uint32_t a2 = pk_both(a);
+    const uint32_t rb = pk_mad_u16(x & 0xff00ffu, a2, 0x800080u), ag = pk_mad_u16((x >> 8) & 0xff00ffu, a2, 0x800080u);
+    return pk_lshr_u16<8>(pk_add_u16(rb, pk_lshr_u16<8>(rb))) | (pk_lshr_u16<8>(pk_add_u16(ag, pk_lshr_u16<8>(ag))) << 8);
 }
 // what the compacted blend does with a queued pixel of a solid-colour path: Cairo's SOURCE lerp (0x7f rounding: lerp_pixel) or
 // pixman's OVER (0x80 rounding: over_pixel of the colour times the coverage); coverage 0 keeps the pixel
@@ -1560,7 +1560,21 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     const int width = FR->width, height = FR->height, tiles_x = FR->tiles_x;
     const swfr_style* __restrict__ styles = FR->styles;
     const Sources bitmaps = {FR->src.bitmaps, FR->src.filters, FR->src.fparams, FR->src.gradients};
-    bool acc_clean = false;                                // the accumulators are zeroed before the first partial path needs them (many strips have none)
+    // The descriptor fields the loops below read -- per strip, per staging round, per partial pair -- loaded here once and held
+    // (T3_FIELD) in the instances that can pay the scalar registers without scratch or a wavefront per SIMD: the solid one.  The
+    // others read them where they are used, as before: pinned, each of them spills vector registers.
+    constexpr bool PIN = SHADERS == 0;
+    [[maybe_unused]] SWFR_GLOBAL_PTR(const StripDesc) p_strips = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(StripTop) p_strip_top = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(const uint8_t) p_cls = nullptr;
+    [[maybe_unused]] SWFR_GLOBAL_PTR(const BandEntry2) p_band_list = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(const RowInfo2) p_rows = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(const Cell) p_cells = nullptr;
+    [[maybe_unused]] uint32_t p_cell_slice = 0u;
+    if constexpr (PIN) {
+        p_strips = (SWFR_GLOBAL_PTR(const StripDesc))FR->strips; p_strip_top = (SWFR_GLOBAL_PTR(StripTop))FR->strip_top; p_cls = (SWFR_GLOBAL_PTR(const uint8_t))FR->cls;
+        p_band_list = (SWFR_GLOBAL_PTR(const BandEntry2))FR->band_list; p_rows = (SWFR_GLOBAL_PTR(const RowInfo2))FR->rows; p_cells = (SWFR_GLOBAL_PTR(const Cell))FR->cells;
+        p_cell_slice = FR->cell_slice;
+        SWFR_PIN_SGPR(p_strips); SWFR_PIN_SGPR(p_strip_top); SWFR_PIN_SGPR(p_cls); SWFR_PIN_SGPR(p_band_list); SWFR_PIN_SGPR(p_rows); SWFR_PIN_SGPR(p_cells); SWFR_PIN_SGPR(p_cell_slice);
+    }
+#define T3_FIELD(name) (PIN ? (decltype(FR->name))p_##name : FR->name)
+    uint32_t acc_clean = 0u;                               // the accumulators are zeroed before the first partial path needs them (many strips have none)
 
     // The wavefront's strips: slots blockIdx.x, + gridDim.x, ... of the launch list.  Two strips' records are in flight while a strip is
     // painted (a persistent launch -- fewer wavefronts than strips -- hides three of a strip's dependent round trips this way): the
@@ -1570,7 +1584,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     const uint32_t n_slots = FR->n_strip_slots, G = gridDim.x;
     auto fetch_desc = [&](uint32_t slot) -> uint32_t {                   // lanes 0..3: the StripDesc of a slot ({~0, ..} beyond the list)
         uint32_t v = ~0u;
-        if (slot < n_slots && lane < 4) v = reinterpret_cast<const uint32_t*>(FR->strips + slot)[lane];
+        if (slot < n_slots && lane < 4) v = reinterpret_cast<const uint32_t*>(T3_FIELD(strips) + slot)[lane];
         return v;
     };
     uint32_t n_wg = ~0u, n_band_begin = 0u, n_nb = 0u;                    // the next strip (wave-uniform) ...
@@ -1588,8 +1602,8 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         const int trow = (int)FR->band_first + (int)(where >> 16) * (int)FR->band_stride;
         n_ty0 = trow * TILE_H + strip * STRIP_H;
         // what the row pass knows about the strip as a whole (StripTop), and the strip's class byte per band entry
-        if (lane < 4) n_top = reinterpret_cast<const uint32_t*>(FR->strip_top + n_wg)[lane];
-        const uint8_t* cl = FR->cls + (size_t)STRIPS_PER_TILE * tiles_x * n_band_begin + (size_t)(n_tcol * STRIPS_PER_TILE + strip) * n_nb;
+        if (lane < 4) n_top = reinterpret_cast<const uint32_t*>(T3_FIELD(strip_top) + n_wg)[lane];
+        const uint8_t* cl = T3_FIELD(cls) + (size_t)STRIPS_PER_TILE * tiles_x * n_band_begin + (size_t)(n_tcol * STRIPS_PER_TILE + strip) * n_nb;
 #pragma unroll
         for (int u = 0; u < T3_CLS_PRE; ++u) if ((uint32_t)(u * 64 + lane) < n_nb) n_cls[u] = (uint32_t)cl[u * 64 + lane];
     };
@@ -1623,7 +1637,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         [[maybe_unused]] int sp = 0, mat = 0;                             // open groups of this strip's walk, and how many of them have had the
                                                                          // strip's pixels set aside for them (wave-uniform; instance 4 only)
 
-        const uint8_t* mycls = FR->cls + (size_t)STRIPS_PER_TILE * tiles_x * band_begin + (size_t)(tcol * STRIPS_PER_TILE + strip) * n_b;   // this strip's class byte per band entry
+        const uint8_t* mycls = T3_FIELD(cls) + (size_t)STRIPS_PER_TILE * tiles_x * band_begin + (size_t)(tcol * STRIPS_PER_TILE + strip) * n_b;   // this strip's class byte per band entry
         auto cls_chunk = [&](uint32_t c0) -> uint32_t {               // the class bytes of entries c0 .. c0 + 63 (c0 a multiple of 64, wave-uniform)
             if (c0 < 64u * T3_CLS_PRE) {
                 uint32_t f = cpre[0];
@@ -1638,13 +1652,13 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         const uint32_t cover_pos = (uint32_t)(top.cover >> 32);
         if (lane == 0 && top.any != 0u) {                                  // (depends on the loaded value: never overtakes the read)
 #ifdef SWFR_EMU
-            StripTop z; z.any = 0u; z.pad = 0u; z.cover = 0ull; FR->strip_top[wg] = z;
+            StripTop z; z.any = 0u; z.pad = 0u; z.cover = 0ull; T3_FIELD(strip_top)[wg] = z;
 #else
             // (the zero is made here: as a loop invariant the compiler kept four zeroed registers alive across the whole strip loop --
             //  in the bitmap instance it spilled them at kernel entry, 16 bytes of scratch per lane)
             uint32_t z = 0u;
             asm volatile("" : "+v"(z));
-            *reinterpret_cast<uint4*>(&FR->strip_top[wg]) = make_uint4(z, z, z, z);
+            *reinterpret_cast<uint4*>(&T3_FIELD(strip_top)[wg]) = make_uint4(z, z, z, z);
 #endif
         }
         const bool uniform = top.any == cover_pos;                        // (wave-uniform)
@@ -1674,12 +1688,12 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                 todo &= ~taken;
                 if (take) {
                     const uint32_t bidx = band_begin + bi;
-                    const uint4* s4 = reinterpret_cast<const uint4*>(&FR->band_list[bidx]);
+                    const uint4* s4 = reinterpret_cast<const uint4*>(&T3_FIELD(band_list)[bidx]);
                     const uint4 q0 = s4[0], q1 = s4[1];
                     uint4 h0 = make_uint4(0u, 0u, 0u, 0u), h1 = h0, h2 = h0, h3 = h0;
                     const bool part = (f & (CLS_PARTIAL | CLS_BOX)) == CLS_PARTIAL;
                     if (part) {
-                        const uint4* r4 = reinterpret_cast<const uint4*>(&FR->rows[(size_t)bidx * TILE_H + (uint32_t)(strip * STRIP_H)]);
+                        const uint4* r4 = reinterpret_cast<const uint4*>(&T3_FIELD(rows)[(size_t)bidx * TILE_H + (uint32_t)(strip * STRIP_H)]);
                         h0 = r4[0]; h1 = r4[1]; h2 = r4[2]; h3 = r4[3];
                     }
                     uint4* e4 = reinterpret_cast<uint4*>(&ent[rank][0]);
@@ -1750,9 +1764,13 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     if (fe & CLS_BOX) {
                         // ---- rectilinear (A.6): exact area of disjoint boxes, alpha = (c>>8) - (c>>16)
                         const uint32_t e_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)eb.y), e_nedges = (uint32_t)__builtin_amdgcn_readfirstlane((int)eb.z);
-                        // (one pixel row of the lane at a time: eight running sums at once cost the shaded instances a wavefront per SIMD)
-#pragma unroll 1
-                        for (int h = 0; h < 2; ++h) {
+                        // (one pixel row of the lane at a time: eight running sums at once cost the shaded instances a wavefront per SIMD.
+                        //  The loop over the two rows stays a loop, and al[] is a shift register in it: the second half starts at zero, each
+                        //  round moves it to the first and puts the round's row there -- al[] is defined as a whole, at constant indices.
+                        //  A body that picks the half at run time, `if (h == 0) al[i] = a; else al[4 + i] = a;`, writes al[] piecemeal: the
+                        //  compiler then carried al[]'s undefined start -- and with it copies of px[] and the masks of the full-cover branch
+                        //  -- from one entry of the walk to the next, and selected each element through a chain of v_cndmask.)
+                        auto box_row = [&](const int h, uint32_t (&a4)[4]) {
                             uint32_t cov[4] = {0u, 0u, 0u, 0u};
                             const int cy = cy0 + 4 * h;
                             for (uint32_t k = 0; k < e_nedges; ++k) {
@@ -1768,10 +1786,16 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                             const int rr = g + 4 * h;
                             const bool in = rr >= row_lo && rr < row_hi;
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const uint32_t a = in ? (((cov[i] >> 8) - (cov[i] >> 16)) & 255u) : 0u;
-                                if (h == 0) al[i] = a; else al[4 + i] = a;
-                            }
+                            for (int i = 0; i < 4; ++i) a4[i] = in ? (((cov[i] >> 8) - (cov[i] >> 16)) & 255u) : 0u;
+                        };
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) al[4 + i] = 0u;
+#pragma unroll 1
+                        for (int h = 0; h < 2; ++h) {
+                            uint32_t a4[4];
+                            box_row(h, a4);
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) { al[i] = al[4 + i]; al[4 + i] = a4[i]; }
                         }
                     } else if (fe & CLS_PARTIAL) {
                         // ---- tor (A.5): the cells of this strip's eight rows of the path, lane = (row, k-th cell)
@@ -1779,16 +1803,16 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                         if (!acc_clean) {                                    // (wave-uniform)
                             *reinterpret_cast<int4*>(&acc[g][4 * cg]) = make_int4(0, 0, 0, 0);     // (the padding columns are never touched)
                             *reinterpret_cast<int4*>(&acc[g + 4][4 * cg]) = make_int4(0, 0, 0, 0);
-                            acc_clean = true;                               // every path leaves them empty behind itself
+                            acc_clean = 1u;                                // every path leaves them empty behind itself
                             lds_barrier();
                         }
                         uint32_t off = 0; int n_c = 0;
                         if (cr >= row_lo && cr < row_hi) {                   // (a row outside the path's rows gets no cells: alpha 0)
                             const uint2 hq = *reinterpret_cast<const uint2*>(&hdr[li][2 * cr]);
                             off = hq.x; n_c = (int)(hq.y & 0xffffu);
-                            if (off > FR->cell_slice - min((uint32_t)n_c, FR->cell_slice)) { atomicOr(&FR->counters[C2_ERROR], E2_CELL_RANGE); n_c = 0; }   // off + n_c > cell_slice
+                            if (off > T3_FIELD(cell_slice) - min((uint32_t)n_c, T3_FIELD(cell_slice))) { atomicOr(&FR->counters[C2_ERROR], E2_CELL_RANGE); n_c = 0; }   // off + n_c > cell_slice
                         }
-                        const Cell* __restrict__ cp = FR->cells + off;
+                        const Cell* __restrict__ cp = T3_FIELD(cells) + off;
                         // the first sixteen cells of every row in one round trip, the rest (long shallow edges) eight per round
                         Cell c0c, c1c; c0c.w = 0; c1c.w = 0;
                         if (ck < n_c) c0c = cp[ck];
@@ -1857,14 +1881,18 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                         }
                     } else {
                         // full cover: every in-frame pixel of the path's rows in this tile has coverage 255
-                        const bool in0 = g >= row_lo && g < row_hi, in1 = g + 4 >= row_lo && g + 4 < row_hi;
-                        if ((SHADERS < 3 || op == 0u) && (SHADERS == 0 || (eflags & BE_SOLID)) && ((eflags & BE_LERP) || (solid >> 24) == 0xffu)) {     // (wave-uniform) the colour itself
+                        // The colour itself (wave-uniform), in every row of the strip -- the usual full cover: eight moves and no per-lane
+                        // test, so that no lane mask of this branch lives beyond it (a mask that crosses the blend below is merged with an
+                        // undefined one at every join up to the loop's end: a dozen scalar instructions per entry).  A cover that the
+                        // path's rectangle or the frame cuts inside the strip goes through the blend: its coverage-255 select is this select.
+                        if (row_lo == 0 && row_hi == STRIP_H && (SHADERS < 3 || op == 0u) && (SHADERS == 0 || (eflags & BE_SOLID)) && ((eflags & BE_LERP) || (solid >> 24) == 0xffu)) {
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) { px[j] = in0 ? solid : px[j]; px[4 + j] = in1 ? solid : px[4 + j]; }
+                            for (int j = 0; j < 8; ++j) px[j] = solid;
                             continue;
                         }
+                        const uint32_t cv0 = g >= row_lo && g < row_hi ? 255u : 0u, cv1 = g + 4 >= row_lo && g + 4 < row_hi ? 255u : 0u;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { al[j] = in0 ? 255u : 0u; al[4 + j] = in1 ? 255u : 0u; }
+                        for (int j = 0; j < 4; ++j) { al[j] = cv0; al[4 + j] = cv1; }
                     }
 #ifdef ABL_T_NOBLEND
                     for (int j = 0; j < 8; ++j) px[j] = al[j] == 255u ? solid : px[j];
@@ -1894,9 +1922,13 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         const bool vec_ok = (width & 3) == 0 && ((uintptr_t)fbp & 15u) == 0u;      // (wave-uniform) every row of the frame starts 16-byte aligned
         if (vec_ok && tx0 + TILE_W <= width && ty0 + STRIP_H <= height) {
             // the strip lies inside the frame (wave-uniform: all but the last tile column / tile row): two stores, no per-lane tests
+            // (each a single 16-byte store from the start: written as uint4 -- a struct of four members, four dword stores until late in
+            //  the compiler -- the second row's last members were merged with the clipped path's per-pixel stores below, and the row left
+            //  the compiler as three partial stores)
+            typedef uint32_t row4 __attribute__((vector_size(16)));
             uint32_t* rowp = fbp + (size_t)cy0 * (size_t)width + cx0;
-            *reinterpret_cast<uint4*>(rowp) = make_uint4(px[0], px[1], px[2], px[3]);
-            *reinterpret_cast<uint4*>(rowp + 4 * (size_t)width) = make_uint4(px[4], px[5], px[6], px[7]);
+            *reinterpret_cast<row4*>(rowp) = row4{px[0], px[1], px[2], px[3]};
+            *reinterpret_cast<row4*>(rowp + 4 * (size_t)width) = row4{px[4], px[5], px[6], px[7]};
         } else {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {

@@ -23,6 +23,17 @@
 #else
 #define SWFR_OPAQUE(x) asm volatile("" : "+v"(x))
 #endif
+// SWFR_PIN_SGPR(x): a wave-uniform value loaded once stays in scalar registers (or in a lane of a spill VGPR) from here on; without
+// it the compiler, short of SGPRs, loads a descriptor field again wherever it is used -- a scalar round trip and a wait inside a loop.
+// (a pinned pointer is declared SWFR_GLOBAL_PTR: behind the asm the compiler no longer knows where a plain pointer came from, and
+//  would reach device memory through flat instructions)
+#ifdef SWFR_EMU
+#define SWFR_PIN_SGPR(x) do { } while (0)
+#define SWFR_GLOBAL_PTR(T) T*
+#else
+#define SWFR_PIN_SGPR(x) asm volatile("" : "+s"(x))
+#define SWFR_GLOBAL_PTR(T) T __attribute__((address_space(1)))*
+#endif
 
 namespace swfr {
 
@@ -87,6 +98,33 @@ __device__ __forceinline__ int lshl_add(int a, int b) {
     return r;
 #endif
 }
+// Packed 16-bit arithmetic on the two halves of a dword (v_pk_mad_u16, v_pk_add_u16, v_pk_lshrrev_b16): each half wraps at 2^16 on
+// its own, nothing crosses from the low half into the high one, so two 8-bit channels in the 0x00ff00ff layout need no mask
+// between the steps of a rounded division by 255 as long as every intermediate fits sixteen bits.
+#ifdef SWFR_EMU
+__device__ __forceinline__ uint32_t pk_mad_u16(uint32_t a, uint32_t b, uint32_t c) {
+    return (((a & 0xffffu) * (b & 0xffffu) + (c & 0xffffu)) & 0xffffu) | ((((a >> 16) * (b >> 16) + (c >> 16)) & 0xffffu) << 16);
+}
+__device__ __forceinline__ uint32_t pk_add_u16(uint32_t a, uint32_t b) {
+    return (((a & 0xffffu) + (b & 0xffffu)) & 0xffffu) | ((((a >> 16) + (b >> 16)) & 0xffffu) << 16);
+}
+template <int SH>
+__device__ __forceinline__ uint32_t pk_lshr_u16(uint32_t a) { return ((a & 0xffffu) >> SH) | (((a >> 16) >> SH) << 16); }
+#else
+typedef unsigned short pk_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_mad_u16(uint32_t a, uint32_t b, uint32_t c) {
+    return __builtin_bit_cast(uint32_t, (pk_u16x2)(__builtin_bit_cast(pk_u16x2, a) * __builtin_bit_cast(pk_u16x2, b) + __builtin_bit_cast(pk_u16x2, c)));
+}
+__device__ __forceinline__ uint32_t pk_add_u16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, (pk_u16x2)(__builtin_bit_cast(pk_u16x2, a) + __builtin_bit_cast(pk_u16x2, b)));
+}
+template <int SH>
+__device__ __forceinline__ uint32_t pk_lshr_u16(uint32_t a) {
+    return __builtin_bit_cast(uint32_t, (pk_u16x2)(__builtin_bit_cast(pk_u16x2, a) >> (unsigned short)SH));
+}
+#endif
+// an 8-bit factor in both halves of a dword
+__device__ __forceinline__ uint32_t pk_both(uint32_t f) { return f | (f << 16); }
 // wave64 inclusive prefix sum with DPP row shifts + row broadcasts (no LDS traffic)
 __device__ __forceinline__ int wave_scan_incl(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
