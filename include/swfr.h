@@ -120,7 +120,7 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
        SWFR_OBJECT_COLOR_TRANSFORM = 3   /* a container (matrix + children) whose `id` names a colour-transform slot (swfr_set_color_transform):
                                             the slot's value at the time of the render call applies to everything below it.  Beyond the
                                             reference, whose display objects carry a matrix and a ratio only */,
-       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7 and 9 and above) */
+       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10 and 12 and above) */
        SWFR_OBJECT_BLEND_MODE = 5,       /* a container (matrix + children) whose `id` is an SWF blend-mode number (SWFR_BLEND_*): every path
                                             drawn below it is composited, each on its own, with the mode's Cairo operator -- what
                                             CanvasRenderer would do if it set ctx.globalCompositeOperation before drawing the object.  It
@@ -133,9 +133,21 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
                                             3..8, 13, 14: the mode's operator; 9..12: SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode";
                                             above 14: SWFR_ERR_INVALID.  A SWFR_OBJECT_BLEND_MODE in force around the layer still applies
                                             per path inside it, against the layer's own pixels.  Layers nest up to SWFR_MAX_LAYER_DEPTH
-                                            deep: deeper is SWFR_ERR_CAPACITY, "LayerDepth".  No layer opacity, no masks; a colour
+                                            deep: deeper is SWFR_ERR_CAPACITY, "LayerDepth".  No layer opacity (masks: SWFR_OBJECT_MASKED_LAYER); a colour
                                             transform around a layer recolours the definitions below it, it does not fade the layer as
-                                            a whole.  DESIGN.md, "Isolated layers" */ };
+                                            a whole.  DESIGN.md, "Isolated layers" */,
+       SWFR_OBJECT_MASKED_LAYER = 11     /* a masked layer: a container (matrix + children) whose children[0] is the MASK subtree and whose
+                                            children[1..] are the content.  Both are drawn as isolated groups that start clear --
+                                            cairo_push_group; the content; content = cairo_pop_group; cairo_push_group; the mask; mask =
+                                            cairo_pop_group; cairo_set_source(content); cairo_set_operator; cairo_mask(mask) -- and per
+                                            pixel the parent's d becomes combine_op(mul_un8(C, Ma), d): C the content's premultiplied
+                                            pixel, Ma the mask group's ALPHA (its colour channels play no part), mul_un8 per channel with
+                                            0x80 rounding, combine_op the unmasked combiner of SWFR_OBJECT_LAYER.  `id` is an SWF
+                                            blend-mode number, accepted exactly as SWFR_OBJECT_LAYER accepts it.  The object's matrix
+                                            applies to both halves.  n_children == 0: SWFR_ERR_INVALID, "MaskedLayerWithoutMask".  A
+                                            masked layer uses TWO levels of SWFR_MAX_LAYER_DEPTH.  Unlike a Flash clip-depth mask the
+                                            mask's alpha counts and so do its strokes (geometry only: put the mask under a colour
+                                            transform with alpha mult 0, add 255).  DESIGN.md, "Masked layers" */ };
 #define SWFR_MAX_LAYER_DEPTH 4
 
 /* SWF blend-mode numbers (PlaceObject3, swf-tree BlendMode).  0, 1: OVER.  3..8, 13, 14: the Cairo operator of the same name
@@ -240,7 +252,13 @@ enum { SWFR_PATH_TOR = 0,   /* general polygon: Cairo "tor" 15x256 scan conversi
           rectangles of the paths between them (those lie inside it).  BEGIN's `lerp` is 0; END's holds the composite's operator in bits
           8..15 and 0 in bits 0..7.  Markers are balanced and nest at most SWFR_MAX_LAYER_DEPTH deep; their `style` is ignored.  Inside a
           group "the surface" of the lerp rule is the group's: its first paint is a SOURCE lerp.  SWFR_ERR_INVALID at upload otherwise */
-       SWFR_PATH_GROUP_BEGIN = 2, SWFR_PATH_GROUP_END = 3 };
+       SWFR_PATH_GROUP_BEGIN = 2, SWFR_PATH_GROUP_END = 3,
+       /* the third marker, of a masked group (SWFR_OBJECT_MASKED_LAYER): BEGIN; content paths; MASK; mask paths; END(operator).  The
+          paths behind MASK are drawn onto a second transparent surface; END multiplies the content's pixels by that surface's alpha
+          (mul_un8 per channel) and composites the product as GROUP_END does.  n_edges 0, lerp 0, the rectangle of its BEGIN and END
+          (the union of all member rectangles, content and mask); at most one MASK per group, and none outside a group; a masked group
+          counts two levels of SWFR_MAX_LAYER_DEPTH; groups nest inside either half.  SWFR_ERR_INVALID at upload otherwise */
+       SWFR_PATH_GROUP_MASK = 4 };
 
 typedef struct {
     uint32_t first_edge, n_edges;

@@ -38,8 +38,9 @@ EXPORTS = [
 OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
 OBJECT_BLEND_MODE = 5
 OBJECT_LAYER = 8                        # an isolated group (swfr.h SWFR_OBJECT_LAYER); `id` is the blend mode it is composited with
-MAX_LAYER_DEPTH = 4
-PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END = 0, 1, 2, 3
+OBJECT_MASKED_LAYER = 11                # a masked layer (swfr.h SWFR_OBJECT_MASKED_LAYER): children[0] the mask, children[1..] the content; `id` the blend mode
+MAX_LAYER_DEPTH = 4                     # (a masked layer takes two levels)
+PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END, PATH_GROUP_MASK = 0, 1, 2, 3, 4
 # SWF blend-mode numbers under swf-tree's names (BlendMode); what the library does with each is swfr.h's SWFR_BLEND_* comment
 BLEND_MODES = {"normal": 1, "layer": 2, "multiply": 3, "screen": 4, "lighten": 5, "darken": 6, "difference": 7, "add": 8,
                "subtract": 9, "invert": 10, "alpha": 11, "erase": 12, "overlay": 13, "hardlight": 14}
@@ -533,6 +534,17 @@ class Renderer:
         if obj.get("matrix") is not None:
             d.has_matrix = 1
             d.matrix = _matrix(obj["matrix"])
+        if obj.get("mask") is not None:
+            # the object inside a type-11 wrapper, where the type-8 wrapper would sit: children[0] a plain container of the "mask" list --
+            # a sibling in the parent's space, outside the object's own matrix, colour transform and blend mode --, children[1] the object;
+            # composited with the mode of "layer" (absent: normal)
+            w = DisplayObject()
+            layer = obj.get("layer")
+            w.type, w.id = OBJECT_MASKED_LAYER, BLEND_MODES["normal"] if layer is None or layer is False else layer_mode_number(layer)
+            inner = {k: v for k, v in obj.items() if k not in ("mask", "layer")}
+            kids = arena.array(DisplayObject, [self._object(arena, {"type": "container", "children": list(obj["mask"])}), self._object(arena, inner)])
+            w.n_children, w.children = 2, C.cast(kids, C.POINTER(DisplayObject))
+            return w
         if obj.get("layer") is not None and obj.get("layer") is not False:
             # the object inside a type-8 wrapper, outside its blend-mode and colour-transform wrappers: the object is drawn as an
             # isolated group and composited as one layer ("layer": True / "normal" / "layer": OVER; a mode name or number: its operator)

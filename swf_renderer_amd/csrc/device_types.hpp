@@ -61,7 +61,7 @@ constexpr int ROWS_CHUNK = 64;       // most pixel rows per k2_rows wavefront (o
 // flags of a band list entry (BandEntry2)
 // a path's byte of Frame2::path_op: bits 0..3 the operator (SWFR_OP_*); what isolated groups add (renderer.cpp, lower_groups; a frame
 // with any of the two marker bits runs k2_tiles<4>): the path is a group marker, or -- inside a group -- blends by the lerp rule
-enum : uint32_t { PATH_OP_MASK = 0x0fu, PATH_OP_LERP = 0x10u, PATH_OP_GROUP_BEGIN = 0x20u, PATH_OP_GROUP_END = 0x40u };
+enum : uint32_t { PATH_OP_MASK = 0x0fu, PATH_OP_LERP = 0x10u, PATH_OP_GROUP_BEGIN = 0x20u, PATH_OP_GROUP_END = 0x40u, PATH_OP_MASKED = 0x80u };
 enum : uint32_t { BE_BOXES = 1u, BE_LERP = 2u, BE_SOLID = 4u, BE_OPAQUE_COVER = 8u /* solid, alpha 255, lerp blend */ };
 
 // One k2_rows wavefront: `rows` (<= 64) consecutive pixel rows of one path.  rec_base is the path's first (edge, row) incidence

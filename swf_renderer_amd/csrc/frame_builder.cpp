@@ -366,6 +366,9 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
         case SWFR_OBJECT_LAYER:
             draw_layer(obj, depth);
             break;
+        case SWFR_OBJECT_MASKED_LAYER:
+            draw_masked_layer(obj, depth);
+            break;
         case SWFR_OBJECT_SHAPE: {
             const DecodedShape* sh = shape(obj.id, false);
             if (!sh) throw StatusError{SWFR_ERR_NOT_FOUND, "unknown shape id"};
@@ -416,6 +419,61 @@ void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth) {
         b.x_min = std::min(b.x_min, p.x_min); b.y_min = std::min(b.y_min, p.y_min);
         b.x_max = std::max(b.x_max, p.x_max); b.y_max = std::max(b.y_max, p.y_max);
     }
+    m = b;
+    m.kind = SWFR_PATH_GROUP_END;
+    m.first_edge = uint32_t(edges_.size());
+    m.lerp = op << 8;
+    paths_.push_back(m);
+}
+
+// A masked layer ("Masked layers"): cairo_push_group; children[1..]; content = cairo_pop_group; cairo_push_group;
+// children[0]; mask = cairo_pop_group; cairo_set_source(content); cairo_set_operator; cairo_mask(mask).  BEGIN; the content's paths;
+// MASK; the mask's paths; END(operator), the three markers sharing the union of all member rectangles.  Each half is a group surface of
+// its own that starts clear; the pair takes two levels of SWFR_MAX_LAYER_DEPTH from its BEGIN on.
+void FrameBuilder::draw_masked_layer(const swfr_display_object& obj, int depth) {
+    const uint32_t op = layer_operator(obj.id);
+    if (obj.n_children == 0) throw StatusError{SWFR_ERR_INVALID, "MaskedLayerWithoutMask"};
+    if (group_depth_ + 2 > SWFR_MAX_LAYER_DEPTH) throw StatusError{SWFR_ERR_CAPACITY, "LayerDepth"};
+    const bool parent_clear = surface_clear_;
+    const size_t begin = paths_.size(), begin_edges = edges_.size(), begin_styles = styles_.size();
+    swfr_path m;
+    std::memset(&m, 0, sizeof m);
+    m.kind = SWFR_PATH_GROUP_BEGIN;
+    m.first_edge = uint32_t(edges_.size());
+    paths_.push_back(m);
+    group_depth_ += 2;
+    surface_clear_ = true;
+    for (uint32_t i = 1; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
+    const bool content_clear = surface_clear_;
+    const size_t mask_at = paths_.size();
+    m.kind = SWFR_PATH_GROUP_MASK;
+    m.first_edge = uint32_t(edges_.size());
+    paths_.push_back(m);
+    surface_clear_ = true;
+    draw(obj.children[0], depth + 1);
+    const bool mask_clear = surface_clear_;
+    group_depth_ -= 2;
+    // libcairo: a still-clear mask is NOTHING_TO_DO under every operator, a still-clear content under OVER and ADD only; the parent's
+    // "still clear" state survives exactly then.  Otherwise -- both drawn on, even with every pixel zero -- the parent counts as drawn
+    const bool nothing_to_do = mask_clear || (content_clear && (op == SWFR_OP_OVER || op == SWFR_OP_ADD));
+    surface_clear_ = parent_clear && nothing_to_do;
+    // a half without a surviving path is transparent: the product mul_un8(C, Ma) is, and changes no pixel under any operator
+    if (nothing_to_do || mask_at == begin + 1 || paths_.size() == mask_at + 1) {
+        paths_.resize(begin);
+        edges_.resize(begin_edges);
+        styles_.resize(begin_styles);
+        return;
+    }
+    swfr_path& b = paths_[begin];
+    b.x_min = b.y_min = INT32_MAX; b.x_max = b.y_max = INT32_MIN;
+    for (size_t i = begin + 1; i < paths_.size(); ++i) {
+        if (i == mask_at) continue;
+        const swfr_path& p = paths_[i];
+        b.x_min = std::min(b.x_min, p.x_min); b.y_min = std::min(b.y_min, p.y_min);
+        b.x_max = std::max(b.x_max, p.x_max); b.y_max = std::max(b.y_max, p.y_max);
+    }
+    swfr_path& k = paths_[mask_at];
+    k.x_min = b.x_min; k.y_min = b.y_min; k.x_max = b.x_max; k.y_max = b.y_max;
     m = b;
     m.kind = SWFR_PATH_GROUP_END;
     m.first_edge = uint32_t(edges_.size());

@@ -78,6 +78,7 @@ private:
     };
     void draw(const swfr_display_object& obj, int depth);
     void draw_layer(const swfr_display_object& obj, int depth);
+    void draw_masked_layer(const swfr_display_object& obj, int depth);
     void draw_path(const StyledPath& p, bool morph, double ratio);
     void trace(const StyledPath& p, bool morph, double ratio);
     void emit_fill(const OwnedFill& f, bool morph, double ratio);

@@ -1543,6 +1543,21 @@ __device__ __forceinline__ void composite_group(uint32_t (&px)[8], const uint32_
     }
 }
 
+// The mask step of a masked group's END (k2_tiles<5>; DESIGN.md, "Masked layers"): `px` holds the mask group's pixels, `c` the content's as they were
+// set aside at the mask's first path; px = mul_un8(content, mask alpha) per channel, pixman's 0x80 rounding, two channels a multiply.
+// The mask's colour channels play no part.
+__device__ __forceinline__ void mask_group(uint32_t (&px)[8], const uint32_t* __restrict__ c) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t a = px[j] >> 24, s = c[j * 64];
+        uint32_t rb = (s & 0x00ff00ffu) * a + 0x00800080u;
+        rb = ((rb + ((rb >> 8) & 0x00ff00ffu)) >> 8) & 0x00ff00ffu;
+        uint32_t ag = ((s >> 8) & 0x00ff00ffu) * a + 0x00800080u;
+        ag = (ag + ((ag >> 8) & 0x00ff00ffu)) & 0xff00ff00u;
+        px[j] = rb | ag;
+    }
+}
+
 template <int SHADERS>
 __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     // per pixel: deltas whose prefix sum along the row is 17 * N(x), N = Cairo's coverage numerator 512 * H(x) - ua(x) (H: the heights
@@ -1635,7 +1650,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) px[j] = 0u;
         [[maybe_unused]] int sp = 0, mat = 0;                             // open groups of this strip's walk, and how many of them have had the
-                                                                         // strip's pixels set aside for them (wave-uniform; instance 4 only)
+                                                                         // strip's pixels set aside for them (wave-uniform; instances 4 and 5 only)
 
         const uint8_t* mycls = T3_FIELD(cls) + (size_t)STRIPS_PER_TILE * tiles_x * band_begin + (size_t)(tcol * STRIPS_PER_TILE + strip) * n_b;   // this strip's class byte per band entry
         auto cls_chunk = [&](uint32_t c0) -> uint32_t {               // the class bytes of entries c0 .. c0 + 63 (c0 a multiple of 64, wave-uniform)
@@ -1699,7 +1714,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     uint4* e4 = reinterpret_cast<uint4*>(&ent[rank][0]);
                     e4[0] = q0; e4[1] = q1; ent[rank][8] = f;
                     // (instance 3: the path's operator beside its entry; a frame without a blended path -- in a batch that has one, or
-                    //  forced through this instance -- has no table; instance 4: the byte also says what isolated groups need, PATH_OP_*)
+                    //  forced through this instance -- has no table; instances 4 and 5: the byte also says what isolated groups need, PATH_OP_*)
                     if constexpr (SHADERS >= 3) ent[rank][9] = FR->path_op ? (uint32_t)FR->path_op[q1.w] : 0u;
                     if (part) { uint4* d4 = reinterpret_cast<uint4*>(&hdr[rank][0]); d4[0] = h0; d4[1] = h1; d4[2] = h2; d4[3] = h3; }
                 }
@@ -1724,15 +1739,29 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     if constexpr (SHADERS >= 3) op = (uint32_t)__builtin_amdgcn_readfirstlane((int)ent[li][9]);
                     const int row_lo = max(e_ymin, ty0) - ty0, row_hi = min(min(e_ymax, ty0 + STRIP_H), height) - ty0;
                     if (row_hi <= row_lo) continue;                    // the path misses this strip of the tile
-                    if constexpr (SHADERS == 4) {
+                    if constexpr (SHADERS >= 4) {
                         // ---- isolated groups: a marker acts on the whole strip, whatever its own coverage (its two markers share a
                         //      rectangle: both reach this strip or neither does, and every path between them lies inside it)
                         if (op & (PATH_OP_GROUP_BEGIN | PATH_OP_GROUP_END)) {                      // (wave-uniform)
                             // BEGIN only counts: the strip's pixels are set aside when the first path of the group reaches this strip
                             // (below).  A group none of whose paths does -- its rectangle is the union of theirs, most of its strips
                             // may be such -- costs two scalar additions: a transparent group changes no pixel under any operator
-                            if (op & PATH_OP_GROUP_BEGIN) ++sp;
+                            if (op & PATH_OP_GROUP_BEGIN) ++sp;     // (also a MASK: the mask's surface is a group opened above the content's)
                             else if (sp > 0) {
+                                if (SHADERS == 5 && (op & PATH_OP_MASKED) && sp > 1) {
+                                    // (instance 5 only: instance 4 stays the code it was, frames with a MASK never run it)
+                                    // the END of a masked group: the mask step first.  The mask's surface was set up in this strip: its
+                                    // alpha times the content that was set aside for it.  It was not: the mask is transparent here, and
+                                    // so is the product -- content that was drawn in this strip is dropped.  Then the content's END
+                                    if (mat == sp) {
+                                        --mat;
+                                        if (mat < SWFR_MAX_LAYER_DEPTH) mask_group(px, layer_stack() + mat * (8 * 64) + lane);
+                                    } else if (mat == sp - 1) {
+#pragma unroll
+                                        for (int j = 0; j < 8; ++j) px[j] = 0u;
+                                    }
+                                    --sp;
+                                }
                                 if (mat == sp) {
                                     --mat;
                                     if (mat < SWFR_MAX_LAYER_DEPTH) composite_group(px, layer_stack() + mat * (8 * 64) + lane, op & PATH_OP_MASK);
@@ -1963,6 +1992,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_SHA
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_BLEND))) void k2_tiles_blend_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<3>(FRAME_PTR(frames, blockIdx.y), fb_to); }
 // frames with an isolated group (SWFR_PATH_GROUP_BEGIN / _END): everything the blend instance does, plus the stack of set-aside strips
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAYER))) void k2_tiles_layer_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<4>(FRAME_PTR(frames, blockIdx.y), fb_to); }
+// frames with a masked group (SWFR_PATH_GROUP_MASK): everything the layer instance does, plus the mask step at a masked group's END.  An
+// instance of its own so that frames with plain layers run the code they ran before
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAYER))) void k2_tiles_mask_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<5>(FRAME_PTR(frames, blockIdx.y), fb_to); }
 
 // ---------------------------------------------------------------------------------------------
 // launchers: `frames` is a device array of n_frames descriptors, blockIdx.y picks one
@@ -2001,7 +2033,8 @@ void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint
     // smaller frames do not fill the GPU and keep one wavefront per strip.
     uint32_t g = max_strips < grid_cap ? max_strips : grid_cap;
     if (grid_cap == ~0u && max_strips > T3_PAIR_FROM) g = (max_strips + 1u) / 2u;
-    if (shader_level >= 4) hipLaunchKernelGGL(k2_tiles_layer_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    if (shader_level >= 5) hipLaunchKernelGGL(k2_tiles_mask_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    else if (shader_level == 4) hipLaunchKernelGGL(k2_tiles_layer_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 3) hipLaunchKernelGGL(k2_tiles_blend_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level >= 2) hipLaunchKernelGGL(k2_tiles_shaded_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 1) hipLaunchKernelGGL(k2_tiles_bitmap_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);

@@ -256,7 +256,7 @@ struct swfr_renderer {
     bool mono = false;                      // SWFR_FLAG_ANTIALIAS_NONE: boxes rounded to pixels, tor paths by k2_rows_mono (Frame2::mono)
     int fast_limit = 16;                    // rows with more active edges go to k2_rows_slow; the row kernel's instance caps it at its 8 or 16 slots (SWFR_FAST_LIMIT: test knob)
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
-    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups; test knob)
+    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups, 5 masked groups; test knob)
     bool rows_wide = false;                 // SWFR_ROWS_WIDE=1: every frame with tor paths runs k2_rows_wide (test knob; aliased frames keep k2_rows_mono)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
     // the host builds one while the GPU works on the other
@@ -371,34 +371,62 @@ inline size_t cls_region_bytes(size_t n_slots, size_t tiles_x, size_t n_strips) 
 void validate_blend_fields(const swfr_path* paths, size_t n_paths) {
     for (size_t i = 0; i < n_paths; ++i) {
         const uint32_t v = paths[i].lerp;
-        if (paths[i].kind == SWFR_PATH_GROUP_BEGIN || paths[i].kind == SWFR_PATH_GROUP_END) continue;      // (validate_groups)
+        if (paths[i].kind >= SWFR_PATH_GROUP_BEGIN) continue;      // (validate_groups)
         if ((v & 0xffu) > 1u || (v >> 8) > SWFR_OP_HARDLIGHT || ((v >> 8) != 0u && (v & 0xffu) != 0u))
             throw StatusError{SWFR_ERR_INVALID, "path blend field: lerp must be 0 or 1, the operator at most 8, and lerp 0 with an operator"};
     }
 }
 
-// the markers of isolated groups (swfr.h, SWFR_PATH_GROUP_BEGIN / _END): balanced, at most SWFR_MAX_LAYER_DEPTH deep, no edges, BEGIN's
-// and END's rectangles equal, every path between them inside that rectangle, the lerp bits zero, END's operator one of SWFR_OP_*
+// the markers of isolated groups (swfr.h, SWFR_PATH_GROUP_BEGIN / _END / _MASK): balanced, at most SWFR_MAX_LAYER_DEPTH deep -- a group
+// with a MASK counting two levels from its BEGIN on --, no edges, the markers' rectangles equal, every path between them inside that
+// rectangle, the lerp bits zero, END's operator one of SWFR_OP_*, at most one MASK per group and none outside one
 void validate_groups(const swfr_path* paths, size_t n_paths) {
-    size_t open[SWFR_MAX_LAYER_DEPTH];
-    int depth = 0;
     auto bad = [](const char* what) { throw StatusError{SWFR_ERR_INVALID, what}; };
+    // which BEGINs open a masked group (a MASK belongs to the innermost group open where it stands)
+    static thread_local std::vector<size_t> opened;
+    static thread_local std::vector<uint8_t> masked;
+    opened.clear();
+    bool any_mask = false;
+    for (size_t i = 0; i < n_paths && !any_mask; ++i) any_mask = paths[i].kind == SWFR_PATH_GROUP_MASK;
+    if (any_mask) {
+        masked.assign(n_paths, 0);
+        for (size_t i = 0; i < n_paths; ++i) {
+            const uint32_t kind = paths[i].kind;
+            if (kind == SWFR_PATH_GROUP_BEGIN) opened.push_back(i);
+            else if (kind == SWFR_PATH_GROUP_END) { if (!opened.empty()) opened.pop_back(); }
+            else if (kind == SWFR_PATH_GROUP_MASK) {
+                if (opened.empty()) bad("GROUP_MASK outside a group");
+                if (masked[opened.back()]) bad("a second GROUP_MASK in one group");
+                masked[opened.back()] = 1;
+            }
+        }
+    }
+    size_t open[SWFR_MAX_LAYER_DEPTH];
+    int depth = 0, levels = 0;
     for (size_t i = 0; i < n_paths; ++i) {
         const swfr_path& p = paths[i];
         if (depth) {
             const swfr_path& g = paths[open[depth - 1]];
             if (p.x_min < g.x_min || p.y_min < g.y_min || p.x_max > g.x_max || p.y_max > g.y_max)
-                bad(p.kind == SWFR_PATH_GROUP_END ? "group markers: the rectangles of GROUP_BEGIN and GROUP_END differ" : "a path lies outside the rectangle of its group");
+                bad(p.kind >= SWFR_PATH_GROUP_END ? "group markers: the rectangles of GROUP_BEGIN and GROUP_END differ" : "a path lies outside the rectangle of its group");
         }
+        if (p.kind > SWFR_PATH_GROUP_MASK) bad("unknown path kind");
         if (p.kind == SWFR_PATH_GROUP_BEGIN) {
             if (p.n_edges != 0u || p.lerp != 0u) bad("GROUP_BEGIN: n_edges and lerp must be 0");
-            if (depth == SWFR_MAX_LAYER_DEPTH) bad("group markers nest deeper than SWFR_MAX_LAYER_DEPTH");
+            const int need = any_mask && masked[i] ? 2 : 1;
+            if (levels + need > SWFR_MAX_LAYER_DEPTH) bad("group markers nest deeper than SWFR_MAX_LAYER_DEPTH");
+            levels += need;
             open[depth++] = i;
         } else if (p.kind == SWFR_PATH_GROUP_END) {
             if (!depth) bad("GROUP_END without a GROUP_BEGIN");
             const swfr_path& g = paths[open[--depth]];
+            levels -= any_mask && masked[open[depth]] ? 2 : 1;
             if (p.n_edges != 0u || (p.lerp & 0xffu) != 0u || (p.lerp >> 8) > SWFR_OP_HARDLIGHT) bad("GROUP_END: n_edges and lerp bits 0..7 must be 0, the operator at most 8");
             if (p.x_min != g.x_min || p.y_min != g.y_min || p.x_max != g.x_max || p.y_max != g.y_max) bad("group markers: the rectangles of GROUP_BEGIN and GROUP_END differ");
+        } else if (p.kind == SWFR_PATH_GROUP_MASK) {
+            const swfr_path& g = paths[open[depth - 1]];                  // (inside a group: checked above)
+            if (p.n_edges != 0u || p.lerp != 0u) bad("GROUP_MASK: n_edges and lerp must be 0");
+            if (p.x_min != g.x_min || p.y_min != g.y_min || p.x_max != g.x_max || p.y_max != g.y_max) bad("group markers: the rectangles of GROUP_BEGIN and GROUP_MASK differ");
         }
     }
     if (depth) bad("GROUP_BEGIN without a GROUP_END");
@@ -407,7 +435,8 @@ void validate_groups(const swfr_path* paths, size_t n_paths) {
 // What the device sees of isolated groups ("Isolated layers").  A marker becomes a box path of ONE box, its rectangle, with
 // a transparent solid style and lerp 0: to k2_bin and the row kernels an ordinary path that reaches exactly the strips of the
 // rectangle, in painter's order, and paints nothing.  What it means travels in the path's operator byte (bits 8..15 of `lerp`, split off
-// into Frame2::path_op by push_scene), which only k2_tiles<3> and <4> read: PATH_OP_GROUP_BEGIN, or PATH_OP_GROUP_END | operator.  A
+// into Frame2::path_op by push_scene), which only k2_tiles<3>, <4> and <5> read: PATH_OP_GROUP_BEGIN, or PATH_OP_GROUP_END | operator
+// (SWFR_PATH_GROUP_MASK: PATH_OP_GROUP_BEGIN | PATH_OP_MASKED, and its group's END carries PATH_OP_MASKED, too: k2_tiles<5>).  A
 // path INSIDE a group loses its lerp bit (so that no kernel derives an opaque cover or a culling record from it: a cover inside a group
 // hides nothing outside) and carries it in PATH_OP_LERP instead, where k2_tiles<4> reads it back for the pixel arithmetic.
 // Returns false when the scene has no marker (nothing is copied).
@@ -421,16 +450,26 @@ bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths
     std::memset(&clear, 0, sizeof clear);
     clear.kind = SWFR_STYLE_SOLID;
     out_s.push_back(clear);
+    // (a MASK is to the device a second BEGIN, flagged PATH_OP_MASKED, and the END of its group pops both: it carries the flag, too)
     int depth = 0;
+    uint32_t masked = 0u;                                        // bit d: the group open at depth d + 1 has had its MASK
     for (size_t i = 0; i < n_paths; ++i) {
         swfr_path& p = out_p[i];
         if (p.kind < SWFR_PATH_GROUP_BEGIN) {
             if (depth) p.lerp = ((p.lerp >> 8) | ((p.lerp & 1u) ? PATH_OP_LERP : 0u)) << 8;
             continue;
         }
-        const bool end = p.kind == SWFR_PATH_GROUP_END;
-        depth += end ? -1 : 1;
-        p.lerp = (end ? (PATH_OP_GROUP_END | (p.lerp >> 8)) : PATH_OP_GROUP_BEGIN) << 8;
+        if (p.kind == SWFR_PATH_GROUP_MASK) {
+            masked |= 1u << (depth - 1);
+            p.lerp = (PATH_OP_GROUP_BEGIN | PATH_OP_MASKED) << 8;
+        } else if (p.kind == SWFR_PATH_GROUP_END) {
+            --depth;
+            p.lerp = (PATH_OP_GROUP_END | (p.lerp >> 8) | ((masked >> depth) & 1u ? PATH_OP_MASKED : 0u)) << 8;
+            masked &= ~(1u << depth);
+        } else {
+            ++depth;
+            p.lerp = PATH_OP_GROUP_BEGIN << 8;
+        }
         p.kind = SWFR_PATH_BOXES; p.fill_rule = 0; p.style = uint32_t(n_styles);
         p.first_edge = uint32_t(out_e.size()); p.n_edges = 1;
         swfr_edge b;
@@ -471,7 +510,7 @@ void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edg
         const swfr_path& p = paths[i];
         if (size_t(p.first_edge) + p.n_edges > n_edges) throw StatusError{SWFR_ERR_INVALID, "path edge range out of bounds"};
         if (p.style >= n_styles && p.kind < SWFR_PATH_GROUP_BEGIN) throw StatusError{SWFR_ERR_INVALID, "path style index out of bounds"};
-        if (p.kind > SWFR_PATH_GROUP_END) throw StatusError{SWFR_ERR_INVALID, "unknown path kind"};
+        if (p.kind > SWFR_PATH_GROUP_MASK) throw StatusError{SWFR_ERR_INVALID, "unknown path kind"};
         if (p.kind == SWFR_PATH_TOR)
             // an edge of the scan converter: a line (x1, y1)-(x2, y2) running downwards, active over [top, bottom) INSIDE its own extent
             // (what the frame builder and Cairo's clipper produce); the per-row stepping of k2_rows is exact only there
@@ -711,7 +750,7 @@ struct SceneLayout {
     bool any_shader = false;
     uint32_t max_path_edges = 0;
     bool rows_wide = false;     // the row kernel's wide instance although no path has more than ROWS_STAGE edges (SWFR_ROWS_WIDE)
-    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators, 4 + isolated groups: picks the tile kernel's instance
+    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators, 4 + isolated groups, 5 + masked groups: picks the tile kernel's instance
     bool any_blend = false;     // some path carries an operator byte (swfr_path::lerp >> 8; lower_groups): the arena gets the path_op table
     std::vector<uint32_t> chunk_base, slot_base, inc_base, band_off;
     std::vector<uint32_t> band_span;     // per path: first tile-row | last tile-row << 16 of its rectangle (0xffff | 0 << 16: none); padded to a multiple of 16 paths
@@ -751,7 +790,7 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
     uint32_t blend_bits = 0;
     for (size_t i = 0; i < n_paths; ++i) blend_bits |= paths[i].lerp;
     L.any_blend = (blend_bits >> 8) != 0u;
-    if (L.any_blend) L.shader_level = (blend_bits >> 8) & (PATH_OP_GROUP_BEGIN | PATH_OP_GROUP_END) ? 4 : 3;
+    if (L.any_blend) L.shader_level = (blend_bits >> 8) & PATH_OP_MASKED ? 5 : ((blend_bits >> 8) & (PATH_OP_GROUP_BEGIN | PATH_OP_GROUP_END) ? 4 : 3);
     // (the test knobs: a higher instance than the frame needs -- with the style table in its full format -- and the wide row kernel)
     L.shader_level = std::max(L.shader_level, r->tiles_shaders);
     L.rows_wide = r->rows_wide;
@@ -1757,7 +1796,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
-    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 4);
+    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 5);
     if (const char* rw = std::getenv("SWFR_ROWS_WIDE")) r->rows_wide = std::atoi(rw) != 0;
     if (const char* bf = std::getenv("SWFR_BATCH_FRAMES")) r->batch_frames = std::max(1, std::atoi(bf));
     if (const char* cr = std::getenv("SWFR_CHUNK_ROWS")) r->force_chunk_rows = std::atoi(cr);
