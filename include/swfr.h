@@ -120,7 +120,7 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
        SWFR_OBJECT_COLOR_TRANSFORM = 3   /* a container (matrix + children) whose `id` names a colour-transform slot (swfr_set_color_transform):
                                             the slot's value at the time of the render call applies to everything below it.  Beyond the
                                             reference, whose display objects carry a matrix and a ratio only */,
-       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10 and 12 and above) */
+       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10, 12 and 14 and above) */
        SWFR_OBJECT_BLEND_MODE = 5,       /* a container (matrix + children) whose `id` is an SWF blend-mode number (SWFR_BLEND_*): every path
                                             drawn below it is composited, each on its own, with the mode's Cairo operator -- what
                                             CanvasRenderer would do if it set ctx.globalCompositeOperation before drawing the object.  It
@@ -133,9 +133,9 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
                                             3..8, 13, 14: the mode's operator; 9..12: SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode";
                                             above 14: SWFR_ERR_INVALID.  A SWFR_OBJECT_BLEND_MODE in force around the layer still applies
                                             per path inside it, against the layer's own pixels.  Layers nest up to SWFR_MAX_LAYER_DEPTH
-                                            deep: deeper is SWFR_ERR_CAPACITY, "LayerDepth".  No layer opacity (masks: SWFR_OBJECT_MASKED_LAYER); a colour
-                                            transform around a layer recolours the definitions below it, it does not fade the layer as
-                                            a whole.  DESIGN.md, "Isolated layers" */,
+                                            deep: deeper is SWFR_ERR_CAPACITY, "LayerDepth".  (Masks: SWFR_OBJECT_MASKED_LAYER.)  A colour
+                                            transform around a layer recolours the definitions below it; fading the layer as a whole
+                                            is SWFR_OBJECT_FADED_LAYER.  DESIGN.md, "Isolated layers" */,
        SWFR_OBJECT_MASKED_LAYER = 11     /* a masked layer: a container (matrix + children) whose children[0] is the MASK subtree and whose
                                             children[1..] are the content.  Both are drawn as isolated groups that start clear --
                                             cairo_push_group; the content; content = cairo_pop_group; cairo_push_group; the mask; mask =
@@ -147,7 +147,17 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
                                             applies to both halves.  n_children == 0: SWFR_ERR_INVALID, "MaskedLayerWithoutMask".  A
                                             masked layer uses TWO levels of SWFR_MAX_LAYER_DEPTH.  Unlike a Flash clip-depth mask the
                                             mask's alpha counts and so do its strokes (geometry only: put the mask under a colour
-                                            transform with alpha mult 0, add 255).  DESIGN.md, "Masked layers" */ };
+                                            transform with alpha mult 0, add 255).  DESIGN.md, "Masked layers" */,
+       /* 12 is not a display-object type */
+       SWFR_OBJECT_FADED_LAYER = 13      /* a layer with an opacity: SWFR_OBJECT_LAYER whose composite is cairo_paint_with_alpha --
+                                            cairo_push_group; the children; cairo_pop_group_to_source; cairo_set_operator;
+                                            cairo_paint_with_alpha(opacity / 255.0) -- so that the children fade as ONE image: per pixel
+                                            the parent's d becomes combine_op(mul_un8(g, opacity), d), g the group's premultiplied pixel,
+                                            mul_un8 per channel, alpha included, with 0x80 rounding.  `id` is mode | opacity << 8: the
+                                            mode an SWF blend-mode number, accepted exactly as SWFR_OBJECT_LAYER accepts it, the opacity
+                                            0..255; id >= 0x10000: SWFR_ERR_INVALID.  Opacity 255 is SWFR_OBJECT_LAYER byte for byte,
+                                            opacity 0 draws nothing.  One level of SWFR_MAX_LAYER_DEPTH; nests with the other two layer
+                                            types.  DESIGN.md, "Layer opacity" */ };
 #define SWFR_MAX_LAYER_DEPTH 4
 
 /* SWF blend-mode numbers (PlaceObject3, swf-tree BlendMode).  0, 1: OVER.  3..8, 13, 14: the Cairo operator of the same name
@@ -250,7 +260,10 @@ enum { SWFR_PATH_TOR = 0,   /* general polygon: Cairo "tor" 15x256 scan conversi
        /* the two markers of an isolated group (SWFR_OBJECT_LAYER): the paths between them are drawn onto a transparent surface, which
           GROUP_END composites onto what was there at GROUP_BEGIN.  Both have n_edges 0 and the same rectangle: the union of the
           rectangles of the paths between them (those lie inside it).  BEGIN's `lerp` is 0; END's holds the composite's operator in bits
-          8..15 and 0 in bits 0..7.  Markers are balanced and nest at most SWFR_MAX_LAYER_DEPTH deep; their `style` is ignored.  Inside a
+          8..15, 0 in bits 0..7 and 16..23, and in bits 24..31 the group's FADE, 255 - opacity (0: a plain group): the group's pixels
+          are multiplied by the opacity (mul_un8 per channel, alpha included) before they are composited, SWFR_OBJECT_FADED_LAYER.  A
+          fade on any other path, or on the END of a group that holds a GROUP_MASK (Cairo has no single call for a masked and faded
+          composite: nest the two), is SWFR_ERR_INVALID.  Markers are balanced and nest at most SWFR_MAX_LAYER_DEPTH deep; their `style` is ignored.  Inside a
           group "the surface" of the lerp rule is the group's: its first paint is a SOURCE lerp.  SWFR_ERR_INVALID at upload otherwise */
        SWFR_PATH_GROUP_BEGIN = 2, SWFR_PATH_GROUP_END = 3,
        /* the third marker, of a masked group (SWFR_OBJECT_MASKED_LAYER): BEGIN; content paths; MASK; mask paths; END(operator).  The

@@ -39,6 +39,7 @@ OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 
 OBJECT_BLEND_MODE = 5
 OBJECT_LAYER = 8                        # an isolated group (swfr.h SWFR_OBJECT_LAYER); `id` is the blend mode it is composited with
 OBJECT_MASKED_LAYER = 11                # a masked layer (swfr.h SWFR_OBJECT_MASKED_LAYER): children[0] the mask, children[1..] the content; `id` the blend mode
+OBJECT_FADED_LAYER = 13                 # a layer with an opacity (swfr.h SWFR_OBJECT_FADED_LAYER): `id` is the blend mode | opacity << 8
 MAX_LAYER_DEPTH = 4                     # (a masked layer takes two levels)
 PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END, PATH_GROUP_MASK = 0, 1, 2, 3, 4
 # SWF blend-mode numbers under swf-tree's names (BlendMode); what the library does with each is swfr.h's SWFR_BLEND_* comment
@@ -534,6 +535,21 @@ class Renderer:
         if obj.get("matrix") is not None:
             d.has_matrix = 1
             d.matrix = _matrix(obj["matrix"])
+        if obj.get("opacity") is not None:
+            # the object inside a type-13 wrapper, where the type-8 wrapper would sit: drawn as an isolated group and composited as one
+            # image at the opacity (an integer 0..255), with the mode of "layer" (absent: normal).  With "mask" the type-13 wrapper goes
+            # around the type-11 wrapper, which composites in normal mode: three layer levels
+            opacity = obj["opacity"]
+            if isinstance(opacity, bool) or not isinstance(opacity, (int, np.integer)) or not 0 <= opacity <= 255:
+                raise SwfrError(ERR_INVALID, "opacity must be an integer 0..255")
+            w = DisplayObject()
+            layer = obj.get("layer")
+            mode = BLEND_MODES["normal"] if layer is None or layer is False else layer_mode_number(layer)
+            w.type, w.id = OBJECT_FADED_LAYER, mode | int(opacity) << 8
+            inner = {k: v for k, v in obj.items() if k not in ("opacity", "layer")}
+            kids = arena.array(DisplayObject, [self._object(arena, inner)])
+            w.n_children, w.children = 1, C.cast(kids, C.POINTER(DisplayObject))
+            return w
         if obj.get("mask") is not None:
             # the object inside a type-11 wrapper, where the type-8 wrapper would sit: children[0] a plain container of the "mask" list --
             # a sibling in the parent's space, outside the object's own matrix, colour transform and blend mode --, children[1] the object;

@@ -364,7 +364,11 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
             for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
             break;
         case SWFR_OBJECT_LAYER:
-            draw_layer(obj, depth);
+            draw_layer(obj, depth, obj.id, 255u);
+            break;
+        case SWFR_OBJECT_FADED_LAYER:
+            if (obj.id >= 0x10000u) throw StatusError{SWFR_ERR_INVALID, "FadedLayerId"};
+            draw_layer(obj, depth, obj.id & 0xffu, obj.id >> 8);
             break;
         case SWFR_OBJECT_MASKED_LAYER:
             draw_masked_layer(obj, depth);
@@ -390,11 +394,13 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
 // cairo_paint.  The children's paths go between a GROUP_BEGIN and a GROUP_END marker whose rectangle is the union of theirs; inside,
 // "the surface" is the group's and starts clear -- known here, so a first paint is settled to a SOURCE lerp at once (a group is never
 // cut across build pieces: only the single container, colour-transform and blend-mode wrappers around the pieces are).
-void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth) {
-    const uint32_t op = layer_operator(obj.id);
+// With an opacity below 255 (SWFR_OBJECT_FADED_LAYER; DESIGN.md, "Layer opacity") the last call is cairo_paint_with_alpha(opacity / 255.0):
+// the END marker carries the fade 255 - opacity in bits 24..31 of its `lerp`.
+void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth, uint32_t mode, uint32_t opacity) {
+    const uint32_t op = layer_operator(mode);
     if (group_depth_ >= SWFR_MAX_LAYER_DEPTH) throw StatusError{SWFR_ERR_CAPACITY, "LayerDepth"};
     const bool parent_clear = surface_clear_;
-    const size_t begin = paths_.size();
+    const size_t begin = paths_.size(), begin_edges = edges_.size(), begin_styles = styles_.size();
     swfr_path m;
     std::memset(&m, 0, sizeof m);
     m.kind = SWFR_PATH_GROUP_BEGIN;
@@ -408,6 +414,15 @@ void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth) {
     // libcairo: painting a still-clear group with OVER or ADD is NOTHING_TO_DO and leaves the parent's "still clear" state alone; under
     // any other operator, and whenever the group was drawn on (even if every pixel of it is zero), the parent counts as drawn
     surface_clear_ = parent_clear && group_clear && (op == SWFR_OP_OVER || op == SWFR_OP_ADD);
+    if (opacity == 0u) {
+        // libcairo: cairo_paint_with_alpha(0) returns at once under all nine operators (each is bounded by the mask): no pixel changes
+        // and the parent's "still clear" state survives even behind a group that was drawn on.  Nothing is emitted
+        surface_clear_ = parent_clear;
+        paths_.resize(begin);
+        edges_.resize(begin_edges);
+        styles_.resize(begin_styles);
+        return;
+    }
     if (paths_.size() == begin + 1) {                         // no path survived: a transparent group changes no pixel under any operator
         paths_.pop_back();
         return;
@@ -422,7 +437,7 @@ void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth) {
     m = b;
     m.kind = SWFR_PATH_GROUP_END;
     m.first_edge = uint32_t(edges_.size());
-    m.lerp = op << 8;
+    m.lerp = (op << 8) | ((255u - opacity) << 24);            // (0 < opacity < 255: libcairo's bookkeeping is the plain layer's, above)
     paths_.push_back(m);
 }
 

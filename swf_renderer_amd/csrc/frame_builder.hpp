@@ -77,7 +77,7 @@ private:
         uint32_t op = 0;          // blend mode of the innermost SWFR_OBJECT_BLEND_MODE wrapper as a path operator (SWFR_OP_*), 0: OVER
     };
     void draw(const swfr_display_object& obj, int depth);
-    void draw_layer(const swfr_display_object& obj, int depth);
+    void draw_layer(const swfr_display_object& obj, int depth, uint32_t mode, uint32_t opacity);
     void draw_masked_layer(const swfr_display_object& obj, int depth);
     void draw_path(const StyledPath& p, bool morph, double ratio);
     void trace(const StyledPath& p, bool morph, double ratio);

@@ -1558,6 +1558,20 @@ __device__ __forceinline__ void mask_group(uint32_t (&px)[8], const uint32_t* __
     }
 }
 
+// The fade step of a faded group's END (k2_tiles<6>; DESIGN.md, "Layer opacity"): px = mul_un8(px, a) per channel, alpha included, `a`
+// the group's opacity (wave-uniform): mask_group's arithmetic with the group itself as the content and a constant for the mask's alpha.
+__device__ __forceinline__ void fade_group(uint32_t (&px)[8], uint32_t a) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t s = px[j];
+        uint32_t rb = (s & 0x00ff00ffu) * a + 0x00800080u;
+        rb = ((rb + ((rb >> 8) & 0x00ff00ffu)) >> 8) & 0x00ff00ffu;
+        uint32_t ag = ((s >> 8) & 0x00ff00ffu) * a + 0x00800080u;
+        ag = (ag + ((ag >> 8) & 0x00ff00ffu)) & 0xff00ff00u;
+        px[j] = rb | ag;
+    }
+}
+
 template <int SHADERS>
 __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     // per pixel: deltas whose prefix sum along the row is 17 * N(x), N = Cairo's coverage numerator 512 * H(x) - ua(x) (H: the heights
@@ -1650,7 +1664,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) px[j] = 0u;
         [[maybe_unused]] int sp = 0, mat = 0;                             // open groups of this strip's walk, and how many of them have had the
-                                                                         // strip's pixels set aside for them (wave-uniform; instances 4 and 5 only)
+                                                                         // strip's pixels set aside for them (wave-uniform; instances 4 to 6 only)
 
         const uint8_t* mycls = T3_FIELD(cls) + (size_t)STRIPS_PER_TILE * tiles_x * band_begin + (size_t)(tcol * STRIPS_PER_TILE + strip) * n_b;   // this strip's class byte per band entry
         auto cls_chunk = [&](uint32_t c0) -> uint32_t {               // the class bytes of entries c0 .. c0 + 63 (c0 a multiple of 64, wave-uniform)
@@ -1714,7 +1728,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     uint4* e4 = reinterpret_cast<uint4*>(&ent[rank][0]);
                     e4[0] = q0; e4[1] = q1; ent[rank][8] = f;
                     // (instance 3: the path's operator beside its entry; a frame without a blended path -- in a batch that has one, or
-                    //  forced through this instance -- has no table; instances 4 and 5: the byte also says what isolated groups need, PATH_OP_*)
+                    //  forced through this instance -- has no table; instances 4 to 6: the byte also says what isolated groups need, PATH_OP_*)
                     if constexpr (SHADERS >= 3) ent[rank][9] = FR->path_op ? (uint32_t)FR->path_op[q1.w] : 0u;
                     if (part) { uint4* d4 = reinterpret_cast<uint4*>(&hdr[rank][0]); d4[0] = h0; d4[1] = h1; d4[2] = h2; d4[3] = h3; }
                 }
@@ -1748,8 +1762,17 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                             // may be such -- costs two scalar additions: a transparent group changes no pixel under any operator
                             if (op & PATH_OP_GROUP_BEGIN) ++sp;     // (also a MASK: the mask's surface is a group opened above the content's)
                             else if (sp > 0) {
-                                if (SHADERS == 5 && (op & PATH_OP_MASKED) && sp > 1) {
-                                    // (instance 5 only: instance 4 stays the code it was, frames with a MASK never run it)
+                                [[maybe_unused]] bool fade_end = false;
+                                if constexpr (SHADERS == 6) {
+                                    // (instance 6 only: instance 5 stays the code it was, frames with a fade never run it)
+                                    // the END of a faded group (its entry's solid word is the fade, 255 - opacity; a masked END's is
+                                    // 0): the group's pixels times the opacity, then the END.  Only where they were set aside in this
+                                    // strip: otherwise px holds the parent's pixels, the group is transparent here and changes nothing
+                                    fade_end = (op & PATH_OP_MASKED) && solid != 0u;
+                                    if (fade_end && mat == sp) fade_group(px, 255u - (solid & 0xffu));
+                                }
+                                if (SHADERS >= 5 && !fade_end && (op & PATH_OP_MASKED) && sp > 1) {
+                                    // (instances 5 and 6 only: instance 4 stays the code it was, frames with a MASK never run it)
                                     // the END of a masked group: the mask step first.  The mask's surface was set up in this strip: its
                                     // alpha times the content that was set aside for it.  It was not: the mask is transparent here, and
                                     // so is the product -- content that was drawn in this strip is dropped.  Then the content's END
@@ -1995,6 +2018,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAY
 // frames with a masked group (SWFR_PATH_GROUP_MASK): everything the layer instance does, plus the mask step at a masked group's END.  An
 // instance of its own so that frames with plain layers run the code they ran before
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAYER))) void k2_tiles_mask_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<5>(FRAME_PTR(frames, blockIdx.y), fb_to); }
+// frames with a faded group (a fade in its GROUP_END): everything the mask instance does, plus the fade step at a faded group's END.  An
+// instance of its own so that frames with masked groups run the code they ran before
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAYER))) void k2_tiles_fade_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<6>(FRAME_PTR(frames, blockIdx.y), fb_to); }
 
 // ---------------------------------------------------------------------------------------------
 // launchers: `frames` is a device array of n_frames descriptors, blockIdx.y picks one
@@ -2033,7 +2059,8 @@ void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint
     // smaller frames do not fill the GPU and keep one wavefront per strip.
     uint32_t g = max_strips < grid_cap ? max_strips : grid_cap;
     if (grid_cap == ~0u && max_strips > T3_PAIR_FROM) g = (max_strips + 1u) / 2u;
-    if (shader_level >= 5) hipLaunchKernelGGL(k2_tiles_mask_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    if (shader_level >= 6) hipLaunchKernelGGL(k2_tiles_fade_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    else if (shader_level == 5) hipLaunchKernelGGL(k2_tiles_mask_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 4) hipLaunchKernelGGL(k2_tiles_layer_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 3) hipLaunchKernelGGL(k2_tiles_blend_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level >= 2) hipLaunchKernelGGL(k2_tiles_shaded_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);

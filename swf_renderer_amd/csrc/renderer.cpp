@@ -256,7 +256,7 @@ struct swfr_renderer {
     bool mono = false;                      // SWFR_FLAG_ANTIALIAS_NONE: boxes rounded to pixels, tor paths by k2_rows_mono (Frame2::mono)
     int fast_limit = 16;                    // rows with more active edges go to k2_rows_slow; the row kernel's instance caps it at its 8 or 16 slots (SWFR_FAST_LIMIT: test knob)
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
-    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups, 5 masked groups; test knob)
+    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups, 5 masked groups, 6 faded groups; test knob)
     bool rows_wide = false;                 // SWFR_ROWS_WIDE=1: every frame with tor paths runs k2_rows_wide (test knob; aliased frames keep k2_rows_mono)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
     // the host builds one while the GPU works on the other
@@ -379,7 +379,9 @@ void validate_blend_fields(const swfr_path* paths, size_t n_paths) {
 
 // the markers of isolated groups (swfr.h, SWFR_PATH_GROUP_BEGIN / _END / _MASK): balanced, at most SWFR_MAX_LAYER_DEPTH deep -- a group
 // with a MASK counting two levels from its BEGIN on --, no edges, the markers' rectangles equal, every path between them inside that
-// rectangle, the lerp bits zero, END's operator one of SWFR_OP_*, at most one MASK per group and none outside one
+// rectangle, the lerp bits zero, END's operator one of SWFR_OP_*, at most one MASK per group and none outside one.  Bits 24..31 of an
+// END's lerp are the group's fade (255 - opacity, swfr.h): on a group without a MASK only, and on no other path (a BEGIN's and a MASK's
+// lerp is 0 as a whole; an ordinary path's is refused by validate_blend_fields)
 void validate_groups(const swfr_path* paths, size_t n_paths) {
     auto bad = [](const char* what) { throw StatusError{SWFR_ERR_INVALID, what}; };
     // which BEGINs open a masked group (a MASK belongs to the innermost group open where it stands)
@@ -421,7 +423,8 @@ void validate_groups(const swfr_path* paths, size_t n_paths) {
             if (!depth) bad("GROUP_END without a GROUP_BEGIN");
             const swfr_path& g = paths[open[--depth]];
             levels -= any_mask && masked[open[depth]] ? 2 : 1;
-            if (p.n_edges != 0u || (p.lerp & 0xffu) != 0u || (p.lerp >> 8) > SWFR_OP_HARDLIGHT) bad("GROUP_END: n_edges and lerp bits 0..7 must be 0, the operator at most 8");
+            if (p.n_edges != 0u || (p.lerp & 0xffu) != 0u || ((p.lerp >> 8) & 0xffffu) > SWFR_OP_HARDLIGHT) bad("GROUP_END: n_edges and lerp bits 0..7 and 16..23 must be 0, the operator at most 8");
+            if ((p.lerp >> 24) != 0u && any_mask && masked[open[depth]]) bad("GROUP_END: a fade on a group with a GROUP_MASK");
             if (p.x_min != g.x_min || p.y_min != g.y_min || p.x_max != g.x_max || p.y_max != g.y_max) bad("group markers: the rectangles of GROUP_BEGIN and GROUP_END differ");
         } else if (p.kind == SWFR_PATH_GROUP_MASK) {
             const swfr_path& g = paths[open[depth - 1]];                  // (inside a group: checked above)
@@ -435,13 +438,19 @@ void validate_groups(const swfr_path* paths, size_t n_paths) {
 // What the device sees of isolated groups ("Isolated layers").  A marker becomes a box path of ONE box, its rectangle, with
 // a transparent solid style and lerp 0: to k2_bin and the row kernels an ordinary path that reaches exactly the strips of the
 // rectangle, in painter's order, and paints nothing.  What it means travels in the path's operator byte (bits 8..15 of `lerp`, split off
-// into Frame2::path_op by push_scene), which only k2_tiles<3>, <4> and <5> read: PATH_OP_GROUP_BEGIN, or PATH_OP_GROUP_END | operator
+// into Frame2::path_op by push_scene), which only k2_tiles<3> to <6> read: PATH_OP_GROUP_BEGIN, or PATH_OP_GROUP_END | operator
 // (SWFR_PATH_GROUP_MASK: PATH_OP_GROUP_BEGIN | PATH_OP_MASKED, and its group's END carries PATH_OP_MASKED, too: k2_tiles<5>).  A
 // path INSIDE a group loses its lerp bit (so that no kernel derives an opaque cover or a culling record from it: a cover inside a group
 // hides nothing outside) and carries it in PATH_OP_LERP instead, where k2_tiles<4> reads it back for the pixel arithmetic.
+// A FADED END (bits 24..31 of its lerp, swfr.h) carries PATH_OP_MASKED as well -- "a step before the composite" -- and, instead of the
+// shared transparent style, one of its own whose `pixel` is the fade: the word k2_bin copies into the band entry (BandEntry2::solid),
+// which the walk of k2_tiles holds as a scalar anyway.  Its alpha byte is 0: no kernel takes it for an opaque cover.  A masked END's
+// solid word is 0, a faded END's is not: that tells the two steps apart (upload refuses a fade on a masked group).  `faded` says
+// whether the scene has such an END: layout_scene then picks k2_tiles<6>.
 // Returns false when the scene has no marker (nothing is copied).
 bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles,
-                  std::vector<swfr_edge>& out_e, std::vector<swfr_path>& out_p, std::vector<swfr_style>& out_s) {
+                  std::vector<swfr_edge>& out_e, std::vector<swfr_path>& out_p, std::vector<swfr_style>& out_s, bool& faded) {
+    faded = false;
     bool any = false;
     for (size_t i = 0; i < n_paths && !any; ++i) any = paths[i].kind >= SWFR_PATH_GROUP_BEGIN;
     if (!any) return false;
@@ -450,6 +459,7 @@ bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths
     std::memset(&clear, 0, sizeof clear);
     clear.kind = SWFR_STYLE_SOLID;
     out_s.push_back(clear);
+    uint32_t fade_style[256] = {0u};                             // the style of a fade value, once it has one (0: none yet): at most 255 more styles
     // (a MASK is to the device a second BEGIN, flagged PATH_OP_MASKED, and the END of its group pops both: it carries the flag, too)
     int depth = 0;
     uint32_t masked = 0u;                                        // bit d: the group open at depth d + 1 has had its MASK
@@ -459,18 +469,30 @@ bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths
             if (depth) p.lerp = ((p.lerp >> 8) | ((p.lerp & 1u) ? PATH_OP_LERP : 0u)) << 8;
             continue;
         }
+        uint32_t fade = 0u;
         if (p.kind == SWFR_PATH_GROUP_MASK) {
             masked |= 1u << (depth - 1);
             p.lerp = (PATH_OP_GROUP_BEGIN | PATH_OP_MASKED) << 8;
         } else if (p.kind == SWFR_PATH_GROUP_END) {
             --depth;
-            p.lerp = (PATH_OP_GROUP_END | (p.lerp >> 8) | ((masked >> depth) & 1u ? PATH_OP_MASKED : 0u)) << 8;
+            fade = p.lerp >> 24;
+            p.lerp = (PATH_OP_GROUP_END | ((p.lerp >> 8) & PATH_OP_MASK) | (((masked >> depth) & 1u) || fade ? PATH_OP_MASKED : 0u)) << 8;
             masked &= ~(1u << depth);
         } else {
             ++depth;
             p.lerp = PATH_OP_GROUP_BEGIN << 8;
         }
         p.kind = SWFR_PATH_BOXES; p.fill_rule = 0; p.style = uint32_t(n_styles);
+        if (fade) {
+            faded = true;
+            if (!fade_style[fade]) {
+                swfr_style st = clear;
+                st.pixel = fade;
+                fade_style[fade] = uint32_t(out_s.size());
+                out_s.push_back(st);
+            }
+            p.style = fade_style[fade];
+        }
         p.first_edge = uint32_t(out_e.size()); p.n_edges = 1;
         swfr_edge b;
         std::memset(&b, 0, sizeof b);
@@ -750,7 +772,7 @@ struct SceneLayout {
     bool any_shader = false;
     uint32_t max_path_edges = 0;
     bool rows_wide = false;     // the row kernel's wide instance although no path has more than ROWS_STAGE edges (SWFR_ROWS_WIDE)
-    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators, 4 + isolated groups, 5 + masked groups: picks the tile kernel's instance
+    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators, 4 + isolated groups, 5 + masked groups, 6 + faded groups: picks the tile kernel's instance
     bool any_blend = false;     // some path carries an operator byte (swfr_path::lerp >> 8; lower_groups): the arena gets the path_op table
     std::vector<uint32_t> chunk_base, slot_base, inc_base, band_off;
     std::vector<uint32_t> band_span;     // per path: first tile-row | last tile-row << 16 of its rectangle (0xffff | 0 << 16: none); padded to a multiple of 16 paths
@@ -762,7 +784,7 @@ struct SceneLayout {
 // src_paths: the paths as the caller drew them, when `paths` holds the column blocks of wide ones (split_wide_paths): a bitmap or
 // gradient style is anchored at the rectangle of its drawing operation, not of a block
 void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
-                  const swfr_style* styles, size_t n_styles, SceneLayout& L, const swfr_path* src_paths = nullptr, size_t n_src_paths = 0) {
+                  const swfr_style* styles, size_t n_styles, SceneLayout& L, const swfr_path* src_paths = nullptr, size_t n_src_paths = 0, bool faded = false) {
     L.n_bands = (r->height + TILE_H - 1) / TILE_H;
     const uint32_t tiles_x = (r->width + TILE_W - 1) / TILE_W;
     // rows per k2_rows wavefront: 64 when that already gives the GPU a thousand wavefronts, fewer (whole tile-rows) for scenes made
@@ -791,6 +813,7 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
     for (size_t i = 0; i < n_paths; ++i) blend_bits |= paths[i].lerp;
     L.any_blend = (blend_bits >> 8) != 0u;
     if (L.any_blend) L.shader_level = (blend_bits >> 8) & PATH_OP_MASKED ? 5 : ((blend_bits >> 8) & (PATH_OP_GROUP_BEGIN | PATH_OP_GROUP_END) ? 4 : 3);
+    if (faded) L.shader_level = 6;                               // (lower_groups met a faded END: the instance that fades)
     // (the test knobs: a higher instance than the frame needs -- with the style table in its full format -- and the wide row kernel)
     L.shader_level = std::max(L.shader_level, r->tiles_shaders);
     L.rows_wide = r->rows_wide;
@@ -1097,7 +1120,8 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
     static thread_local std::vector<swfr_edge> group_e;
     static thread_local std::vector<swfr_path> group_p;
     static thread_local std::vector<swfr_style> group_s;
-    if (lower_groups(edges, n_edges, paths, n_paths, styles, n_styles, group_e, group_p, group_s)) {   // (frames with an isolated group only)
+    bool faded = false;
+    if (lower_groups(edges, n_edges, paths, n_paths, styles, n_styles, group_e, group_p, group_s, faded)) {   // (frames with an isolated group only)
         edges = group_e.data(); n_edges = group_e.size(); paths = group_p.data(); n_paths = group_p.size(); styles = group_s.data(); n_styles = group_s.size();
     }
     static thread_local std::vector<swfr_edge> split_e;
@@ -1111,7 +1135,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
     SceneLayout& L = layout_scratch;
     if (src_paths) resolve_variants(r, src_paths, n_src_paths, styles, n_styles, up_stream, si == 0);
     else resolve_variants(r, paths, n_paths, styles, n_styles, up_stream, si == 0);
-    layout_scene(r, edges, n_edges, paths, n_paths, styles, n_styles, L, src_paths, n_src_paths);
+    layout_scene(r, edges, n_edges, paths, n_paths, styles, n_styles, L, src_paths, n_src_paths, faded);
     sc.n_edges = n_edges; sc.n_paths = n_paths; sc.n_styles = n_styles; sc.any_shader = L.any_shader; sc.shader_level = L.shader_level;
     sc.n_chunks = L.n_chunks; sc.chunk_rows = L.chunk_rows; sc.n_bands = L.n_bands; sc.n_rows = L.n_rows;
     sc.n_strips = L.n_strips; sc.n_strip_slots = L.n_strip_slots; sc.n_incidences = L.incidences;
@@ -1493,9 +1517,10 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
                 r->builder->build(stages[first + k]);
                 F.e = r->builder->edges(); F.p = r->builder->paths(); F.s = r->builder->styles();
                 validate_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size());
+                bool faded = false;
                 {
                     std::vector<swfr_edge> ge; std::vector<swfr_path> gp; std::vector<swfr_style> gs;
-                    if (lower_groups(F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), ge, gp, gs)) { F.e.swap(ge); F.p.swap(gp); F.s.swap(gs); }
+                    if (lower_groups(F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), ge, gp, gs, faded)) { F.e.swap(ge); F.p.swap(gp); F.s.swap(gs); }
                 }
                 resolve_variants(r, F.p.data(), F.p.size(), F.s.data(), F.s.size(), G.stream, false);
                 {
@@ -1503,8 +1528,8 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
                     if (split_wide_paths(F.e.data(), F.p.data(), F.p.size(), se, sp)) {
                         const std::vector<swfr_path> orig = F.p;
                         F.e.swap(se); F.p.swap(sp);
-                        layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L, orig.data(), orig.size());
-                    } else layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L);
+                        layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L, orig.data(), orig.size(), faded);
+                    } else layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L, nullptr, 0, faded);
                 }
                 arena_bytes += scene_arena_bytes(F.L, F.e.size(), F.p.size(), F.s.size());
                 const SceneLayout& L = F.L;
@@ -1796,7 +1821,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
-    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 5);
+    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 6);
     if (const char* rw = std::getenv("SWFR_ROWS_WIDE")) r->rows_wide = std::atoi(rw) != 0;
     if (const char* bf = std::getenv("SWFR_BATCH_FRAMES")) r->batch_frames = std::max(1, std::atoi(bf));
     if (const char* cr = std::getenv("SWFR_CHUNK_ROWS")) r->force_chunk_rows = std::atoi(cr);
