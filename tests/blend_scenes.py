@@ -1,6 +1,6 @@
 """Blend-mode scenes ("Blend modes"), built from tests/scenarios.py pieces, and their libcairo reference: CanvasReplay with
 cairo_set_operator around every object that carries a "blend_mode" -- what CanvasRenderer would do if it set
-ctx.globalCompositeOperation before drawing the object.  tools/make_blend_goldens.py writes goldens() to
+ctx.globalCompositeOperation before drawing the object.  tools/make_composite_goldens.py writes goldens() to
 tests/golden/cairo_blend_*.npz (premultiplied RGBA; key = scene name); the tests rebuild the scenes from here, so a golden file holds
 pixels only.
 """

@@ -13,10 +13,11 @@ import numpy as np
 
 import blend_model as bm
 import layer_model as lm
+import mask_model as mk
 import scenarios
 
 MODES = ["normal"] + sorted(bm.MODES)                 # the nine operators, by the names "blend_mode" / "layer" take
-BEGIN, END = lm.PATH_GROUP_BEGIN, lm.PATH_GROUP_END
+BEGIN, END, MASK = lm.PATH_GROUP_BEGIN, lm.PATH_GROUP_END, mk.PATH_GROUP_MASK
 STRIP_W, STRIP_H, TILE_H = 64, 8, 16
 ROUND, CHUNK, PREFETCH = 16, 64, 128                  # k2_tiles: entries staged per round, class bytes per chunk, class bytes fetched up front
 
@@ -156,11 +157,14 @@ def rand_composited_scene(rng, width=None, height=None, min_children=0, leaves=N
 class RawFrame:
     """A frame in swfr_upload_edges form (include/swfr.h), written path by path.  Coordinates are pixels (floats are rounded to 24.8);
     colours premultiplied ARGB words; `op` an operator name of MODES.  A path's rectangle is its extents cut to the frame; a group's
-    markers get the union of the rectangles of the paths between them when the group is closed."""
+    markers get the union of the rectangles of the paths between them when the group is closed.  A group is begin(); paths; end(op),
+    or, masked, begin(); content; mask(); mask paths; end(op); end(op, opacity) puts the fade 255 - opacity into bits 24..31 of the
+    END's lerp."""
 
     def __init__(self, W, H):
         self.W, self.H = W, H
         self.rows, self.paths, self.pixels, self.open = [], [], [], []
+        self.masks = []                                              # per open group: the index of its MASK marker, or None
 
     @staticmethod
     def _fx(v):
@@ -205,11 +209,18 @@ class RawFrame:
 
     def begin(self):
         self.open.append(len(self.paths))
+        self.masks.append(None)
         self.paths.append([len(self.rows), 0, BEGIN, 0, 0, 0, 0, 0, 0, 0])
         return self
 
-    def end(self, op="normal"):
-        b = self.open.pop()
+    def mask(self):
+        assert self.masks and self.masks[-1] is None
+        self.masks[-1] = len(self.paths)
+        self.paths.append([len(self.rows), 0, MASK, 0, 0, 0, 0, 0, 0, 0])
+        return self
+
+    def end(self, op="normal", opacity=255):
+        b, m = self.open.pop(), self.masks.pop()
         rects = [p[6:10] for p in self.paths[b + 1:] if p[6] < p[8] and p[7] < p[9]]
         rect = [min(r[0] for r in rects), min(r[1] for r in rects), max(r[2] for r in rects), max(r[3] for r in rects)] if rects else [0, 0, 0, 0]
         self.paths[b][6:10] = rect
@@ -224,12 +235,19 @@ class RawFrame:
                 inner += 1
             elif p[2] == END:
                 inner -= 1
-        self.paths.append([len(self.rows), 0, END, 0, 0, bm.OPERATORS["over" if op == "normal" else op] << 8, *rect])
+        if m is not None:
+            self.paths[m][6:10] = rect
+        self.paths.append([len(self.rows), 0, END, 0, 0, bm.OPERATORS["over" if op == "normal" else op] << 8 | (255 - int(opacity)) << 24, *rect])
         return self
 
     @property
     def depth(self):
         return len(self.open)
+
+    @property
+    def levels(self):
+        """the levels of SWFR_MAX_LAYER_DEPTH the open groups take: two for one that holds a MASK"""
+        return sum(2 if m is not None else 1 for m in self.masks)
 
     def arrays(self):
         from swf_renderer_amd import api

@@ -1,0 +1,353 @@
+"""What the device tests of the compositing features share (tests/test_{blend,layer,mask,fade}_gpu.py, tests/test_composite_fuzz_gpu.py):
+handles, the routes a frame can take to the device, the comparisons, and every libcairo golden of a family through every route.
+
+A family is one row of FAMILIES: its scenes module (files(), golden_path(), LINEAR_BOUND), the SWFR_TILES_SHADERS value of its
+k2_tiles instance, and what differs between the families' golden runs.  A new compositing feature adds a scenes module and a row.
+
+The routes of a golden file, by their number (under the emulator, where a frame takes seconds, a route takes every fourth scene of a
+file, the offset moving with the number so that the routes together still see most scenes): 0 swfr_build_frame on a host-only handle
+and swfr_render_edges on another, then resident frames; 1 the same under SWFR_GRAPHS=1; 2 two band handles; 3 render_batch with
+unlike frames; 4 render; 5 render with the family's instance forced.
+
+Every comparison prints a line ending in "differing pixels N max M"; after every frame the handle's swfr_stats show no capacity
+refusal.  Runs on an MI355X (-m gpu) and under tools/emu/run.py.
+"""
+import hashlib
+import json
+import os
+from collections import namedtuple
+
+import numpy as np
+import pytest
+
+import blend_scenes
+import fade_scenes
+import frame_model
+import helpers
+import layer_scenes
+import mask_scenes
+from helpers import diff_stats, oracle_render
+from host_frames import build_on_host
+
+EMU = bool(os.environ.get("SWFR_EMULATOR"))
+REFUSALS = ("pairtest_limit", "start_group_limit", "history_limit")
+
+# forced_render: the goldens go through render with the instance forced too (under the emulator both runs then take every fourth scene,
+# routes 4 and 5; blend and layer render every scene, and have the through_instance_N tests of their own files instead)
+# layouts: the band layouts of route 2 (contiguous_bands of swfr_create)
+Family = namedtuple("Family", "name scenes instance forced_render layouts")
+FAMILIES = {f.name: f for f in (Family("blend", blend_scenes, "3", False, (True,)), Family("layer", layer_scenes, "4", False, (True, False)),
+                                Family("mask", mask_scenes, "5", True, (True, False)), Family("fade", fade_scenes, "6", True, (True, False)))}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def need_gpu(gpu):
+    """(imported by a device test module: its tests need a GPU and the built library)"""
+    import swf_renderer_amd as S
+    assert os.path.exists(S.library_path()), "libswfr.so must be built: the product has no fallback"
+
+
+# ---------------------------------------------------------------------------------------------------------------- comparisons
+def check(family, got, want, sc, msg):
+    """exact unless the scene says otherwise (a linear gradient: the family's LINEAR_BOUND)"""
+    n, mx = diff_stats(got, want)
+    print(family.name, msg, "differing pixels", n, "max", mx)
+    if sc["exact"]:
+        assert (n, mx) == (0, 0), msg
+    else:
+        assert mx <= family.scenes.LINEAR_BOUND, (msg, n, mx)
+
+
+def zero(got, want, msg):
+    n, mx = diff_stats(got, want)
+    print("composite", msg, "differing pixels", n, "max", mx)
+    assert (n, mx) == (0, 0), msg
+
+
+def not_refused(r, msg):
+    st = r.stats()
+    assert st["frames"] >= 1 and all(st[k] == 0 for k in REFUSALS), (msg, st)
+
+
+# ---------------------------------------------------------------------------------------------------------------- handles and routes
+def handle(W, H, aliased=False, **kw):
+    import swf_renderer_amd as S
+    return S.Renderer(W, H, antialias="none" if aliased else "default", **kw)
+
+
+def renderer_for(sc, aliased, **kw):
+    """a handle of the scene's size and fill rule that holds the scene's bitmaps"""
+    r = handle(sc["width"], sc["height"], aliased, even_odd=bool(sc.get("even_odd")), **kw)
+    for b in sc.get("bitmaps", []):
+        r.add_bitmap(b)
+    return r
+
+
+def through_edges(W, H, arrays, aliased=False, resident=0, **kw):
+    r = handle(W, H, aliased, **kw)
+    try:
+        r.render_edges(*arrays)
+        img = r.read_image(premultiplied=True)
+        if resident:
+            r.render_resident(resident)
+            assert (r.read_image(premultiplied=True) == img).all(), "resident frames differ from the first"
+        not_refused(r, "render_edges")
+        return img
+    finally:
+        r.close()
+
+
+def through_render(sc, aliased=False, **kw):
+    r = handle(sc["width"], sc["height"], aliased, **kw)
+    try:
+        r.render(sc["stage"])
+        not_refused(r, "render")
+        return r.read_image(premultiplied=True)
+    finally:
+        r.close()
+
+
+def two_bands(W, H, contiguous, draw, aliased=False, make=None):
+    """the frame assembled from two handles, each drawing its own tile rows (`draw(handle)`; `make(**bands)`: the handle)"""
+    out = np.zeros((H, W, 4), np.uint8)
+    n = -(-((H + 15) // 16) // 2)                                    # tile rows per handle
+    for rank in range(2):
+        bands = dict(band_index=rank, band_count=2, contiguous_bands=contiguous)
+        r = make(**bands) if make else handle(W, H, aliased, **bands)
+        try:
+            draw(r)
+            img = r.read_image(premultiplied=True)
+            not_refused(r, "bands")
+        finally:
+            r.close()
+        t = np.arange(H) // 16
+        rows = ((t >= rank * n) & (t < (rank + 1) * n)) if contiguous else (t % 2 == rank)
+        out[rows] = img[rows]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the goldens
+def golden_scenes(family, fname, route, thin=True):
+    """([(name, scene)], aliased, the golden file) of one route"""
+    make, aliased = family.scenes.files()[fname]
+    items = sorted(make().items())
+    gold = np.load(family.scenes.golden_path(fname))
+    if EMU and thin:
+        items = items[route % 4::4]
+    else:
+        assert [n for n, _ in items] == sorted(gold.files)
+    return items, aliased, gold
+
+
+def built_for_another_handle(sc, aliased):
+    """swfr_build_frame's arrays for the scene.  They must not name colour-transformed textures: those belong to the handle that walked
+    the stage, so such a frame could not be handed to another handle (a cxform_* scene with a bitmap -- there is none today)"""
+    from swf_renderer_amd import api
+    e, p, s = build_on_host(sc, aliased)
+    assert not any(st.kind == api.STYLE_BITMAP and st.bitmap >= api.VARIANT_BASE for st in s)
+    return e, p, s
+
+
+def goldens_through_render(family, fname, monkeypatch, forced=False):
+    if forced:
+        monkeypatch.setenv("SWFR_TILES_SHADERS", family.instance)
+    else:
+        monkeypatch.delenv("SWFR_TILES_SHADERS", raising=False)
+    assert family.forced_render or not forced
+    items, aliased, gold = golden_scenes(family, fname, 4 + forced, thin=family.forced_render)
+    for name, sc in items:
+        r = renderer_for(sc, aliased)
+        try:
+            r.render(sc["stage"])
+            check(family, r.read_image(premultiplied=True), gold[name], sc, (fname, name, forced))
+            not_refused(r, name)
+        finally:
+            r.close()
+
+
+def goldens_through_render_edges(family, fname):
+    """swfr_build_frame on one handle, swfr_render_edges on another: operators, fades and groups travel in the paths"""
+    items, aliased, gold = golden_scenes(family, fname, 0)
+    for name, sc in items:
+        e, p, s = built_for_another_handle(sc, aliased)
+        r = renderer_for(sc, aliased)
+        try:
+            r.render_edges(e, p, s)
+            check(family, r.read_image(premultiplied=True), gold[name], sc, (fname, name, "render_edges"))
+            r.render_resident(3)
+            check(family, r.read_image(premultiplied=True), gold[name], sc, (fname, name, "resident"))
+            not_refused(r, name)
+        finally:
+            r.close()
+
+
+def goldens_with_graphs(family, fname, monkeypatch):
+    monkeypatch.setenv("SWFR_GRAPHS", "1")
+    items, aliased, gold = golden_scenes(family, fname, 1)
+    for name, sc in items:
+        e, p, s = built_for_another_handle(sc, aliased)
+        r = renderer_for(sc, aliased)
+        try:
+            r.upload_edges(e, p, s)
+            r.render_resident(3)
+            check(family, r.read_image(premultiplied=True), gold[name], sc, (fname, name, "graphs"))
+        finally:
+            r.close()
+
+
+def goldens_through_two_band_handles(family, fname, contiguous):
+    assert contiguous in family.layouts
+    items, aliased, gold = golden_scenes(family, fname, 2)
+    for name, sc in items:
+        out = two_bands(sc["width"], sc["height"], contiguous, lambda r: r.render(sc["stage"]), make=lambda **kw: renderer_for(sc, aliased, **kw))
+        check(family, out, gold[name], sc, (fname, name, "bands", contiguous))
+
+
+def goldens_through_render_batch_with_unlike_frames(family, fname):
+    """The file's scenes of one frame size as ONE batch, a plain frame (no group, no blended path: no operator table) after every third
+    of them: composited and plain frames, solid, bitmap and gradient frames in one group, so in one launch of the family's instance.
+    Into a device tensor where there is a device for it (every frame checked), and by the per-frame route (the last frame is what stays).
+    The plain frame is held against the oracle; aliased, where there is no oracle, against tests/frame_model.py -- the exact model of
+    the aliased rule over the frame builder's arrays; the other frames against libcairo."""
+    items, aliased, gold = golden_scenes(family, fname, 3)
+    for w, h in sorted({(sc["width"], sc["height"]) for _, sc in items}):
+        group = [(name, sc) for name, sc in items if (sc["width"], sc["height"]) == (w, h)]
+        plain = dict(width=w, height=h, exact=True, stage={"children": blend_scenes._with_ground(dict(width=w, height=h))})
+        plain_want = frame_model.render(*built_for_another_handle(plain, True), w, h, aliased=True) if aliased else oracle_render(plain)
+        frames = []                                                  # (message, scenario, expected pixels)
+        for k, (name, sc) in enumerate(group):
+            frames.append((name, sc, gold[name]))
+            if k % 3 == 0:
+                frames.append(("plain", plain, plain_want))
+        r = handle(w, h, aliased)
+        try:
+            seen = set()
+            for _, sc, _ in frames:
+                for b in sc.get("bitmaps", []):
+                    if b["id"] not in seen:
+                        seen.add(b["id"])
+                        r.add_bitmap(b)
+            stages = [sc["stage"] for _, sc, _ in frames]
+            if not EMU:                                              # (device tensors need the GPU)
+                import torch
+                out = torch.zeros((len(stages), h, w, 4), dtype=torch.uint8, device="cuda")
+                r.render_batch(stages, out.data_ptr(), h * w * 4)
+                got = out.cpu().numpy()
+                for k, (name, sc, want) in enumerate(frames):
+                    check(family, got[k], want, sc, (fname, name, "batch", k))
+            for cut in sorted({1, 2, len(frames) // 2, len(frames)}):
+                if 0 < cut <= len(frames):
+                    r.render_batch(stages[:cut])
+                    name, sc, want = frames[cut - 1]
+                    check(family, r.read_image(premultiplied=True), want, sc, (fname, name, "per-frame route", cut))
+            not_refused(r, fname)
+        finally:
+            r.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- the corpus through an instance
+def force_instance(monkeypatch, family, rows="narrow"):
+    monkeypatch.setenv("SWFR_TILES_SHADERS", family.instance)
+    if rows == "wide":
+        monkeypatch.setenv("SWFR_ROWS_WIDE", "1")
+    else:
+        monkeypatch.delenv("SWFR_ROWS_WIDE", raising=False)
+
+
+def scenario_through_instance(family, sc, name, rows, monkeypatch):
+    """byte-identical to what the instance picked for the scenario gives, and its libcairo golden"""
+    from helpers import golden, product_render
+    monkeypatch.delenv("SWFR_TILES_SHADERS", raising=False)
+    base = product_render(sc)
+    force_instance(monkeypatch, family, rows)
+    got = product_render(sc)
+    assert diff_stats(got, base) == (0, 0), name
+    n, mx = diff_stats(got, golden("cairo_" + name, "rgba_premul"))
+    assert ((n, mx) == (0, 0)) if sc["exact"] else mx <= 1, (name, n, mx)
+
+
+def aliased_scenarios_through_instance(family, scenarios, monkeypatch):
+    from helpers import golden, product_render
+    force_instance(monkeypatch, family)
+    for name, sc in sorted(scenarios.items()):
+        n, mx = diff_stats(product_render(sc, antialias="none"), golden("cairo_aliased_" + name, "rgba_premul"))
+        assert ((n, mx) == (0, 0)) if sc["exact"] else mx <= 1, (name, n, mx)
+
+
+def structural_scenes_through_instance(family, rows, monkeypatch):
+    """the tests/helpers.py scenes that tests/test_gpu_instances.py runs per instance"""
+    from helpers import product_render
+    force_instance(monkeypatch, family, rows)
+    rng = np.random.default_rng(5)
+    for it in range(12 if EMU else 40):
+        sc, info = helpers.rand_polygon_scene(rng, it)
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), ("poly", it, info)
+    rng = np.random.default_rng(11)
+    for it in range(6 if EMU else 20):
+        sc = helpers.rand_layered_translucent_scene(rng)
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), ("layered", it)
+    rng = np.random.default_rng(78)
+    for it in range(8 if EMU else 30):
+        sc = helpers.rand_stroked_scene(rng)
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), ("stroked", it)
+    for teeth in (12, 40, 140):
+        for eo in (False, True):
+            sc = helpers.crowded_rows_scene(teeth, eo)
+            assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), ("comb", teeth, eo)
+    for teeth in (9, 16):
+        for y_top in (0, -7):
+            sc = helpers.frame_top_scene(teeth, y_top, False)
+            assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), ("top", teeth, y_top)
+    for case in helpers.SOAK_TIE_CASES:
+        sc = helpers.soak_scene(*case)
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), case
+    for name in ("soak_big_7000_2285_child3", "soak_mixed_7100_2196_child0_1"):
+        sc = json.load(open(os.path.join(helpers.GOLD, name + ".json")))
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), name
+    for key, sc in helpers.uncovered_path_row_scenes():
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), key
+    for key, sc in helpers.wide_frame_scenes().items():
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), key
+    rng = np.random.default_rng(4040)
+    for i in range(3 if EMU else 12):
+        sc = helpers.rand_dense_scene(rng)
+        assert diff_stats(product_render(sc), oracle_render(sc)) == (0, 0), ("dense", i)
+    if not EMU:
+        W, H, fx, cols, scene = helpers.synth_scene(helpers.TWENTY_THOUSAND_PATHS)
+        r = handle(W, H)
+        try:
+            r.render_edges(*scene)
+            assert diff_stats(r.read_image(premultiplied=True), helpers.oracle_polys(fx, cols, W, H)) == (0, 0)
+        finally:
+            r.close()
+
+
+def s1_4k_known_answer_through_instance(family, monkeypatch):
+    if EMU:
+        pytest.skip("a 4K frame: minutes on the emulator")
+    from swf_renderer_amd import synth
+    force_instance(monkeypatch, family)
+    W, H, _, _, scene = helpers.synth_scene(synth.S1)
+    r = handle(W, H)
+    try:
+        r.render_edges(*scene)
+        assert hashlib.sha256(r.read_image(premultiplied=True).tobytes()).hexdigest() == synth.S1_SHA256_PREMUL
+        r.render_resident(3)                                         # (overlapped frames: the tile pass in its paired launch shape)
+        assert hashlib.sha256(r.read_image(premultiplied=True).tobytes()).hexdigest() == synth.S1_SHA256_PREMUL
+    finally:
+        r.close()
+
+
+def s1_4k_crops(family, fname, aliased=False):
+    """the family's S1 frame at 4K against its committed crops and the hash of the whole frame"""
+    if EMU:
+        pytest.skip("a 4K frame: minutes on the emulator")
+    sc = family.scenes.s1_stage()
+    gold = np.load(family.scenes.golden_path(fname))
+    img = helpers.product_render(sc, **({"antialias": "none"} if aliased else {}))
+    for key in gold.files:
+        if key == "sha256":
+            continue
+        x, y = map(int, key.split("_"))
+        assert (img[y:y + 256, x:x + 256] == gold[key]).all(), key
+    assert hashlib.sha256(img.tobytes()).digest() == gold["sha256"].tobytes()

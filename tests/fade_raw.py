@@ -1,5 +1,5 @@
-"""Raw frames with faded groups for the instance of the tile kernel that fades, checked against tests/fade_frame_model.py: frames
-written directly as swfr_upload_edges arrays (mask_raw.MaskFrame plus the fade bits of GROUP_END), aimed at the walk of k2_tiles<6>
+"""Raw frames with faded groups for the instance of the tile kernel that fades, checked against tests/frame_model.py: frames
+written directly as swfr_upload_edges arrays (composite_scenes.RawFrame with faded ENDs), aimed at the walk of k2_tiles<6>
 over one strip's list -- a faded END in a strip its group reached and in one it reached by its rectangle alone, the faded END on
 either side of the staging rounds (16 entries), the class-byte chunks (64) and the prefetched class bytes (128), four nested faded
 groups set aside by one path, a faded group around a masked one whose content misses the strip, the opacities at both ends of the
@@ -13,15 +13,6 @@ from composite_scenes import BEGIN, END, MODES, STRIP_H, add_member, premultipli
 MASK = mr.MASK
 
 
-class FadeFrame(mr.MaskFrame):
-    """MaskFrame whose groups may close with an opacity: end(op, opacity) puts the fade 255 - opacity into bits 24..31 of the END's lerp"""
-
-    def end(self, op="normal", opacity=255):
-        super().end(op)
-        self.paths[-1][5] |= (255 - int(opacity)) << 24
-        return self
-
-
 def fade_of(path):
     return (int(path["lerp"]) & 0xffffffff) >> 24
 
@@ -31,7 +22,7 @@ def reach_cases_frame(op="normal", opacity=128, W=256, H=16, seed=0):
     strip row and column 3 of the lower one; every other strip the group reaches by its rectangle alone -- there the faded END finds
     the parent's pixels in place and must leave them alone.  Plain paths before and after in every strip."""
     rng = np.random.default_rng(seed)
-    fr = FadeFrame(W, H)
+    fr = cs.RawFrame(W, H)
     fr.rect_tor(-1, -1, W + 1, H + 1, premultiplied(rng, 150), 1)
     fr.tor([(2, 1), (250, 3), (120, 15)], premultiplied(rng, 90))
     t = lambda: premultiplied(rng, int(rng.integers(60, 250)))      # (members kept inside their own tile column and strip row)
@@ -50,7 +41,7 @@ def fade_sizes_frame(rng, n_members, n_before, n_after=3, W=70, H=13, end_op=Non
     """composite_scenes.raw_group_sizes_frame with a faded END: `n_before` plain entries, ONE faded group of `n_members` members,
     `n_after` plain entries, every one reaching the strip in the frame's top left corner: BEGIN sits at list position n_before, the
     faded END at n_before + n_members + 1"""
-    fr = FadeFrame(W, H)
+    fr = cs.RawFrame(W, H)
     c0, o0 = int(rng.integers(0, 6)), int(rng.integers(0, 9))
     for i in range(n_before):
         add_member(fr, rng, ("full_translucent", "box", "partial")[i % 3], MODES[(o0 + i) % 9] if i else "normal", 0, 0, first=i == 0)
@@ -72,7 +63,7 @@ def nested_fades_frame(which, W=200, H=45, seed=0):
     which = "around_masked_alone": a faded group whose only member is a masked group whose content misses strip (0, 0): the faded END
     there meets pixels the mask step has just cleared, set aside by the mask's path alone."""
     rng = np.random.default_rng(seed + len(which))
-    fr = FadeFrame(W, H)
+    fr = cs.RawFrame(W, H)
     add_member(fr, rng, "partial", "normal", 0, 0, first=True)
     fr.rect_tor(0, 2, W, 5, premultiplied(rng, 120))
     if which == "four_by_one_path":
@@ -115,7 +106,7 @@ def nested_fades_frame(which, W=200, H=45, seed=0):
 def rand_raw_faded_frame(rng, W=200, H=45, items=60):
     """mask_raw.rand_raw_masked_frame's walk with fades: random nesting of plain, faded and masked groups up to the four levels, small
     members scattered over several tile rows and columns"""
-    fr = FadeFrame(W, H)
+    fr = cs.RawFrame(W, H)
     painted = [False]
 
     def member():
@@ -167,7 +158,7 @@ def rand_raw_faded_frame(rng, W=200, H=45, items=60):
 
 def many_faded_groups_frame(rng, W=512, H=256, groups=1000):
     """a thousand small faded groups of one to three members, now and then one inside another, plain paths between them"""
-    fr = FadeFrame(W, H)
+    fr = cs.RawFrame(W, H)
     fr.rect_tor(-1, -1, W + 1, H + 1, premultiplied(rng, 200), 1)
 
     def members(x, y):

@@ -4,7 +4,7 @@ tests/mask_scenes.py pieces, and their libcairo reference: MaskReplay with, arou
     cairo_push_group; the object (with its "mask", composited in normal mode, if it has one); cairo_pop_group_to_source;
     cairo_set_operator(the mode of "layer", absent: OVER); cairo_paint_with_alpha(opacity / 255.0)
 
-tools/make_fade_goldens.py writes goldens() to tests/golden/cairo_fade_*.npz (premultiplied RGBA; key = scene name); the tests rebuild
+tools/make_composite_goldens.py writes goldens() to tests/golden/cairo_fade_*.npz (premultiplied RGBA; key = scene name); the tests rebuild
 the scenes from here, so a golden file holds pixels only.  Every scene is at most 128 x 64.
 """
 import ctypes
@@ -239,7 +239,7 @@ def files():
 
 
 def solid_scenes():
-    """(file name, scene name, scene, aliased) of every golden scene whose styles are all solid: what tests/fade_frame_model.py can draw"""
+    """(file name, scene name, scene, aliased) of every golden scene whose styles are all solid: what tests/frame_model.py can draw"""
     for fname, (make, aliased) in sorted(files().items()):
         for name, sc in sorted(make().items()):
             if not sc.get("bitmaps") and "gradient" not in name:

@@ -3,8 +3,8 @@
     render(edges, paths, styles, W, H, even_odd_from_paths=True, aliased=False) -> H x W x 4 premultiplied RGBA
 
 `edges` / `paths` are EDGE_DTYPE / PATH_DTYPE arrays and `styles` Style structs: what Renderer.build_frame returns and what
-Renderer.render_edges takes, in the PUBLIC form of swfr_path -- `lerp` is lerp | operator << 8, groups are SWFR_PATH_GROUP_BEGIN / _END
-marker paths, END carrying the composite's operator.  Paths are painted in order onto a clear frame.
+Renderer.render_edges takes, in the PUBLIC form of swfr_path -- `lerp` is lerp | operator << 8 | fade << 24, groups are
+SWFR_PATH_GROUP_BEGIN / _MASK / _END marker paths.  Paths are painted in order onto a clear frame.
 
 - Coverage of a path, 0..255 per pixel of its rectangle (nothing is painted outside it):
   antialiased tor paths -- the oracle's scan converter (OracleBackend.fill_edges) over the path's rectangle, opaque white on a clear
@@ -13,23 +13,35 @@ marker paths, END carrying the composite's operator.  Paths are painted in order
   the spans and boxes of tests/mono_model.py, every covered pixel at 255.
 - A path whose lerp bit is set is a SOURCE lerp (blend_model.lerp_source); otherwise its operator's combiner on mul_un8(colour,
   coverage) (blend_model.blend; operator 0 is OVER).
-- GROUP_BEGIN sets the pixels of its rectangle aside and starts them clear; GROUP_END composites what was drawn since onto what was set
-  aside with layer_model.composite(operator).  Members lie inside the rectangle and a transparent group pixel leaves its destination
-  as it is under all nine operators (tests/layer_model.py), so working inside the rectangle is the rule on a surface of the frame's size.
-- Solid styles only: bitmap and gradient sources under operators stay pinned by the libcairo goldens.
+- A group is BEGIN; paths; END(operator), or, masked, BEGIN; content paths; MASK; mask paths; END(operator).  BEGIN sets the pixels
+  of its rectangle aside and starts them clear.  MASK sets what was drawn since -- the content -- aside in turn and starts clear
+  again; the END of a masked group multiplies the content by the alpha of what was drawn since MASK (mask_model.masked).  An END
+  whose `lerp` carries a fade, 255 - opacity, in bits 24..31 multiplies the group's pixels by the opacity (fade_model.faded: every
+  channel, alpha included).  Then END composites the group onto what BEGIN set aside with layer_model.composite(operator).
+  Members lie inside the group's rectangle and a transparent group pixel leaves its destination as it is under all nine operators
+  (tests/layer_model.py), so working inside the rectangle is the rule on a surface of the frame's size.
+- Groups nest to SWFR_MAX_LAYER_DEPTH levels; a masked group counts two from its BEGIN on.
+- Refused with ValueError, as swfr_upload_edges refuses them: an unknown operator or lerp value, lerp bits beside an operator,
+  bits 16..23 of `lerp`; a fade on anything but the END of an unmasked group; markers that do not pair up, carry another rectangle
+  than their BEGIN, or nest too deep; a MASK with edges or a lerp field, outside a group or second in its group; a path outside its
+  group's rectangle.
+- Solid styles only (NotImplementedError otherwise): bitmap and gradient sources under operators stay pinned by the libcairo goldens.
 
 The model states the rule; it shares no code with the kernels (swf_renderer_amd/csrc) and knows nothing of strips, staging rounds,
 class bytes or culling.  All work is cropped to a path's rectangle: a 4K frame of thousands of small paths stays affordable.
-tests/test_frame_model.py pins it against the committed libcairo goldens, live libcairo and the oracle.
+tests/test_frame_model.py, tests/test_mask_frame_model.py and tests/test_fade_frame_model.py pin it against the committed libcairo
+goldens, live libcairo and the oracle.
 """
 import numpy as np
 
 import blend_model as bm
+import fade_model as fd
 import layer_model as lm
+import mask_model as mk
 import mono_model as mm
 from oracle import oracle_backend as ob
 
-PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END = 0, 1, 2, 3
+PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END, PATH_GROUP_MASK = 0, 1, 2, 3, 4
 STYLE_SOLID = 0
 OPERATOR_NAMES = {v: ("normal" if k == "over" else k) for k, v in bm.OPERATORS.items()}      # SWFR_OP_* -> blend_model's mode names
 
@@ -104,28 +116,62 @@ def path_coverage(edges, p, W, H, even_odd_from_paths=True, aliased=False):
     return rect, (tor_coverage(e, rect, even_odd) if kind == PATH_TOR else box_coverage(e, rect))
 
 
+def masked_begins(paths):
+    """the indices of the GROUP_BEGINs whose group holds a MASK (a MASK belongs to the innermost group open where it stands)"""
+    out, opened = set(), []
+    for i, p in enumerate(paths):
+        kind = int(p["kind"])
+        if kind == PATH_GROUP_BEGIN:
+            opened.append(i)
+        elif kind == PATH_GROUP_END and opened:
+            opened.pop()
+        elif kind == PATH_GROUP_MASK:
+            if not opened or opened[-1] in out:
+                raise ValueError("GROUP_MASK outside a group, or a second one in its group")
+            out.add(opened[-1])
+    return out
+
+
 def render(edges, paths, styles, W, H, even_odd_from_paths=True, aliased=False):
-    """premultiplied RGBA (H x W x 4 uint8) of a frame in swfr_upload_edges form"""
+    """premultiplied RGBA (H x W x 4 uint8) of a frame in swfr_upload_edges form, masked and faded groups included"""
     edges, paths = np.asarray(edges), np.asarray(paths)
+    two = masked_begins(paths)
     img = np.zeros((H, W, 4), np.uint8)
-    stack = []                                                   # open groups: (rectangle, the pixels set aside)
-    for p in paths:
-        kind, field = int(p["kind"]), int(p["lerp"])
-        lerp, op = field & 0xff, field >> 8
+    stack = []                                                   # open groups: [rectangle, the parent's pixels, the content's or None, levels]
+    levels = 0
+    for i, p in enumerate(paths):
+        kind, field = int(p["kind"]), int(p["lerp"]) & 0xffffffff
+        lerp, op, fade = field & 0xff, (field >> 8) & 0xffff, field >> 24
+        if fade and kind != PATH_GROUP_END:
+            raise ValueError("swfr_path::lerp %#x: a fade on a path that is no GROUP_END" % field)
         if op not in OPERATOR_NAMES or lerp > 1:
             raise ValueError("swfr_path::lerp %#x: no such operator or lerp value" % field)
         x0, y0, x1, y1 = rect = _rect(p, W, H)
         if kind == PATH_GROUP_BEGIN:
-            if field or len(stack) == lm.MAX_DEPTH:
+            need = 2 if i in two else 1
+            if field or levels + need > lm.MAX_DEPTH:
                 raise ValueError("GROUP_BEGIN with a lerp field, or deeper than SWFR_MAX_LAYER_DEPTH")
-            stack.append((rect, img[y0:y1, x0:x1].copy()))
+            levels += need
+            stack.append([rect, img[y0:y1, x0:x1].copy(), None, need])
+            img[y0:y1, x0:x1] = 0
+            continue
+        if kind == PATH_GROUP_MASK:
+            if not stack or stack[-1][0] != rect or field or int(p["n_edges"]) or stack[-1][2] is not None:
+                raise ValueError("GROUP_MASK outside a group, with another rectangle than its group's, with edges or a lerp field, or a second one")
+            stack[-1][2] = img[y0:y1, x0:x1].copy()
             img[y0:y1, x0:x1] = 0
             continue
         if kind == PATH_GROUP_END:
             if not stack or stack[-1][0] != rect or lerp:
                 raise ValueError("GROUP_END without its GROUP_BEGIN, or with lerp bits")
-            _, below = stack.pop()
-            img[y0:y1, x0:x1] = lm.composite(OPERATOR_NAMES[op], img[y0:y1, x0:x1], below)
+            _, below, content, need = stack.pop()
+            levels -= need
+            if fade and content is not None:
+                raise ValueError("GROUP_END: a fade on a group with a GROUP_MASK")
+            g = img[y0:y1, x0:x1] if content is None else mk.masked(content, img[y0:y1, x0:x1])
+            if fade:
+                g = fd.faded(g, 255 - fade)
+            img[y0:y1, x0:x1] = lm.composite(OPERATOR_NAMES[op], g, below)
             continue
         if stack:
             g = stack[-1][0]

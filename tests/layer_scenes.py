@@ -1,6 +1,6 @@
 """Isolated-layer scenes ("Isolated layers"), built from tests/scenarios.py and tests/blend_scenes.py pieces, and their
 libcairo reference: BlendReplay with cairo_push_group / cairo_pop_group_to_source / cairo_set_operator / cairo_paint around every object
-that carries "layer".  tools/make_layer_goldens.py writes goldens() to tests/golden/cairo_layer_*.npz (premultiplied RGBA; key = scene
+that carries "layer".  tools/make_composite_goldens.py writes goldens() to tests/golden/cairo_layer_*.npz (premultiplied RGBA; key = scene
 name); the tests rebuild the scenes from here, so a golden file holds pixels only.
 """
 import ctypes
@@ -151,7 +151,7 @@ def structure_scenes(modes=None):
     ground = _with_ground(dict(width=W, height=H))
     fade = mk.cxform(mult=(256, 200, 128, 160), add=(0, 20, 60, 0))
     # (triangles whose pixels tell a SOURCE lerp's 0x7f rounding from OVER's 0x80: most do in a few pixels, some in none --
-    #  tools/make_layer_goldens.py checks these with libcairo)
+    #  tools/make_composite_goldens.py checks these with libcairo)
     follow = [_shape([(14.6, 7.3), (2.2, 44.1), (41.6, 29.3)], (84, 23, 95, 196)), _shape([(60.4, 43.4), (41.1, 33.1), (9.9, 2.8)], (31, 64, 179, 128))]
     for mode in modes:
         other = "hardlight" if mode != "hardlight" else "darken"
@@ -211,7 +211,7 @@ def structure_scenes(modes=None):
 
 def wrong_rule_scenes():
     """For the scenes whose point is the bookkeeping: name -> (the same pixels by other means or None, the rule it must NOT be confused
-    with).  tools/make_layer_goldens.py checks with libcairo that the first renders the same pixels and the second differs in at least
+    with).  tools/make_composite_goldens.py checks with libcairo that the first renders the same pixels and the second differs in at least
     one.  A clear-state scene's group changes no pixel, so the scene without it is the rule "the parent stays clear", and the scene
     with an opaque speck in a corner the triangles do not touch -- the speck painted into the expected image too -- the rule "the
     parent counts as drawn".  The parent stays clear behind a still-clear group under OVER and ADD only; the group holding a clear

@@ -1,5 +1,5 @@
-"""Raw frames with masked groups for the mask instance of the tile kernel, checked against tests/mask_frame_model.py: frames
-written directly as swfr_upload_edges arrays (composite_scenes.RawFrame plus the MASK marker), aimed at the walk of k2_tiles<5> over one
+"""Raw frames with masked groups for the mask instance of the tile kernel, checked against tests/frame_model.py: frames
+written directly as swfr_upload_edges arrays (composite_scenes.RawFrame with MASK markers), aimed at the walk of k2_tiles<5> over one
 strip's list -- the four reach cases of a strip (content reaches it or not, mask reaches it or not), MASK and the masked END on either
 side of the staging rounds (16 entries), the class-byte chunks (64) and the prefetched class bytes (128), halves of 15 .. 65 members,
 nesting, all nine operators, groups across tile rows -- and strip_mask_reach, what a frame's strips see, from the arrays alone."""
@@ -12,41 +12,11 @@ from composite_scenes import BEGIN, END, MODES, STRIP_H, STRIP_W, add_member, pr
 MASK = mk.PATH_GROUP_MASK
 
 
-class MaskFrame(cs.RawFrame):
-    """RawFrame whose groups may hold a MASK marker: begin(); content; mask(); mask paths; end(op)"""
-
-    def __init__(self, W, H):
-        super().__init__(W, H)
-        self.masks = []                                              # per open group: the index of its MASK marker, or None
-
-    def begin(self):
-        self.masks.append(None)
-        return super().begin()
-
-    def mask(self):
-        assert self.masks and self.masks[-1] is None
-        self.masks[-1] = len(self.paths)
-        self.paths.append([len(self.rows), 0, MASK, 0, 0, 0, 0, 0, 0, 0])
-        return self
-
-    def end(self, op="normal"):
-        b = self.open[-1]
-        m = self.masks.pop()
-        super().end(op)
-        if m is not None:
-            self.paths[m][6:10] = self.paths[b][6:10]
-        return self
-
-    @property
-    def levels(self):
-        return sum(2 if m is not None else 1 for m in self.masks)
-
-
 def masked_sizes_frame(rng, n_content, n_mask, n_before, n_after=3, W=70, H=13, end_op=None):
     """`n_before` plain entries, ONE masked group of `n_content` content and `n_mask` mask members, `n_after` plain entries, every one
     reaching the strip in the frame's top left corner: BEGIN sits at list position n_before, MASK at n_before + n_content + 1, END at
     n_before + n_content + n_mask + 2"""
-    fr = MaskFrame(W, H)
+    fr = cs.RawFrame(W, H)
     c0, o0 = int(rng.integers(0, 6)), int(rng.integers(0, 9))
     for i in range(n_before):
         add_member(fr, rng, ("full_translucent", "box", "partial")[i % 3], MODES[(o0 + i) % 9] if i else "normal", 0, 0, first=i == 0)
@@ -67,7 +37,7 @@ def reach_cases_frame(op="normal", W=256, H=16, seed=0):
     content alone column 1, the mask alone column 2, neither column 3 (which the group reaches by its rectangle alone: a member of each
     half lies in column 3 of the OTHER strip row).  Plain paths before and after in every strip."""
     rng = np.random.default_rng(seed)
-    fr = MaskFrame(W, H)
+    fr = cs.RawFrame(W, H)
     fr.rect_tor(-1, -1, W + 1, H + 1, premultiplied(rng, 150), 1)
     fr.tor([(2, 1), (250, 3), (120, 15)], premultiplied(rng, 90))
     t = lambda: premultiplied(rng, int(rng.integers(60, 250)))      # (members kept inside their own tile column and strip row)
@@ -95,7 +65,7 @@ def nested_masks_frame(which, W=200, H=45, seed=0):
     column 0 while its mask does: the outer group's pixels must survive the mask step untouched.
     which = "in_content": masked inside the content half of a masked group, both reaching every column."""
     rng = np.random.default_rng(seed + len(which))
-    fr = MaskFrame(W, H)
+    fr = cs.RawFrame(W, H)
     add_member(fr, rng, "partial", "normal", 0, 0, first=True)
     fr.rect_tor(0, 2, W, 5, premultiplied(rng, 120))
     if which == "four_by_one_path":
@@ -144,7 +114,7 @@ def nested_masks_frame(which, W=200, H=45, seed=0):
 def rand_raw_masked_frame(rng, W=200, H=45, items=60):
     """composite_scenes.rand_raw_nested_frame with masks: random nesting of plain and masked groups up to the four levels, small
     members scattered over several tile rows and columns, so that every strip takes its own branch of the reach cases"""
-    fr = MaskFrame(W, H)
+    fr = cs.RawFrame(W, H)
     painted = [False]
 
     def member():
@@ -200,7 +170,7 @@ def rand_raw_masked_frame(rng, W=200, H=45, items=60):
 
 def many_masked_groups_frame(rng, W=512, H=256, groups=1000):
     """a thousand small masked groups of one to three members a half, now and then one inside another, plain paths between them"""
-    fr = MaskFrame(W, H)
+    fr = cs.RawFrame(W, H)
     fr.rect_tor(-1, -1, W + 1, H + 1, premultiplied(rng, 200), 1)
 
     def half(x, y):

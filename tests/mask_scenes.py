@@ -5,7 +5,7 @@ pieces, and their libcairo reference: LayerReplay with, around every object that
     cairo_set_source(content); cairo_set_operator(the mode of "layer", absent: OVER); cairo_mask(mask)
 
 the mask list drawn in the parent's space, outside the object's own matrix, colour transform and blend mode.
-tools/make_mask_goldens.py writes goldens() to tests/golden/cairo_mask_*.npz (premultiplied RGBA; key = scene name); the tests rebuild
+tools/make_composite_goldens.py writes goldens() to tests/golden/cairo_mask_*.npz (premultiplied RGBA; key = scene name); the tests rebuild
 the scenes from here, so a golden file holds pixels only.  Every scene is at most 128 x 64.
 """
 import ctypes
@@ -282,7 +282,7 @@ def files():
 
 
 def solid_scenes():
-    """(file name, scene name, scene, aliased) of every golden scene whose styles are all solid: what tests/mask_frame_model.py can draw"""
+    """(file name, scene name, scene, aliased) of every golden scene whose styles are all solid: what tests/frame_model.py can draw"""
     for fname, (make, aliased) in sorted(files().items()):
         for name, sc in sorted(make().items()):
             if not sc.get("bitmaps") and "gradient" not in name:

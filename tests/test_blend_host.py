@@ -1,7 +1,6 @@
 """Blend modes on the host side (no GPU, host-only handles): the display-object type, the refused modes, the operator field
 swfr_build_frame emits -- ADD on a still-clear surface settling to a SOURCE lerp, in single and in threaded builds -- and what
 swfr_upload_edges refuses."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -9,36 +8,9 @@ import pytest
 
 import blend_model as bm
 import blend_scenes as bs
+import host_frames as hf
 import scenarios
 from scenarios import _rgba
-
-
-def _host(w=64, h=48, **kw):
-    import swf_renderer_amd as S
-    from swf_renderer_amd import api
-    return S.Renderer(w, h, device=api.DEVICE_HOST_ONLY, **kw)
-
-
-def _raw_stage(obj_type, obj_id, child_shape_id):
-    from swf_renderer_amd import api
-    kid = api.DisplayObject()
-    kid.type, kid.id = api.OBJECT_SHAPE, child_shape_id
-    kids = (api.DisplayObject * 1)(kid)
-    d = api.DisplayObject()
-    d.type, d.id = obj_type, obj_id
-    d.n_children, d.children = 1, C.cast(kids, C.POINTER(api.DisplayObject))
-    objs = (api.DisplayObject * 1)(d)
-    s = api.Stage()
-    s.width = s.height = 16
-    s.n_children, s.children = 1, C.cast(objs, C.POINTER(api.DisplayObject))
-    return s, (kids, objs)
-
-
-def _build_raw(r, s):
-    n = C.c_size_t()
-    args = (C.byref(C.c_void_p()), C.byref(C.c_size_t()), C.byref(C.c_void_p()), C.byref(n), C.byref(C.c_void_p()), C.byref(C.c_size_t()))
-    rc = r.L.swfr_build_frame(r.h, C.byref(s), *args)
-    return rc, r.L.swfr_last_error(r.h).decode(), n.value
 
 
 def test_object_type_and_mode_numbers():
@@ -50,20 +22,20 @@ def test_object_type_and_mode_numbers():
     assert api.blend_mode_number(8) == 8
     with pytest.raises(api.SwfrError):
         api.blend_mode_number("dodge")
-    r = _host()
+    r = hf.host()
     try:
         sid = r.register_shape(scenarios._poly_shape([(0, 0), (200, 0), (200, 200)], {"type": "solid", "color": _rgba(9, 9, 9, 100)}))
         for mode in (0, 1, 3, 4, 5, 6, 7, 8, 13, 14):
-            rc, _, n_paths = _build_raw(r, _raw_stage(api.OBJECT_BLEND_MODE, mode, sid)[0])
+            rc, _, n_paths = hf.build_raw(r, hf.raw_stage(api.OBJECT_BLEND_MODE, mode, sid)[0])
             assert rc == api.OK and n_paths == 1, mode
         for mode in (2, 9, 10, 11, 12):
-            rc, err, _ = _build_raw(r, _raw_stage(api.OBJECT_BLEND_MODE, mode, sid)[0])
+            rc, err, _ = hf.build_raw(r, hf.raw_stage(api.OBJECT_BLEND_MODE, mode, sid)[0])
             assert (rc, err) == (api.ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode"), mode
         for mode in (15, 16, 255, 0xffffffff):
-            rc, _, _ = _build_raw(r, _raw_stage(api.OBJECT_BLEND_MODE, mode, sid)[0])
+            rc, _, _ = hf.build_raw(r, hf.raw_stage(api.OBJECT_BLEND_MODE, mode, sid)[0])
             assert rc == api.ERR_INVALID, mode
         for t in (4, 6, 7):                                          # not display-object types, before and after
-            rc, err, _ = _build_raw(r, _raw_stage(t, 3, sid)[0])
+            rc, err, _ = hf.build_raw(r, hf.raw_stage(t, 3, sid)[0])
             assert (rc, err) == (api.ERR_INVALID, "UnexpectedDisplayObjectType"), t
     finally:
         r.close()
@@ -76,7 +48,7 @@ def _tri(colour, **kw):
 @pytest.mark.parametrize("mode", sorted(bm.MODES))
 def test_operator_field_of_built_paths(mode):
     op = bm.OPERATORS[mode]
-    r = _host()
+    r = hf.host()
     try:
         for alpha in (255, 119):
             # first paint of the frame, then a later one
@@ -95,7 +67,7 @@ def test_operator_field_of_built_paths(mode):
 
 def test_normal_wrapper_changes_nothing():
     sc = scenarios.scenarios()["translucent_stack"]
-    r = _host(sc["width"], sc["height"])
+    r = hf.host(sc["width"], sc["height"])
     try:
         plain = r.build_frame(sc["stage"])
         for mode in ("normal", 0, 1):
@@ -129,7 +101,7 @@ def test_threaded_build_is_the_single_walk(mode, first_blended):
     for threads in ("1", "8"):
         os.environ["SWFR_BUILD_THREADS"] = threads
         try:
-            r = _host()
+            r = hf.host()
             out.append(r.build_frame(stage))
             r.close()
         finally:
@@ -144,7 +116,7 @@ def test_threaded_build_is_the_single_walk(mode, first_blended):
 
 
 def test_clear_source_under_an_operator_still_counts_as_drawn():
-    r = _host()
+    r = hf.host()
     try:
         for mode, lerps in (("multiply", [bm.OPERATORS["multiply"] << 8, 0]), ("add", [1]), ("normal", [1])):
             _, p, _ = r.build_frame({"children": [_tri((255, 255, 255, 0), blend_mode=mode), _tri((200, 100, 50, 119))]})
@@ -155,7 +127,7 @@ def test_clear_source_under_an_operator_still_counts_as_drawn():
 
 def test_upload_refuses_a_malformed_blend_field():
     from swf_renderer_amd import api
-    r = _host()
+    r = hf.host()
     try:
         e, p, s = r.build_frame({"children": [_tri((200, 100, 50, 119), blend_mode="screen")]})
         assert int(p["lerp"][0]) == bm.OPERATORS["screen"] << 8

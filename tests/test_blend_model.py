@@ -6,26 +6,11 @@ import numpy as np
 import pytest
 
 import blend_model as bm
+from cairo_pixels import random_premultiplied, surface_bytes
 from oracle import cairo_backend as cb
 
 needs_cairo = pytest.mark.skipif(not cb.available(), reason="libcairo not installed")
 N = 4096                                   # pixels (= random triples) per operator and destination kind
-
-
-def _surface_bytes(be):
-    be.lib.cairo_surface_flush(be.surf)
-    stride = be.lib.cairo_image_surface_get_stride(be.surf)
-    ptr = be.lib.cairo_image_surface_get_data(be.surf)
-    return np.ctypeslib.as_array(ptr, shape=(be.h, stride))[:, : be.w * 4].reshape(be.h, be.w, 4)
-
-
-def _random_premultiplied(rng, n, kind):
-    if kind == "clear":
-        return np.zeros((n, 4), np.uint8)
-    a = np.full(n, 255) if kind == "opaque" else rng.integers(0, 256, n)
-    a[: n // 16] = rng.choice([0, 1, 254, 255], n // 16) if kind != "opaque" else 255
-    rgb = (rng.integers(0, 256, (n, 3)) * a[:, None] + 127) // 255
-    return np.concatenate([rgb, a[:, None]], 1).astype(np.uint8)
 
 
 def _paint(dst, colours, widths, operator, mark_dirty=True):
@@ -36,7 +21,7 @@ def _paint(dst, colours, widths, operator, mark_dirty=True):
     try:
         be.clear_all()
         if dst is not None:
-            _surface_bytes(be)[0] = dst[:, [2, 1, 0, 3]]
+            surface_bytes(be)[0] = dst[:, [2, 1, 0, 3]]
             be.lib.cairo_surface_mark_dirty(be.surf)
         be.lib.cairo_set_operator(be.cr, operator)
         for i in range(n):
@@ -68,7 +53,7 @@ def _triples(seed):
 def test_model_is_libcairo(mode, ground):
     rng, colours, widths, cov = _triples(sorted(bm.MODES).index(mode) * 3 + 11)
     # ("clear_pixels": transparent pixels of a surface that has been drawn on -- not Cairo's "still clear" surface, which is below)
-    dst = _random_premultiplied(rng, N, "clear" if ground == "clear_pixels" else ground)
+    dst = random_premultiplied(rng, N, "clear" if ground == "clear_pixels" else ground)
     got = _paint(dst, colours, widths, bm.CAIRO_OPERATORS[mode])
     c = bm.source_pixel(colours[:, 0], colours[:, 1], colours[:, 2], colours[:, 3])
     want = bm.blend(mode, c, cov, dst)
@@ -100,8 +85,8 @@ def test_add_on_a_clear_surface_is_source_and_the_others_are_not():
 
 def test_no_coverage_changes_nothing():
     rng = np.random.default_rng(3)
-    d = _random_premultiplied(rng, 20000, "translucent")
-    c = _random_premultiplied(rng, 20000, "translucent")
+    d = random_premultiplied(rng, 20000, "translucent")
+    c = random_premultiplied(rng, 20000, "translucent")
     for mode in list(bm.MODES) + ["normal"]:
         assert (bm.blend(mode, c, np.zeros(20000, np.int64), d) == d).all(), mode
 

@@ -16,94 +16,18 @@ c. test_the_raw_corpus_reaches_what_it_claims computes from the arrays what the 
 Observed on an MI355X: 66 passed, every comparison 0 differing bytes, 32 s (tests/test_layer_gpu.py beside it: 41 s).  DESIGN.md,
 section 5 ("The frame model"), has the table of kernel mutations this file catches.
 """
-import os
-
 import numpy as np
 import pytest
 
 import composite_scenes as cs
 import frame_model as fm
 import helpers
-from helpers import diff_stats
+from device_routes import EMU, handle, not_refused, through_edges, through_render, two_bands, zero
+from device_routes import need_gpu  # noqa: F401 (the module's autouse fixture)
+from host_frames import build_on_host
 
 pytestmark = pytest.mark.gpu
-EMU = bool(os.environ.get("SWFR_EMULATOR"))
-REFUSALS = ("pairtest_limit", "start_group_limit", "history_limit")
-
 GROUP_SIZES, NESTINGS = cs.GROUP_SIZES, cs.NESTINGS
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(gpu):
-    import swf_renderer_amd as S
-    assert os.path.exists(S.library_path()), "libswfr.so must be built: the product has no fallback"
-
-
-def _zero(got, want, msg):
-    n, mx = diff_stats(got, want)
-    print("composite", msg, "differing pixels", n, "max", mx)
-    assert (n, mx) == (0, 0), msg
-
-
-def _not_refused(r, msg):
-    st = r.stats()
-    assert st["frames"] >= 1 and all(st[k] == 0 for k in REFUSALS), (msg, st)
-
-
-def _handle(W, H, aliased=False, **kw):
-    import swf_renderer_amd as S
-    return S.Renderer(W, H, antialias="none" if aliased else "default", **kw)
-
-
-def _build(sc, aliased=False):
-    """swfr_build_frame's arrays on a host-only handle"""
-    from swf_renderer_amd import api
-    host = _handle(sc["width"], sc["height"], aliased, device=api.DEVICE_HOST_ONLY, even_odd=bool(sc.get("even_odd")))
-    try:
-        return host.build_frame(sc["stage"])
-    finally:
-        host.close()
-
-
-def _through_edges(W, H, arrays, aliased=False, resident=0, **kw):
-    r = _handle(W, H, aliased, **kw)
-    try:
-        r.render_edges(*arrays)
-        img = r.read_image(premultiplied=True)
-        if resident:
-            r.render_resident(resident)
-            assert (r.read_image(premultiplied=True) == img).all(), "resident frames differ from the first"
-        _not_refused(r, "render_edges")
-        return img
-    finally:
-        r.close()
-
-
-def _through_render(sc, aliased=False, **kw):
-    r = _handle(sc["width"], sc["height"], aliased, **kw)
-    try:
-        r.render(sc["stage"])
-        _not_refused(r, "render")
-        return r.read_image(premultiplied=True)
-    finally:
-        r.close()
-
-
-def _two_bands(W, H, contiguous, draw, aliased=False):
-    """the frame assembled from two handles, each drawing its own tile rows (`draw(handle)`)"""
-    out = np.zeros((H, W, 4), np.uint8)
-    n = -(-((H + 15) // 16) // 2)
-    for rank in range(2):
-        r = _handle(W, H, aliased, band_index=rank, band_count=2, contiguous_bands=contiguous)
-        try:
-            draw(r)
-            img = r.read_image(premultiplied=True)
-            _not_refused(r, "bands")
-        finally:
-            r.close()
-        t = np.arange(H) // 16
-        rows = ((t >= rank * n) & (t < (rank + 1) * n)) if contiguous else (t % 2 == rank)
-        out[rows] = img[rows]
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- a. display trees
@@ -116,17 +40,17 @@ def test_stage_fuzz_through_render(aliased, rows, monkeypatch):
         monkeypatch.delenv("SWFR_ROWS_WIDE", raising=False)
     for seed in range(3 if EMU else 24):
         sc = cs.rand_composited_scene(np.random.default_rng(5000 + seed + 100 * aliased))
-        want = fm.render(*_build(sc, aliased), sc["width"], sc["height"], aliased=aliased)
-        _zero(_through_render(sc, aliased), want, ("render", aliased, rows, seed))
+        want = fm.render(*build_on_host(sc, aliased), sc["width"], sc["height"], aliased=aliased)
+        zero(through_render(sc, aliased), want, ("render", aliased, rows, seed))
 
 
 @pytest.mark.parametrize("aliased", [False, True], ids=["antialiased", "aliased"])
 def test_stage_fuzz_through_render_edges_and_resident_frames(aliased):
     for seed in range(2 if EMU else 12):
         sc = cs.rand_composited_scene(np.random.default_rng(5300 + seed))
-        arrays = _build(sc, aliased)
+        arrays = build_on_host(sc, aliased)
         want = fm.render(*arrays, sc["width"], sc["height"], aliased=aliased)
-        _zero(_through_edges(sc["width"], sc["height"], arrays, aliased, resident=3), want, ("render_edges", aliased, seed))
+        zero(through_edges(sc["width"], sc["height"], arrays, aliased, resident=3), want, ("render_edges", aliased, seed))
 
 
 def test_stage_fuzz_with_graphs(monkeypatch):
@@ -134,9 +58,9 @@ def test_stage_fuzz_with_graphs(monkeypatch):
     for seed in range(2 if EMU else 8):
         aliased = bool(seed % 2)
         sc = cs.rand_composited_scene(np.random.default_rng(5400 + seed))
-        arrays = _build(sc, aliased)
+        arrays = build_on_host(sc, aliased)
         want = fm.render(*arrays, sc["width"], sc["height"], aliased=aliased)
-        _zero(_through_edges(sc["width"], sc["height"], arrays, aliased, resident=3), want, ("graphs", aliased, seed))
+        zero(through_edges(sc["width"], sc["height"], arrays, aliased, resident=3), want, ("graphs", aliased, seed))
 
 
 @pytest.mark.parametrize("contiguous", [True, False], ids=["contiguous", "interleaved"])
@@ -144,9 +68,9 @@ def test_stage_fuzz_through_two_band_handles(contiguous):
     for seed in range(2 if EMU else 8):
         aliased = bool(seed % 2)
         sc = cs.rand_composited_scene(np.random.default_rng(5500 + seed), height=int(16 * (2 + seed % 4) + 1 + seed))
-        want = fm.render(*_build(sc, aliased), sc["width"], sc["height"], aliased=aliased)
-        got = _two_bands(sc["width"], sc["height"], contiguous, lambda r: r.render(sc["stage"]), aliased)
-        _zero(got, want, ("bands", contiguous, aliased, seed))
+        want = fm.render(*build_on_host(sc, aliased), sc["width"], sc["height"], aliased=aliased)
+        got = two_bands(sc["width"], sc["height"], contiguous, lambda r: r.render(sc["stage"]), aliased)
+        zero(got, want, ("bands", contiguous, aliased, seed))
 
 
 @pytest.mark.parametrize("aliased", [False, True], ids=["antialiased", "aliased"])
@@ -165,9 +89,9 @@ def test_stage_fuzz_through_render_batch_with_unlike_frames(aliased):
         if k % 3 == 2:
             sc = helpers.rand_layered_translucent_scene(rng)
             frames.append(dict(sc, stage={"children": [dict(kid, blend_mode=cs.MODES[1 + i % 8]) if i else kid for i, kid in enumerate(sc["stage"]["children"])]}))
-    wants = [fm.render(*_build(sc, aliased), W, H, aliased=aliased) for sc in frames]
+    wants = [fm.render(*build_on_host(sc, aliased), W, H, aliased=aliased) for sc in frames]
     stages = [sc["stage"] for sc in frames]
-    r = _handle(W, H, aliased)
+    r = handle(W, H, aliased)
     try:
         if not EMU:                                               # (device tensors need the GPU)
             import torch
@@ -175,11 +99,11 @@ def test_stage_fuzz_through_render_batch_with_unlike_frames(aliased):
             r.render_batch(stages, out.data_ptr(), H * W * 4)
             got = out.cpu().numpy()
             for k, want in enumerate(wants):
-                _zero(got[k], want, ("batch", aliased, k))
+                zero(got[k], want, ("batch", aliased, k))
         for cut in sorted({1, 2, len(frames) // 2, len(frames)}):
             r.render_batch(stages[:cut])
-            _zero(r.read_image(premultiplied=True), wants[cut - 1], ("per-frame route", aliased, cut))
-        _not_refused(r, "batch")
+            zero(r.read_image(premultiplied=True), wants[cut - 1], ("per-frame route", aliased, cut))
+        not_refused(r, "batch")
     finally:
         r.close()
 
@@ -188,8 +112,8 @@ def test_stage_fuzz_one_4k_frame():
     if EMU:
         pytest.skip("a 4K frame: minutes on the emulator")
     sc = cs.rand_composited_scene(np.random.default_rng(5700), width=3840, height=2160, leaves=24)
-    want = fm.render(*_build(sc), 3840, 2160)
-    _zero(_through_render(sc), want, "4K stage")
+    want = fm.render(*build_on_host(sc), 3840, 2160)
+    zero(through_render(sc), want, "4K stage")
 
 
 # ---------------------------------------------------------------------------------------------------------------- b. raw frames
@@ -198,13 +122,13 @@ def _check_raw(fr, msg, monkeypatch, also_markerless=True, **kw):
     instance (SWFR_TILES_SHADERS is read when the handle is created)"""
     arrays = fr.arrays()
     monkeypatch.delenv("SWFR_TILES_SHADERS", raising=False)
-    _zero(_through_edges(fr.W, fr.H, arrays, **kw), fm.render(*arrays, fr.W, fr.H), (msg, "groups"))
+    zero(through_edges(fr.W, fr.H, arrays, **kw), fm.render(*arrays, fr.W, fr.H), (msg, "groups"))
     if also_markerless:
         plain = cs.without_markers(*arrays)
         want = fm.render(*plain, fr.W, fr.H)
-        _zero(_through_edges(fr.W, fr.H, plain, **kw), want, (msg, "markerless"))
+        zero(through_edges(fr.W, fr.H, plain, **kw), want, (msg, "markerless"))
         monkeypatch.setenv("SWFR_TILES_SHADERS", "4")
-        _zero(_through_edges(fr.W, fr.H, plain, **kw), want, (msg, "markerless, instance 4"))
+        zero(through_edges(fr.W, fr.H, plain, **kw), want, (msg, "markerless, instance 4"))
         monkeypatch.delenv("SWFR_TILES_SHADERS", raising=False)
 
 
@@ -252,8 +176,8 @@ def test_groups_across_tile_rows_and_band_boundaries(contiguous):
         W, H = ((203, 45), (130, 37), (70, 77))[seed % 3]
         fr = cs.rand_raw_nested_frame(np.random.default_rng(6800 + seed), W=W, H=H, items=50, member_size=(10, 70))
         arrays = fr.arrays()
-        got = _two_bands(W, H, contiguous, lambda r: r.render_edges(*arrays))
-        _zero(got, fm.render(*arrays, W, H), ("raw bands", contiguous, seed))
+        got = two_bands(W, H, contiguous, lambda r: r.render_edges(*arrays))
+        zero(got, fm.render(*arrays, W, H), ("raw bands", contiguous, seed))
 
 
 @pytest.mark.parametrize("kind", ["tor", "box"])

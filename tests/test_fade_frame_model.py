@@ -1,4 +1,4 @@
-"""tests/fade_frame_model.py pinned without a GPU: the committed libcairo goldens of the fade scenes whose styles are all solid through
+"""tests/frame_model.py's faded groups pinned without a GPU: the committed libcairo goldens of the fade scenes whose styles are all solid through
 the model over swfr_build_frame (host-only handles), byte for byte; and random composited trees -- faded, masked and plain groups
 nested up to the depth limit -- against live libcairo, which is also the random check of the frame builder's bookkeeping around faded
 groups.  Zero differing pixels."""
@@ -6,13 +6,12 @@ import numpy as np
 import pytest
 
 import composite_scenes as cs
-import fade_frame_model as ffm
 import fade_model as fd
 import fade_scenes as fs
-import mask_frame_model as mfm
+import frame_model as fm
 from helpers import diff_stats
+from host_frames import build_on_host
 from oracle import cairo_backend as cb
-from test_frame_model import _build
 
 needs_cairo = pytest.mark.skipif(not cb.available(), reason="libcairo not installed")
 MASK = fd.PATH_GROUP_MASK
@@ -27,41 +26,32 @@ def test_solid_goldens_through_the_model():
     checked = fades = 0
     for fname, name, sc, aliased in fs.solid_scenes():
         gold = np.load(fs.golden_path(fname))
-        arrays = _build(sc, aliased)
+        arrays = build_on_host(sc, aliased)
         assert all(int(st.kind) == api.STYLE_SOLID for st in arrays[2]), (fname, name)
         fades += _fades(arrays[1])
-        assert diff_stats(ffm.render(*arrays, sc["width"], sc["height"], aliased=aliased), gold[name]) == (0, 0), (fname, name)
+        assert diff_stats(fm.render(*arrays, sc["width"], sc["height"], aliased=aliased), gold[name]) == (0, 0), (fname, name)
         checked += 1
     print("fade goldens through the model:", checked, "scenes,", fades, "faded ENDs")
     assert checked >= 2 * (63 + 8 + 16 + 81) and fades > checked // 3
 
 
-def test_without_fades_it_is_mask_frame_model():
-    import mask_scenes as ms
-    for seed in range(10):
-        sc = ms.rand_masked_scene(np.random.default_rng(500 + seed))
-        arrays = _build(sc)
-        assert (ffm.render(*arrays, sc["width"], sc["height"]) == mfm.render(*arrays, sc["width"], sc["height"])).all()
-
-
 def test_the_model_refuses_what_the_header_refuses():
-    import fade_raw as fr
-    f = fr.FadeFrame(32, 16)
+    f = cs.RawFrame(32, 16)
     f.begin().box(1, 1, 9, 9, 0x80402010, 1).end("add", opacity=100)
     e, p, s = f.arrays()
     assert [int(k) for k in p["kind"]] == [2, 1, 3] and int(p["lerp"][2]) == fd.end_lerp(6, 100)
-    ffm.render(e, p, s, 32, 16)
+    fm.render(e, p, s, 32, 16)
     for edit in (lambda q: q["lerp"].__setitem__(0, 1 << 24), lambda q: q["lerp"].__setitem__(1, 1 | (1 << 24)),
                  lambda q: q["lerp"].__setitem__(2, int(q["lerp"][2]) | (1 << 16))):
         q = p.copy()
         edit(q)
         with pytest.raises(ValueError):
-            ffm.render(e, q, s, 32, 16)
-    m = fr.FadeFrame(32, 16)                                         # a fade on the END of a group that holds a MASK
+            fm.render(e, q, s, 32, 16)
+    m = cs.RawFrame(32, 16)                                         # a fade on the END of a group that holds a MASK
     m.begin().box(1, 1, 9, 9, 0x80402010, 1).mask().box(2, 2, 8, 8, 0x80000000, 1).end("add", opacity=100)
     e, p, s = m.arrays()
     with pytest.raises(ValueError):
-        ffm.render(e, p, s, 32, 16)
+        fm.render(e, p, s, 32, 16)
 
 
 @needs_cairo
@@ -71,8 +61,8 @@ def test_random_faded_trees_equal_libcairo(aliased, seeds):
     for seed in range(seeds):
         sc = fs.rand_faded_scene(np.random.default_rng(7000 + seed + 10000 * aliased))
         assert max(fs._levels(k) for k in sc["stage"]["children"]) <= fd.MAX_DEPTH       # (no case is refused or skipped)
-        arrays = _build(sc, aliased)
-        two = mfm.masked_begins(arrays[1])
+        arrays = build_on_host(sc, aliased)
+        two = fm.masked_begins(arrays[1])
         levels, stack = 0, []
         for i, (k, v) in enumerate(zip(arrays[1]["kind"].tolist(), arrays[1]["lerp"].tolist())):
             if k == cs.BEGIN:
@@ -85,7 +75,7 @@ def test_random_faded_trees_equal_libcairo(aliased, seeds):
                 levels -= stack.pop()
         fades += _fades(arrays[1])
         masks += int((arrays[1]["kind"] == MASK).sum())
-        n, _ = diff_stats(ffm.render(*arrays, sc["width"], sc["height"], aliased=aliased), fs.cairo_render(sc, aliased))
+        n, _ = diff_stats(fm.render(*arrays, sc["width"], sc["height"], aliased=aliased), fs.cairo_render(sc, aliased))
         differing += n
         assert n == 0, (seed, aliased, sc["width"], sc["height"])
     print("random faded trees against libcairo:", seeds, "seeds, aliased" if aliased else "seeds,", fades, "faded groups,", masks,
@@ -101,7 +91,7 @@ def test_threaded_build_of_faded_trees_is_the_single_walk_and_equals_libcairo(al
         out = []
         for threads in ("1", "3"):
             monkeypatch.setenv("SWFR_BUILD_THREADS", threads)
-            out.append(_build(sc, aliased))
+            out.append(build_on_host(sc, aliased))
         assert out[0][0].tobytes() == out[1][0].tobytes() and out[0][1].tobytes() == out[1][1].tobytes()
         assert _fades(out[0][1]) > 0
-        assert diff_stats(ffm.render(*out[1], sc["width"], sc["height"], aliased=aliased), fs.cairo_render(sc, aliased)) == (0, 0), seed
+        assert diff_stats(fm.render(*out[1], sc["width"], sc["height"], aliased=aliased), fs.cairo_render(sc, aliased)) == (0, 0), seed

@@ -6,7 +6,7 @@ a. Every libcairo golden of tests/fade_scenes.py -- every file, every scene -- t
    SWFR_TILES_SHADERS forced to 6; frames WITHOUT a fade -- the scenario corpus, the layer and mask goldens, raw layer and mask frames
    -- forced through the instance that fades.  Zero differing bytes (linear-gradient scenes: LINEAR_BOUND of tests/test_layer_gpu.py;
    mul_un8 by the opacity has slope <= 1, so the bound carries over).
-b. Raw frames of 70 x 13 up to 256 x 64 (tests/fade_raw.py) against tests/fade_frame_model.py, zero differing bytes: a faded END in a
+b. Raw frames of 70 x 13 up to 256 x 64 (tests/fade_raw.py) against tests/frame_model.py, zero differing bytes: a faded END in a
    strip its group reached and in one it reached by its rectangle alone, under all nine operators; a faded END as the last entry
    before and the first behind list positions 16, 64 and 128; four nested faded groups set aside by one path; a faded group around a
    masked one whose content misses the strip; opacities 0, 1, 254 and 255; random nesting of plain, faded and masked groups over
@@ -17,183 +17,50 @@ b. Raw frames of 70 x 13 up to 256 x 64 (tests/fade_raw.py) against tests/fade_f
 Runs on an MI355X (-m gpu) and, with smaller counts, under tools/emu/run.py.  DESIGN.md, section 5 ("The fade model"), has the table of
 kernel mutations this file catches.
 """
-import os
-
 import numpy as np
 import pytest
 
 import composite_scenes as cs
-import fade_frame_model as ffm
+import device_routes as dr
 import fade_raw as fr_
 import fade_scenes as ms
 import frame_model
-import mask_frame_model as mfm
 from composite_scenes import CHUNK, PREFETCH, ROUND
-from helpers import diff_stats, oracle_render
-from test_composite_fuzz_gpu import _handle, _not_refused, _through_edges, _two_bands, _zero
+from device_routes import EMU, renderer_for, through_edges, two_bands, zero
+from device_routes import need_gpu  # noqa: F401 (the module's autouse fixture)
+from helpers import diff_stats
 
 pytestmark = pytest.mark.gpu
-EMU = bool(os.environ.get("SWFR_EMULATOR"))
-FILES = ms.files()
-FADE_INSTANCE = "6"                          # SWFR_TILES_SHADERS of the k2_tiles instance that fades
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(gpu):
-    import swf_renderer_amd as S
-    assert os.path.exists(S.library_path()), "libswfr.so must be built: the product has no fallback"
-
-
-def _check(got, want, sc, msg):
-    n, mx = diff_stats(got, want)
-    print("fade", msg, "differing pixels", n, "max", mx)
-    if sc["exact"]:
-        assert (n, mx) == (0, 0), msg
-    else:
-        assert mx <= ms.LINEAR_BOUND, (msg, n, mx)
-
-
-def _renderer(sc, aliased, **kw):
-    r = _handle(sc["width"], sc["height"], aliased, even_odd=bool(sc.get("even_odd")), **kw)
-    for b in sc.get("bitmaps", []):
-        r.add_bitmap(b)
-    return r
-
-
-def _scenes(fname, route):
-    """the file's scenes (under the emulator, where a frame takes seconds, every fourth, the offset moving with the route)"""
-    make, aliased = FILES[fname]
-    items = sorted(make().items())
-    if EMU:
-        items = items[route % 4::4]
-    return items, aliased, np.load(ms.golden_path(fname))
-
-
-def _built_on_a_host_handle(sc, aliased):
-    from swf_renderer_amd import api
-    host = _renderer(sc, aliased, device=api.DEVICE_HOST_ONLY)
-    try:
-        e, p, s = host.build_frame(sc["stage"])
-    finally:
-        host.close()
-    assert not any(st.kind == api.STYLE_BITMAP and st.bitmap >= api.VARIANT_BASE for st in s)
-    return e, p, s
+FAMILY = dr.FAMILIES["fade"]
+FILES = sorted(FAMILY.scenes.files())
 
 
 # ---------------------------------------------------------------------------------------------------------------- a. the goldens
 @pytest.mark.parametrize("forced", [False, True], ids=["picked", "forced"])
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_through_render(fname, forced, monkeypatch):
-    if forced:
-        monkeypatch.setenv("SWFR_TILES_SHADERS", FADE_INSTANCE)
-    else:
-        monkeypatch.delenv("SWFR_TILES_SHADERS", raising=False)
-    items, aliased, gold = _scenes(fname, 4 + forced)
-    if not EMU:
-        assert sorted(n for n, _ in items) == sorted(gold.files)
-    for name, sc in items:
-        r = _renderer(sc, aliased)
-        try:
-            r.render(sc["stage"])
-            _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, forced))
-            _not_refused(r, name)
-        finally:
-            r.close()
+    dr.goldens_through_render(FAMILY, fname, monkeypatch, forced)
 
 
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_through_render_edges(fname):
-    """swfr_build_frame on one handle, swfr_render_edges on another: the fade travels in the END marker's lerp"""
-    items, aliased, gold = _scenes(fname, 0)
-    for name, sc in items:
-        e, p, s = _built_on_a_host_handle(sc, aliased)
-        r = _renderer(sc, aliased)
-        try:
-            r.render_edges(e, p, s)
-            _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, "render_edges"))
-            r.render_resident(3)
-            _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, "resident"))
-            _not_refused(r, name)
-        finally:
-            r.close()
+    dr.goldens_through_render_edges(FAMILY, fname)
 
 
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_with_graphs(fname, monkeypatch):
-    monkeypatch.setenv("SWFR_GRAPHS", "1")
-    items, aliased, gold = _scenes(fname, 1)
-    for name, sc in items:
-        e, p, s = _built_on_a_host_handle(sc, aliased)
-        r = _renderer(sc, aliased)
-        try:
-            r.upload_edges(e, p, s)
-            r.render_resident(3)
-            _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, "graphs"))
-        finally:
-            r.close()
+    dr.goldens_with_graphs(FAMILY, fname, monkeypatch)
 
 
-@pytest.mark.parametrize("contiguous", [True, False], ids=["contiguous", "interleaved"])
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("contiguous", FAMILY.layouts, ids=["contiguous", "interleaved"])
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_through_two_band_handles(fname, contiguous):
-    items, aliased, gold = _scenes(fname, 2)
-    for name, sc in items:
-        h = sc["height"]
-        out = np.zeros_like(gold[name])
-        n = -(-((h + 15) // 16) // 2)                             # tile-rows per handle
-        for rank in range(2):
-            r = _renderer(sc, aliased, band_index=rank, band_count=2, contiguous_bands=contiguous)
-            try:
-                r.render(sc["stage"])
-                img = r.read_image(premultiplied=True)
-            finally:
-                r.close()
-            t = np.arange(h) // 16
-            rows = ((t >= rank * n) & (t < (rank + 1) * n)) if contiguous else (t % 2 == rank)
-            out[rows] = img[rows]
-        _check(out, gold[name], sc, (fname, name, "bands", contiguous))
+    dr.goldens_through_two_band_handles(FAMILY, fname, contiguous)
 
 
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_through_render_batch_with_unlike_frames(fname):
-    """The file's scenes of one frame size as ONE batch, a plain frame (no group, no blended path: no operator table) after every third
-    of them.  Into a device tensor where there is a device for it (every frame checked), and by the per-frame route."""
-    import swf_renderer_amd as S
-    from layer_scenes import _with_ground
-    items, aliased, gold = _scenes(fname, 3)
-    for w, h in sorted({(sc["width"], sc["height"]) for _, sc in items}):
-        group = [(name, sc) for name, sc in items if (sc["width"], sc["height"]) == (w, h)]
-        plain = dict(width=w, height=h, exact=True, stage={"children": _with_ground(dict(width=w, height=h))})
-        plain_want = frame_model.render(*_built_on_a_host_handle(plain, True), w, h, aliased=True) if aliased else oracle_render(plain)
-        frames = []
-        for k, (name, sc) in enumerate(group):
-            frames.append((name, sc, gold[name]))
-            if k % 3 == 0:
-                frames.append(("plain", plain, plain_want))
-        r = S.Renderer(w, h, antialias="none" if aliased else "default")
-        try:
-            seen = set()
-            for _, sc, _ in frames:
-                for b in sc.get("bitmaps", []):
-                    if b["id"] not in seen:
-                        seen.add(b["id"])
-                        r.add_bitmap(b)
-            stages = [sc["stage"] for _, sc, _ in frames]
-            if not EMU:                                           # (device tensors need the GPU)
-                import torch
-                out = torch.zeros((len(stages), h, w, 4), dtype=torch.uint8, device="cuda")
-                r.render_batch(stages, out.data_ptr(), h * w * 4)
-                got = out.cpu().numpy()
-                for k, (name, sc, want) in enumerate(frames):
-                    _check(got[k], want, sc, (fname, name, "batch", k))
-            for cut in sorted({1, 2, len(frames) // 2, len(frames)}):
-                if 0 < cut <= len(frames):
-                    r.render_batch(stages[:cut])
-                    name, sc, want = frames[cut - 1]
-                    _check(r.read_image(premultiplied=True), want, sc, (fname, name, "per-frame route", cut))
-            _not_refused(r, fname)
-        finally:
-            r.close()
+    dr.goldens_through_render_batch_with_unlike_frames(FAMILY, fname)
 
 
 def test_a_fade_is_visible():
@@ -201,7 +68,7 @@ def test_a_fade_is_visible():
     group faded as a whole from the same children under a colour transform with that alpha multiplier"""
     gold = np.load(ms.golden_path("cairo_fade_operators"))
     for name, sc in sorted(ms.operator_scenes().items())[:: 9 if EMU else 1]:
-        r = _renderer(sc, False)
+        r = renderer_for(sc, False)
         try:
             r.render({"children": ms.without_opacity(sc["stage"]["children"])})
             assert (r.read_image(premultiplied=True) != gold[name]).any(), name
@@ -219,7 +86,7 @@ def test_frames_without_a_fade_through_the_instance_that_fades(monkeypatch):
     import mask_scenes
     import scenarios
     from helpers import golden, product_render
-    monkeypatch.setenv("SWFR_TILES_SHADERS", FADE_INSTANCE)
+    monkeypatch.setenv("SWFR_TILES_SHADERS", FAMILY.instance)
     SC = scenarios.scenarios()
     for name in sorted(SC)[:: 9 if EMU else 1]:
         sc = SC[name]
@@ -232,31 +99,31 @@ def test_frames_without_a_fade_through_the_instance_that_fades(monkeypatch):
     for first, depth in cs.NESTINGS[:: 4 if EMU else 1]:
         fr = cs.raw_nesting_frame(first, depth)
         arrays = fr.arrays()
-        _zero(_through_edges(fr.W, fr.H, arrays), frame_model.render(*arrays, fr.W, fr.H), ("layers through the fade instance", first, depth))
+        zero(through_edges(fr.W, fr.H, arrays), frame_model.render(*arrays, fr.W, fr.H), ("layers through the fade instance", first, depth))
     for fname, (make, aliased) in sorted(mask_scenes.files().items()):
         gold = np.load(mask_scenes.golden_path(fname))
         for name, sc in sorted(make().items())[:: 11 if EMU else 1]:
-            r = _renderer(sc, aliased)
+            r = renderer_for(sc, aliased)
             try:
                 r.render(sc["stage"])
-                _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, "masks through the fade instance"))
+                dr.check(FAMILY, r.read_image(premultiplied=True), gold[name], sc, (fname, name, "masks through the fade instance"))
             finally:
                 r.close()
     for op in cs.MODES[:: 4 if EMU else 1]:
         fr = mr.reach_cases_frame(op, seed=cs.MODES.index(op))
         arrays = fr.arrays()
-        _zero(_through_edges(fr.W, fr.H, arrays), mfm.render(*arrays, fr.W, fr.H), ("mask reach through the fade instance", op))
+        zero(through_edges(fr.W, fr.H, arrays), frame_model.render(*arrays, fr.W, fr.H), ("mask reach through the fade instance", op))
     for which in ("four_by_one_path", "outer_survives", "in_content"):
         fr = mr.nested_masks_frame(which)
         arrays = fr.arrays()
-        _zero(_through_edges(fr.W, fr.H, arrays), mfm.render(*arrays, fr.W, fr.H), ("mask nesting through the fade instance", which))
+        zero(through_edges(fr.W, fr.H, arrays), frame_model.render(*arrays, fr.W, fr.H), ("mask nesting through the fade instance", which))
 
 
 # ---------------------------------------------------------------------------------------------------------------- b. raw frames
 def _check_raw(fr, msg, **kw):
     arrays = fr.arrays()
-    want = ffm.render(*arrays, fr.W, fr.H)
-    _zero(_through_edges(fr.W, fr.H, arrays, **kw), want, msg)
+    want = frame_model.render(*arrays, fr.W, fr.H)
+    zero(through_edges(fr.W, fr.H, arrays, **kw), want, msg)
     return arrays, want
 
 
@@ -277,7 +144,7 @@ def test_a_faded_end_where_the_group_reached_and_where_it_did_not(op):
     e, p, s = arrays
     plain = p[np.isin(np.arange(len(p)), [0, 1, len(p) - 1])]
     ground = frame_model.render(e, plain, s, fr.W, fr.H)
-    unfaded = ffm.render(*_without_fades(arrays), fr.W, fr.H)
+    unfaded = frame_model.render(*_without_fades(arrays), fr.W, fr.H)
     assert (want[:8, 64:128] == ground[:8, 64:128]).all() and (want[:8, 192:] == ground[:8, 192:]).all() and (want[8:, :192] == ground[8:, :192]).all()
     assert (want[:8, :64] != ground[:8, :64]).any() and (want[:8, :64] != unfaded[:8, :64]).any() and (want[8:, 192:] != unfaded[8:, 192:]).any()
 
@@ -330,7 +197,7 @@ def test_nesting(which):
         assert rc["together"] == 4, rc["together"]                   # four faded groups set aside by one path
     else:
         assert rc["after_dropped"]                                   # the faded END right behind a mask step that dropped its product
-    assert (want != ffm.render(*_without_fades(arrays), fr.W, fr.H)).any()
+    assert (want != frame_model.render(*_without_fades(arrays), fr.W, fr.H)).any()
 
 
 @pytest.mark.parametrize("opacity", [0, 1, 254, 255])
@@ -358,7 +225,7 @@ def test_random_nesting_across_tile_rows_and_band_boundaries():
         fades += int(((arrays[1]["lerp"].astype(np.int64) & 0xffffffff) >> 24 != 0).sum())
         if seed % 4 == 0:
             for contiguous in (True, False):
-                _zero(_two_bands(W, H, contiguous, lambda r: r.render_edges(*arrays)), want, ("random raw bands", seed, contiguous))
+                zero(two_bands(W, H, contiguous, lambda r: r.render_edges(*arrays)), want, ("random raw bands", seed, contiguous))
     assert (cases == {True, False} and fades > 40) or EMU
 
 

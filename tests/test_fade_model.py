@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 
 import blend_model as bm
+from cairo_pixels import random_premultiplied, surface_bytes
 import fade_model as fd
 import layer_model as lm
 from oracle import cairo_backend as cb
-from test_blend_model import _random_premultiplied, _surface_bytes
 
 needs_cairo = pytest.mark.skipif(not cb.available(), reason="libcairo not installed")
 N = 1024                                   # pixels (= random pairs) per operator, destination kind and opacity
@@ -36,7 +36,7 @@ def _fade(dst, group, operator, opacity, n, probe=None):
     try:
         be.clear_all()
         if dst is not None:
-            _surface_bytes(be)[0] = dst[:, [2, 1, 0, 3]]
+            surface_bytes(be)[0] = dst[:, [2, 1, 0, 3]]
             lib.cairo_surface_mark_dirty(be.surf)
         lib.cairo_push_group(cr)
         if group is not None:
@@ -65,8 +65,8 @@ def _fade(dst, group, operator, opacity, n, probe=None):
 
 
 def _group(rng, n):
-    group = _random_premultiplied(rng, n, "translucent")
-    group[n // 2: n // 2 + n // 16] = _random_premultiplied(rng, n // 16, "opaque")
+    group = random_premultiplied(rng, n, "translucent")
+    group[n // 2: n // 2 + n // 16] = random_premultiplied(rng, n // 16, "opaque")
     group[-n // 16:] = 0
     return group
 
@@ -78,7 +78,7 @@ def test_model_is_libcairo_at_every_opacity(mode, ground):
     rng = np.random.default_rng(sorted(fd.MODES).index(mode) * 11 + 41)
     group = np.stack([_group(rng, N) for _ in range(4)])                     # (the rows of pairs take turns over the opacities)
     # ("clear_pixels": transparent pixels of a surface that has been drawn on; "still_clear": Cairo's still-clear surface)
-    dst = None if ground == "still_clear" else np.stack([_random_premultiplied(rng, N, "clear" if ground == "clear_pixels" else ground) for _ in range(4)])
+    dst = None if ground == "still_clear" else np.stack([random_premultiplied(rng, N, "clear" if ground == "clear_pixels" else ground) for _ in range(4)])
     d = np.zeros((4, N, 4), np.uint8) if dst is None else dst
     rows = np.arange(256) % 4
     got = np.stack([_fade(None if dst is None else dst[k % 4], group[k % 4], bm.CAIRO_OPERATORS[mode], k, N) for k in range(256)])
@@ -95,7 +95,7 @@ def test_opacity_255_is_the_plain_layer_and_0_is_nothing():
     rng = np.random.default_rng(9)
     group = _group(rng, 20000)
     for kind in ("translucent", "opaque", "clear"):
-        d = _random_premultiplied(rng, 20000, kind)
+        d = random_premultiplied(rng, 20000, kind)
         for mode in fd.MODES:
             assert (fd.composite(mode, group, 255, d) == lm.composite(mode, group, d)).all(), (mode, kind)
             assert (fd.composite(mode, group, 0, d) == d).all(), (mode, kind)
@@ -118,7 +118,7 @@ def test_clear_surface_bookkeeping_is_libcairos(mode):
     zero = np.zeros((n, 4), np.uint8)
     probe = (97, 184, 252, 38)             # (0x7f and 0x80 rounding differ at one coverage value per channel value at most: this colour has one)
     lerp = _fade(None, None, CAIRO_OPERATOR_OVER, 255, n, probe)[1]           # nothing at all happened to the parent
-    over = _fade(_random_premultiplied(np.random.default_rng(1), n, "clear"), None, CAIRO_OPERATOR_OVER, 255, n, probe)[1]   # a drawn-on parent
+    over = _fade(random_premultiplied(np.random.default_rng(1), n, "clear"), None, CAIRO_OPERATOR_OVER, 255, n, probe)[1]   # a drawn-on parent
     assert (lerp != over).any()                              # (the probe tells the two states apart)
     for group_clear in (True, False):
         for opacity in (0, 1, 128, 254, 255):
@@ -129,6 +129,6 @@ def test_clear_surface_bookkeeping_is_libcairos(mode):
             if opacity == 255:
                 assert stays == lm.parent_stays_clear(mode, group_clear)
     # a parent that was drawn on stays drawn on, at opacity 0, too
-    d = _random_premultiplied(np.random.default_rng(2), n, "clear")
+    d = random_premultiplied(np.random.default_rng(2), n, "clear")
     for opacity in (0, 128):
         assert (_fade(d, None, bm.CAIRO_OPERATORS[mode], opacity, n, probe)[1] == over).all()

@@ -15,6 +15,7 @@ import helpers
 import layer_model as lm
 import layer_scenes as ls
 from helpers import diff_stats, oracle_render
+from host_frames import build_on_host
 from oracle import cairo_backend as cb
 
 needs_cairo = pytest.mark.skipif(not cb.available(), reason="libcairo not installed")
@@ -25,20 +26,8 @@ ALL_SOLID = (["cairo_layer_overlap", "cairo_layer_aliased_overlap", "cairo_blend
 GOLDEN_SCENES = 636                                     # counted: the scenes of tests/layer_scenes.py and tests/blend_scenes.py whose built styles are all solid
 
 
-def _build(sc, aliased=False):
-    import swf_renderer_amd as S
-    from swf_renderer_amd import api
-    r = S.Renderer(sc["width"], sc["height"], device=api.DEVICE_HOST_ONLY, even_odd=bool(sc.get("even_odd")), antialias="none" if aliased else "default")
-    try:
-        for b in sc.get("bitmaps", []):
-            r.add_bitmap(b)
-        return r.build_frame(sc["stage"])
-    finally:
-        r.close()
-
-
 def _model(sc, aliased=False):
-    return fm.render(*_build(sc, aliased), sc["width"], sc["height"], aliased=aliased)
+    return fm.render(*build_on_host(sc, aliased), sc["width"], sc["height"], aliased=aliased)
 
 
 def test_goldens_through_the_model():
@@ -48,7 +37,7 @@ def test_goldens_through_the_model():
         for fname, (make, aliased) in sorted(mod.files().items()):
             gold = np.load(mod.golden_path(fname))
             for name, sc in sorted(make().items()):
-                arrays = _build(sc, aliased)
+                arrays = build_on_host(sc, aliased)
                 if any(int(st.kind) != api.STYLE_SOLID for st in arrays[2]):
                     with pytest.raises(NotImplementedError):
                         fm.render(*arrays, sc["width"], sc["height"], aliased=aliased)
@@ -91,7 +80,7 @@ def test_random_composited_trees_equal_libcairo(aliased, seeds):
     differing = groups = deepest = 0
     for seed in range(seeds):
         sc = cs.rand_composited_scene(np.random.default_rng(1000 + seed + 10000 * aliased))
-        arrays = _build(sc, aliased)
+        arrays = build_on_host(sc, aliased)
         depth = 0
         for k in arrays[1]["kind"].tolist():
             depth += (k == cs.BEGIN) - (k == cs.END)
@@ -115,7 +104,7 @@ def test_threaded_build_is_the_single_walk_and_equals_libcairo(aliased):
         for threads in ("1", "2", "3", "8"):
             os.environ["SWFR_BUILD_THREADS"] = threads
             try:
-                built.append(_build(sc, aliased))
+                built.append(build_on_host(sc, aliased))
             finally:
                 del os.environ["SWFR_BUILD_THREADS"]
         for other in built[1:]:

@@ -8,29 +8,13 @@ import pytest
 
 import blend_model as bm
 import blend_scenes as bs
+import host_frames as hf
 import layer_model as lm
 import layer_scenes as ls
 import scenarios
 from scenarios import _rgba
-from test_blend_host import _build_raw, _host, _raw_stage
 
 BEGIN, END = lm.PATH_GROUP_BEGIN, lm.PATH_GROUP_END
-
-
-def _tri(colour, dx=0.0, **kw):
-    return bs._shape([(2 + dx, 2), (40 + dx, 5), (20 + dx, 44)], colour, **kw)
-
-
-def _lerps(p):
-    return [int(v) for v in p["lerp"]]
-
-
-def _kinds(p):
-    return [int(v) for v in p["kind"]]
-
-
-def _rects(p):
-    return [tuple(int(p[k][i]) for k in ("x_min", "y_min", "x_max", "y_max")) for i in range(len(p))]
 
 
 def test_object_type_and_mode_numbers():
@@ -39,22 +23,22 @@ def test_object_type_and_mode_numbers():
     assert (api.PATH_GROUP_BEGIN, api.PATH_GROUP_END) == (BEGIN, END)
     assert api.layer_mode_number(True) == 1 and api.layer_mode_number("layer") == 2 and api.layer_mode_number("Multiply") == 3
     assert api.layer_mode_number(14) == 14
-    r = _host()
+    r = hf.host()
     try:
         sid = r.register_shape(scenarios._poly_shape([(0, 0), (200, 0), (200, 200)], {"type": "solid", "color": _rgba(9, 9, 9, 100)}))
         for mode in (0, 1, 2, 3, 4, 5, 6, 7, 8, 13, 14):
-            rc, _, n_paths = _build_raw(r, _raw_stage(api.OBJECT_LAYER, mode, sid)[0])
+            rc, _, n_paths = hf.build_raw(r, hf.raw_stage(api.OBJECT_LAYER, mode, sid)[0])
             assert rc == api.OK and n_paths == 3, mode               # BEGIN, the triangle, END
         for mode in (9, 10, 11, 12):
-            rc, err, _ = _build_raw(r, _raw_stage(api.OBJECT_LAYER, mode, sid)[0])
+            rc, err, _ = hf.build_raw(r, hf.raw_stage(api.OBJECT_LAYER, mode, sid)[0])
             assert (rc, err) == (api.ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode"), mode
         for mode in (15, 16, 255, 0xffffffff):
-            rc, _, _ = _build_raw(r, _raw_stage(api.OBJECT_LAYER, mode, sid)[0])
+            rc, _, _ = hf.build_raw(r, hf.raw_stage(api.OBJECT_LAYER, mode, sid)[0])
             assert rc == api.ERR_INVALID, mode
         for t in (4, 6, 7, 9, 10):                                   # not display-object types
-            rc, err, _ = _build_raw(r, _raw_stage(t, 3, sid)[0])
+            rc, err, _ = hf.build_raw(r, hf.raw_stage(t, 3, sid)[0])
             assert (rc, err) == (api.ERR_INVALID, "UnexpectedDisplayObjectType"), t
-        rc, err, _ = _build_raw(r, _raw_stage(api.OBJECT_BLEND_MODE, 2, sid)[0])      # "layer" stays refused as a per-path blend mode
+        rc, err, _ = hf.build_raw(r, hf.raw_stage(api.OBJECT_BLEND_MODE, 2, sid)[0])      # "layer" stays refused as a per-path blend mode
         assert (rc, err) == (api.ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode")
     finally:
         r.close()
@@ -64,18 +48,18 @@ def test_layer_key_lowers_to_a_type_8_wrapper_outside_the_others():
     """"layer" on a container, a shape and a morph shape; with "blend_mode" on the same object the paths carry the blend operator and
     the END marker the layer's"""
     SC = scenarios.scenarios()
-    r = _host(100, 100)
+    r = hf.host(100, 100)
     try:
         for layer, op in ((True, 0), ("normal", 0), ("layer", 0), (2, 0), ("screen", bm.OPERATORS["screen"]), (13, bm.OPERATORS["overlay"])):
-            _, p, _ = r.build_frame({"children": [_tri((9, 9, 9, 200), layer=layer)]})
-            assert _kinds(p) == [BEGIN, 0, END] and _lerps(p) == [0, 1, op << 8], layer
-        _, p, _ = r.build_frame({"children": [_tri((1, 1, 1, 255)), {"type": "container", "layer": "add", "blend_mode": "multiply", "children": [
-            _tri((9, 9, 9, 200)), _tri((9, 90, 9, 200), 7)]}]})
+            _, p, _ = r.build_frame({"children": [hf.tri((9, 9, 9, 200), layer=layer)]})
+            assert hf.kinds(p) == [BEGIN, 0, END] and hf.lerps(p) == [0, 1, op << 8], layer
+        _, p, _ = r.build_frame({"children": [hf.tri((1, 1, 1, 255)), {"type": "container", "layer": "add", "blend_mode": "multiply", "children": [
+            hf.tri((9, 9, 9, 200)), hf.tri((9, 90, 9, 200), 7)]}]})
         mul = bm.OPERATORS["multiply"] << 8
-        assert _kinds(p) == [0, BEGIN, 0, 0, END] and _lerps(p) == [1, 0, mul, mul, bm.OPERATORS["add"] << 8]
+        assert hf.kinds(p) == [0, BEGIN, 0, 0, END] and hf.lerps(p) == [1, 0, mul, mul, bm.OPERATORS["add"] << 8]
         morph = SC["morph_round_stroke_090"]["stage"]["children"][0]
         _, p, _ = r.build_frame({"children": [dict(morph, layer="darken")]})
-        assert _kinds(p)[0] == BEGIN and _kinds(p)[-1] == END and len(p) > 3 and _lerps(p)[-1] == bm.OPERATORS["darken"] << 8
+        assert hf.kinds(p)[0] == BEGIN and hf.kinds(p)[-1] == END and len(p) > 3 and hf.lerps(p)[-1] == bm.OPERATORS["darken"] << 8
         assert r.build_frame({"children": [dict(morph, layer=False)]})[1].tobytes() == r.build_frame({"children": [morph]})[1].tobytes()
     finally:
         r.close()
@@ -83,15 +67,15 @@ def test_layer_key_lowers_to_a_type_8_wrapper_outside_the_others():
 
 def test_depth_limit():
     from swf_renderer_amd import api
-    r = _host()
+    r = hf.host()
     try:
         def nest(n):
-            obj = _tri((9, 9, 9, 200))
+            obj = hf.tri((9, 9, 9, 200))
             for k in range(n):
-                obj = {"type": "container", "layer": ls.MODES[k % 9], "children": [_tri((k, 9, 9, 100), k), obj]}
+                obj = {"type": "container", "layer": ls.MODES[k % 9], "children": [hf.tri((k, 9, 9, 100), k), obj]}
             return {"children": [obj]}
         _, p, _ = r.build_frame(nest(4))
-        assert _kinds(p) == [BEGIN, 0, BEGIN, 0, BEGIN, 0, BEGIN, 0, 0, END, END, END, END]
+        assert hf.kinds(p) == [BEGIN, 0, BEGIN, 0, BEGIN, 0, BEGIN, 0, 0, END, END, END, END]
         with pytest.raises(api.SwfrError) as ei:
             r.build_frame(nest(5))
         assert ei.value.code == api.ERR_CAPACITY and "LayerDepth" in str(ei.value)
@@ -109,20 +93,20 @@ def test_depth_limit():
 
 
 def test_marker_rectangles_and_balance():
-    r = _host(64, 48)
+    r = hf.host(64, 48)
     try:
-        _, p, _ = r.build_frame({"children": [_tri((1, 2, 3, 255)), ls._layer("multiply", [
+        _, p, _ = r.build_frame({"children": [hf.tri((1, 2, 3, 255)), ls._layer("multiply", [
             bs._rect(10, 12, 20, 30, (9, 9, 9, 100)), ls._layer("add", [bs._rect(40.5, 3.25, 70, 20, (9, 9, 9, 100)), bs._rect(90, 3, 99, 9, (1, 1, 1, 9))]),
             bs._rect(5, 40, 12, 60, (9, 9, 9, 100))])]})
-        assert _kinds(p) == [0, BEGIN, 1, BEGIN, 1, END, 1, END]
-        rects = _rects(p)
+        assert hf.kinds(p) == [0, BEGIN, 1, BEGIN, 1, END, 1, END]
+        rects = hf.rects(p)
         assert rects[1] == rects[7] == (5, 3, 64, 48)                # the union of its members, clipped to the frame
         assert rects[3] == rects[5] == rects[4] == (40, 3, 64, 20)   # (the member off the frame left no path)
         assert all(int(p["n_edges"][i]) == 0 for i in (1, 3, 5, 7))
-        assert _lerps(p) == [1, 0, 1, 0, 1, bm.OPERATORS["add"] << 8, 0, bm.OPERATORS["multiply"] << 8]
+        assert hf.lerps(p) == [1, 0, 1, 0, 1, bm.OPERATORS["add"] << 8, 0, bm.OPERATORS["multiply"] << 8]
         # a group without surviving paths emits nothing
         _, p, _ = r.build_frame({"children": [ls._layer("screen", []), ls._layer("screen", [bs._rect(90, 3, 99, 9, (1, 1, 1, 9))]),
-                                              ls._layer("normal", [_tri((255, 255, 255, 0))])]})
+                                              ls._layer("normal", [hf.tri((255, 255, 255, 0))])]})
         assert len(p) == 0
     finally:
         r.close()
@@ -131,19 +115,19 @@ def test_marker_rectangles_and_balance():
 def test_lerp_of_the_first_and_later_paths_inside_a_group():
     """inside a group the surface is the group's: its first paint is a SOURCE lerp whatever lies below in the parent, later ones OVER,
     an opaque solid a lerp; ADD on the still-clear group surface is SOURCE; the other operators are never a lerp"""
-    r = _host()
+    r = hf.host()
     try:
-        ground = _tri((1, 2, 3, 255))
-        _, p, _ = r.build_frame({"children": [ground, ls._layer("normal", [_tri((9, 9, 9, 100)), _tri((9, 9, 9, 100), 3), _tri((9, 9, 9, 255), 5)])]})
-        assert _lerps(p) == [1, 0, 1, 0, 1, 0]
+        ground = hf.tri((1, 2, 3, 255))
+        _, p, _ = r.build_frame({"children": [ground, ls._layer("normal", [hf.tri((9, 9, 9, 100)), hf.tri((9, 9, 9, 100), 3), hf.tri((9, 9, 9, 255), 5)])]})
+        assert hf.lerps(p) == [1, 0, 1, 0, 1, 0]
         add, mul = bm.OPERATORS["add"] << 8, bm.OPERATORS["multiply"] << 8
-        _, p, _ = r.build_frame({"children": [ground, ls._layer("screen", [_tri((9, 9, 9, 100), blend_mode="add"), _tri((9, 9, 9, 255), 3, blend_mode="add")])]})
-        assert _lerps(p) == [1, 0, 1, add, bm.OPERATORS["screen"] << 8]
-        _, p, _ = r.build_frame({"children": [ground, ls._layer("screen", [_tri((9, 9, 9, 255), blend_mode="multiply"), _tri((9, 9, 9, 100), 3)])]})
-        assert _lerps(p) == [1, 0, mul, 0, bm.OPERATORS["screen"] << 8]
+        _, p, _ = r.build_frame({"children": [ground, ls._layer("screen", [hf.tri((9, 9, 9, 100), blend_mode="add"), hf.tri((9, 9, 9, 255), 3, blend_mode="add")])]})
+        assert hf.lerps(p) == [1, 0, 1, add, bm.OPERATORS["screen"] << 8]
+        _, p, _ = r.build_frame({"children": [ground, ls._layer("screen", [hf.tri((9, 9, 9, 255), blend_mode="multiply"), hf.tri((9, 9, 9, 100), 3)])]})
+        assert hf.lerps(p) == [1, 0, mul, 0, bm.OPERATORS["screen"] << 8]
         # a nested group starts clear again
-        _, p, _ = r.build_frame({"children": [ls._layer("normal", [_tri((9, 9, 9, 100)), ls._layer("normal", [_tri((9, 9, 9, 100), 3)]), _tri((9, 9, 9, 100), 5)])]})
-        assert _lerps(p) == [0, 1, 0, 1, 0, 0, 0]
+        _, p, _ = r.build_frame({"children": [ls._layer("normal", [hf.tri((9, 9, 9, 100)), ls._layer("normal", [hf.tri((9, 9, 9, 100), 3)]), hf.tri((9, 9, 9, 100), 5)])]})
+        assert hf.lerps(p) == [0, 1, 0, 1, 0, 0, 0]
     finally:
         r.close()
 
@@ -151,22 +135,22 @@ def test_lerp_of_the_first_and_later_paths_inside_a_group():
 @pytest.mark.parametrize("mode", ls.MODES)
 def test_parents_clear_state_after_each_kind_of_group(mode):
     """the lerp of a translucent path behind the group says what the group left of the parent's "still clear" state"""
-    r = _host()
+    r = hf.host()
     try:
-        after = _tri((200, 100, 50, 119), 9)
-        clear_fill = _tri((255, 255, 255, 0))
+        after = hf.tri((200, 100, 50, 119), 9)
+        clear_fill = hf.tri((255, 255, 255, 0))
 
         def following(group_kids):
             _, p, _ = r.build_frame({"children": [ls._layer(mode, group_kids), after]})
-            return _lerps(p)[-1]
+            return hf.lerps(p)[-1]
         for kids, still_clear in (([], True), ([bs._rect(90, 3, 99, 9, (1, 1, 1, 9))], True), ([clear_fill], True),
                                   ([dict(clear_fill, blend_mode="add")], True), ([dict(clear_fill, blend_mode="multiply")], False),
                                   ([ls._layer("normal", [])], True), ([ls._layer("screen", [])], False)):
             assert following(kids) == (1 if lm.parent_stays_clear(mode, still_clear) else 0), (mode, kids)
-        assert following([_tri((9, 9, 9, 100))]) == 0                # a group that painted
+        assert following([hf.tri((9, 9, 9, 100))]) == 0                # a group that painted
         # a parent that was drawn on stays drawn on
-        _, p, _ = r.build_frame({"children": [_tri((1, 1, 1, 9)), ls._layer(mode, []), after]})
-        assert _lerps(p) == [1, 0]
+        _, p, _ = r.build_frame({"children": [hf.tri((1, 1, 1, 9)), ls._layer(mode, []), after]})
+        assert hf.lerps(p) == [1, 0]
     finally:
         r.close()
 
@@ -194,13 +178,13 @@ def test_threaded_build_is_the_single_walk():
     for threads in ("1", "8"):
         os.environ["SWFR_BUILD_THREADS"] = threads
         try:
-            r = _host()
+            r = hf.host()
             out.append(r.build_frame(stage))
             r.close()
         finally:
             del os.environ["SWFR_BUILD_THREADS"]
     assert out[0][0].tobytes() == out[1][0].tobytes() and out[0][1].tobytes() == out[1][1].tobytes()
-    kinds, lerps = _kinds(out[0][1]), _lerps(out[0][1])
+    kinds, lerps = hf.kinds(out[0][1]), hf.lerps(out[0][1])
     assert kinds.count(BEGIN) == kinds.count(END) == 80
     assert kinds[0] == BEGIN and lerps[1] == 1                       # the empty ADD layer left the frame clear; the first group's first paint
     depth = 0
@@ -213,11 +197,11 @@ def test_threaded_build_is_the_single_walk():
 
 def test_upload_validates_the_markers():
     from swf_renderer_amd import api
-    r = _host()
+    r = hf.host()
     try:
-        e, p, s = r.build_frame({"children": [_tri((1, 2, 3, 255)), ls._layer("multiply", [
-            _tri((9, 9, 9, 100)), ls._layer("add", [_tri((9, 9, 9, 100), 3)]), _tri((9, 9, 9, 100), 5)])]})
-        assert _kinds(p) == [0, BEGIN, 0, BEGIN, 0, END, 0, END]
+        e, p, s = r.build_frame({"children": [hf.tri((1, 2, 3, 255)), ls._layer("multiply", [
+            hf.tri((9, 9, 9, 100)), ls._layer("add", [hf.tri((9, 9, 9, 100), 3)]), hf.tri((9, 9, 9, 100), 5)])]})
+        assert hf.kinds(p) == [0, BEGIN, 0, BEGIN, 0, END, 0, END]
 
         def refused(edit, code=api.ERR_INVALID):
             q = p.copy()

@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 
 import blend_model as bm
+from cairo_pixels import random_premultiplied, surface_bytes
 import layer_model as lm
 from oracle import cairo_backend as cb
-from test_blend_model import _random_premultiplied, _surface_bytes
 
 needs_cairo = pytest.mark.skipif(not cb.available(), reason="libcairo not installed")
 N = 4096                                   # pixels (= random pairs) per operator and destination kind
@@ -27,7 +27,7 @@ def _composite(dst, group, operator):
     try:
         be.clear_all()
         if dst is not None:
-            _surface_bytes(be)[0] = dst[:, [2, 1, 0, 3]]
+            surface_bytes(be)[0] = dst[:, [2, 1, 0, 3]]
             lib.cairo_surface_mark_dirty(be.surf)
         lib.cairo_push_group(cr)
         target = lib.cairo_get_group_target(cr)
@@ -50,11 +50,11 @@ def _composite(dst, group, operator):
 @pytest.mark.parametrize("ground", ["opaque", "translucent", "clear_pixels", "still_clear"])
 def test_model_is_libcairo(mode, ground):
     rng = np.random.default_rng(sorted(lm.MODES).index(mode) * 5 + 17)
-    group = _random_premultiplied(rng, N, "translucent")
-    group[N // 2: N // 2 + N // 16] = _random_premultiplied(rng, N // 16, "opaque")
+    group = random_premultiplied(rng, N, "translucent")
+    group[N // 2: N // 2 + N // 16] = random_premultiplied(rng, N // 16, "opaque")
     group[-N // 16:] = 0
     # ("clear_pixels": transparent pixels of a surface that has been drawn on; "still_clear": Cairo's still-clear surface)
-    dst = None if ground == "still_clear" else _random_premultiplied(rng, N, "clear" if ground == "clear_pixels" else ground)
+    dst = None if ground == "still_clear" else random_premultiplied(rng, N, "clear" if ground == "clear_pixels" else ground)
     got = _composite(dst, group, bm.CAIRO_OPERATORS[mode])
     d = np.zeros((N, 4), np.uint8) if dst is None else dst
     want = lm.composite(mode, group, d)
@@ -68,7 +68,7 @@ def test_model_is_libcairo(mode, ground):
 def test_a_transparent_group_pixel_changes_nothing():
     rng = np.random.default_rng(3)
     for kind in ("translucent", "opaque", "clear"):
-        d = _random_premultiplied(rng, 20000, kind)
+        d = random_premultiplied(rng, 20000, kind)
         for mode in lm.MODES:
             assert (lm.composite(mode, np.zeros_like(d), d) == d).all(), (mode, kind)
 
@@ -94,7 +94,7 @@ def test_committed_goldens_are_what_libcairo_renders():
 @needs_cairo
 def test_bookkeeping_scenes_discriminate():
     """every clear-state scene follows layer_model.parent_stays_clear and differs from the other rule in at least one pixel; a single
-    path in an OVER layer differs from the plain path (tools/make_layer_goldens.py checks the same before it writes)"""
+    path in an OVER layer differs from the plain path (tools/make_composite_goldens.py checks the same before it writes)"""
     import layer_scenes as ls
     scenes = ls.structure_scenes()
     wrong = ls.wrong_rule_scenes()

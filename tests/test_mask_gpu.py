@@ -4,7 +4,7 @@ a. Every libcairo golden of tests/mask_scenes.py -- every file, every scene -- t
    SWFR_GRAPHS=1, two-band handles (contiguous and interleaved) and render_batch with masked and plain frames in one group; and with
    SWFR_TILES_SHADERS forced to 5; frames WITHOUT a mask -- the scenario corpus, layer goldens, raw layer frames -- forced through
    instance 5.  Zero differing bytes (linear-gradient scenes: LINEAR_BOUND of tests/test_layer_gpu.py).
-b. Raw frames of 70 x 13 up to 256 x 64 (tests/mask_raw.py) against tests/mask_frame_model.py, zero differing bytes: the four reach
+b. Raw frames of 70 x 13 up to 256 x 64 (tests/mask_raw.py) against tests/frame_model.py, zero differing bytes: the four reach
    cases of a strip under all nine operators; MASK and the masked END as the last entry before and the first behind list positions
    16, 64 and 128; halves of 15 .. 65 members; masked inside masked with four levels set aside by one path; a masked group whose
    content never reaches a strip in which an outer group's pixels are set aside; random nesting over several tile rows, through
@@ -14,189 +14,58 @@ b. Raw frames of 70 x 13 up to 256 x 64 (tests/mask_raw.py) against tests/mask_f
 Runs on an MI355X (-m gpu) and, with smaller counts, under tools/emu/run.py.  DESIGN.md, section 5 ("The mask model"), has the table of
 kernel mutations this file catches.
 """
-import os
-
 import numpy as np
 import pytest
 
 import composite_scenes as cs
+import device_routes as dr
 import frame_model
-import mask_frame_model as mfm
 import mask_raw as mr
 import mask_scenes as ms
 from composite_scenes import CHUNK, PREFETCH, ROUND
-from helpers import diff_stats, oracle_render
-from test_composite_fuzz_gpu import _handle, _not_refused, _through_edges, _two_bands, _zero
+from device_routes import EMU, renderer_for, through_edges, two_bands, zero
+from device_routes import need_gpu  # noqa: F401 (the module's autouse fixture)
+from helpers import diff_stats
 
 pytestmark = pytest.mark.gpu
-EMU = bool(os.environ.get("SWFR_EMULATOR"))
-FILES = ms.files()
 MASK, END = mr.MASK, cs.END
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(gpu):
-    import swf_renderer_amd as S
-    assert os.path.exists(S.library_path()), "libswfr.so must be built: the product has no fallback"
-
-
-def _check(got, want, sc, msg):
-    n, mx = diff_stats(got, want)
-    print("mask", msg, "differing pixels", n, "max", mx)
-    if sc["exact"]:
-        assert (n, mx) == (0, 0), msg
-    else:
-        assert mx <= ms.LINEAR_BOUND, (msg, n, mx)
-
-
-def _renderer(sc, aliased, **kw):
-    r = _handle(sc["width"], sc["height"], aliased, even_odd=bool(sc.get("even_odd")), **kw)
-    for b in sc.get("bitmaps", []):
-        r.add_bitmap(b)
-    return r
-
-
-def _scenes(fname, route):
-    """the file's scenes (under the emulator, where a frame takes seconds, every fourth, the offset moving with the route)"""
-    make, aliased = FILES[fname]
-    items = sorted(make().items())
-    if EMU:
-        items = items[route % 4::4]
-    return items, aliased, np.load(ms.golden_path(fname))
-
-
-def _built_on_a_host_handle(sc, aliased):
-    from swf_renderer_amd import api
-    host = _renderer(sc, aliased, device=api.DEVICE_HOST_ONLY)
-    try:
-        e, p, s = host.build_frame(sc["stage"])
-    finally:
-        host.close()
-    assert not any(st.kind == api.STYLE_BITMAP and st.bitmap >= api.VARIANT_BASE for st in s)
-    return e, p, s
+FAMILY = dr.FAMILIES["mask"]
+FILES = sorted(FAMILY.scenes.files())
 
 
 # ---------------------------------------------------------------------------------------------------------------- a. the goldens
 @pytest.mark.parametrize("forced", [False, True], ids=["picked", "forced_5"])
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_through_render(fname, forced, monkeypatch):
-    if forced:
-        monkeypatch.setenv("SWFR_TILES_SHADERS", "5")
-    else:
-        monkeypatch.delenv("SWFR_TILES_SHADERS", raising=False)
-    items, aliased, gold = _scenes(fname, 4 + forced)
-    if not EMU:
-        assert sorted(n for n, _ in items) == sorted(gold.files)
-    for name, sc in items:
-        r = _renderer(sc, aliased)
-        try:
-            r.render(sc["stage"])
-            _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, forced))
-            _not_refused(r, name)
-        finally:
-            r.close()
+    dr.goldens_through_render(FAMILY, fname, monkeypatch, forced)
 
 
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_through_render_edges(fname):
-    """swfr_build_frame on one handle, swfr_render_edges on another: the masked groups travel as marker paths"""
-    items, aliased, gold = _scenes(fname, 0)
-    for name, sc in items:
-        e, p, s = _built_on_a_host_handle(sc, aliased)
-        r = _renderer(sc, aliased)
-        try:
-            r.render_edges(e, p, s)
-            _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, "render_edges"))
-            r.render_resident(3)
-            _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, "resident"))
-            _not_refused(r, name)
-        finally:
-            r.close()
+    dr.goldens_through_render_edges(FAMILY, fname)
 
 
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_with_graphs(fname, monkeypatch):
-    monkeypatch.setenv("SWFR_GRAPHS", "1")
-    items, aliased, gold = _scenes(fname, 1)
-    for name, sc in items:
-        e, p, s = _built_on_a_host_handle(sc, aliased)
-        r = _renderer(sc, aliased)
-        try:
-            r.upload_edges(e, p, s)
-            r.render_resident(3)
-            _check(r.read_image(premultiplied=True), gold[name], sc, (fname, name, "graphs"))
-        finally:
-            r.close()
+    dr.goldens_with_graphs(FAMILY, fname, monkeypatch)
 
 
-@pytest.mark.parametrize("contiguous", [True, False], ids=["contiguous", "interleaved"])
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("contiguous", FAMILY.layouts, ids=["contiguous", "interleaved"])
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_through_two_band_handles(fname, contiguous):
-    items, aliased, gold = _scenes(fname, 2)
-    for name, sc in items:
-        h = sc["height"]
-        out = np.zeros_like(gold[name])
-        n = -(-((h + 15) // 16) // 2)                             # tile-rows per handle
-        for rank in range(2):
-            r = _renderer(sc, aliased, band_index=rank, band_count=2, contiguous_bands=contiguous)
-            try:
-                r.render(sc["stage"])
-                img = r.read_image(premultiplied=True)
-            finally:
-                r.close()
-            t = np.arange(h) // 16
-            rows = ((t >= rank * n) & (t < (rank + 1) * n)) if contiguous else (t % 2 == rank)
-            out[rows] = img[rows]
-        _check(out, gold[name], sc, (fname, name, "bands", contiguous))
+    dr.goldens_through_two_band_handles(FAMILY, fname, contiguous)
 
 
-@pytest.mark.parametrize("fname", sorted(FILES))
+@pytest.mark.parametrize("fname", FILES)
 def test_goldens_through_render_batch_with_unlike_frames(fname):
-    """The file's scenes of one frame size as ONE batch, a plain frame (no group, no blended path: no operator table) after every third
-    of them.  Into a device tensor where there is a device for it (every frame checked), and by the per-frame route."""
-    import swf_renderer_amd as S
-    from layer_scenes import _with_ground
-    items, aliased, gold = _scenes(fname, 3)
-    for w, h in sorted({(sc["width"], sc["height"]) for _, sc in items}):
-        group = [(name, sc) for name, sc in items if (sc["width"], sc["height"]) == (w, h)]
-        plain = dict(width=w, height=h, exact=True, stage={"children": _with_ground(dict(width=w, height=h))})
-        plain_want = frame_model.render(*_built_on_a_host_handle(plain, True), w, h, aliased=True) if aliased else oracle_render(plain)
-        frames = []
-        for k, (name, sc) in enumerate(group):
-            frames.append((name, sc, gold[name]))
-            if k % 3 == 0:
-                frames.append(("plain", plain, plain_want))
-        r = S.Renderer(w, h, antialias="none" if aliased else "default")
-        try:
-            seen = set()
-            for _, sc, _ in frames:
-                for b in sc.get("bitmaps", []):
-                    if b["id"] not in seen:
-                        seen.add(b["id"])
-                        r.add_bitmap(b)
-            stages = [sc["stage"] for _, sc, _ in frames]
-            if not EMU:                                           # (device tensors need the GPU)
-                import torch
-                out = torch.zeros((len(stages), h, w, 4), dtype=torch.uint8, device="cuda")
-                r.render_batch(stages, out.data_ptr(), h * w * 4)
-                got = out.cpu().numpy()
-                for k, (name, sc, want) in enumerate(frames):
-                    _check(got[k], want, sc, (fname, name, "batch", k))
-            for cut in sorted({1, 2, len(frames) // 2, len(frames)}):
-                if 0 < cut <= len(frames):
-                    r.render_batch(stages[:cut])
-                    name, sc, want = frames[cut - 1]
-                    _check(r.read_image(premultiplied=True), want, sc, (fname, name, "per-frame route", cut))
-            _not_refused(r, fname)
-        finally:
-            r.close()
+    dr.goldens_through_render_batch_with_unlike_frames(FAMILY, fname)
 
 
 def test_a_mask_is_visible():
     """the feature is visible: every operator scene differs from the same scene drawn without its mask"""
     gold = np.load(ms.golden_path("cairo_mask_operators"))
     for name, sc in sorted(ms.operator_scenes().items())[:: 9 if EMU else 1]:
-        r = _renderer(sc, False)
+        r = renderer_for(sc, False)
         try:
             r.render({"children": ms.without_masks(sc["stage"]["children"])})
             assert (r.read_image(premultiplied=True) != gold[name]).any(), name
@@ -210,7 +79,7 @@ def test_frames_without_a_mask_through_instance_5(monkeypatch):
     import layer_scenes as ls
     import scenarios
     from helpers import golden, product_render
-    monkeypatch.setenv("SWFR_TILES_SHADERS", "5")
+    monkeypatch.setenv("SWFR_TILES_SHADERS", FAMILY.instance)
     SC = scenarios.scenarios()
     for name in sorted(SC)[:: 9 if EMU else 1]:
         sc = SC[name]
@@ -223,14 +92,14 @@ def test_frames_without_a_mask_through_instance_5(monkeypatch):
     for first, depth in cs.NESTINGS[:: 4 if EMU else 1]:
         fr = cs.raw_nesting_frame(first, depth)
         arrays = fr.arrays()
-        _zero(_through_edges(fr.W, fr.H, arrays), frame_model.render(*arrays, fr.W, fr.H), ("layers through 5", first, depth))
+        zero(through_edges(fr.W, fr.H, arrays), frame_model.render(*arrays, fr.W, fr.H), ("layers through 5", first, depth))
 
 
 # ---------------------------------------------------------------------------------------------------------------- b. raw frames
 def _check_raw(fr, msg, **kw):
     arrays = fr.arrays()
-    want = mfm.render(*arrays, fr.W, fr.H)
-    _zero(_through_edges(fr.W, fr.H, arrays, **kw), want, msg)
+    want = frame_model.render(*arrays, fr.W, fr.H)
+    zero(through_edges(fr.W, fr.H, arrays, **kw), want, msg)
     return arrays, want
 
 
@@ -311,7 +180,7 @@ def test_nesting(which):
         b = [i for i, k in enumerate(kinds) if k == cs.BEGIN][1]
         en = [i for i, k in enumerate(kinds) if k == cs.END][0]
         without = np.concatenate([p[:b], p[en + 1:]])
-        assert (want[:8, :64] == mfm.render(e, without, s, fr.W, fr.H)[:8, :64]).all()
+        assert (want[:8, :64] == frame_model.render(e, without, s, fr.W, fr.H)[:8, :64]).all()
 
 
 def test_random_nesting_across_tile_rows_and_band_boundaries():
@@ -324,7 +193,7 @@ def test_random_nesting_across_tile_rows_and_band_boundaries():
         cases |= mr.strip_mask_reach(W, H, arrays[1])["cases"]
         if seed % 4 == 0:
             for contiguous in (True, False):
-                _zero(_two_bands(W, H, contiguous, lambda r: r.render_edges(*arrays)), want, ("random raw bands", seed, contiguous))
+                zero(two_bands(W, H, contiguous, lambda r: r.render_edges(*arrays)), want, ("random raw bands", seed, contiguous))
     assert len(cases) == 4 or EMU
 
 

@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 
 import blend_model as bm
+from cairo_pixels import random_premultiplied, surface_bytes
 import mask_model as mk
 from oracle import cairo_backend as cb
-from test_blend_model import _random_premultiplied, _surface_bytes
 
 needs_cairo = pytest.mark.skipif(not cb.available(), reason="libcairo not installed")
 N = 4096                                   # pixels (= random triples) per operator and ground kind
@@ -51,7 +51,7 @@ def _mask(dst, content, mask, operator, n, probe=None):
     try:
         be.clear_all()
         if dst is not None:
-            _surface_bytes(be)[0] = dst[:, [2, 1, 0, 3]]
+            surface_bytes(be)[0] = dst[:, [2, 1, 0, 3]]
             lib.cairo_surface_mark_dirty(be.surf)
         c = _group(be, content, n)
         m = _group(be, mask, n)
@@ -76,10 +76,10 @@ def _mask(dst, content, mask, operator, n, probe=None):
 
 
 def _triples(rng):
-    content = _random_premultiplied(rng, N, "translucent")
-    content[N // 2: N // 2 + N // 16] = _random_premultiplied(rng, N // 16, "opaque")
-    mask = _random_premultiplied(rng, N, "translucent")
-    mask[N // 4: N // 4 + N // 16] = _random_premultiplied(rng, N // 16, "opaque")
+    content = random_premultiplied(rng, N, "translucent")
+    content[N // 2: N // 2 + N // 16] = random_premultiplied(rng, N // 16, "opaque")
+    mask = random_premultiplied(rng, N, "translucent")
+    mask[N // 4: N // 4 + N // 16] = random_premultiplied(rng, N // 16, "opaque")
     mask[-N // 16:] = 0                                      # transparent mask pixels
     content[-N // 8: -N // 16] = 0                           # transparent content pixels under a live mask
     return content, mask
@@ -91,7 +91,7 @@ def _triples(rng):
 def test_model_is_libcairo(mode, ground):
     rng = np.random.default_rng(sorted(mk.MODES).index(mode) * 7 + 29)
     content, mask = _triples(rng)
-    dst = None if ground == "still_clear" else _random_premultiplied(rng, N, "clear" if ground == "clear_pixels" else ground)
+    dst = None if ground == "still_clear" else random_premultiplied(rng, N, "clear" if ground == "clear_pixels" else ground)
     got = _mask(dst, content, mask, bm.CAIRO_OPERATORS[mode], N)
     d = np.zeros((N, 4), np.uint8) if dst is None else dst
     want = mk.composite(mode, content, mask, d)
@@ -110,7 +110,7 @@ def test_the_masks_colour_plays_no_part_and_transparency_changes_nothing():
     other[:, :3] = (other[:, 3:4].astype(int) * rng.integers(0, 256, (N, 3)) // 255).astype(np.uint8)
     assert (other[:, :3] != mask[:, :3]).any()
     for kind in ("translucent", "opaque", "clear"):
-        d = _random_premultiplied(rng, N, kind)
+        d = random_premultiplied(rng, N, kind)
         for mode in mk.MODES:
             assert (mk.composite(mode, content, mask, d) == mk.composite(mode, content, other, d)).all()
             assert (mk.composite(mode, content, np.zeros_like(mask), d) == d).all(), (mode, kind)
@@ -130,7 +130,7 @@ def test_clear_surface_bookkeeping_is_libcairos(mode):
     zero = np.zeros((n, 4), np.uint8)
     probe = (97, 184, 252, 38)             # (0x7f and 0x80 rounding differ at one coverage value per channel value at most: this colour has one)
     lerp = _mask(None, None, None, CAIRO_OPERATOR_OVER, n, probe)[1]          # nothing at all happened to the parent
-    over = _mask(_random_premultiplied(np.random.default_rng(1), n, "clear"), None, None, CAIRO_OPERATOR_OVER, n, probe)[1]   # a drawn-on parent
+    over = _mask(random_premultiplied(np.random.default_rng(1), n, "clear"), None, None, CAIRO_OPERATOR_OVER, n, probe)[1]   # a drawn-on parent
     assert (lerp != over).any()                              # (the probe tells the two states apart)
     for content_clear in (True, False):
         for mask_clear in (True, False):
@@ -139,5 +139,5 @@ def test_clear_surface_bookkeeping_is_libcairos(mode):
             stays = mk.nothing_to_do(mode, content_clear, mask_clear)
             assert (after == (lerp if stays else over)).all(), (mode, content_clear, mask_clear, stays)
     # a parent that was drawn on stays drawn on
-    d = _random_premultiplied(np.random.default_rng(2), n, "clear")
+    d = random_premultiplied(np.random.default_rng(2), n, "clear")
     assert (_mask(d, None, None, bm.CAIRO_OPERATORS[mode], n, probe)[1] == over).all()
