@@ -77,6 +77,12 @@ typedef struct {
     int32_t focal_point;                 /* focal gradient, Sfixed8P8 epsilons */
     uint32_t bitmap_id;                  /* bitmap */
     uint8_t repeating, smoothed;
+    uint8_t spread;                      /* gradients: the SWF GradientSpread number -- 0 pad, 1 reflect, 2 repeat: the gradient's Cairo pattern
+                                            with cairo_pattern_set_extend(PAD | REFLECT | REPEAT).  Anything else: SWFR_ERR_INVALID,
+                                            "UnknownGradientSpread".  Radial and focal gradients follow pixman's walker bit for bit; a LINEAR
+                                            gradient with a spread other than pad is SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"
+                                            (refused, never approximated).  Ignored for solid and bitmap fills.  The field lies in what was
+                                            the struct's tail padding: size and offsets are unchanged.  DESIGN.md, "Gradient spread modes" */
 } swfr_fill_style;
 
 typedef struct {
@@ -304,7 +310,9 @@ typedef struct {
     float stop_rgba[SWFR_MAX_STOPS][4];  /* straight, 0..1 */
     uint32_t bitmap;                     /* registered bitmap id; 65536 + k: texture k of the colour-transformed bitmaps of the frame the
                                             handle's last scene walk built (swfr_build_frame), valid on that handle until its next walk */
-    uint32_t extend;                     /* 0 none, 1 repeat */
+    uint32_t extend;                     /* bitmap: 0 none, 1 repeat.  Radial / linear: 0 pad, 1 repeat, 2 reflect (cairo_pattern_set_extend);
+                                            any other value on a gradient style is SWFR_ERR_INVALID at upload, and 1 or 2 on a LINEAR
+                                            style SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread" */
 } swfr_style;
 
 /* Upload a scene (kept resident in HBM), then rasterize it.  swfr_render_edges = upload + render. */

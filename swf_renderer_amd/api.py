@@ -94,7 +94,7 @@ class ColorStop(C.Structure):
 class FillStyle(C.Structure):
     _fields_ = [("type", C.c_uint32), ("color", Rgba8), ("morph_color", Rgba8), ("matrix", Matrix), ("n_stops", C.c_uint32),
                 ("stops", C.POINTER(ColorStop)), ("focal_point", C.c_int32), ("bitmap_id", C.c_uint32),
-                ("repeating", C.c_uint8), ("smoothed", C.c_uint8)]
+                ("repeating", C.c_uint8), ("smoothed", C.c_uint8), ("spread", C.c_uint8)]
 
 
 class LineStyle(C.Structure):
@@ -278,6 +278,19 @@ def load_library():
 
 # ---- swf-tree JSON -> C structs ------------------------------------------------------------------
 _FILL_TYPES = {"solid": 0, "linear-gradient": 1, "radial-gradient": 2, "focal-gradient": 3, "bitmap": 4}
+_SPREADS = {"pad": 0, "reflect": 1, "repeat": 2}            # swf-tree GradientSpread
+
+
+def _spread(v):
+    """fill["gradient"]["spread"]: a name of _SPREADS or its SWF number; absent: pad.  (A number the library does not know still goes
+    to it, to be refused there.)"""
+    if v is None:
+        return 0
+    if isinstance(v, str) and v.lower() in _SPREADS:
+        return _SPREADS[v.lower()]
+    if isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 255:
+        return v
+    raise SwfrError(ERR_INVALID, "UnknownGradientSpread")
 
 
 class _Arena:
@@ -329,6 +342,7 @@ def _fill(arena, s):
         arr = arena.array(ColorStop, stops)
         f.n_stops = len(stops)
         f.stops = C.cast(arr, C.POINTER(ColorStop))
+        f.spread = _spread(s["gradient"].get("spread"))
     if "focal_point" in s:
         fp = s["focal_point"]
         f.focal_point = int(fp["epsilons"]) if isinstance(fp, dict) else int(round(float(fp) * 256))

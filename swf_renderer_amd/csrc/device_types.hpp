@@ -101,7 +101,7 @@ struct DevFilter {
     // what the bitmap shader needs of the style and of the bitmap table, so that one load of this record is all it waits for
     const uint32_t* pixels;  // premultiplied ARGB, tight rows (bitmap styles)
     uint32_t width, height;
-    uint32_t extend;         // 0 none, 1 repeat
+    uint32_t extend;         // bitmap: 0 none, 1 repeat; gradient: 0 pad, 1 repeat, 2 reflect (swfr_style::extend)
     uint32_t kind;           // SWFR_STYLE_*
     uint32_t pad2[2];
 };
@@ -110,15 +110,19 @@ static_assert(sizeof(DevFilter) == 96, "DevFilter layout");
 // A radial gradient as pixman holds it for one drawing operation (host: radial_of; cairo-image-source.c _pixman_image_for_gradient,
 // pixman-radial-gradient.c, pixman-gradient-walker.c): the 16.16 sample position as for bitmaps, the circles after Cairo's
 // fit-to-range scaling, the constant terms of the quadratic, and one single-precision colour ramp per interval between stops
-// (PAD sentinels at both ends).  DevFilter::pad of the style holds its index + 1 into the handle's gradient table.
+// (PAD sentinels at both ends; REPEAT and REFLECT: the stops themselves, the ramp is formed per pixel).  DevFilter::pad of the style holds its index + 1 into the handle's gradient table.
 struct DevGradient {
     int64_t base_x, base_y;
     int32_t m00, m01, m10, m11;
     int32_t c1x, c1y, c1r, dx, dy, dr;       // 16.16
-    int32_t n_intervals, pad;
+    int32_t n_intervals, extend;             // extend: 0 pad, 1 repeat, 2 reflect (swfr_style::extend)
     double a, inva, mindr;
-    int32_t x[SWFR_MAX_STOPS + 2];           // interval boundaries: INT32_MIN, stop offsets, INT32_MAX
-    float ramp[SWFR_MAX_STOPS + 1][8];       // a_s, a_b, r_s, r_b, g_s, g_b, b_s, b_b
+    int32_t x[SWFR_MAX_STOPS + 2];           // interval boundaries: INT32_MIN, stop offsets, INT32_MAX; extend != 0: the sentinel stops of the repeat kind at both ends
+    float ramp[SWFR_MAX_STOPS + 1][8];       // a_s, a_b, r_s, r_b, g_s, g_b, b_s, b_b (pad only)
+    // extend != 0: what gradient_walker_reset needs per pixel -- the stops' 16-bit colours (a, r, g, b; sentinels at both ends) and
+    // the left edge of the operation's rectangle, where pixman starts the walker of a scanline
+    uint16_t col[SWFR_MAX_STOPS + 2][4];
+    int32_t x_min, pad;
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------

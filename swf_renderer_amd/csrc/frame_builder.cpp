@@ -674,6 +674,11 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         const double m[6] = {inv.xx, inv.yx, inv.xy, inv.yy, inv.x0, inv.y0};
         std::memcpy(st.inv, m, sizeof m);
         const double R = 16384.0;
+        // cairo_pattern_set_extend of the SWF spread (0 pad, 1 reflect, 2 repeat) -- beyond the reference, which never reads the
+        // field.  A linear gradient is the float64 extension: next to a repeat seam a +-1 LSB model can land a whole colour away,
+        // so a spread one is refused
+        st.extend = s.spread == 1 ? 2u : s.spread == 2 ? 1u : 0u;
+        if (s.type == SWFR_FILL_LINEAR_GRADIENT && st.extend) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"};
         if (s.type == SWFR_FILL_LINEAR_GRADIENT) {
             st.kind = SWFR_STYLE_LINEAR;
             st.c0x = -R; st.c1x = R;

@@ -1218,6 +1218,12 @@ __device__ __forceinline__ uint32_t shade_bitmap(uint32_t style_index, const Sou
 }
 // SHADERS: 0 solid colours only, 1 + bitmaps, 2 + gradients, 3 + blend operators (what an unblended entry gets is instance 2's),
 // 4 + isolated groups (what an entry that is no group marker gets is instance 3's)
+// a gradient's pixel: a radial gradient with a spread mode (DevFilter::extend of a gradient style: 1 repeat, 2 reflect) has a shader call of
+// its own, everything else is shade()'s as before (wave-uniform: one style per band entry)
+__device__ __forceinline__ uint32_t shade_gradient(const swfr_style* __restrict__ styles, uint32_t style, const Sources& src, int cx, int cy) {
+    if (src.filters[style].extend && src.filters[style].kind == SWFR_STYLE_RADIAL && src.filters[style].pad > 0) return shade_spread(src, style, cx, cy);
+    return shade(styles[style], style, src, cx, cy);
+}
 template <int SHADERS>
 __device__ __forceinline__ uint32_t blend2(uint32_t dst, uint32_t a, uint32_t eflags, uint32_t solid, const swfr_style* __restrict__ styles,
                                            uint32_t style, const Sources& src, int cx, int cy) {
@@ -1227,7 +1233,7 @@ __device__ __forceinline__ uint32_t blend2(uint32_t dst, uint32_t a, uint32_t ef
     }
     uint32_t c;
     if (SHADERS == 1) c = shade_bitmap(style, src, cx, cy);
-    else c = src.filters[style].kind == SWFR_STYLE_BITMAP ? shade_bitmap(style, src, cx, cy) : shade(styles[style], style, src, cx, cy);
+    else c = src.filters[style].kind == SWFR_STYLE_BITMAP ? shade_bitmap(style, src, cx, cy) : shade_gradient(styles, style, src, cx, cy);
     const uint32_t s = mul_un8(c, a);
     return (eflags & BE_LERP) ? s : over_pixel(s, dst);
 }
@@ -1484,7 +1490,7 @@ __device__ __forceinline__ void blend8_op(uint32_t (&px)[8], const uint32_t (&al
             for (int i = 0; i < 4; ++i) {
                 const uint32_t a = al[4 * h + i];
                 uint32_t c = 0u;
-                if (a) c = bitmap ? shade_bitmap(style, src, cx0 + i, cy0 + 4 * h) : shade(styles[style], style, src, cx0 + i, cy0 + 4 * h);
+                if (a) c = bitmap ? shade_bitmap(style, src, cx0 + i, cy0 + 4 * h) : shade_gradient(styles, style, src, cx0 + i, cy0 + 4 * h);
                 sp[i] = mul_un8_24(c, a);
             }
         }

@@ -587,6 +587,87 @@ __device__ uint32_t shade_radial(const DevGradient& G, int px, int py) {
     return 0u;
 }
 
+// shade_radial's position once more, for the spread walker below: false where the gradient is not defined (pixman writes 0 there and
+// does not ask the walker), else the 48.16 position the walker is asked for
+__device__ __forceinline__ bool radial_position(const DevGradient& G, int px, int py, long long& pos) {
+    const long long vx = G.base_x + (long long)px * G.m00 + (long long)py * G.m01 - G.c1x;
+    const long long vy = G.base_y + (long long)px * G.m10 + (long long)py * G.m11 - G.c1y;
+    const long long bi = vx * G.dx + vy * G.dy + (long long)G.c1r * G.dr;
+    const long long ci = vx * vx + vy * vy - (long long)G.c1r * G.c1r;
+    const double a = G.a, b = (double)bi, c = (double)ci, dr = (double)G.dr;
+    if (a == 0) {
+        if (b == 0) return false;
+        const double t = 65536 / 2 * c / b;
+        if (t * dr >= G.mindr) { pos = (long long)t; return true; }
+        return false;
+    }
+    const double discr = b * b + a * -c;
+    if (discr >= 0) {
+        const double sq = __dsqrt_rn(discr), t0 = (b + sq) * G.inva, t1 = (b - sq) * G.inva;
+        if (t0 * dr >= G.mindr) { pos = (long long)t0; return true; }
+        else if (t1 * dr >= G.mindr) { pos = (long long)t1; return true; }
+    }
+    return false;
+}
+// pixman-gradient-walker.c under REPEAT (G.extend 1) and REFLECT (2): gradient_walker_reset at this pixel's position -- the position
+// folded into [0, 1] (mirrored in an odd period of REFLECT), the first stop beyond it, the interval mirrored back and shifted into the
+// position's own period, slope and offset of every channel in single precision FROM THOSE SHIFTED ENDS (so they differ from period to
+// period), then the pixel as radial_walker_pixel forms it.  Operation for operation in pixman's order; the build does not contract.
+// pixman's walker keeps its interval along a scanline and resets only when the position leaves [left_x, right_x).  A fresh reset finds
+// the same interval except where the position sits exactly on a stop in an odd period of REFLECT: there it picks the interval that
+// ENDS at the stop, while a walker that came from the other side (positions falling along the scanline) is still in the one that
+// BEGINS there -- another ramp, equal at the stop only up to rounding, and another colour altogether at two coincident stops.  So
+// there, and only there, the samples to the left in the same row decide: the nearest one that the gradient defines and that is not
+// this very position puts the walker into the interval that begins at the stop iff it lies inside it; none (the operation's
+// rectangle starts here): the fresh reset.  (libcairo skips samples whose coverage is zero; this looks at every sample of the
+// rectangle -- the two agree unless the shape's first covered pixel of a run is such a sample.)
+// A shader call of its own beside shade() (raster2.hip, shade_gradient, picks per style): shade() -- the padded walker, the linear
+// extension, the bitmap filters -- stays the code it was, instruction for instruction, and keeps its registers.
+__device__ __noinline__ uint32_t shade_spread(const Sources bitmaps, uint32_t style_index, int px, int py) {
+    const DevGradient& G = bitmaps.gradients[bitmaps.filters[style_index].pad - 1];
+    if (!G.n_intervals) return 0u;
+    long long pos;
+    if (!radial_position(G, px, py, pos)) return 0u;
+    const int low = (int)(pos & 0xffff);
+    const bool odd = G.extend == 2 && (pos & 0x10000);
+    const int x = odd ? 0x10000 - low : low;
+    int n = 1;
+#pragma nounroll
+    while (n < G.n_intervals && !(x < G.x[n])) ++n;
+    int il = n - 1;
+    if (odd && G.x[il] == x) {
+        int first = il;
+#pragma nounroll
+        while (first > 1 && G.x[first - 1] == x) --first;           // the first of the stops at x: the interval that begins here (in the scanline's direction) ends at the stop before it
+        const long long end = pos - low + 0x10000 - G.x[first - 1];
+#pragma nounroll
+        for (int qx = px - 1; qx >= G.x_min; --qx) {
+            long long q;
+            if (!radial_position(G, qx, py, q) || q == pos) continue;
+            if (q > pos && q < end) il = first - 1;
+            break;
+        }
+    }
+    const int ia = odd ? il + 1 : il, ib = odd ? il : il + 1;        // the interval's left and right stop once it is mirrored back
+    const long long shift = pos - low;
+    const long long lx = (odd ? 0x10000 - G.x[ia] : G.x[ia]) + shift, rx = (odd ? 0x10000 - G.x[ib] : G.x[ib]) + shift;
+    const float flx = (float)lx * (1.0f / 65536.0f), frx = (float)rx * (1.0f / 65536.0f), w = frx - flx;
+    const bool flat = -1.17549435e-38f < w && w < 1.17549435e-38f;   // FLOAT_IS_ZERO
+    const float w_rec = 1.0f / w;
+    const float y = (float)pos * (1.0f / 65536.0f);
+    float fa = 0.f;
+    uint32_t out = 0u;
+#pragma nounroll
+    for (int ch = 0; ch < 4; ++ch) {                                 // a, r, g, b
+        const float l = G.col[ia][ch] * (1.0f / 257.0f), r = G.col[ib][ch] * (1.0f / 257.0f);
+        const float off = flat ? (l + r) / 510.0f : (l * frx - r * flx) * w_rec * (1.0f / 255.0f);
+        const float slope = flat ? 0.0f : (r - l) * w_rec * (1.0f / 255.0f);
+        const float v = slope * y + off;
+        if (ch == 0) { fa = 255.f * v; out = ((uint32_t)(fa + .5f) << 24) & 0xff000000u; }
+        else out |= ((uint32_t)(fa * v + .5f) & 0xffu) << (24 - 8 * ch);
+    }
+    return out;
+}
 __device__ __noinline__ uint32_t shade(const swfr_style& s, uint32_t style_index, const Sources bitmaps, int px, int py) {
     if (s.kind == SWFR_STYLE_RADIAL) {
         const int gi = bitmaps.filters[style_index].pad;

@@ -503,6 +503,16 @@ bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths
     return true;
 }
 
+// swfr_style::extend of a gradient style: 0 pad, 1 repeat, 2 reflect; a linear gradient -- the float64 extension -- pads only
+void validate_gradient_extend(const swfr_style* styles, size_t n_styles) {
+    for (size_t i = 0; i < n_styles; ++i) {
+        const swfr_style& s = styles[i];
+        if (s.kind != SWFR_STYLE_RADIAL && s.kind != SWFR_STYLE_LINEAR) continue;
+        if (s.extend > 2) throw StatusError{SWFR_ERR_INVALID, "gradient extend must be 0 (pad), 1 (repeat) or 2 (reflect)"};
+        if (s.kind == SWFR_STYLE_LINEAR && s.extend) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"};
+    }
+}
+
 void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
                     const swfr_style* styles, size_t n_styles) {
     // end points within +-32768 px (2^23 in 24.8): inside that range the int64 products of the closed-form edge evaluation cannot overflow
@@ -659,6 +669,10 @@ Affine pattern_matrix(const swfr_style& st) {
 // A radial gradient as cairo 1.16 hands it to pixman 0.40 and as pixman evaluates it: circles scaled into +-16383 (the matrix
 // takes the inverse factor), 16.16 circles and stops, 16-bit colours, single-precision ramps per interval (gradient_walker_reset),
 // PAD sentinels.  The device evaluates B and C of the quadratic as exact 64-bit integers, the root in doubles, the ramp in floats.
+// Under REPEAT or REFLECT (swfr_style::extend 1, 2) the ramp of an interval depends on the period the position lies in -- pixman
+// forms it in single precision from the interval's ends shifted into that period -- so no table can hold it: the device gets the
+// 16.16 stops with the sentinels of the repeat kind, the 16-bit colours and the left edge of the operation's rectangle, where
+// pixman starts a scanline's walker, and resets per pixel (raster_common.hip, shade_spread).
 DevGradient radial_of(const swfr_style& st, const int rect[4]) {
     DevGradient g;
     std::memset(&g, 0, sizeof g);
@@ -692,6 +706,19 @@ DevGradient radial_of(const swfr_style& st, const int rect[4]) {
     }
     g.x[0] = INT32_MIN; g.x[n + 1] = INT32_MAX;
     if (n) { std::memcpy(col[0], col[1], sizeof col[0]); std::memcpy(col[n + 1], col[n], sizeof col[0]); }
+    if (st.extend && n) {
+        // _pixman_gradient_walker_init's sentinel stops: REPEAT -- the last stop one period down, the first one period up;
+        // REFLECT -- the first stop mirrored at 0, the last mirrored at 1
+        g.extend = int32_t(st.extend); g.x_min = rect[0];
+        if (st.extend == 1) {
+            g.x[0] = g.x[n] - 0x10000; g.x[n + 1] = g.x[1] + 0x10000;
+            std::memcpy(col[0], col[n], sizeof col[0]); std::memcpy(col[n + 1], col[1], sizeof col[0]);
+        } else {
+            g.x[0] = -g.x[1]; g.x[n + 1] = 0x20000 - g.x[n];
+        }
+        std::memcpy(g.col, col, sizeof col);
+        return g;
+    }
     for (int k = 0; k <= n && n; ++k) {
         const int64_t left_x = g.x[k], right_x = g.x[k + 1];
         const float lx = left_x * (1.0f / 65536.0f), rx = right_x * (1.0f / 65536.0f);
@@ -1215,6 +1242,7 @@ int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size
            const swfr_style* styles, size_t n_styles, uint32_t* fb_override = nullptr) {
     validate_groups(paths, n_paths);
     validate_blend_fields(paths, n_paths);                       // (a malformed blend field is refused as such even by a host-only handle)
+    validate_gradient_extend(styles, n_styles);                  // (and so is a gradient's extend)
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
     validate_scene(r, edges, n_edges, paths, n_paths, styles, n_styles);
     return upload2(r, si, all_sets, edges, n_edges, paths, n_paths, styles, n_styles, fb_override, false);

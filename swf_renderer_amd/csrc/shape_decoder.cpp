@@ -29,6 +29,9 @@ OwnedFill own_fill(const swfr_fill_style& s, bool morph) {
     f.style = s;
     if (morph && s.type != SWFR_FILL_SOLID) throw std::runtime_error("Unknown fill type");  // decode-swf-morph-shape.ts:94-106
     if (s.type > SWFR_FILL_BITMAP) throw std::runtime_error("UnknownFillStyle");
+    const bool gradient = s.type != SWFR_FILL_SOLID && s.type != SWFR_FILL_BITMAP;
+    if (gradient && s.spread > 2) throw std::runtime_error("UnknownGradientSpread");   // swf-tree GradientSpread: 0 pad, 1 reflect, 2 repeat
+    if (!gradient) f.style.spread = 0;
     if (s.n_stops && s.stops) f.stops.assign(s.stops, s.stops + s.n_stops);
     f.style.stops = nullptr;
     f.style.n_stops = uint32_t(f.stops.size());
