@@ -46,6 +46,9 @@ __device__ __forceinline__ uint32_t col_bit(int t) { return (uint32_t)t < 32u ? 
 #define R3_BIAS (1 << 24)                                                   // cells are 24.8 positions within +-2^23: biased keys are positive
 #define R3_INVALID(s) (0xF0000000u | ((uint32_t)(s) << 5) | (uint32_t)(s))   // sorts behind every cell; distinct per slot; low bits = the slot
 #define R3_KEY(c, dir, s) ((((uint32_t)((c) + R3_BIAS)) << 5) | ((dir) > 0 ? 16u : 0u) | (uint32_t)(s))          // (cell, direction, slot): cell < 2^25, slot < 16
+// The unrolled slot loops stop at the wave-uniform bound nm (2, 4, 6, 8 or 16: even) with ONE scalar test per pair of slots, and leave
+// at the first that fails: the slots behind the bound are neither initialised nor tested one by one (no loop below reads them).
+#define R3_PAST(s, nm) ((((s) & 1) == 0) && (s) >= (nm))
 // compare-exchange of the sort networks: keys alone, or keys with one payload word
 #define R3_CE(i, j) do { const uint32_t lo_ = min(key[i], key[j]), hi_ = max(key[i], key[j]); key[i] = lo_; key[j] = hi_; } while (0)
 #define R3_CEP(i, j) do { const bool sw_ = key[i] > key[j]; const uint32_t lo_ = min(key[i], key[j]), hi_ = max(key[i], key[j]); \
@@ -151,6 +154,12 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
     }
     TRACE(1);                                                            // chunk, path and band records in
     R3MARK(1);
+    // The two tables every row of the chunk is written to -- the cells and the row headers -- are stored through pointers loaded here
+    // once and held (R3_FIELD): read where they are used, each FULL slot, sample pass and header pays a scalar round trip and a wait in
+    // front of its store address.
+    // (requested here, beside the other records; held from the end of the staging loop on)
+    SWFR_GLOBAL_PTR(Cell) p_cells = (SWFR_GLOBAL_PTR(Cell))FR->cells; SWFR_GLOBAL_PTR(RowInfo2) p_rows = (SWFR_GLOBAL_PTR(RowInfo2))FR->rows;
+#define R3_FIELD(name) ((decltype(FR->name))p_##name)
     const int fast_limit = min((int)FR->fast_limit, NS);
     // ---- stage the edges that can be active in this chunk's rows (path order kept)
     const int lo_s = (int)ck.first_row * 15, hi_s = lo_s + chunk_rows * 15;
@@ -203,6 +212,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         if (!ok) { n_list = 0; forced_over = live && cnt > 0; }
     }
     lds_barrier();
+    SWFR_PIN_SGPR(p_cells); SWFR_PIN_SGPR(p_rows);
     R3MARK(2);
     // ---- lanes = staged edges: the chunk's rows an edge is active in, as a bit mask over the rows; rows it starts or ends inside
     uint32_t rb_lo = 0, rb_hi = 0;
@@ -253,8 +263,8 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         amask_t m = amask;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            key[s] = R3_INVALID(s); c1[s] = 0x7fffffff; qt[s] = qb[s] = 0; rl[s] = 0;
-            if (s >= nmax) continue;                          // wave-uniform
+            if (R3_PAST(s, nmax)) break;                      // wave-uniform
+            key[s] = R3_INVALID(s); c1[s] = 0x7fffffff;
             const int k = m ? r3_first(m) : 0;                // (no edge left: the first staged record, the results are not used)
             m &= m - 1;
             slot_edge[s][lane] = (uint8_t)k;
@@ -289,7 +299,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
     unsigned tie_bits = 0;                                     // bit p: the edges at sorted positions p and p + 1 share a cell
 #pragma unroll
     for (int p = 0; p + 1 < NS; ++p) {
-        if (p + 1 >= nmax) continue;                          // wave-uniform
+        if (R3_PAST(p + 1, nmax)) break;                      // wave-uniform
         if (c1[p] > c1[p + 1]) full = false;                  // (slots without an edge sort last with the largest c1: never a violation)
         if ((key[p] >> 5) == (key[p + 1] >> 5)) { tie_bits |= 1u << p; deep = true; }
     }
@@ -301,7 +311,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
             bool real = false;
 #pragma unroll
             for (int p = 0; p + 1 < NS; ++p) {
-                if (p + 1 >= nmax) continue;
+                if (R3_PAST(p + 1, nmax)) break;
                 if ((tie_bits >> p) & 1u) {
                     const FastEdge& ea = staged[slot_edge[key[p] & 15u][lane]];
                     const FastEdge& eb = staged[slot_edge[key[p + 1] & 15u][lane]];
@@ -325,7 +335,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         int w = 0;
 #pragma unroll
         for (int p = 0; p < NS; ++p) {
-            if (p >= nmax) continue;                          // wave-uniform
+            if (R3_PAST(p, nmax)) break;                      // wave-uniform
             const bool in_b = ((unsigned)w & fmask) != 0;
             w += (key[p] & 16u) ? 1 : -1;
             const bool in_a = ((unsigned)w & fmask) != 0;
@@ -337,7 +347,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            if (s >= nmax) continue;
+            if (R3_PAST(s, nmax)) break;
             if (mode == ROW_FULL && s < n) roles |= (uint32_t)slot_role[s][lane] << (2 * s);
         }
     }
@@ -348,7 +358,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
     if (mode == ROW_FULL && ri != ~0u) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            if (s >= nmax) continue;                          // wave-uniform
+            if (R3_PAST(s, nmax)) break;                      // wave-uniform
             if (R3_ROLE(s) != 0) n_cells += full_span(qt[s], qb[s]);
         }
     }
@@ -368,10 +378,10 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         uint32_t off = my_room;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            if (s >= nmax) continue;
+            if (R3_PAST(s, nmax)) break;
             if (R3_ROLE(s) != 0) {
                 const FastEdge& e = staged[slot_edge[s][lane]];
-                full_cells3(qt[s], qb[s], rl[s], e.DX, e.D, e.invW, e.fq, e.fr, (R3_ROLE(s) & 1u) ? 0 : -1, P.x_min, P.x_max, &FR->cells[off]);
+                full_cells3(qt[s], qb[s], rl[s], e.DX, e.D, e.invW, e.fq, e.fr, (R3_ROLE(s) & 1u) ? 0 : -1, P.x_min, P.x_max, &R3_FIELD(cells)[off]);
                 off += (uint32_t)full_span(qt[s], qb[s]);
             }
         }
@@ -386,7 +396,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         inter = 0; cov = 0;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            if (s >= nmax) continue;
+            if (R3_PAST(s, nmax)) break;
             if (R3_ROLE(s) != 0) {
                 const int a = qt[s] >> 8, b = qb[s] >> 8;
                 const int tlo = (min(a, b) >> 6) - tbase, thi = (max(a, b) >> 6) - tbase;          // (arithmetic shifts: floor)
@@ -410,11 +420,14 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
 #endif
     const int g = lane >> 4, sub = lane & 15;
     while (pending) {
-        unsigned long long m = pending;
-        int R = -1;
-        for (int t = 0; t <= g; ++t) { if (!m) { R = -1; break; } R = __ffsll((long long)m) - 1; m &= m - 1; }
-        const unsigned long long pass_rows = pending;           // its four lowest bits set are this pass's rows
-        for (int t = 0; t < 4 && pending; ++t) pending &= pending - 1;
+        // the pass's rows are the four lowest bits set in `pending` (fewer in the last pass): found ONCE, by the scalar unit -- the lanes'
+        // own row, the pass's slot bound and the rows' rooms all come from this walk
+        int Rg[4], Rs[4];                                        // Rg[t]: the pass's t-th row, -1 if it has none; Rs[t]: that row, or the first: a lane that can always be read
+        unsigned long long pass_rows = pending;                  // (in the end: the bits of this pass's rows)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { Rg[t] = pending ? __ffsll((long long)pending) - 1 : -1; Rs[t] = Rg[t] >= 0 ? Rg[t] : Rg[0]; pending &= pending - 1; }
+        pass_rows &= ~pending;
+        const int R = g == 0 ? Rg[0] : (g == 1 ? Rg[1] : (g == 2 ? Rg[2] : Rg[3]));
         // cross-lane reads must run with every lane active: ds_bpermute returns 0 for a disabled source lane
         const int Rsrc = R >= 0 ? R : 0;
         const int nR = __shfl(n, Rsrc);
@@ -424,18 +437,14 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         if (sizeof(amask_t) == 8) mR = (amask_t)(((uint64_t)(uint32_t)__shfl((int)(uint32_t)((uint64_t)amask >> 32), Rsrc) << 32) | (uint64_t)(uint32_t)__shfl((int)(uint32_t)amask, Rsrc));
         else mR = (amask_t)(uint32_t)__shfl((int)(uint32_t)amask, Rsrc);
         // the slot loops of this pass stop at the most active edges of ITS rows (wave-uniform)
-        int nmaxp = 0;
-        {
-            unsigned long long m2 = pass_rows;
-            for (int t = 0; t < 4 && m2; ++t) { nmaxp = max(nmaxp, __builtin_amdgcn_readlane(n, __ffsll((long long)m2) - 1)); m2 &= m2 - 1; }
-            nmaxp = nmaxp > 8 ? 16 : nmaxp > 6 ? 8 : nmaxp > 4 ? 6 : nmaxp > 2 ? 4 : 2;
-        }
+        int nmaxp = max(max(__builtin_amdgcn_readlane(n, Rs[0]), __builtin_amdgcn_readlane(n, Rs[1])), max(__builtin_amdgcn_readlane(n, Rs[2]), __builtin_amdgcn_readlane(n, Rs[3])));
+        nmaxp = nmaxp > 8 ? 16 : nmaxp > 6 ? 8 : nmaxp > 4 ? 6 : nmaxp > 2 ? 4 : 2;
         const bool sampling = R >= 0 && sub < 15;
         const int ss = rR * 15 + sub;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
+            if (R3_PAST(s, nmaxp)) break;                        // wave-uniform
             key[s] = R3_INVALID(s);
-            if (s >= nmaxp) continue;                            // wave-uniform
             const int k = mR ? r3_first(mR) : 0;
             mR &= mR - 1;
             const FastEdge& e = staged[k];
@@ -457,12 +466,11 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
             int w = 0; bool in_prev = false;
 #pragma unroll
             for (int p = 0; p < NS; ++p) {
-                cw[p] = 0;
-                if (p >= nmaxp) continue;                        // wave-uniform
+                if (R3_PAST(p, nmaxp)) break;                    // wave-uniform
                 const bool valid = key[p] < 0xF0000000u;
-                const uint32_t cellp = key[p] >> 5, celln = key[p + 1 < NS ? p + 1 : p] >> 5;
+                const uint32_t cellp = key[p] >> 5;
                 if (valid) w += (key[p] & 16u) ? 1 : -1;
-                const bool last = p + 1 >= NS || cellp != celln;
+                const bool last = p + 1 >= nmaxp || cellp != (key[p + 1 < NS ? p + 1 : p] >> 5);       // (the slot behind the pass's bound holds nothing)
                 const bool in_now = ((unsigned)w & fmask) != 0;
                 const bool emit = valid && last && in_now != in_prev;
                 if (valid && last) in_prev = in_now;
@@ -501,7 +509,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         for (int j = 0; j < NW; ++j) hn[j] = 0u;
 #pragma unroll
         for (int p = 0; p < NS; ++p) {
-            if (p >= nmaxp) continue;                            // wave-uniform
+            if (R3_PAST(p, nmaxp)) break;                        // wave-uniform
             const uint32_t pw = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cw[p], 0x111, 0xf, 0xf, false);
             const bool run = ((em_prev >> p) & 1u) != 0u && ((pw ^ cw[p]) >> 19) == 0u;
             if (((emk >> p) & 1u) != 0u && !run) hn[p >> 3] |= 1u << (4 * (p & 7));
@@ -519,7 +527,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         uint32_t n_merged = 0;                                   // the runs of the positions before p; in the end the row's cells
 #pragma unroll
         for (int p = 0; p < NS; ++p) {
-            if (p >= nmaxp) continue;
+            if (R3_PAST(p, nmaxp)) break;
             const int q = 4 * (p & 7);
             if ((emk >> p) & 1u) {
                 const uint32_t v = (uint32_t)((int)(cw[p] << 13) >> 13);
@@ -545,8 +553,8 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
         if (sub == 0 && R >= 0) { sub_masks[g][0] = a_int; sub_masks[g][1] = a_and; sub_masks[g][2] = a_or; }
         lds_barrier();                                          // the pass's cells and masks are staged
         {   // the row lanes of this pass take their masks over (my_t: the lane's place among the pass's four rows)
-            const int my_t = (int)__popcll(pass_rows & ((1ull << lane) - 1ull));
-            if (((pass_rows >> lane) & 1ull) != 0ull && my_t < 4) { m_inter = sub_masks[my_t][0]; m_and = sub_masks[my_t][1]; m_or = sub_masks[my_t][2]; }
+            const int my_t = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(pass_rows >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pass_rows, 0u));
+            if (lane_bit(pass_rows, lane) != 0u) { m_inter = sub_masks[my_t][0]; m_and = sub_masks[my_t][1]; m_or = sub_masks[my_t][2]; }
         }
         // ---- copy out (coalesced) into the rows' room, row headers
         {
@@ -554,14 +562,8 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
             const uint32_t c2 = (uint32_t)__builtin_amdgcn_readlane((int)n_merged, 47), c3 = (uint32_t)__builtin_amdgcn_readlane((int)n_merged, 63);
             const uint32_t total = c0 + c1r + c2 + c3;
             // where the rooms of the pass's rows start: the row lanes know (exclusive prefix of the rooms), every lane asks
-            int Rg[4];
-            {
-                unsigned long long m2 = pass_rows;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { Rg[t] = m2 ? __ffsll((long long)m2) - 1 : 0; m2 &= m2 - 1; }
-            }
-            const uint32_t b0 = (uint32_t)__shfl((int)my_room, Rg[0]), b1 = (uint32_t)__shfl((int)my_room, Rg[1]);
-            const uint32_t b2 = (uint32_t)__shfl((int)my_room, Rg[2]), b3 = (uint32_t)__shfl((int)my_room, Rg[3]);
+            const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)my_room, Rs[0]), b1 = (uint32_t)__builtin_amdgcn_readlane((int)my_room, Rs[1]);
+            const uint32_t b2 = (uint32_t)__builtin_amdgcn_readlane((int)my_room, Rs[2]), b3 = (uint32_t)__builtin_amdgcn_readlane((int)my_room, Rs[3]);
             // (the staged word becomes the cell: its low 19 bits are sum(V), what is left the column; the staging is left cleared)
             for (uint32_t t = (uint32_t)lane; t < total; t += 64) {
                 const int gg = t < c0 ? 0 : (t < c0 + c1r ? 1 : (t < c0 + c1r + c2 ? 2 : 3));
@@ -570,13 +572,13 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
                 const uint32_t w = sub_cells[gg][t - pre];
                 sub_cells[gg][t - pre] = 0u;
                 const uint32_t v = (uint32_t)((int)(w << 13) >> 13);
-                if (wave_base != ~0u) FR->cells[bb + (t - pre)] = Cell{(w - v) | (v & 0x7ffffu)};
+                if (wave_base != ~0u) R3_FIELD(cells)[bb + (t - pre)] = Cell{(w - v) | (v & 0x7ffffu)};
             }
             if (sub == 0 && R >= 0 && riR != ~0u) {          // the first sample lane of each of the pass's rows writes its header
                 const uint32_t bb = g == 0 ? b0 : (g == 1 ? b1 : (g == 2 ? b2 : b3));
                 const uint32_t cg = g == 0 ? c0 : (g == 1 ? c1r : (g == 2 ? c2 : c3));
                 RowInfo2 h; h.off = wave_base == ~0u ? 0u : bb; h.n = wave_base == ~0u ? (uint16_t)0 : (uint16_t)cg; h.mode = (uint16_t)ROW_SUB;
-                FR->rows[riR] = h;
+                R3_FIELD(rows)[riR] = h;
             }
         }
         lds_barrier();                                          // the staging has been read: the next pass may overwrite it
@@ -588,7 +590,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
     if (ri != ~0u && lane < chunk_rows && mode != ROW_SUB) {
         RowInfo2 h; h.off = 0; h.n = 0; h.mode = (uint16_t)(slow ? (uint32_t)ROW_DEFER : (in_path && !live) ? (uint32_t)ROW_FOREIGN : mode);   // (another rank's row: not known here)
         if (mode == ROW_FULL && !slow && wave_base != ~0u) { h.off = my_room; h.n = (uint16_t)n_cells; }
-        FR->rows[ri] = h;
+        R3_FIELD(rows)[ri] = h;
     }
     // ---- rows left to the slow-row kernel
     {
@@ -690,6 +692,7 @@ __device__ __forceinline__ void rows3_chunk_body(FramePtr FR, uint32_t block) {
             }
         }
     }
+#undef R3_FIELD
     TRACE(7);
     TRACE_OUT(1, block);
 }
