@@ -12,6 +12,10 @@ The walker keeps state along a scanline (it resets only when the position leaves
 rectangle both ways: `stateful` -- one walker per scanline, started at the rectangle's left edge, what libcairo does -- and `fresh`,
 a reset at every pixel.  Where the two can differ at all is counted (`on_left_end`: positions that sit exactly on the left end of
 the interval the walker is in while a fresh reset picks another interval) and so is where they do (`state_pixels`).
+
+pixman asks the walker only for pixels whose coverage is not zero, and libcairo composites a shape span by span under
+CAIRO_ANTIALIAS_NONE and box by box where its outline is rectilinear on whole pixels: source(covered=, per_run=).  frame() composes a whole frame of one shape from that and a coverage, and beside it what a walker
+gives that sees every sample of the rectangle -- the device's rule -- and where the two differ (`caveat`).
 """
 import math
 
@@ -235,12 +239,17 @@ def pixman_stops(stops):
     return [(fixed(o), (short(a), short(r), short(g), short(b))) for o, r, g, b, a in stops]
 
 
-def source(m, circles, stops, extend, rect, covered=None):
+def source(m, circles, stops, extend, rect, covered=None, per_run=False):
     """The source pixels of a radial gradient over the rectangle: dict(stateful=, fresh= (uint32 ARGB, premultiplied), on_left_end=,
-    state_pixels=).  `covered` (bool per pixel; default all): the pixels pixman evaluates -- those with a non-zero mask."""
+    state_pixels=).  `covered` (bool per pixel; default all): the pixels pixman evaluates -- those with a non-zero mask; the walker
+    of a row skips the others.  `per_run` (with `covered`): the stateful walker starts anew at the first pixel of every covered run of
+    a row -- libcairo where it composites a shape span by span or box by box, each a scanline of its own (frame())."""
     valid, pos = radial_positions(m, circles, rect)
+    starts = np.zeros(valid.shape, bool)
     if covered is not None:
         valid = valid & covered
+        if per_run:
+            starts[:, 1:] = covered[:, 1:] & ~covered[:, :-1]
     h, w = pos.shape
     S = pixman_stops(stops)
     out = {}
@@ -250,6 +259,8 @@ def source(m, circles, stops, extend, rect, covered=None):
     for yy in range(h):
         walker, fresh = Walker(S, extend), Walker(S, extend)
         for xx in range(w):
+            if starts[yy, xx]:
+                walker = Walker(S, extend)
             if not valid[yy, xx]:
                 continue
             p = int(pos[yy, xx])
@@ -268,6 +279,37 @@ def source(m, circles, stops, extend, rect, covered=None):
     out["on_left_end"] = on_left_end
     out["state_pixels"] = int((out["stateful"] != out["fresh"]).sum())
     out["exact_hits"] = sum(1 for (yy, xx), fr in zip(where, iv["fresh"]) if int(pos[yy, xx]) in (fr[0], fr[1]))
+    return out
+
+
+def mul_un8(rgba, a):
+    """pixman's MUL_UN8 of every channel of HxWx4 bytes by the HxW bytes a: (t + (t >> 8)) >> 8 with t = c * a + 0x80"""
+    t = rgba.astype(np.int64) * a.astype(np.int64)[..., None] + 0x80
+    return ((t + (t >> 8)) >> 8).astype(np.uint8)
+
+
+def frame(m, circles, stops, extend, rect, alpha, per_run):
+    """One shape filled with the gradient over a clear frame.  `alpha` is the shape's coverage over the whole frame (H x W bytes, zero
+    outside `rect`, the operation's rectangle).  On a clear surface OVER leaves source IN coverage, mul_un8(source, alpha).
+    `per_run`: libcairo composites the shape piece by piece -- under CAIRO_ANTIALIAS_NONE span by span, and in either mode a
+    rectilinear outline on whole pixels box by box -- and not once through a mask.  dict of
+        truth         libcairo: pixman asks the walker for the pixels with coverage only -- through a mask, one walker per row of the
+                      rectangle that skips the others; piece by piece, a walker per covered run of a row (source's per_run)
+        every_sample  the device's documented rule ("Gradient spread modes"): a walker that sees every sample of the row
+                      from the rectangle's left edge on, covered or not
+        caveat        H x W bool, where the two differ: a covered run that begins exactly on a stop in an odd reflected period
+    all premultiplied R, G, B, A bytes of the frame's size."""
+    x0, y0, x1, y1 = rect
+    inside = np.zeros(alpha.shape, bool)
+    inside[y0:y1, x0:x1] = True
+    assert not alpha[~inside].any(), "coverage outside the operation's rectangle"
+    a = alpha[y0:y1, x0:x1]
+    out = {}
+    for key, kw in (("truth", dict(covered=a > 0, per_run=per_run)), ("every_sample", {})):
+        img = np.zeros(alpha.shape + (4,), np.uint8)
+        img[y0:y1, x0:x1] = mul_un8(rgba_bytes(source(m, circles, stops, extend, rect, **kw)["stateful"]), a)
+        out[key] = img
+    out["caveat"] = (out["truth"] != out["every_sample"]).any(-1)
     return out
 
 

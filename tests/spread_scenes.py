@@ -14,6 +14,10 @@ something else.  Antialiased, a scanline starts at the rectangle's left edge; al
 scanline starts wherever a run of covered pixels does -- hence the whole shape.
 tools/make_spread_goldens.py checks that: the padded rendering of every plain scene equals the oracle's.
 
+The `runstart` files hold the exact boxes cut back to stepped polygons whose covered runs begin on a pixel where pixman's walker state
+decides the colour (runstart_places finds them with tests/spread_model.py).  They stay out of files(), the list of what every device
+route must reproduce byte for byte: there the device keeps its every-sample rule ("Gradient spread modes").
+
 A non-pad LINEAR gradient is refused by the product (NotImplementedGradientSpread), so the non-pad scenes are radial and focal; one
 padded linear scene rides along at LINEAR_BOUND.
 """
@@ -226,6 +230,65 @@ def _kinds_of(prefix):
     return lambda spread: {n: s for n, s in kind_scenes(spread).items() if n.startswith(prefix)}
 
 
+# ---- covered runs that begin on a sample where the walker's state decides ("Gradient spread modes": the caveat)
+def _stepped(rect, x, gap):
+    """the rectangle's first row whole, the rows below from column x on -- and, with a gap, a block at the rectangle's left edge too, so
+    that the run at x is the second of its row.  Whole pixels; the pixel extents stay the rectangle's."""
+    x0, y0, x1, y1 = rect
+    if not gap:
+        return [(x0, y0), (x1, y0), (x1, y1), (x, y1), (x, y0 + 1), (x0, y0 + 1)]
+    xg = x0 + (x - x0) // 2
+    return [(x0, y0), (x1, y0), (x1, y1), (x, y1), (x, y0 + 1), (xg, y0 + 1), (xg, y1), (x0, y1)]
+
+
+def runstart_places():
+    """[(exact case, column, the rows where a fresh reset paints otherwise there)] -- found by tests/spread_model.py in the REFLECT
+    exact cases, not written down: every column that holds a pixel where the stateful walker and a fresh reset disagree"""
+    import numpy as np
+    import spread_model as sm
+    out = []
+    for name, (_, md) in sorted(exact_cases("reflect").items()):
+        x0, y0, x1, y1 = md["rect"]
+        src = sm.source(sm.pattern_matrix(md["matrices"]), md["circles"], md["stops"], sm.REFLECT, md["rect"])
+        ys, xs = np.nonzero(src["stateful"] != src["fresh"])
+        for x in sorted(set(int(v) for v in xs)):
+            rows = [int(y) + y0 for y in ys[xs == x]]
+            if x > 0 and min(rows) > y0:         # (a run cannot begin left of the rectangle; the first row stays whole)
+                out.append((name, x + x0, rows))
+    return out
+
+
+def runstart_cases(spread, aliased=False):
+    """name -> a tests/spread_fuzz.py case: the exact case's box cut back to a stepped polygon whose covered runs begin in the column
+    of a state pixel; for the last place also with a block left of a gap in the same rows, that once more off the pixel grid, and as a box that begins in the column
+    (`edge`: no sample lies to the left inside the rectangle, so there the every-sample rule is libcairo's).  The same outlines under
+    either spread: REPEAT has no such pixel, and must show none.  `caveat`: whether REFLECT shows caveat pixels there (`rows`, `column`)."""
+    import spread_fuzz as sf
+    out = {}
+    places = runstart_places()
+    for k, (name, x, rows) in enumerate(places):
+        kind = [kd for kd in KINDS if name.startswith(kd.replace("+", "_pos").replace("-", "_neg"))][0]
+        radius, _, stops = EXACT["r" + name.split("_r", 1)[1]]
+        rect = exact_cases(spread)[name][1]["rect"]
+        stops = [(t, tuple(c) + (255,) * (4 - len(c))) for t, c in stops]
+        eps = {"radial": 0, "focal+": 192, "focal-": -192}[kind]
+        make = lambda pts, **kw: sf.make_case(W, H, aliased, spread, kind, _matrix(radius, 100.5, 22.5), eps, stops, pts, "runstart", column=x, rows=rows, **kw)
+        for gap in ((False, True) if k == len(places) - 1 else (False,)):
+            key = "%s_x%d%s" % (name, x, "_gap" if gap else "")
+            out[key] = make(_stepped(rect, x, gap), edge=False, caveat=True)
+            assert out[key]["model"]["rect"] == tuple(rect)
+        if k == len(places) - 1:                 # the gap once more with one corner off the grid: antialiased, libcairo then composites through
+            pts = _stepped(rect, x, True)        # a mask and ONE walker crosses the gap, skipping its samples
+            out["%s_x%d_mask" % (name, x)] = make(pts[:-1] + [(pts[-1][0], pts[-1][1] - 0.5)], edge=False, caveat=bool(aliased))
+        if k == len(places) - 1:                 # the rectangle itself begins in the column: every walker starts there, the device's too
+            out["%s_x%d_edge" % (name, x)] = make(_box(x, rect[1], rect[2], rect[3]), edge=True, caveat=False)
+    return out
+
+
+def runstart_scenes(spread):
+    return {name: case["scene"] for name, case in runstart_cases(spread).items()}
+
+
 GROUPS = {"radial": _kinds_of("radial"), "focal_pos": _kinds_of("focal_pos"), "focal_neg": _kinds_of("focal_neg"), "exact": exact_scenes,
           "structure": lambda spread: dict(structure_scenes(spread), **wide_scenes(spread))}
 
@@ -247,5 +310,13 @@ def files():
     return out
 
 
+def runstart_files():
+    """the same for the run-start scenes.  They are NOT in files(): the device paints them by its every-sample rule, a whole colour
+    away from libcairo in the caveat pixels of spread_model.frame (tests/test_spread_fuzz_gpu.py pins both)"""
+    return {"cairo_spread_%s%s_runstart" % ("aliased_" if aliased else "", spread): ((lambda s=spread: runstart_scenes(s)), aliased)
+            for aliased in (False, True) for spread in SPREADS}
+
+
 def goldens():
-    return {fname: {name: cairo_render(sc, aliased) for name, sc in sorted(make().items())} for fname, (make, aliased) in files().items()}
+    return {fname: {name: cairo_render(sc, aliased) for name, sc in sorted(make().items())}
+            for fname, (make, aliased) in dict(files(), **runstart_files()).items()}

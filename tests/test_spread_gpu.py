@@ -1,6 +1,7 @@
 """Gradient spread modes on the device (raster_common.hip, spread_walker_pixel: every k2_tiles instance from 2 up runs it).
 
-Every libcairo golden of tests/spread_scenes.py -- reflected and repeated radial and focal gradients, antialiased and aliased -- through
+Every libcairo golden of tests/spread_scenes.py's files() (the run-start scenes, where the device keeps a rule of its own, and random
+frames are in tests/test_spread_fuzz_gpu.py) -- reflected and repeated radial and focal gradients, antialiased and aliased -- through
 render (also with the instance forced to 2), swfr_render_edges (+ resident frames), SWFR_GRAPHS=1, two-band handles (contiguous and
 interleaved) and render_batch with unlike frames (padded and spread gradients, and plain frames, in one launch); the structure file
 once through each of the instances 3 to 6.  Zero differing bytes; the padded linear scene alone stays at LINEAR_BOUND.

@@ -1,7 +1,9 @@
 """tests/spread_model.py -- pixman's radial gradient under REPEAT and REFLECT in Python integers and numpy.float32 -- against the
 committed libcairo goldens of the exact-sample boxes and against live libcairo on random stops and matrices (skipped where libcairo is
 absent), zero differing bytes; and the count DESIGN.md quotes: on how many pixels a walker that keeps its state along the scanline
-(libcairo's, the rule) and a fresh reset per pixel disagree.  No GPU, no product code."""
+(libcairo's, the rule) and a fresh reset per pixel disagree.  And the frame reference of the device fuzz (tests/spread_fuzz.py: spread_model.frame over a coverage
+made without libcairo) against live libcairo's whole frame, on the generator's random cases and on the aimed run-start scenes, zero
+differing bytes, with the count of caveat pixels -- where the device's every-sample rule paints otherwise.  No GPU, no kernel."""
 import ctypes
 
 import numpy as np
@@ -12,6 +14,7 @@ import spread_scenes as ss
 
 EXTEND = {"reflect": sm.REFLECT, "repeat": sm.REPEAT}
 CASES = 2000                                     # per gradient kind and spread, against live libcairo
+FRAMES = 130                                     # per spread, kind, antialias mode and frame size: 1 560 frames a spread
 
 
 @pytest.mark.parametrize("spread", ss.SPREADS)
@@ -107,3 +110,65 @@ def test_model_is_libcairo_on_random_gradients(spread, kind):
         done += 1
     print("spread model,", spread, kind, "random gradients:", CASES, "cases,", CASES * (rect[2] - rect[0]) * (rect[3] - rect[1]), "pixels,", ends,
           "samples on an interval end,", state, "pixels a fresh reset paints otherwise")
+
+
+@pytest.mark.parametrize("kind", ss.KINDS)
+@pytest.mark.parametrize("spread", ss.SPREADS)
+def test_composed_frames_are_libcairo_on_random_cases(spread, kind):
+    """what tests/test_spread_fuzz_gpu.py holds the device against (its cases are the first of these) is what libcairo paints: the whole
+    frame, and the coverage that went into it"""
+    from oracle import cairo_backend as cb
+    if not cb.available():
+        pytest.skip("libcairo not available")
+    import spread_fuzz as sf
+    done = caveat = covered = piecewise = 0
+    shapes, strips, tiles, many_stops = {}, 0, 0, 0
+    for aliased in (False, True):
+        for size in sf.SIZES:
+            for case in sf.cases(spread, kind, aliased, size, FRAMES):
+                e = sf.expected(case)
+                msg = (spread, kind, aliased, size, case["index"], case["shape"])
+                assert (e["alpha"] == ss.cairo_render(case["white"], aliased)[..., 3]).all(), msg
+                assert (e["truth"] == ss.cairo_render(case["scene"], aliased)).all(), msg
+                assert not e["caveat"][e["alpha"] == 0].any()
+                done += 1
+                caveat += int(e["caveat"].sum())
+                covered += int((e["alpha"] > 0).sum())
+                piecewise += case["per_run"]
+                shapes[case["shape"]] = shapes.get(case["shape"], 0) + 1
+                sx, sy = sf.crossings(case)
+                strips, tiles, many_stops = strips + sx, tiles + sy, many_stops + (len(case["model"]["stops"]) > 12)
+    print("spread frames,", spread, kind, "random cases:", done, "frames,", covered, "covered pixels,", caveat, "caveat pixels;", shapes, piecewise,
+          "composited piece by piece,", strips, "across a strip boundary,", tiles, "across a tile boundary,", many_stops, "with 13 to 16 stops")
+    assert done == 4 * FRAMES and set(shapes) == set(sf.SHAPES) and strips and tiles and many_stops
+    assert caveat <= covered // 1000, "caveat pixels are no longer rare: the device fuzz would be vacuous"
+
+
+@pytest.mark.parametrize("spread", ss.SPREADS)
+def test_composed_frames_are_libcairo_on_the_run_start_scenes(spread):
+    """the aimed scenes: the composed frame is the committed golden (and live libcairo, where there is one); under REFLECT every scene
+    has caveat pixels, those in the column its runs begin in at the rows the model named -- bar the `edge` scene, whose rectangle begins
+    there: it shows libcairo's colour of the stepped scenes without a caveat, and the `mask` scene when antialiased, where one walker
+    crosses the gap and arrives as the device's does; under REPEAT there is none"""
+    from oracle import cairo_backend as cb
+    import spread_fuzz as sf
+    for aliased in (False, True):
+        gold = np.load(ss.golden_path("cairo_spread_%s%s_runstart" % ("aliased_" if aliased else "", spread)))
+        cases = ss.runstart_cases(spread, aliased)
+        assert sorted(cases) == sorted(gold.files) and len(cases) >= 5 and {n.rsplit("_", 1)[1] for n in cases} >= {"gap", "mask", "edge"}
+        for name, case in sorted(cases.items()):
+            e = sf.expected(case)
+            assert (e["truth"] == gold[name]).all(), (name, aliased)
+            if cb.available():
+                assert (gold[name] == ss.cairo_render(case["scene"], aliased)).all(), (name, aliased)
+            where = [(int(y), int(x)) for y, x in np.argwhere(e["caveat"])]
+            print("spread frames,", spread, "aliased" if aliased else "antialiased", name, "caveat pixels", where)
+            assert where == ([(y, case["column"]) for y in case["rows"]] if spread == "reflect" and case["caveat"] else []), name
+            if spread == "reflect" and case["edge"]:                 # libcairo's colour of the stepped scene, not the every-sample one
+                step = sf.expected(cases[name[:-len("_edge")]])
+                for y in case["rows"]:
+                    at = (y, case["column"])
+                    assert (gold[name][at] == step["truth"][at]).all() and (gold[name][at] != step["every_sample"][at]).any(), name
+    # the runs begin in a strip other than the rectangle's first (64-pixel strips), and the scenes stay out of the exact routes
+    assert any(c["model"]["rect"][0] // 64 != c["column"] // 64 for c in ss.runstart_cases(spread).values())
+    assert not any(f.endswith("_runstart") for f in ss.files())

@@ -10,6 +10,8 @@ usage: python tools/make_spread_goldens.py [--check]
   cairo_spread_<spread>_exact.npz     pixel-aligned boxes whose samples fall exactly on stops and on period seams
   cairo_spread_<spread>_structure.npz rotated and skewed matrices, an object matrix, a colour transform, "blend_mode", "layer", "mask",
                                       "opacity", a padded gradient beside a spread one, the padded linear extension, a 300 x 40 frame
+  cairo_spread_<spread>_runstart.npz  the exact boxes cut back to stepped polygons whose covered runs begin on a pixel where the walker's
+                                      state decides the colour (tests/spread_scenes.py, runstart_cases)
   cairo_spread_aliased_*.npz          the same under CAIRO_ANTIALIAS_NONE
   No file may be larger than the largest blend golden.
 
@@ -18,6 +20,9 @@ The gates, before anything is written and under --check; a scene that fails one 
                   from its padded rendering, and its reflect rendering from its repeat rendering, in at least one pixel
   exact samples   tests/spread_model.py must paint every box of the exact file as libcairo does, byte for byte, and report at least one
                   sample exactly on an interval end per gradient kind and spread
+  run starts      tests/spread_model.py's frame() must compose every run-start scene as libcairo paints it, in both antialias modes, from
+                  a coverage made without libcairo; its caveat pixels -- where a walker that sees every sample of the rectangle paints
+                  otherwise -- are printed: some under REFLECT in either mode, none under REPEAT
   pixman's range  the padded rendering of every scene of the kind and exact files must equal the oracle's (a gradient whose shape leaves
                   pixman's 16.16 range is not what libcairo says it is: tests/spread_scenes.py)
 """
@@ -76,6 +81,21 @@ def gates():
         for kind, n in sorted(hits.items()):
             if n == 0:
                 print("NO SAMPLE ON AN INTERVAL END", spread, kind)
+                bad += 1
+    # run starts
+    import spread_fuzz as sf
+    for spread in ss.SPREADS:
+        for aliased in (False, True):
+            total = 0
+            for name, case in sorted(ss.runstart_cases(spread, aliased).items()):
+                e = sf.expected(case)
+                n = int((e["truth"] != ss.cairo_render(case["scene"], aliased)).any(-1).sum())
+                where = [(int(y), int(x)) for y, x in np.argwhere(e["caveat"])]
+                print("model" if n == 0 else "MODEL DIFFERS", spread, "aliased" if aliased else "antialiased", name, "differing pixels", n, "caveat pixels", where)
+                bad += n != 0
+                total += len(where)
+            if (total == 0) != (spread == "repeat"):
+                print("CAVEAT PIXELS", spread, aliased, total)
                 bad += 1
     return bad
 
