@@ -83,6 +83,13 @@ typedef struct {
                                             gradient with a spread other than pad is SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"
                                             (refused, never approximated).  Ignored for solid and bitmap fills.  The field lies in what was
                                             the struct's tail padding: size and offsets are unchanged.  DESIGN.md, "Gradient spread modes" */
+    uint8_t pad;                         /* bitmap: 1 = a padded ("clipped") fill, SWF fill types 0x41 / 0x43 -- the bitmap's Cairo pattern with
+                                            cairo_pattern_set_extend(CAIRO_EXTEND_PAD): a sample outside the bitmap reads the nearest edge
+                                            texel (the coordinates clamped per axis) and the fill is not cut to the bitmap's rectangle.
+                                            0: `repeating` decides as before (EXTEND_REPEAT / EXTEND_NONE, the reference's behaviour), byte
+                                            for byte.  pad = 1 together with repeating != 0, or pad > 1: SWFR_ERR_INVALID, "InvalidBitmapPad".
+                                            Ignored for solid and gradient fills.  Offset 59, in the remaining tail padding: size (64) and
+                                            every other offset are unchanged.  DESIGN.md, "Padded bitmap fills" */
 } swfr_fill_style;
 
 typedef struct {
@@ -310,7 +317,7 @@ typedef struct {
     float stop_rgba[SWFR_MAX_STOPS][4];  /* straight, 0..1 */
     uint32_t bitmap;                     /* registered bitmap id; 65536 + k: texture k of the colour-transformed bitmaps of the frame the
                                             handle's last scene walk built (swfr_build_frame), valid on that handle until its next walk */
-    uint32_t extend;                     /* bitmap: 0 none, 1 repeat.  Radial / linear: 0 pad, 1 repeat, 2 reflect (cairo_pattern_set_extend);
+    uint32_t extend;                     /* bitmap: 0 none, 1 repeat, 2 pad (CAIRO_EXTEND_PAD: swfr_fill_style::pad).  Radial / linear: 0 pad, 1 repeat, 2 reflect (cairo_pattern_set_extend);
                                             any other value on a gradient style is SWFR_ERR_INVALID at upload, and 1 or 2 on a LINEAR
                                             style SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread" */
 } swfr_style;

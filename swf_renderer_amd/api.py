@@ -94,7 +94,7 @@ class ColorStop(C.Structure):
 class FillStyle(C.Structure):
     _fields_ = [("type", C.c_uint32), ("color", Rgba8), ("morph_color", Rgba8), ("matrix", Matrix), ("n_stops", C.c_uint32),
                 ("stops", C.POINTER(ColorStop)), ("focal_point", C.c_int32), ("bitmap_id", C.c_uint32),
-                ("repeating", C.c_uint8), ("smoothed", C.c_uint8), ("spread", C.c_uint8)]
+                ("repeating", C.c_uint8), ("smoothed", C.c_uint8), ("spread", C.c_uint8), ("pad", C.c_uint8)]
 
 
 class LineStyle(C.Structure):
@@ -350,6 +350,7 @@ def _fill(arena, s):
         f.bitmap_id = s["bitmap_id"]
         f.repeating = 1 if s.get("repeating") else 0
         f.smoothed = 1 if s.get("smoothed") else 0
+        f.pad = 1 if s.get("pad") else 0                             # a clipped fill (SWF fill types 0x41 / 0x43): CAIRO_EXTEND_PAD
     return f
 
 

@@ -101,7 +101,7 @@ struct DevFilter {
     // what the bitmap shader needs of the style and of the bitmap table, so that one load of this record is all it waits for
     const uint32_t* pixels;  // premultiplied ARGB, tight rows (bitmap styles)
     uint32_t width, height;
-    uint32_t extend;         // bitmap: 0 none, 1 repeat; gradient: 0 pad, 1 repeat, 2 reflect (swfr_style::extend)
+    uint32_t extend;         // bitmap: 0 none, 1 repeat, 2 pad; gradient: 0 pad, 1 repeat, 2 reflect (swfr_style::extend)
     uint32_t kind;           // SWFR_STYLE_*
     uint32_t pad2[2];
 };

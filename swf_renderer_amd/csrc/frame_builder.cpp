@@ -657,7 +657,7 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         std::memcpy(st.inv, m, sizeof m);
         const int32_t lut = stack_.back().lut;
         st.bitmap = lut < 0 ? s.bitmap_id : VARIANT_BASE + variant_of(s.bitmap_id, lut);
-        st.extend = s.repeating ? 1 : 0;
+        st.extend = s.pad ? 2 : s.repeating ? 1 : 0;               // (pad and repeating together are refused when the shape is registered)
         styles_.push_back(st);
         style_index = uint32_t(styles_.size() - 1);
     } else {
@@ -717,8 +717,9 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
     y0 = std::max(y0, 0);
     x1 = std::min(x1, int(w_));
     y1 = std::min(y1, int(h_));
-    if (s.type == SWFR_FILL_BITMAP && !s.repeating) {
-        // OVER is bounded by its source (_cairo_pattern_get_extents of an EXTEND_NONE surface pattern): the bitmap's rectangle in
+    if (s.type == SWFR_FILL_BITMAP && !s.repeating && !s.pad) {
+        // OVER is bounded by its source (_cairo_pattern_get_extents of an EXTEND_NONE surface pattern; a repeating or padded one is
+        // unbounded): the bitmap's rectangle in
         // device space; an axis the filter magnifies is padded by half a source pixel and rounded to the nearest pixel edge,
         // the others are rounded out
         const swfr_style& st = styles_[style_index];

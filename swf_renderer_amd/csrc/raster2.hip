@@ -1132,7 +1132,8 @@ __device__ __forceinline__ void bilinear_taps_at(const DevFilter& flt, long long
         xa = wrap_mod(xa, bw, 1.0f / (float)bw); xb = xa + 1 == bw ? 0 : xa + 1;
         ya = wrap_mod(ya, bh, 1.0f / (float)bh); yb = ya + 1 == bh ? 0 : ya + 1;
     } else {
-        wf |= (xa < 0 || xa >= bw ? 1u << 14 : 0u) | (xb < 0 || xb >= bw ? 1u << 15 : 0u) | (ya < 0 || ya >= bh ? 1u << 16 : 0u) | (yb < 0 || yb >= bh ? 1u << 17 : 0u);
+        // (a padded bitmap, extend 2, reads the clamped texels as they are: no outside flags -- wave-uniform, like `repeat`)
+        if (flt.extend != 2) wf |= (xa < 0 || xa >= bw ? 1u << 14 : 0u) | (xb < 0 || xb >= bw ? 1u << 15 : 0u) | (ya < 0 || ya >= bh ? 1u << 16 : 0u) | (yb < 0 || yb >= bh ? 1u << 17 : 0u);
         xa = min(max(xa, 0), bw - 1); xb = min(max(xb, 0), bw - 1); ya = min(max(ya, 0), bh - 1); yb = min(max(yb, 0), bh - 1);
     }
     const uint32_t rowa = (uint32_t)ya * flt.width, rowb = (uint32_t)yb * flt.width;     // (a bitmap has fewer than 2^32 texels)
@@ -1203,7 +1204,13 @@ __device__ __forceinline__ uint32_t shade_bitmap(uint32_t style_index, const Sou
                 int rx = x1 + j;
                 uint32_t pixel;
                 if (repeat) { rx = ((rx % bw) + bw) % bw; pixel = bm.pixels[(size_t)ry * bm.width + rx]; }
-                else pixel = (rx < 0 || ry < 0 || rx >= bw || ry >= bh) ? 0u : bm.pixels[(size_t)ry * bm.width + rx];
+                else {
+                    // none and pad read the texel at the clamped coordinates (always inside the bitmap); outside, none takes transparent
+                    // black instead and pad -- CAIRO_EXTEND_PAD: the nearest edge texel, per axis -- keeps it
+                    const int cx = min(max(rx, 0), bw - 1), cy = min(max(ry, 0), bh - 1);
+                    pixel = bm.pixels[(size_t)cy * bm.width + cx];
+                    if (flt.extend != 2 && (cx != rx || cy != ry)) pixel = 0u;
+                }
                 const int f = (int)((fy * fx + 0x8000) >> 16);
                 sr += (int)((pixel >> 16) & 255u) * f; sg += (int)((pixel >> 8) & 255u) * f; sb += (int)(pixel & 255u) * f; sa += (int)(pixel >> 24) * f;
             }

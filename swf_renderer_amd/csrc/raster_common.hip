@@ -699,6 +699,8 @@ __device__ __noinline__ uint32_t shade(const swfr_style& s, uint32_t style_index
         t = fmin(fmax(t, 0.0), 1.0);
         return gradient_color(s, t);
     }
+    // (No kernel instance reaches this branch for a bitmap today: they all sample through raster2.hip's shade_bitmap.  Its extend
+    //  2 -- CAIRO_EXTEND_PAD, the coordinates clamped per axis -- is therefore held by reading alone, not by any test.)
     const DevBitmap bm = bitmaps.bitmaps[s.bitmap];
     const DevFilter flt = bitmaps.filters[style_index];
     // pixman's own 16.16 sample position of this pixel's centre
@@ -721,12 +723,14 @@ __device__ __noinline__ uint32_t shade(const swfr_style& s, uint32_t style_index
             if (!fy) continue;
             int ry = y1 + i;
             if (s.extend == 1) ry = ((ry % (int)bm.height) + (int)bm.height) % (int)bm.height;
+            else if (s.extend == 2) ry = min(max(ry, 0), (int)bm.height - 1);      // CAIRO_EXTEND_PAD: the nearest edge texel, per axis
             for (int j = 0; j < flt.cw; ++j) {
                 const int32_t fx = xp0[j];
                 if (!fx) continue;
                 int rx = x1 + j;
                 uint32_t pixel;
                 if (s.extend == 1) { rx = ((rx % (int)bm.width) + (int)bm.width) % (int)bm.width; pixel = bm.pixels[(size_t)ry * bm.width + rx]; }
+                else if (s.extend == 2) pixel = bm.pixels[(size_t)ry * bm.width + min(max(rx, 0), (int)bm.width - 1)];
                 else pixel = (rx < 0 || ry < 0 || rx >= (int)bm.width || ry >= (int)bm.height) ? 0u : bm.pixels[(size_t)ry * bm.width + rx];
                 const int f = (int)((fy * fx + 0x8000) >> 16);
                 sr += (int)((pixel >> 16) & 255u) * f; sg += (int)((pixel >> 8) & 255u) * f; sb += (int)(pixel & 255u) * f; sa += (int)(pixel >> 24) * f;
@@ -748,6 +752,8 @@ __device__ __noinline__ uint32_t shade(const swfr_style& s, uint32_t style_index
             xx = ((xx % (int)bm.width) + (int)bm.width) % (int)bm.width;
             yy = ((yy % (int)bm.height) + (int)bm.height) % (int)bm.height;
             c[k] = bm.pixels[(size_t)yy * bm.width + xx];
+        } else if (s.extend == 2) {
+            c[k] = bm.pixels[(size_t)min(max(yy, 0), (int)bm.height - 1) * bm.width + min(max(xx, 0), (int)bm.width - 1)];
         } else {
             c[k] = (xx < 0 || yy < 0 || xx >= (int)bm.width || yy >= (int)bm.height) ? 0u : bm.pixels[(size_t)yy * bm.width + xx];
         }

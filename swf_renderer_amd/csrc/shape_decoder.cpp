@@ -2,6 +2,7 @@
 #include "shape_decoder.hpp"
 
 #include <charconv>
+#include <cstddef>
 #include <cmath>
 #include <deque>
 #include <stdexcept>
@@ -24,6 +25,10 @@ struct Layer {
     std::vector<StyleBucket> fills, lines;
 };
 
+// spread and pad lie in what was the struct's tail padding (include/swfr.h): the layout callers compiled against must not move
+static_assert(sizeof(swfr_fill_style) == 64 && offsetof(swfr_fill_style, repeating) == 56 && offsetof(swfr_fill_style, smoothed) == 57 &&
+              offsetof(swfr_fill_style, spread) == 58 && offsetof(swfr_fill_style, pad) == 59, "swfr_fill_style layout");
+
 OwnedFill own_fill(const swfr_fill_style& s, bool morph) {
     OwnedFill f;
     f.style = s;
@@ -32,6 +37,9 @@ OwnedFill own_fill(const swfr_fill_style& s, bool morph) {
     const bool gradient = s.type != SWFR_FILL_SOLID && s.type != SWFR_FILL_BITMAP;
     if (gradient && s.spread > 2) throw std::runtime_error("UnknownGradientSpread");   // swf-tree GradientSpread: 0 pad, 1 reflect, 2 repeat
     if (!gradient) f.style.spread = 0;
+    // a clipped bitmap fill (SWF fill types 0x41 / 0x43): CAIRO_EXTEND_PAD; a fill cannot both repeat and pad
+    if (s.type == SWFR_FILL_BITMAP && (s.pad > 1 || (s.pad && s.repeating))) throw std::runtime_error("InvalidBitmapPad");
+    if (s.type != SWFR_FILL_BITMAP) f.style.pad = 0;
     if (s.n_stops && s.stops) f.stops.assign(s.stops, s.stops + s.n_stops);
     f.style.stops = nullptr;
     f.style.n_stops = uint32_t(f.stops.size());
