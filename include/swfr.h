@@ -291,7 +291,10 @@ typedef struct {
     uint32_t kind;                       /* SWFR_PATH_* */
     uint32_t fill_rule;                  /* 0 nonzero, 1 even-odd */
     uint32_t style;                      /* index into styles */
-    uint32_t lerp;                       /* bits 0..7: 1: SOURCE-lerp blend (opaque source or clear surface), 0: OVER;
+    uint32_t lerp;                       /* bits 0..7: 1: SOURCE-lerp blend (opaque source or clear surface), 0: OVER.  With a bitmap or
+                                            gradient style 1 means mul_un8(source pixel, coverage) with the destination ignored, and
+                                            is defined only where the surface (the frame's, or inside a group the group's) is
+                                            still clear under the path's rectangle: swfr_build_frame sets it while the surface is clear;
                                             bits 8..15: operator (SWFR_OP_*), 0: what bits 0..7 say.  An operator needs lerp bits 0
                                             (SWFR_ERR_INVALID at upload otherwise); the rest of the word must be 0 */
     int32_t x_min, y_min, x_max, y_max;  /* pixel rectangle of the converter (polygon extents ∩ frame) */

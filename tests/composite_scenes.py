@@ -6,6 +6,10 @@
 - RawFrame and the raw_* corpora: frames written directly as swfr_upload_edges arrays, aimed at the walk of k2_tiles<3|4> over one
   strip's list: groups whose BEGIN, first member and END fall on either side of the staging rounds (16 entries), the class-byte chunks
   (64) and the prefetched class bytes (128); nesting with the first path of a strip at every level; opaque covers around groups.
+- shaded=True gives the trees bitmap and radial / focal leaves; a RawFrame path may carry a bitmap or radial style of its own
+  (bitmap_style, radial_style), and SHADED_CLASSES / shaded_frames aim one such member at each branch of the bitmap fetch of the tile
+  pass, in every setting a member can stand in (tests/test_shaded_composite_fuzz_gpu.py); shaded_reach counts, from the sample positions
+  of tests/pad_model.py, which branch each wavefront takes.
 - strip_lists / strip_reach: what a frame's strips see, from the arrays alone (by path rectangle, as helpers.strip_path_counts), so
   that a test can show that its frames reach the positions it is about.
 """
@@ -33,15 +37,101 @@ def _cxform(rng):
     return d
 
 
-def rand_composited_scene(rng, width=None, height=None, min_children=0, leaves=None):
+SHADED_BITMAP_SIZES = ((1, 1), (1, 6), (5, 1), (2, 2), (3, 3), (3, 5), (7, 5), (7, 7), (47, 48))      # (width, height)
+SPREAD_NAMES = ("pad", "reflect", "repeat")
+
+
+def rand_texels(rng, bw, bh, opaque=False):
+    """(bh, bw, 4) straight RGBA bytes: a third of the texels translucent, some of those alpha 0 (as pad_scenes.random_box_case's)"""
+    px = rng.integers(0, 256, (bh, bw, 4)).astype(np.uint8)
+    if opaque:
+        px[..., 3] = 255
+    else:
+        px[..., 3] = np.where(rng.integers(0, 3, (bh, bw)) == 0, np.where(rng.integers(0, 4, (bh, bw)) == 0, 0, px[..., 3]), 255)
+    return px
+
+
+def _shaded_leaf(rng, W, H, bitmaps, shape, polygon):
+    """a shape with a bitmap fill (all three edge rules, magnified and minified, rotated and mirrored, often at negative offsets) or a
+    radial / focal gradient with one of the three spreads, the polygon within reach of pixman's 16.16 positions"""
+    if rng.integers(0, 2):
+        bid = int(rng.choice(sorted(bitmaps)))
+        bw, bh = bitmaps[bid][:2]
+        if rng.integers(0, 3) == 0:
+            kx, ky = float(rng.uniform(0.3, 0.74)), float(rng.uniform(0.3, 3.0))                # minified: the convolution
+            if rng.integers(0, 2):
+                kx, ky = ky, kx
+        else:
+            kx, ky = float(rng.uniform(0.76, 12.0)), float(rng.uniform(0.76, 12.0))
+        if bw > 16:
+            kx, ky = min(kx, 3.0), min(ky, 3.0)
+        t = float(rng.uniform(-3.2, 3.2)) if rng.integers(0, 3) == 0 else 0.0
+        c, s = np.cos(t), np.sin(t)
+        if rng.integers(0, 4) == 0:
+            kx = -kx                                                                          # mirrored
+        extend = ("none", "repeat", "pad")[int(rng.integers(0, 3))]
+        matrix = scenarios._m(20 * kx * c, 20 * ky * c, int(rng.integers(-W * 6, W * 20)), int(rng.integers(-H * 6, H * 20)), 20 * kx * s, -20 * ky * s)
+        fill = {"type": "bitmap", "bitmap_id": bid, "repeating": extend == "repeat", "smoothed": True, "matrix": matrix}
+        if extend == "pad":
+            fill["pad"] = True
+        if rng.integers(0, 3) == 0:
+            x0, y0 = float(rng.integers(-4, W - 8)), float(rng.integers(-4, H - 4))
+            x1, y1 = x0 + float(rng.integers(8, W)), y0 + float(rng.integers(3, H))
+            pts = np.array([(x0, y0), (x1, y0), (x1, y1), (x0, y1)])
+        else:
+            pts = polygon(bool(rng.integers(0, 2)))
+        return shape(scenarios._poly_shape(np.rint(pts * 20), fill))
+    focal = bool(rng.integers(0, 2))
+    radius = float(rng.uniform(6, 0.45 * max(W, H)))
+    cx, cy = float(rng.uniform(0, W)), float(rng.uniform(0, H))
+    n = int(rng.integers(1, 6))
+    ratios = sorted(int(v) for v in rng.integers(0, 256, n))
+    if n > 2 and rng.integers(0, 3) == 0:
+        ratios[1] = ratios[0]
+    colors = [(ratios[i], (int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.choice([255, 255, 128, 0, 37])))) for i in range(n)]
+    t = float(rng.uniform(-3.2, 3.2)) if rng.integers(0, 2) else 0.0
+    c, s = np.cos(t), np.sin(t)
+    k = radius * 20 / 16384.0
+    fill = {"type": "focal-gradient" if focal else "radial-gradient", "gradient": dict(scenarios._grad(colors), spread=SPREAD_NAMES[int(rng.integers(0, 3))]),
+            "matrix": scenarios._m(k * c, k * c, round(cx * 20), round(cy * 20), k * s, -k * s)}
+    if focal:
+        fill["focal_point"] = {"epsilons": int(rng.integers(-200, 201))}
+    reach = (0.8 if focal else 1.25) * radius                        # (rotated: within two radii of the centre and of the focus on both axes)
+    m = int(rng.integers(3, 7))
+    pts = np.stack([cx + rng.uniform(-reach, reach, m), cy + rng.uniform(-reach, reach, m)], -1)
+    return shape(scenarios._poly_shape(np.rint(pts * 20), fill))
+
+
+def _without_transforms_around_bitmaps(obj):
+    """the tree with "color_transform" taken off every object that holds a bitmap fill: a recoloured bitmap is a variant texture of the
+    handle that walked the stage, which neither tests/frame_model.py nor another handle can be given"""
+    def holds(o):
+        if isinstance(o, dict):
+            return (o.get("type") == "bitmap" and "bitmap_id" in o) or any(holds(v) for v in o.values())
+        return isinstance(o, list) and any(holds(v) for v in o)
+    if isinstance(obj, list):
+        return [_without_transforms_around_bitmaps(o) for o in obj]
+    if isinstance(obj, dict):
+        return {k: _without_transforms_around_bitmaps(v) for k, v in obj.items() if not (k == "color_transform" and holds(obj))}
+    return obj
+
+
+def rand_composited_scene(rng, width=None, height=None, min_children=0, leaves=None, shaded=False):
     """One frame: a random tree over about `leaves` shapes.  Always present: a translucent first path on the clear surface (sometimes
     inside a layer), an empty layer, layers wholly and partly off the frame, clear sources (alpha 0, plain and under an operator),
     opaque covers of the whole frame below, between, inside and above layers, colour-transform wrappers, all nine operators on layers
     and "blend_mode" containers, layers nested up to four deep.  The width is no multiple of 64 (often none of 4), the height no
-    multiple of 16 (often none of 8).  min_children: at least so many children of the stage (a threaded build cuts pieces of 64)."""
+    multiple of 16 (often none of 8).  min_children: at least so many children of the stage (a threaded build cuts pieces of 64).
+    shaded: two leaves in five are bitmap fills (texels registered as straight RGBA, sc["raw_bitmaps"]) and radial / focal gradients
+    (_shaded_leaf); off, every seed draws what it always drew."""
     W = width if width is not None else int(rng.integers(1, 4)) * 64 + int(rng.integers(1, 64))
     H = height if height is not None else int(rng.integers(1, 5)) * 16 + int(rng.integers(1, 16))
     rgba = scenarios._rgba
+    raw_bitmaps = {}
+    if shaded:
+        for k, i in enumerate(rng.choice(len(SHADED_BITMAP_SIZES), 4, replace=False)):
+            bw, bh = SHADED_BITMAP_SIZES[int(i)]
+            raw_bitmaps[21 + k] = (bw, bh, rand_texels(rng, bw, bh, opaque=k == 0).tobytes())
 
     def color(alpha=None):
         a = alpha if alpha is not None else int(rng.choice([255, 255, int(rng.integers(1, 255)), int(rng.integers(1, 255)), 1, 254, 0]))
@@ -66,6 +156,8 @@ def rand_composited_scene(rng, width=None, height=None, min_children=0, leaves=N
         return shape(scenarios._poly_shape(np.rint(pts * 20), {"type": "solid", "color": color(255)}))
 
     def leaf():
+        if shaded and rng.integers(0, 5) < 2:
+            return _shaded_leaf(rng, W, H, raw_bitmaps, shape, polygon)
         kind = ("solid", "rect_fill", "rect_stroke", "stroke")[int(rng.integers(0, 4))]
         big = bool(rng.integers(0, 3) == 0)
         if kind == "solid":
@@ -150,7 +242,57 @@ def rand_composited_scene(rng, width=None, height=None, min_children=0, leaves=N
     while len(kids) < min_children:
         budget[0] = 8
         kids += members(0)
+    if shaded:
+        return dict(width=W, height=H, raw_bitmaps=raw_bitmaps, stage={"children": _without_transforms_around_bitmaps(kids)})
     return dict(width=W, height=H, stage={"children": kids})
+
+
+def cairo_render_shaded(sc, aliased=False):
+    """premultiplied RGBA of a shaded tree through libcairo: the canvas replay of the fade scenes over a CairoBackend whose surface
+    patterns take CAIRO_EXTEND_PAD where the fill says "pad" and whose gradients take their fill's spread"""
+    import ctypes
+
+    import blend_scenes as bs
+    import fade_scenes as fs
+    import mask_scenes as ms
+    import pad_scenes as ps
+    import spread_scenes as ss
+    from oracle import cairo_backend as cb
+
+    class Backend(cb.CairoBackend):
+        surface_extend, gradient_extend = None, ss.CAIRO_EXTEND["pad"]
+
+        def set_fill_pattern(self, bitmap, repeat):
+            super().set_fill_pattern(bitmap, repeat)
+            if self.surface_extend is not None:
+                self._fill = self._fill[:2] + (self.surface_extend,)
+
+        def set_fill_radial(self, *a):
+            super().set_fill_radial(*a)
+            self.lib.cairo_pattern_set_extend(self._fill[1], self.gradient_extend)
+
+    class Replay(fs.FadeReplay):
+        def _draw_path(self, path):
+            fill = path.get("fill", {})
+            self.be.surface_extend = ps.CAIRO_EXTEND["pad"] if fill.get("repeating") == "pad" else None
+            self.be.gradient_extend = ss.CAIRO_EXTEND[(fill.get("gradient") or {}).get("spread", "pad")]
+            return super()._draw_path(path)
+
+    be = Backend(sc["width"], sc["height"])
+    try:
+        if aliased:
+            f = be.lib.cairo_set_antialias
+            f.restype, f.argtypes = None, [ctypes.c_void_p, ctypes.c_int]
+            f(be.cr, bs.CAIRO_ANTIALIAS_NONE)
+        low = ms._lowering(sc.get("bitmaps", []))
+        stage = low.lower(ps.for_cairo(sc["stage"]))
+        rp = Replay(be, linear_extension=True)
+        for bid, (w, h, px) in list(low.extra.items()) + list(sc.get("raw_bitmaps", {}).items()):
+            rp.bitmaps[bid] = be.create_bitmap(w, h, px)
+        rp.render(stage)
+        return be.premultiplied_rgba().copy()
+    finally:
+        be.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------- raw frames
@@ -165,6 +307,7 @@ class RawFrame:
         self.W, self.H = W, H
         self.rows, self.paths, self.pixels, self.open = [], [], [], []
         self.masks = []                                              # per open group: the index of its MASK marker, or None
+        self.bitmaps = {}                                            # id -> (width, height, straight RGBA bytes): what the bitmap styles name
 
     @staticmethod
     def _fx(v):
@@ -178,16 +321,17 @@ class RawFrame:
             y0 = y1 = min(max(y0, 0), self.H)
         return x0, y0, x1, y1
 
-    def _path(self, kind, rows, rect, argb, lerp, op, even_odd=False):
+    def _path(self, kind, rows, rect, argb, lerp, op, even_odd=False, style=None):
+        """style: for a bitmap or radial path, rect -> its api.Style (one style per path: it belongs to the path's rectangle)"""
         assert not (lerp and op != "normal")
         first = len(self.rows)
         self.rows += rows
         field = int(lerp) | (bm.OPERATORS["over" if op == "normal" else op] << 8)
         self.paths.append([first, len(rows), kind, int(even_odd), len(self.pixels), field, *rect])
-        self.pixels.append(argb & 0xffffffff)
+        self.pixels.append(style(rect) if style is not None else argb & 0xffffffff)
         return self
 
-    def tor(self, pts, argb, lerp=0, op="normal", even_odd=False):
+    def tor(self, pts, argb, lerp=0, op="normal", even_odd=False, style=None):
         p = [(self._fx(x), self._fx(y)) for x, y in pts]
         rows = []
         for a, b in zip(p, p[1:] + p[:1]):
@@ -195,17 +339,17 @@ class RawFrame:
                 rows.append((a[0], a[1], b[0], b[1], a[1], b[1], 1, 0))
             elif a[1] > b[1]:
                 rows.append((b[0], b[1], a[0], a[1], b[1], a[1], -1, 0))
-        return self._path(0, rows, self._rect([q[0] for q in p], [q[1] for q in p]), argb, lerp, op, even_odd)
+        return self._path(0, rows, self._rect([q[0] for q in p], [q[1] for q in p]), argb, lerp, op, even_odd, style)
 
-    def rect_tor(self, x0, y0, x1, y1, argb, lerp=0, op="normal"):
-        return self.tor([(x0, y0), (x1, y0), (x1, y1), (x0, y1)], argb, lerp, op)
+    def rect_tor(self, x0, y0, x1, y1, argb, lerp=0, op="normal", style=None):
+        return self.tor([(x0, y0), (x1, y0), (x1, y1), (x0, y1)], argb, lerp, op, style=style)
 
-    def box(self, x0, y0, x1, y1, argb, lerp=0, op="normal"):
+    def box(self, x0, y0, x1, y1, argb, lerp=0, op="normal", style=None):
         """a box path of one box, cut to the frame (a box lies inside its path's rectangle)"""
         a = [max(self._fx(x0), 0), max(self._fx(y0), 0), min(self._fx(x1), self.W * 256), min(self._fx(y1), self.H * 256)]
         if a[0] >= a[2] or a[1] >= a[3]:
-            return self._path(1, [], self._rect([a[0]], [a[1]])[:2] * 2, argb, lerp, op)
-        return self._path(1, [(a[0], a[1], a[2], a[3], a[1], a[3], 1, 0)], self._rect([a[0], a[2]], [a[1], a[3]]), argb, lerp, op)
+            return self._path(1, [], self._rect([a[0]], [a[1]])[:2] * 2, argb, lerp, op, style=style)
+        return self._path(1, [(a[0], a[1], a[2], a[3], a[1], a[3], 1, 0)], self._rect([a[0], a[2]], [a[1], a[3]]), argb, lerp, op, style=style)
 
     def begin(self):
         self.open.append(len(self.paths))
@@ -258,7 +402,18 @@ class RawFrame:
         p = np.zeros(len(self.paths), api.PATH_DTYPE)
         for i, row in enumerate(self.paths):
             p[i] = tuple(row)
-        return e, p, [api.solid_style(px) for px in self.pixels]
+        return e, p, [px if isinstance(px, api.Style) else api.solid_style(px) for px in self.pixels]
+
+    def add_bitmap(self, texels):
+        """registers (h, w, 4) straight RGBA texels with the frame; the id a bitmap style names"""
+        bid = 31 + len(self.bitmaps)
+        self.bitmaps[bid] = (texels.shape[1], texels.shape[0], np.ascontiguousarray(texels, np.uint8).tobytes())
+        return bid
+
+    def model_bitmaps(self):
+        """the frame's bitmaps as tests/frame_model.py takes them: {id: (h, w) premultiplied 0xAARRGGBB}"""
+        import pad_model as pm
+        return {bid: pm.premultiply(np.frombuffer(px, np.uint8).reshape(h, w, 4)) for bid, (w, h, px) in self.bitmaps.items()}
 
 
 def without_markers(edges, paths, styles):
@@ -621,3 +776,343 @@ def assert_reach(rc):
     assert rc["sibling_reuse"] and rc["marker_only_between"]
     for edge in (ROUND, CHUNK, PREFETCH):                             # the blend instance: operators on both sides of the boundaries
         assert {edge - 1, edge, edge + 1} <= rc["operator_positions"], edge
+
+
+# ---------------------------------------------------------------------------------------------------------------- shaded members
+# (tests/test_shaded_composite_fuzz_gpu.py)  Each class is aimed at one branch of the bitmap fetch of the tile pass; which branch a
+# strip takes is worked out from the positions of tests/pad_model.py (strip_halves), and the matrices are drawn until it is the one.
+SHADED_CLASSES = ("bitmap_inside_plain", "bitmap_inside_translucent", "bitmap_inside_partial", "bitmap_rim_none", "bitmap_rim_repeat",
+                  "bitmap_rim_pad", "bitmap_minified", "radial_spread")
+RAW_BITMAP_SIZES = ((1, 1), (1, 5), (2, 2), (3, 3), (5, 3), (7, 7), (47, 48))          # (width, height)
+GRADIENT_R = 16384.0
+
+
+def bitmap_style(bid, extend, kx, ky, ox, oy, t=0.0):
+    """the api.Style of bitmap `bid` drawn with texels of kx x ky pixels (negative: mirrored), turned by t, the bitmap's corner at pixel
+    (ox, oy); `inv` is Cairo's pattern matrix, the inverse of that placement"""
+    import spread_model as sm
+    from swf_renderer_amd import api
+    c, s = float(np.cos(t)), float(np.sin(t))
+    st = api.Style()
+    st.kind, st.bitmap, st.extend = api.STYLE_BITMAP, bid, extend
+    st.inv[:] = sm.invert((kx * c, kx * s, -ky * s, ky * c, float(ox), float(oy)))
+    return st
+
+
+def radial_style(extend, radius, cx, cy, stops, focal=0.0, t=0.0):
+    """the api.Style of a radial (focal: a focal) gradient of `radius` pixels around pixel (cx, cy), as the frame builder writes it: the
+    circles (focal R, 0, 0) -> (0, 0, R) with R = 16384.  stops: [(ratio 0..255, (r, g, b, a) bytes, straight)]"""
+    import spread_model as sm
+    from swf_renderer_amd import api
+    c, s = float(np.cos(t)), float(np.sin(t))
+    k = radius / GRADIENT_R
+    st = api.Style()
+    st.kind, st.extend = api.STYLE_RADIAL, extend
+    st.inv[:] = sm.invert((k * c, k * s, -k * s, k * c, float(cx), float(cy)))
+    st.c0x, st.c0y, st.r0, st.c1x, st.c1y, st.r1 = focal * GRADIENT_R, 0.0, 0.0, 0.0, 0.0, GRADIENT_R
+    st.n_stops = len(stops)
+    for i, (ratio, rgba) in enumerate(stops):
+        st.stop_offset[i] = ratio / 255.0
+        for ch in range(4):
+            st.stop_rgba[i][ch] = rgba[ch] / 255.0
+    return st
+
+
+def strip_halves(st, rect, bw, bh, sx, sy):
+    """What the two row halves (four rows by 64 columns each: one wavefront's 256 samples) of the strip at (sx, sy) see of a bitmap
+    style whose path has the rectangle rect, from the sample positions of tests/pad_model.py: [(bilinear, inside)] -- whether the filter
+    is the bilinear one and whether every one of the 256 samples has its four taps strictly inside the bitmap"""
+    import pad_model as pm
+    import spread_model as sm
+    inv = tuple(float(v) for v in st.inv)
+    bilinear = pm.filter_of(inv) is None
+    (bx, by), ((m00, m01), (m10, m11)) = sm.to_pixman(inv, rect)
+    out = []
+    for h in (0, 1):
+        px, py = np.meshgrid(np.arange(sx, sx + STRIP_W, dtype=np.int64), np.arange(sy + 4 * h, sy + 4 * h + 4, dtype=np.int64))
+        tx, ty = (bx + px * m00 + py * m01 - 0x8000) >> 16, (by + px * m10 + py * m11 - 0x8000) >> 16
+        out.append((bilinear, bool(((tx >= 0) & (tx <= bw - 2) & (ty >= 0) & (ty <= bh - 2)).all())))
+    return out
+
+
+def _covered_halves(rect, y0):
+    """the row halves of the strip at row y0 that the rectangle's rows meet"""
+    return [h for h in (0, 1) if rect[1] < y0 + 4 * h + 4 and rect[3] > y0 + 4 * h]
+
+
+def add_shaded_member(fr, rng, cls, op, x0, y0, lerp=0):
+    """One path of class `cls` of SHADED_CLASSES in the strip at (x0, y0), under `op` or with the lerp bit.
+
+    bitmap_inside_plain        whole pixel rows of whole row halves right across the strip, an opaque bitmap so far magnified that every
+                               tap of the half lies inside it: the `inside` fetch and the `plain` copy
+    bitmap_inside_translucent  the same, texels translucent and alpha 0 among them: `inside`, arithmetic
+    bitmap_inside_partial      a triangle or a box off the pixel grid over such a strip: `inside`, coverage below 255 and lanes without any
+    bitmap_rim_none/repeat/pad the bitmap's edge runs through the strip (1 x 1, 1 x n and 2 x 2 bitmaps, rotated and mirrored, corners at
+                               negative positions): the general fetch with its outside flags, wrap and clamp
+    bitmap_minified            a scale below 0.75 on an axis: the convolution, the edge rule going round
+    radial_spread              a radial or focal gradient, reflected, repeated or padded"""
+    assert cls in SHADED_CLASSES and not (lerp and op != "normal")
+    whole = cls in ("bitmap_inside_plain", "bitmap_inside_translucent") or (cls != "bitmap_inside_partial" and rng.integers(0, 2))
+    if whole:
+        h0, h1 = [(0, 1), (1, 2), (0, 2)][int(rng.integers(0, 3))]
+        geometry = ("rect", (x0 - int(rng.integers(0, 3)), y0 + 4 * h0, x0 + STRIP_W + int(rng.integers(0, 9)), y0 + 4 * h1))
+    elif rng.integers(0, 2):
+        xa, ya = x0 + float(rng.uniform(0, 40)), y0 + float(rng.uniform(0, 5))
+        geometry = ("box", (xa, ya, xa + float(rng.uniform(2, 40)), ya + float(rng.uniform(1.5, 6))))
+    else:
+        xa, ya = x0 + float(rng.uniform(0, 50)), y0 + float(rng.uniform(0, 4))
+        geometry = ("tor", [(xa, ya), (xa + float(rng.uniform(3, 50)), ya + float(rng.uniform(0, 3))), (xa + float(rng.uniform(-4, 20)), ya + float(rng.uniform(2, 8)))])
+
+    def bitmap(rect):
+        inside = cls.startswith("bitmap_inside")
+        sizes = [s for s in RAW_BITMAP_SIZES if not inside or min(s) > 1]
+        halves = _covered_halves(rect, y0) or [0]
+        for _ in range(400):
+            bw, bh = sizes[int(rng.integers(0, len(sizes)))]
+            if inside:
+                kx, ky = 64.0 / (bw - 1) * float(rng.uniform(1.1, 2.5)), max(0.8, 4.0 / (bh - 1) * float(rng.uniform(1.1, 4.0)))
+                t = float(rng.uniform(-0.02, 0.02)) if rng.integers(0, 3) == 0 else 0.0
+                u, v = float(rng.uniform(0.6, max(0.7, bw - 0.6 - 64.0 / kx))), float(rng.uniform(0.6, max(0.7, bh - 0.6 - 8.0 / ky)))
+                ox, oy = x0 + 0.5 - kx * u, y0 + 0.5 - ky * v
+                if rng.integers(0, 4) == 0:                          # mirrored: the strip's right edge at u
+                    kx, ox = -kx, x0 + 63.5 + kx * u
+                extend = int(rng.integers(0, 3))
+            else:
+                if cls == "bitmap_minified":
+                    kx, ky = float(rng.uniform(0.3, 0.74)), float(rng.uniform(0.3, 3.0))
+                    if rng.integers(0, 2):
+                        kx, ky = ky, kx
+                    extend = int(rng.integers(0, 3))
+                else:
+                    kx, ky = float(rng.uniform(0.76, 12.0)), float(rng.uniform(0.76, 12.0))
+                    extend = {"bitmap_rim_none": 0, "bitmap_rim_repeat": 1, "bitmap_rim_pad": 2}[cls]
+                t = float(rng.uniform(-3.2, 3.2)) if rng.integers(0, 3) == 0 else 0.0
+                if rng.integers(0, 4) == 0:
+                    kx = -kx
+                ox, oy = x0 + float(rng.uniform(-12, 56)), y0 + float(rng.uniform(-5, 6))       # the bitmap's corner in or just off the strip
+            st = bitmap_style(0, extend, kx, ky, ox, oy, t)
+            seen = strip_halves(st, rect, bw, bh, x0, y0)
+            if inside and all(seen[h] == (True, True) for h in halves):
+                break
+            if cls == "bitmap_minified" and not seen[0][0]:
+                break
+            if cls.startswith("bitmap_rim") and seen[0][0] and not any(seen[h][1] for h in halves):
+                break
+        else:
+            raise AssertionError("no matrix found for " + cls)
+        st.bitmap = fr.add_bitmap(rand_texels(rng, bw, bh, opaque=cls == "bitmap_inside_plain"))
+        return st
+
+    def radial(rect):
+        radius = float(rng.uniform(30, 48))
+        stops = sorted((int(rng.integers(0, 256)), tuple(int(v) for v in rng.integers(0, 256, 3)) + (int(rng.choice([255, 255, 128, 0, 37])),)) for _ in range(int(rng.integers(1, 5))))
+        focal = float(rng.uniform(-0.7, 0.7)) if rng.integers(0, 2) else 0.0
+        return radial_style(int(rng.choice([1, 2, 1, 2, 0])), radius, x0 + 32 + float(rng.uniform(-14, 14)), y0 + 4 + float(rng.uniform(-5, 5)), stops, focal,
+                            float(rng.uniform(-3.2, 3.2)) if rng.integers(0, 2) else 0.0)
+
+    style = radial if cls == "radial_spread" else bitmap
+    if geometry[0] == "rect":
+        fr.rect_tor(*geometry[1], 0, lerp, op, style=style)
+    elif geometry[0] == "box":
+        fr.box(*geometry[1], 0, lerp, op, style=style)
+    else:
+        fr.tor(geometry[1], 0, lerp, op, style=style)
+
+
+SHADED_MODES = ("plain", "lerp") + tuple(MODES[1:])      # unblended, the lerp bit as a first paint, each of the eight operators
+SHADED_SETTINGS = ("alone", "group", "mask_content", "mask", "fade_1", "fade_128", "fade_254", "nested")
+SHADED_BEHIND = (0, 15, 16, 17)                           # plain entries before it: either side of a staging round
+SHADED_SIZES = (((130, 21), ((0, 0), (64, 8), (0, 8), (128, 16), (64, 0))), ((70, 13), ((0, 0), (64, 8), (0, 8))))       # frame, strips
+
+
+def shaded_frame(cls, mode, setting, k, size, strip, seed):
+    """One frame: `k` plain solid entries in the strip, then one member of class `cls` -- unblended, with the lerp bit (a first paint:
+    then nothing comes before it on its surface) or under the operator `mode` -- alone, in a group, as the content or as the mask of
+    a masked group, in a faded group or two groups deep; a solid path on top."""
+    rng = np.random.default_rng(seed)
+    W, H = size
+    x0, y0 = strip
+    fr = RawFrame(W, H)
+    lerp = mode == "lerp"
+    op = "normal" if mode in ("plain", "lerp") else mode
+    if lerp and setting == "alone":
+        k = 0
+    for i in range(k):
+        add_member(fr, rng, ("full_translucent", "box", "partial")[i % 3], MODES[(seed + 2 * i) % 9] if i else "normal", x0, y0, first=i == 0)
+    member = lambda: add_shaded_member(fr, rng, cls, op, x0, y0, lerp)
+    end_op = MODES[seed % 9]
+    if setting == "alone":
+        member()
+    elif setting == "group":
+        fr.begin()
+        member()
+        add_member(fr, rng, "partial", MODES[(seed + 1) % 9], x0, y0)
+        fr.end(end_op)
+    elif setting == "mask_content":
+        fr.begin()
+        member()
+        add_member(fr, rng, "box", MODES[(seed + 1) % 9], x0, y0)
+        fr.mask()
+        add_member(fr, rng, "partial", "normal", x0, y0, first=True)
+        add_member(fr, rng, "full_translucent", "normal", x0, y0)
+        fr.end(end_op)
+    elif setting == "mask":
+        fr.begin()
+        add_member(fr, rng, "full_translucent", "normal", x0, y0, first=True)
+        add_member(fr, rng, "partial", MODES[(seed + 1) % 9], x0, y0)
+        fr.mask()
+        member()
+        fr.end(end_op)
+    elif setting.startswith("fade"):
+        fr.begin()
+        member()
+        add_member(fr, rng, "partial", MODES[(seed + 1) % 9], x0, y0)
+        fr.end(end_op, opacity=int(setting.split("_")[1]))
+    else:
+        fr.begin()
+        add_member(fr, rng, "partial", "normal", x0, y0, first=True)
+        fr.begin()
+        member()
+        fr.end(MODES[(seed + 4) % 9])
+        add_member(fr, rng, "box", MODES[(seed + 1) % 9], x0, y0)
+        fr.end(end_op)
+    add_member(fr, rng, "partial", MODES[(seed + 3) % 9], x0, y0)
+    return fr
+
+
+def shaded_frames(cls):
+    """(label, frame) of one member class: every mode x every setting; the count of entries before it, the frame size and the strip
+    go round"""
+    ci = SHADED_CLASSES.index(cls)
+    n = 0
+    for mi, mode in enumerate(SHADED_MODES):
+        for si, setting in enumerate(SHADED_SETTINGS):
+            k = SHADED_BEHIND[(mi + si + ci) % 4]
+            size, strips = SHADED_SIZES[(mi + si // 2) % 2]
+            strip = strips[n % len(strips)]
+            yield (cls, mode, setting, k, size, strip), shaded_frame(cls, mode, setting, k, size, strip, 7000 + 100 * ci + n)
+            n += 1
+
+
+def shaded_reach(frames):
+    """What the wavefronts of the tile pass see of the shaded paths of `frames` (RawFrames), from the arrays, the coverage of
+    tests/frame_model.py and the sample positions of tests/pad_model.py -- never from the kernel.  A dict of counts:
+    per (path, strip, row half with coverage) of an unblended bitmap path  ("inside", plain) / ("general", extend) / ("convolution", extend)
+        -- inside: all 256 samples strictly inside the bitmap; plain: coverage 255 at all of them and every source pixel opaque;
+    per shaded path  ("lerp",), ("operator", name), ("setting", "group" | "mask_content" | "mask" | "faded" | "nested")"""
+    import frame_model as fm
+    import pad_model as pm
+    out = {}
+
+    def count(*key):
+        out[key] = out.get(key, 0) + 1
+    for fr in frames:
+        edges, paths, styles = fr.arrays()
+        texels = fr.model_bitmaps()
+        ends, opened = {}, []                                        # BEGIN index -> (MASK index or None, END index)
+        for i, p in enumerate(paths):
+            kind = int(p["kind"])
+            if kind == BEGIN:
+                opened.append([i, None])
+            elif kind == MASK:
+                opened[-1][1] = i
+            elif kind == END:
+                b, m = opened.pop()
+                ends[b] = (m, i)
+        stack = []
+        for i, p in enumerate(paths):
+            kind = int(p["kind"])
+            if kind == BEGIN:
+                stack.append(i)
+                continue
+            if kind == END:
+                stack.pop()
+                continue
+            st = styles[int(p["style"])]
+            if kind == MASK or int(st.kind) == fm.STYLE_SOLID:
+                continue
+            field = int(p["lerp"])
+            if field & 1:
+                count("lerp")
+            if field >> 8:
+                count("operator", MODES[0] if not field >> 8 else fm.OPERATOR_NAMES[field >> 8])
+            if stack:
+                m, e = ends[stack[-1]]
+                count("setting", "group" if m is None else ("mask_content" if i < m else "mask"))
+                if int(paths[e]["lerp"]) >> 24:
+                    count("setting", "faded")
+                if len(stack) > 1:
+                    count("setting", "nested")
+            if int(st.kind) != fm.STYLE_BITMAP or field >> 8:
+                continue
+            rect, cov = fm.path_coverage(edges, p, fr.W, fr.H)
+            bmp = texels[int(st.bitmap)]
+            inv = tuple(float(v) for v in st.inv)
+            for sy in range(rect[1] // STRIP_H * STRIP_H, rect[3], STRIP_H):
+                for sx in range(rect[0] // STRIP_W * STRIP_W, rect[2], STRIP_W):
+                    seen = strip_halves(st, tuple(int(p[k]) for k in ("x_min", "y_min", "x_max", "y_max")), bmp.shape[1], bmp.shape[0], sx, sy)
+                    for h, (bilinear, inside) in enumerate(seen):
+                        block = np.zeros((4, STRIP_W), np.uint8)                             # the half's coverage, zero outside the rectangle
+                        ya, yb, xa, xb = max(sy + 4 * h, rect[1]), min(sy + 4 * h + 4, rect[3]), max(sx, rect[0]), min(sx + STRIP_W, rect[2])
+                        if ya < yb and xa < xb:
+                            block[ya - sy - 4 * h:yb - sy - 4 * h, xa - sx:xb - sx] = cov[ya - rect[1]:yb - rect[1], xa - rect[0]:xb - rect[0]]
+                        if not block.any():
+                            continue                                 # (the kernel skips a half without coverage as a whole)
+                        if not bilinear:
+                            count("convolution", int(st.extend))
+                        elif not inside:
+                            count("general", int(st.extend))
+                        else:
+                            src = pm.source_pixels(inv, bmp, (sx, sy + 4 * h, sx + STRIP_W, sy + 4 * h + 4), int(st.extend),
+                                                   tuple(int(p[k]) for k in ("x_min", "y_min", "x_max", "y_max")))
+                            count("inside", bool((block == 255).all() and ((src >> 24) == 255).all()))
+    return out
+
+
+def assert_shaded_reach(rc, least=5):
+    """every branch of the bitmap fetch and every place a shaded member can stand, each at least `least` times"""
+    need = [("inside", True), ("inside", False), ("lerp",)] + [(f, e) for f in ("general", "convolution") for e in (0, 1, 2)]
+    need += [("operator", m) for m in MODES[1:]] + [("setting", s) for s in ("group", "mask_content", "mask", "faded", "nested")]
+    for key in need:
+        assert rc.get(key, 0) >= least, (key, rc.get(key, 0))
+
+
+def lerp_beside_painted_frame(seed, W=130, H=21):
+    """A bitmap path with the lerp bit whose own rectangle is still clear while the rest of its strip is not: solid boxes right of
+    column 38 and below row 8, then the bitmap -- a box off the pixel grid or a triangle -- left of them.  A lerp ignores its
+    destination, so the pixels of the strip outside the path have to be kept lane by lane."""
+    rng = np.random.default_rng(7950 + seed)
+    fr = RawFrame(W, H)
+    fr.box(38, 0, 64 + float(rng.uniform(3, 40)), 7.5, premultiplied(rng, int(rng.integers(60, 255))), 1)
+    fr.rect_tor(0, 9, W, 14, premultiplied(rng, int(rng.integers(60, 255))), 0, MODES[seed % 9])
+    bw, bh = ((7, 7), (3, 3), (47, 48), (2, 2))[seed % 4]
+    bid = fr.add_bitmap(rand_texels(rng, bw, bh, opaque=seed % 3 == 0))
+    k = 70.0 / max(bw - 1, 1) if seed % 2 else float(rng.uniform(0.9, 6))
+    style = lambda rect: bitmap_style(bid, seed % 3, k, k, -1.5 - (k if seed % 2 else 0) * 0.6, -2.25 - (k if seed % 2 else 0) * 0.2)
+    if seed % 2:
+        fr.box(1.3, 0.6, 36.4, 7.7, 0, 1, style=style)
+    else:
+        fr.tor([(2.2, 0.4), (37.1, 3.3), (9.6, 7.8)], 0, 1, style=style)
+    add_member(fr, rng, "partial", MODES[(seed + 3) % 9], 0, 0)
+    return fr
+
+
+def last_column_frame(seed, W=70, H=13):
+    """Whole rows of the first strip filled from a bitmap so placed that the samples' left taps run up to the bitmap's LAST column and
+    no further (their right taps are then outside it: wrapped, clamped or transparent), every row tap inside: one column short of the
+    all-inside shortcut.  -> (frame, the set of left-tap columns of the strip's samples, the bitmap's width)"""
+    import spread_model as sm
+    rng = np.random.default_rng(7970 + seed)
+    fr = RawFrame(W, H)
+    if seed % 2:
+        fr.rect_tor(-1, -1, W + 1, H + 1, premultiplied(rng, int(rng.integers(40, 255))), 1)
+    bw, bh = ((2, 4), (3, 5), (7, 7), (5, 4))[seed % 4]
+    bid = fr.add_bitmap(rand_texels(rng, bw, bh, opaque=seed % 5 == 0))
+    kx, ky = float(rng.uniform(72, 88)), 12.0
+    st = bitmap_style(bid, seed % 3, kx, ky, 0.5 - kx * (bw - 1.1), 0.5 - ky * 1.0)
+    fr.rect_tor(0, 0, STRIP_W + 2, 8, 0, 0 if seed % 2 else 1, style=lambda rect: st)
+    (bx, by), ((m00, m01), (m10, m11)) = sm.to_pixman(tuple(st.inv), fr.paths[-1][6:10])
+    px, py = np.meshgrid(np.arange(STRIP_W, dtype=np.int64), np.arange(8, dtype=np.int64))
+    ty = (by + px * m10 + py * m11 - 0x8000) >> 16
+    assert ty.min() >= 0 and ty.max() <= bh - 3
+    return fr, set(((bx + px * m00 + py * m01 - 0x8000) >> 16).ravel().tolist()), bw

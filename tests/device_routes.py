@@ -70,21 +70,25 @@ def not_refused(r, msg):
 
 
 # ---------------------------------------------------------------------------------------------------------------- handles and routes
-def handle(W, H, aliased=False, **kw):
+def handle(W, H, aliased=False, bitmaps=None, **kw):
+    """bitmaps: {id: (width, height, straight RGBA bytes)} registered on the handle (a RawFrame's, a scene's "raw_bitmaps")"""
     import swf_renderer_amd as S
-    return S.Renderer(W, H, antialias="none" if aliased else "default", **kw)
+    r = S.Renderer(W, H, antialias="none" if aliased else "default", **kw)
+    for bid, (w, h, px) in (bitmaps or {}).items():
+        r.register_bitmap(bid, w, h, px)
+    return r
 
 
 def renderer_for(sc, aliased, **kw):
     """a handle of the scene's size and fill rule that holds the scene's bitmaps"""
-    r = handle(sc["width"], sc["height"], aliased, even_odd=bool(sc.get("even_odd")), **kw)
+    r = handle(sc["width"], sc["height"], aliased, bitmaps=sc.get("raw_bitmaps"), even_odd=bool(sc.get("even_odd")), **kw)
     for b in sc.get("bitmaps", []):
         r.add_bitmap(b)
     return r
 
 
-def through_edges(W, H, arrays, aliased=False, resident=0, **kw):
-    r = handle(W, H, aliased, **kw)
+def through_edges(W, H, arrays, aliased=False, resident=0, bitmaps=None, **kw):
+    r = handle(W, H, aliased, bitmaps, **kw)
     try:
         r.render_edges(*arrays)
         img = r.read_image(premultiplied=True)
@@ -98,7 +102,7 @@ def through_edges(W, H, arrays, aliased=False, resident=0, **kw):
 
 
 def through_render(sc, aliased=False, **kw):
-    r = handle(sc["width"], sc["height"], aliased, **kw)
+    r = handle(sc["width"], sc["height"], aliased, sc.get("raw_bitmaps"), **kw)
     try:
         r.render(sc["stage"])
         not_refused(r, "render")
@@ -107,13 +111,14 @@ def through_render(sc, aliased=False, **kw):
         r.close()
 
 
-def two_bands(W, H, contiguous, draw, aliased=False, make=None):
-    """the frame assembled from two handles, each drawing its own tile rows (`draw(handle)`; `make(**bands)`: the handle)"""
+def two_bands(W, H, contiguous, draw, aliased=False, make=None, bitmaps=None):
+    """the frame assembled from two handles, each drawing its own tile rows (`draw(handle)`; `make(**bands)`: the handle; `bitmaps`:
+    registered on both)"""
     out = np.zeros((H, W, 4), np.uint8)
     n = -(-((H + 15) // 16) // 2)                                    # tile rows per handle
     for rank in range(2):
         bands = dict(band_index=rank, band_count=2, contiguous_bands=contiguous)
-        r = make(**bands) if make else handle(W, H, aliased, **bands)
+        r = make(**bands) if make else handle(W, H, aliased, bitmaps, **bands)
         try:
             draw(r)
             img = r.read_image(premultiplied=True)

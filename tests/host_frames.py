@@ -17,9 +17,28 @@ def build_on_host(sc, aliased=False):
     try:
         for b in sc.get("bitmaps", []):
             r.add_bitmap(b)
+        for bid, (w, h, px) in sc.get("raw_bitmaps", {}).items():
+            r.register_bitmap(bid, w, h, px)
         return r.build_frame(sc["stage"])
     finally:
         r.close()
+
+
+def bitmaps_of(sc):
+    """{id: (h, w) uint32 premultiplied 0xAARRGGBB}: the texels of the scene's bitmaps as tests/frame_model.py takes them -- the
+    DefineBitmap tags of sc["bitmaps"] through the oracle's decoder, sc["raw_bitmaps"] ({id: (w, h, straight RGBA bytes)}) as they are"""
+    import numpy as np
+
+    import pad_model as pm
+    from oracle import canvas_replay as cr
+    out = {}
+    for tag in sc.get("bitmaps", []):
+        data = tag["data"]
+        w, h, rgba = cr.decode_x_swf_bmp(bytes.fromhex(data) if isinstance(data, str) else bytes(data))
+        out[tag["id"]] = pm.premultiply(np.frombuffer(rgba, np.uint8).reshape(h, w, 4))
+    for bid, (w, h, rgba) in sc.get("raw_bitmaps", {}).items():
+        out[bid] = pm.premultiply(np.frombuffer(rgba, np.uint8).reshape(h, w, 4))
+    return out
 
 
 def raw_stage(obj_type, obj_id, child_shape_id):

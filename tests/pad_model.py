@@ -124,6 +124,66 @@ def convolution(bitmap, fx, fy, flt, extend):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- the fetch, on arrays
+def texels(bitmap, x, y, extend):
+    """texel() for int64 arrays of coordinates -> uint32"""
+    h, w = bitmap.shape
+    if extend == REPEAT:
+        return bitmap[y % h, x % w]
+    if extend == PAD:
+        return bitmap[np.clip(y, 0, h - 1), np.clip(x, 0, w - 1)]
+    ok = (x >= 0) & (x < w) & (y >= 0) & (y < h)
+    return np.where(ok, bitmap[np.clip(y, 0, h - 1), np.clip(x, 0, w - 1)], 0).astype(np.uint32)
+
+
+def bilinear_many(bitmap, fx, fy, extend):
+    """bilinear() for int64 arrays of 16.16 positions (tests/test_shaded_frame_model.py holds the two equal)"""
+    fx, fy = np.asarray(fx, np.int64), np.asarray(fy, np.int64)
+    bx, by = fx - 0x8000, fy - 0x8000
+    x0, y0, wx, wy = bx >> 16, by >> 16, (bx >> 9) & 0x7f, (by >> 9) & 0x7f
+    c = [texels(bitmap, x0 + (k & 1), y0 + (k >> 1), extend).astype(np.int64) for k in range(4)]
+    w = [(128 - wx) * (128 - wy), wx * (128 - wy), (128 - wx) * wy, wx * wy]
+    out = np.zeros(fx.shape, np.int64)
+    for sh in (0, 8, 16, 24):
+        out |= ((sum(((c[k] >> sh) & 255) * w[k] for k in range(4)) >> 14) & 255) << sh
+    return out.astype(np.uint32)
+
+
+def convolution_many(bitmap, fx, fy, flt, extend):
+    """convolution() for int64 arrays of 16.16 positions"""
+    fx, fy = np.asarray(fx, np.int64), np.asarray(fy, np.int64)
+    (cw, xbits, xt), (ch, ybits, yt) = flt
+    xsh, ysh = 16 - xbits, 16 - ybits
+    x = (fx & ~((1 << xsh) - 1)) + ((1 << xsh) >> 1)
+    y = (fy & ~((1 << ysh) - 1)) + ((1 << ysh) >> 1)
+    xw, yw = np.array(xt, np.int64)[(x & 0xffff) >> xsh], np.array(yt, np.int64)[(y & 0xffff) >> ysh]      # [..., tap]
+    x1, y1 = (x - 1 - (((cw << 16) - 65536) >> 1)) >> 16, (y - 1 - (((ch << 16) - 65536) >> 1)) >> 16
+    acc = [np.zeros(fx.shape, np.int64) for _ in range(4)]
+    for i in range(ch):
+        for j in range(cw):
+            on = (yw[..., i] != 0) & (xw[..., j] != 0)
+            if not on.any():
+                continue
+            p = texels(bitmap, x1 + j, y1 + i, extend).astype(np.int64)
+            f = np.where(on, (yw[..., i] * xw[..., j] + 0x8000) >> 16, 0)
+            for k, sh in enumerate((0, 8, 16, 24)):
+                acc[k] += ((p >> sh) & 255) * f
+    out = np.zeros(fx.shape, np.int64)
+    for k, sh in enumerate((0, 8, 16, 24)):
+        out |= np.clip((acc[k] + 0x8000) >> 16, 0, 255) << sh
+    return out.astype(np.uint32)
+
+
+def source_pixels(m, bitmap, rect, extend, anchor=None):
+    """the source pixels (premultiplied 0xAARRGGBB) of the rectangle (x0, y0, x1, y1) for the pattern matrix m; `anchor`: the
+    operation's rectangle where that is another (the rectangle cut to the frame is what is asked for)"""
+    (bx, by), ((m00, m01), (m10, m11)) = sm.to_pixman(m, anchor or rect)
+    px, py = np.meshgrid(np.arange(rect[0], rect[2], dtype=np.int64), np.arange(rect[1], rect[3], dtype=np.int64))
+    fx, fy = bx + px * m00 + py * m01, by + px * m10 + py * m11
+    flt = filter_of(m)
+    return bilinear_many(bitmap, fx, fy, extend) if flt is None else convolution_many(bitmap, fx, fy, flt, extend)
+
+
 def placement(bitmap, fx, fy, flt):
     """where a sample's taps lie: "inside" (every tap in the bitmap), "outside" (none) or "rim" -- taps of weight zero not counted"""
     h, w = bitmap.shape

@@ -25,6 +25,7 @@ PAD, REPEAT, REFLECT = 0, 1, 2               # swfr_style::extend of a gradient 
 CAIRO_EXTEND = {PAD: 3, REPEAT: 1, REFLECT: 2}
 F = np.float32
 FLT_MIN = 1.17549435e-38
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
 # ---------------------------------------------------------------------------------------------------------------- matrices
@@ -138,12 +139,14 @@ def short(v):
 
 
 class Walker:
-    """pixman_gradient_walker_t for REPEAT and REFLECT: stops is [(x 16.16, (a, r, g, b) 16 bit)], sorted"""
+    """pixman_gradient_walker_t: stops is [(x 16.16, (a, r, g, b) 16 bit)], sorted"""
 
     def __init__(self, stops, extend):
-        assert extend in (REPEAT, REFLECT) and stops
+        assert extend in (PAD, REPEAT, REFLECT) and stops
         first, last = stops[0], stops[-1]
-        if extend == REPEAT:
+        if extend == PAD:
+            self.stops = [(INT32_MIN, first[1])] + list(stops) + [(INT32_MAX, last[1])]
+        elif extend == REPEAT:
             self.stops = [(last[0] - 0x10000, last[1])] + list(stops) + [(first[0] + 0x10000, first[1])]
         else:
             self.stops = [(-first[0], first[1])] + list(stops) + [(0x20000 - last[0], last[1])]
@@ -152,6 +155,13 @@ class Walker:
 
     def reset(self, pos):
         """gradient_walker_reset: (left_x, right_x, left colour, right colour)"""
+        if self.extend == PAD:                                       # (the position as it is, between the sentinels at the ends of int32)
+            S = self.stops
+            n = 1
+            while n < len(S) - 1 and not pos < S[n][0]:
+                n += 1
+            (self.left_x, self.left_c), (self.right_x, self.right_c) = S[n - 1], S[n]
+            return self.left_x, self.right_x, self.left_c, self.right_c
         low = pos & 0xffff                                           # ((int32_t) pos & 0xffff: the low bits of a two's complement number)
         odd = self.extend == REFLECT and bool(pos & 0x10000)
         x = 0x10000 - low if odd else low
@@ -182,7 +192,7 @@ def ramp_pixels(pos, lx, rx, lc, rc):
     k = F(1.0) / F(65536.0)
     flx, frx = lx.astype(F) * k, rx.astype(F) * k
     w = frx - flx
-    flat = np.abs(w) < F(FLT_MIN)
+    flat = (np.abs(w) < F(FLT_MIN)) | (lx == INT32_MIN) | (rx == INT32_MAX)      # (PAD's sentinels: the end stop's colour)
     with np.errstate(divide="ignore", invalid="ignore"):
         w_rec = F(1.0) / w
     y = pos.astype(F) * k

@@ -1,5 +1,5 @@
-"""tests/frame_model.py pinned without a GPU: the committed libcairo goldens of the blend and layer scenes through the model over
-swfr_build_frame (host-only handles), random composited trees against live libcairo -- which is also the first random check of the frame
+"""tests/frame_model.py pinned without a GPU: the committed libcairo goldens of the layer, blend, mask, fade, pad and spread scenes --
+bitmap and radial sources included -- through the model over swfr_build_frame (host-only handles), random composited trees against live libcairo -- which is also the first random check of the frame
 builder's clear-surface bookkeeping around groups, in single and threaded builds -- and the model against the oracle on plain frames,
 where OVER and the lerp rule are the ones the rest of the suite already trusts.  Zero differing bytes everywhere.  And the reach of
 the raw corpus of tests/test_composite_fuzz_gpu.py, computed from the arrays."""
@@ -23,7 +23,8 @@ needs_cairo = pytest.mark.skipif(not cb.available(), reason="libcairo not instal
 # golden files every scene of which is solid: all of them must go through the model
 ALL_SOLID = (["cairo_layer_overlap", "cairo_layer_aliased_overlap", "cairo_blend_solids", "cairo_blend_aliased_solids", "cairo_blend_structure",
               "cairo_blend_aliased_structure"] + ["cairo_layer_%sstructure_%s" % (a, m) for a in ("", "aliased_") for m in ls.MODES])
-GOLDEN_SCENES = 636                                     # counted: the scenes of tests/layer_scenes.py and tests/blend_scenes.py whose built styles are all solid
+GOLDEN_SCENES = 1667                                    # counted: every scene of the golden files below but those with a linear gradient (46 of them), and 13 run-start scenes
+SOLID_GOLDEN_SCENES = 636                               # ... of them, the scenes of tests/layer_scenes.py and tests/blend_scenes.py whose built styles are all solid
 
 
 def _model(sc, aliased=False):
@@ -31,26 +32,64 @@ def _model(sc, aliased=False):
 
 
 def test_goldens_through_the_model():
+    """Every committed libcairo golden of the layer, blend, mask, fade, pad and spread scenes through the model: zero differing bytes.
+    A scene may be left out (NotImplementedError) for one reason only: a linear gradient -- a float ramp within 1 LSB by design -- or a
+    colour-transformed (variant) texture, whose texels belong to the handle that walked the stage (the pad cxform files).  Padded
+    radial gradients are drawn (tests/test_shaded_frame_model.py holds them against the oracle).  Of the run-start goldens of the
+    spread scenes (tests/spread_scenes.py, runstart_cases) those go through whose case shows no caveat pixel -- every REPEAT one, and
+    the REFLECT ones marked so; the others pin libcairo's covered-samples walker in their caveat pixels, not the every-sample rule,
+    and there the model must differ from the golden, in those few pixels only."""
+    import fade_scenes as fs
+    import mask_scenes as ms
+    import pad_scenes as ps
+    import spread_scenes as ss
+    from host_frames import bitmaps_of
     from swf_renderer_amd import api
-    checked, per_file = 0, {}
-    for mod in (ls, bs):
-        for fname, (make, aliased) in sorted(mod.files().items()):
-            gold = np.load(mod.golden_path(fname))
-            for name, sc in sorted(make().items()):
-                arrays = build_on_host(sc, aliased)
-                if any(int(st.kind) != api.STYLE_SOLID for st in arrays[2]):
-                    with pytest.raises(NotImplementedError):
-                        fm.render(*arrays, sc["width"], sc["height"], aliased=aliased)
-                    per_file.setdefault(fname, [0, 0])[1] += 1
-                    continue
-                assert diff_stats(fm.render(*arrays, sc["width"], sc["height"], aliased=aliased), gold[name]) == (0, 0), (fname, name)
-                per_file.setdefault(fname, [0, 0])[0] += 1
-                checked += 1
+    checked = solid = variants = 0
+    per_file = {}
+    files = [(mod, fname, v) for mod in (ls, bs, ms, fs, ps, ss) for fname, v in sorted(mod.files().items())]
+    files += [(ps, fname, v) for fname, v in sorted(ps.cxform_files().items())]
+    for mod, fname, (make, aliased) in files:
+        gold = np.load(mod.golden_path(fname))
+        for name, sc in sorted(make().items()):
+            arrays = build_on_host(sc, aliased)
+            styles = arrays[2]
+            linear = any(int(st.kind) == api.STYLE_LINEAR for st in styles)
+            variant = any(int(st.kind) == api.STYLE_BITMAP and int(st.bitmap) >= api.VARIANT_BASE for st in styles)
+            if linear or variant:
+                with pytest.raises(NotImplementedError):
+                    fm.render(*arrays, sc["width"], sc["height"], aliased=aliased, bitmaps=bitmaps_of(sc))
+                per_file.setdefault(fname, [0, 0])[1] += 1
+                variants += variant
+                continue
+            assert diff_stats(fm.render(*arrays, sc["width"], sc["height"], aliased=aliased, bitmaps=bitmaps_of(sc)), gold[name]) == (0, 0), (fname, name)
+            per_file.setdefault(fname, [0, 0])[0] += 1
+            checked += 1
+            solid += mod in (ls, bs) and all(int(st.kind) == api.STYLE_SOLID for st in styles)
+    runstart = 0
+    for fname, (_, aliased) in sorted(ss.runstart_files().items()):
+        gold = np.load(ss.golden_path(fname))
+        spread = "reflect" if "reflect" in fname else "repeat"
+        for name, case in sorted(ss.runstart_cases(spread, aliased).items()):
+            sc = case["scene"]
+            n, _ = diff_stats(fm.render(*build_on_host(sc, aliased), sc["width"], sc["height"], aliased=aliased), gold[name])
+            if spread == "reflect" and case["caveat"]:
+                assert 0 < n <= 4, (fname, name, n)                  # (the golden is libcairo's side of the caveat)
+            else:
+                assert n == 0, (fname, name, n)
+                runstart += 1
+    checked += runstart
     for fname in ALL_SOLID:
         assert per_file[fname][0] > 0 and per_file[fname][1] == 0, (fname, per_file[fname])
+    for fname, (ok, left_out) in per_file.items():                   # the files with bitmap and gradient sources: all but their linear scenes
+        if "_sources" in fname:
+            assert ok >= 8 and left_out <= 2, (fname, ok, left_out)
+        if fname.startswith("cairo_pad_") and "cxform" not in fname:
+            assert ok > 0 and left_out == 0, (fname, ok, left_out)
     layer_aa = sum(v[0] for k, v in per_file.items() if k.startswith("cairo_layer_") and "aliased" not in k)
-    print("goldens through the model:", checked, "scenes,", layer_aa, "of them antialiased layer scenes")
-    assert layer_aa >= 174 and checked >= GOLDEN_SCENES, (layer_aa, checked)
+    print("goldens through the model:", checked, "scenes,", solid, "of them solid layer and blend scenes,", layer_aa, "antialiased layer scenes;", variants, "left out for a variant texture")
+    assert layer_aa >= 174 + 9 * 8 and solid >= SOLID_GOLDEN_SCENES and checked >= GOLDEN_SCENES, (layer_aa, solid, checked)
+    assert variants > 0 and runstart >= 13
 
 
 def test_a_transparent_group_pixel_leaves_the_destination_alone():
