@@ -1602,18 +1602,21 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     const int width = FR->width, height = FR->height, tiles_x = FR->tiles_x;
     const swfr_style* __restrict__ styles = FR->styles;
     const Sources bitmaps = {FR->src.bitmaps, FR->src.filters, FR->src.fparams, FR->src.gradients};
-    // The descriptor fields the loops below read -- per strip, per staging round, per partial pair -- loaded here once and held
-    // (T3_FIELD) in the instances that can pay the scalar registers without scratch or a wavefront per SIMD: the solid one.  The
-    // others read them where they are used, as before: pinned, each of them spills vector registers.
+    // The descriptor fields the loops below read in front of a fetch of the strip being painted -- per staging round, per partial pair
+    // -- loaded here once and held (T3_FIELD) in the instances that can pay the scalar registers without scratch or a wavefront per
+    // SIMD: the solid one.  The others read them where they are used, as before: pinned, each of them spills vector registers.
+    // `strips` and `strip_top` are read where they are used in every instance: off the strip's critical path (the descriptor of the
+    // strip after next, the next strip's record, the record's clear).  Held too, they were two scalar registers more than the solid
+    // instance has -- two lanes of an 81st vector register, the one register above six wavefronts per SIMD (T2_WAVES).
     constexpr bool PIN = SHADERS == 0;
-    [[maybe_unused]] SWFR_GLOBAL_PTR(const StripDesc) p_strips = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(StripTop) p_strip_top = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(const uint8_t) p_cls = nullptr;
+    [[maybe_unused]] SWFR_GLOBAL_PTR(const uint8_t) p_cls = nullptr;
     [[maybe_unused]] SWFR_GLOBAL_PTR(const BandEntry2) p_band_list = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(const RowInfo2) p_rows = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(const Cell) p_cells = nullptr;
     [[maybe_unused]] uint32_t p_cell_slice = 0u;
     if constexpr (PIN) {
-        p_strips = (SWFR_GLOBAL_PTR(const StripDesc))FR->strips; p_strip_top = (SWFR_GLOBAL_PTR(StripTop))FR->strip_top; p_cls = (SWFR_GLOBAL_PTR(const uint8_t))FR->cls;
+        p_cls = (SWFR_GLOBAL_PTR(const uint8_t))FR->cls;
         p_band_list = (SWFR_GLOBAL_PTR(const BandEntry2))FR->band_list; p_rows = (SWFR_GLOBAL_PTR(const RowInfo2))FR->rows; p_cells = (SWFR_GLOBAL_PTR(const Cell))FR->cells;
         p_cell_slice = FR->cell_slice;
-        SWFR_PIN_SGPR(p_strips); SWFR_PIN_SGPR(p_strip_top); SWFR_PIN_SGPR(p_cls); SWFR_PIN_SGPR(p_band_list); SWFR_PIN_SGPR(p_rows); SWFR_PIN_SGPR(p_cells); SWFR_PIN_SGPR(p_cell_slice);
+        SWFR_PIN_SGPR(p_cls); SWFR_PIN_SGPR(p_band_list); SWFR_PIN_SGPR(p_rows); SWFR_PIN_SGPR(p_cells); SWFR_PIN_SGPR(p_cell_slice);
     }
 #define T3_FIELD(name) (PIN ? (decltype(FR->name))p_##name : FR->name)
     uint32_t acc_clean = 0u;                               // the accumulators are zeroed before the first partial path needs them (many strips have none)
@@ -1626,7 +1629,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     const uint32_t n_slots = FR->n_strip_slots, G = gridDim.x;
     auto fetch_desc = [&](uint32_t slot) -> uint32_t {                   // lanes 0..3: the StripDesc of a slot ({~0, ..} beyond the list)
         uint32_t v = ~0u;
-        if (slot < n_slots && lane < 4) v = reinterpret_cast<const uint32_t*>(T3_FIELD(strips) + slot)[lane];
+        if (slot < n_slots && lane < 4) v = reinterpret_cast<const uint32_t*>(FR->strips + slot)[lane];
         return v;
     };
     uint32_t n_wg = ~0u, n_band_begin = 0u, n_nb = 0u;                    // the next strip (wave-uniform) ...
@@ -1644,7 +1647,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         const int trow = (int)FR->band_first + (int)(where >> 16) * (int)FR->band_stride;
         n_ty0 = trow * TILE_H + strip * STRIP_H;
         // what the row pass knows about the strip as a whole (StripTop), and the strip's class byte per band entry
-        if (lane < 4) n_top = reinterpret_cast<const uint32_t*>(T3_FIELD(strip_top) + n_wg)[lane];
+        if (lane < 4) n_top = reinterpret_cast<const uint32_t*>(FR->strip_top + n_wg)[lane];
         const uint8_t* cl = T3_FIELD(cls) + (size_t)STRIPS_PER_TILE * tiles_x * n_band_begin + (size_t)(n_tcol * STRIPS_PER_TILE + strip) * n_nb;
 #pragma unroll
         for (int u = 0; u < T3_CLS_PRE; ++u) if ((uint32_t)(u * 64 + lane) < n_nb) n_cls[u] = (uint32_t)cl[u * 64 + lane];
@@ -1694,13 +1697,13 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         const uint32_t cover_pos = (uint32_t)(top.cover >> 32);
         if (lane == 0 && top.any != 0u) {                                  // (depends on the loaded value: never overtakes the read)
 #ifdef SWFR_EMU
-            StripTop z; z.any = 0u; z.pad = 0u; z.cover = 0ull; T3_FIELD(strip_top)[wg] = z;
+            StripTop z; z.any = 0u; z.pad = 0u; z.cover = 0ull; FR->strip_top[wg] = z;
 #else
             // (the zero is made here: as a loop invariant the compiler kept four zeroed registers alive across the whole strip loop --
             //  in the bitmap instance it spilled them at kernel entry, 16 bytes of scratch per lane)
             uint32_t z = 0u;
             asm volatile("" : "+v"(z));
-            *reinterpret_cast<uint4*>(&T3_FIELD(strip_top)[wg]) = make_uint4(z, z, z, z);
+            *reinterpret_cast<uint4*>(&FR->strip_top[wg]) = make_uint4(z, z, z, z);
 #endif
         }
         const bool uniform = top.any == cover_pos;                        // (wave-uniform)
@@ -2014,7 +2017,8 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
 
 
 #ifndef T2_WAVES
-#define T2_WAVES 5                    // (96 VGPRs; round 4: five or six wavefronts per SIMD time alike on S1, five is a tenth faster on S0)
+#define T2_WAVES 6                    // the solid instance: at most 80 VGPRs, no scratch, no spilled register (tests/test_wave_budget.py): six wavefronts per SIMD
+                                      // (the kernel's time follows its resident wavefronts: DESIGN.md 6.1 "Six wavefronts per SIMD")
 #endif
 // (two entry points per kernel: one frame, its descriptor passed by value -- the fields arrive with the kernel arguments, no memory
 //  round trip -- and a batch of frames, blockIdx.y indexing an array of descriptors in device memory)
