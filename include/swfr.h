@@ -90,6 +90,18 @@ typedef struct {
                                             for byte.  pad = 1 together with repeating != 0, or pad > 1: SWFR_ERR_INVALID, "InvalidBitmapPad".
                                             Ignored for solid and gradient fills.  Offset 59, in the remaining tail padding: size (64) and
                                             every other offset are unchanged.  DESIGN.md, "Padded bitmap fills" */
+    uint8_t filter;                      /* bitmap: the Cairo filter of the bitmap's surface pattern.  0 = CAIRO_FILTER_GOOD, what was always
+                                            drawn, byte for byte (bilinear at 0.75 x and above, pixman's separable convolution below);
+                                            `smoothed` is still ignored, as the reference ignores it.  1 = CAIRO_FILTER_NEAREST, an
+                                            unsmoothed fill (SWF fill types 0x42 / 0x43): with f pixman's 16.16 position of the pixel centre,
+                                            the ONE texel ((fx - 1) >> 16, (fy - 1) >> 16) -- a sample exactly on a texel edge reads the
+                                            texel to the left of / above it -- at every scale (no convolution), the extend applied to that
+                                            coordinate; an EXTEND_NONE fill is cut to the bitmap's rectangle padded by 0.004 source pixels
+                                            and rounded to the nearest pixel edge on both axes.  Combines freely with `repeating` and `pad`.
+                                            Above 1: SWFR_ERR_INVALID, "UnknownBitmapFilter".  Ignored for solid and gradient fills.  A
+                                            decoder that wants Flash's result sets filter = smoothed ? 0 : 1.  Offset 60, in the remaining
+                                            tail padding: size (64) and every other offset are unchanged.  DESIGN.md, "Unsmoothed bitmap
+                                            fills" */
 } swfr_fill_style;
 
 typedef struct {
@@ -323,6 +335,9 @@ typedef struct {
     uint32_t extend;                     /* bitmap: 0 none, 1 repeat, 2 pad (CAIRO_EXTEND_PAD: swfr_fill_style::pad).  Radial / linear: 0 pad, 1 repeat, 2 reflect (cairo_pattern_set_extend);
                                             any other value on a gradient style is SWFR_ERR_INVALID at upload, and 1 or 2 on a LINEAR
                                             style SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread" */
+    uint32_t filter;                     /* bitmap: 0 CAIRO_FILTER_GOOD, 1 CAIRO_FILTER_NEAREST (swfr_fill_style::filter); any other value on a
+                                            bitmap style is SWFR_ERR_INVALID at upload.  Ignored for every other kind.  Offset 436, in what
+                                            was the struct's tail padding: the size (440) and every other offset are unchanged */
 } swfr_style;
 
 /* Upload a scene (kept resident in HBM), then rasterize it.  swfr_render_edges = upload + render. */

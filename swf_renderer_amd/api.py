@@ -94,7 +94,7 @@ class ColorStop(C.Structure):
 class FillStyle(C.Structure):
     _fields_ = [("type", C.c_uint32), ("color", Rgba8), ("morph_color", Rgba8), ("matrix", Matrix), ("n_stops", C.c_uint32),
                 ("stops", C.POINTER(ColorStop)), ("focal_point", C.c_int32), ("bitmap_id", C.c_uint32),
-                ("repeating", C.c_uint8), ("smoothed", C.c_uint8), ("spread", C.c_uint8), ("pad", C.c_uint8)]
+                ("repeating", C.c_uint8), ("smoothed", C.c_uint8), ("spread", C.c_uint8), ("pad", C.c_uint8), ("filter", C.c_uint8)]
 
 
 class LineStyle(C.Structure):
@@ -158,7 +158,7 @@ class Style(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("pixel", C.c_uint32), ("inv", C.c_double * 6),
                 ("c0x", C.c_double), ("c0y", C.c_double), ("r0", C.c_double), ("c1x", C.c_double), ("c1y", C.c_double), ("r1", C.c_double),
                 ("n_stops", C.c_uint32), ("stop_offset", C.c_float * MAX_STOPS), ("stop_rgba", (C.c_float * 4) * MAX_STOPS),
-                ("bitmap", C.c_uint32), ("extend", C.c_uint32)]
+                ("bitmap", C.c_uint32), ("extend", C.c_uint32), ("filter", C.c_uint32)]
 
 
 class Timing(C.Structure):
@@ -293,6 +293,21 @@ def _spread(v):
     raise SwfrError(ERR_INVALID, "UnknownGradientSpread")
 
 
+_FILTERS = {"good": 0, "nearest": 1}                         # cairo_filter_t GOOD / NEAREST, as swfr_fill_style::filter numbers them
+
+
+def _filter(v):
+    """fill["filter"] of a bitmap fill: a name of _FILTERS or its number; absent: good.  (A number the library does not know still goes
+    to it, to be refused there.)"""
+    if v is None:
+        return 0
+    if isinstance(v, str) and v.lower() in _FILTERS:
+        return _FILTERS[v.lower()]
+    if isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 255:
+        return v
+    raise SwfrError(ERR_INVALID, "UnknownBitmapFilter")
+
+
 class _Arena:
     """Keeps every ctypes object referenced by pointer alive for the duration of one call; collects the call's colour transforms."""
 
@@ -351,6 +366,7 @@ def _fill(arena, s):
         f.repeating = 1 if s.get("repeating") else 0
         f.smoothed = 1 if s.get("smoothed") else 0
         f.pad = 1 if s.get("pad") else 0                             # a clipped fill (SWF fill types 0x41 / 0x43): CAIRO_EXTEND_PAD
+        f.filter = _filter(s.get("filter"))                          # "nearest": an unsmoothed fill (0x42 / 0x43), CAIRO_FILTER_NEAREST
     return f
 
 

@@ -103,7 +103,9 @@ struct DevFilter {
     uint32_t width, height;
     uint32_t extend;         // bitmap: 0 none, 1 repeat, 2 pad; gradient: 0 pad, 1 repeat, 2 reflect (swfr_style::extend)
     uint32_t kind;           // SWFR_STYLE_*
-    uint32_t pad2[2];
+    uint32_t nearest;        // bitmap: 1 = CAIRO_FILTER_NEAREST (swfr_style::filter): the one texel at ((fx - 1) >> 16, (fy - 1) >> 16); `on` is then 0
+                             // and base_x / base_y are pixman's position + 0x8000 - 1: the bilinear sample's "half a texel back" is then pixman_fixed_e back
+    uint32_t pad2;
 };
 static_assert(sizeof(DevFilter) == 96, "DevFilter layout");
 

@@ -658,6 +658,7 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         const int32_t lut = stack_.back().lut;
         st.bitmap = lut < 0 ? s.bitmap_id : VARIANT_BASE + variant_of(s.bitmap_id, lut);
         st.extend = s.pad ? 2 : s.repeating ? 1 : 0;               // (pad and repeating together are refused when the shape is registered)
+        st.filter = s.filter;                                      // 0 CAIRO_FILTER_GOOD, 1 CAIRO_FILTER_NEAREST (above 1: refused with the shape)
         styles_.push_back(st);
         style_index = uint32_t(styles_.size() - 1);
     } else {
@@ -721,15 +722,21 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         // OVER is bounded by its source (_cairo_pattern_get_extents of an EXTEND_NONE surface pattern; a repeating or padded one is
         // unbounded): the bitmap's rectangle in
         // device space; an axis the filter magnifies is padded by half a source pixel and rounded to the nearest pixel edge,
-        // the others are rounded out
+        // the others are rounded out.  CAIRO_FILTER_NEAREST pads by 0.004 source pixels ("this avoids rounding errors") and rounds
+        // to the nearest pixel edge on both axes, whatever the scale
         const swfr_style& st = styles_[style_index];
         Affine pm;
         pm.xx = st.inv[0]; pm.yx = st.inv[1]; pm.xy = st.inv[2]; pm.yy = st.inv[3]; pm.x0 = st.inv[4]; pm.y0 = st.inv[5];
         const BitmapInfo& bi = store()->bitmaps_.find(s.bitmap_id)->second;
         double sx0 = 0, sy0 = 0, sx1 = bi.width, sy1 = bi.height;
         bool round_x = false, round_y = false;
-        if (std::hypot(pm.xx, pm.yx) < 1.0) { sx0 -= 0.5; sx1 += 0.5; round_x = true; }
-        if (std::hypot(pm.xy, pm.yy) < 1.0) { sy0 -= 0.5; sy1 += 0.5; round_y = true; }
+        if (st.filter == 1) {
+            sx0 -= 0.004; sx1 += 0.004; sy0 -= 0.004; sy1 += 0.004;
+            round_x = round_y = true;
+        } else {
+            if (std::hypot(pm.xx, pm.yx) < 1.0) { sx0 -= 0.5; sx1 += 0.5; round_x = true; }
+            if (std::hypot(pm.xy, pm.yy) < 1.0) { sy0 -= 0.5; sy1 += 0.5; round_y = true; }
+        }
         Affine im = pm;
         if (im.invert_cairo()) {
             double bx0 = 0, by0 = 0, bx1 = 0, by1 = 0;

@@ -1120,13 +1120,21 @@ __device__ __forceinline__ int wrap_mod(int x, int n, float inv_n) {
     const int r = x % n;
     return r < 0 ? r + n : r;
 }
+// CAIRO_FILTER_NEAREST (DevFilter::nearest, wave-uniform like `extend`) is the bilinear sample with two scalars changed: the position
+// moved back by pixman_fixed_e instead of half a texel -- the texel ((fx - 1) >> 16, (fy - 1) >> 16), so a sample exactly on a texel edge
+// reads the texel before it -- and the 7-bit weights forced to zero, which makes the mix c00 * 16384 >> 14 = c00 and the outside flags
+// of tap (a, a) "the texel is outside".  The extend is applied to that tap as to any other.  The first scalar is the host's: a
+// nearest style's base_x / base_y are 0x8000 - 1 further on (good_filter), so the `- 0x8000` below stands as it stood; the second is
+// this mask -- arithmetic, not a select: a select on flt.nearest made the compiler lay the bitmap routes out twice, at 65 VGPR
+// spills more (profiles/nearest_kernel_resources.txt).
+__device__ __forceinline__ uint32_t weight_mask(const DevFilter& flt) { return (flt.nearest - 1u) & 0x3fffu; }
 // bxp, byp: pixman's 16.16 sample position of the pixel centre, half a texel back (64-bit sums; the caller steps them along a row:
 // whole multiples of the matrix entries, so every position is the exact sum)
 __device__ __forceinline__ void bilinear_taps_at(const DevFilter& flt, long long bxp, long long byp, BilinearTap& t) {
     const bool repeat = flt.extend == 1;
     const int bw = (int)flt.width, bh = (int)flt.height;
     const int x0 = (int)(bxp >> 16), y0 = (int)(byp >> 16);
-    uint32_t wf = ((uint32_t)bxp >> 9 & 0x7fu) | (((uint32_t)byp >> 9 & 0x7fu) << 7);
+    uint32_t wf = (((uint32_t)bxp >> 9 & 0x7fu) | (((uint32_t)byp >> 9 & 0x7fu) << 7)) & weight_mask(flt);
     int xa = x0, xb = x0 + 1, ya = y0, yb = y0 + 1;
     if (repeat) {
         xa = wrap_mod(xa, bw, 1.0f / (float)bw); xb = xa + 1 == bw ? 0 : xa + 1;
@@ -1372,7 +1380,7 @@ __device__ __forceinline__ void blend8(uint32_t (&px)[8], const uint32_t (&al)[8
                 const int x0 = (int)(bxp >> 16), y0 = (int)(byp >> 16);
                 inside = inside && (unsigned)x0 < (unsigned)bw1 && (unsigned)y0 < (unsigned)bh1;
                 o[i] = __umul24((uint32_t)y0, flt.width) + (uint32_t)x0;          // (meaningless unless inside)
-                wf[i] = ((uint32_t)bxp >> 9 & 0x7fu) | (((uint32_t)byp >> 9 & 0x7fu) << 7);
+                wf[i] = (((uint32_t)bxp >> 9 & 0x7fu) | (((uint32_t)byp >> 9 & 0x7fu) << 7)) & weight_mask(flt);
             }
             if (__ballot(!inside) == 0ull) {                       // wave-uniform
                 const uint32_t* __restrict__ row_b = texels + flt.width;

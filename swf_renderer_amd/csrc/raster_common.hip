@@ -700,7 +700,8 @@ __device__ __noinline__ uint32_t shade(const swfr_style& s, uint32_t style_index
         return gradient_color(s, t);
     }
     // (No kernel instance reaches this branch for a bitmap today: they all sample through raster2.hip's shade_bitmap.  Its extend
-    //  2 -- CAIRO_EXTEND_PAD, the coordinates clamped per axis -- is therefore held by reading alone, not by any test.)
+    //  2 -- CAIRO_EXTEND_PAD, the coordinates clamped per axis -- is therefore held by reading alone, not by any test; so is
+    //  CAIRO_FILTER_NEAREST, DevFilter::nearest.)
     const DevBitmap bm = bitmaps.bitmaps[s.bitmap];
     const DevFilter flt = bitmaps.filters[style_index];
     // pixman's own 16.16 sample position of this pixel's centre
@@ -740,10 +741,13 @@ __device__ __noinline__ uint32_t shade(const swfr_style& s, uint32_t style_index
         sa = min(max(sa, 0ll), 255ll); sr = min(max(sr, 0ll), 255ll); sg = min(max(sg, 0ll), 255ll); sb = min(max(sb, 0ll), 255ll);
         return ((uint32_t)sa << 24) | ((uint32_t)sr << 16) | ((uint32_t)sg << 8) | (uint32_t)sb;
     }
-    // bilinear with 7-bit weights (what CAIRO_FILTER_GOOD becomes for scales > .75)
+    // bilinear with 7-bit weights (what CAIRO_FILTER_GOOD becomes for scales > .75).  CAIRO_FILTER_NEAREST is the same sample with
+    // the weights forced to zero -- c[0] * 16384 >> 14, the one texel -- at a position the host has moved by 0x8000 - 1 (good_filter:
+    // base_x, base_y), so that "half a texel back" lands pixman_fixed_e back
     const long long bxp = fxp - 0x8000, byp = fyp - 0x8000;
     const int x0 = (int)(bxp >> 16), y0 = (int)(byp >> 16);
-    const int wx = (int)((bxp >> 9) & 0x7f), wy = (int)((byp >> 9) & 0x7f);
+    const int wmask = (int)((flt.nearest - 1u) & 0x7fu);
+    const int wx = (int)((bxp >> 9) & 0x7f) & wmask, wy = (int)((byp >> 9) & 0x7f) & wmask;
     uint32_t c[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

@@ -513,6 +513,12 @@ void validate_gradient_extend(const swfr_style* styles, size_t n_styles) {
     }
 }
 
+// swfr_style::filter of a bitmap style: 0 CAIRO_FILTER_GOOD, 1 CAIRO_FILTER_NEAREST; every other kind ignores the field
+void validate_bitmap_filter(const swfr_style* styles, size_t n_styles) {
+    for (size_t i = 0; i < n_styles; ++i)
+        if (styles[i].kind == SWFR_STYLE_BITMAP && styles[i].filter > 1) throw StatusError{SWFR_ERR_INVALID, "bitmap filter must be 0 (good) or 1 (nearest)"};
+}
+
 void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
                     const swfr_style* styles, size_t n_styles) {
     // end points within +-32768 px (2^23 in 24.8): inside that range the int64 products of the closed-form edge evaluation cannot overflow
@@ -742,6 +748,9 @@ DevFilter good_filter(const swfr_style& st, const int rect[4], std::vector<int32
     if (st.kind != SWFR_STYLE_BITMAP) return f;
     const PixmanPosition pos = pixman_transform_of(pattern_matrix(st), rect);
     f.base_x = pos.base_x; f.base_y = pos.base_y; f.m00 = pos.m00; f.m01 = pos.m01; f.m10 = pos.m10; f.m11 = pos.m11;
+    // CAIRO_FILTER_NEAREST: one texel at every scale -- no convolution however small the scale (`on` stays 0) -- fetched by the bilinear
+    // routes with their weights masked to zero; their "half a texel back" must land pixman_fixed_e back, so the base moves by the rest
+    if (st.filter == 1) { f.nearest = 1; f.base_x += 0x8000 - 1; f.base_y += 0x8000 - 1; return f; }
     const double xx = st.inv[0], yx = st.inv[1], xy = st.inv[2], yy = st.inv[3], x0 = st.inv[4], y0 = st.inv[5];
     if (good_use_bilinear(xx, xy, x0) && good_use_bilinear(yx, yy, y0)) return f;
     double dx = std::hypot(xx, xy), dy = std::hypot(yx, yy);
@@ -1243,6 +1252,7 @@ int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size
     validate_groups(paths, n_paths);
     validate_blend_fields(paths, n_paths);                       // (a malformed blend field is refused as such even by a host-only handle)
     validate_gradient_extend(styles, n_styles);                  // (and so is a gradient's extend)
+    validate_bitmap_filter(styles, n_styles);                    // (and a bitmap's filter)
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
     validate_scene(r, edges, n_edges, paths, n_paths, styles, n_styles);
     return upload2(r, si, all_sets, edges, n_edges, paths, n_paths, styles, n_styles, fb_override, false);

@@ -25,9 +25,10 @@ struct Layer {
     std::vector<StyleBucket> fills, lines;
 };
 
-// spread and pad lie in what was the struct's tail padding (include/swfr.h): the layout callers compiled against must not move
+// spread, pad and filter lie in what was the struct's tail padding (include/swfr.h): the layout callers compiled against must not move
 static_assert(sizeof(swfr_fill_style) == 64 && offsetof(swfr_fill_style, repeating) == 56 && offsetof(swfr_fill_style, smoothed) == 57 &&
-              offsetof(swfr_fill_style, spread) == 58 && offsetof(swfr_fill_style, pad) == 59, "swfr_fill_style layout");
+              offsetof(swfr_fill_style, spread) == 58 && offsetof(swfr_fill_style, pad) == 59 && offsetof(swfr_fill_style, filter) == 60, "swfr_fill_style layout");
+static_assert(sizeof(swfr_style) == 440 && offsetof(swfr_style, extend) == 432 && offsetof(swfr_style, filter) == 436, "swfr_style layout");
 
 OwnedFill own_fill(const swfr_fill_style& s, bool morph) {
     OwnedFill f;
@@ -40,6 +41,9 @@ OwnedFill own_fill(const swfr_fill_style& s, bool morph) {
     // a clipped bitmap fill (SWF fill types 0x41 / 0x43): CAIRO_EXTEND_PAD; a fill cannot both repeat and pad
     if (s.type == SWFR_FILL_BITMAP && (s.pad > 1 || (s.pad && s.repeating))) throw std::runtime_error("InvalidBitmapPad");
     if (s.type != SWFR_FILL_BITMAP) f.style.pad = 0;
+    // the Cairo filter of a bitmap fill: 0 CAIRO_FILTER_GOOD, 1 CAIRO_FILTER_NEAREST (an unsmoothed fill, SWF fill types 0x42 / 0x43)
+    if (s.type == SWFR_FILL_BITMAP && s.filter > 1) throw std::runtime_error("UnknownBitmapFilter");
+    if (s.type != SWFR_FILL_BITMAP) f.style.filter = 0;
     if (s.n_stops && s.stops) f.stops.assign(s.stops, s.stops + s.n_stops);
     f.style.stops = nullptr;
     f.style.n_stops = uint32_t(f.stops.size());
