@@ -81,7 +81,7 @@ typedef struct {
                                             with cairo_pattern_set_extend(PAD | REFLECT | REPEAT).  Anything else: SWFR_ERR_INVALID,
                                             "UnknownGradientSpread".  Radial and focal gradients follow pixman's walker bit for bit; a LINEAR
                                             gradient with a spread other than pad is SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"
-                                            (refused, never approximated).  Ignored for solid and bitmap fills.  The field lies in what was
+                                            (refused, never approximated) unless the handle has SWFR_FLAG_LINEAR_PIXMAN, which draws it as pixman does.  Ignored for solid and bitmap fills.  The field lies in what was
                                             the struct's tail padding: size and offsets are unchanged.  DESIGN.md, "Gradient spread modes" */
     uint8_t pad;                         /* bitmap: 1 = a padded ("clipped") fill, SWF fill types 0x41 / 0x43 -- the bitmap's Cairo pattern with
                                             cairo_pattern_set_extend(CAIRO_EXTEND_PAD): a sample outside the bitmap reads the nearest edge
@@ -226,6 +226,10 @@ int swfr_set_color_transform(swfr_renderer *r, uint32_t slot, const swfr_color_t
 #define SWFR_FLAG_ANTIALIAS_NONE 4u      /* aliased edges: cairo_set_antialias(cr, CAIRO_ANTIALIAS_NONE), node-canvas's
                                             ctx.antialias = 'none' (the reference always antialiases): polygons are sampled at pixel
                                             centres, rectilinear paths rounded to whole pixels; every render route honours it */
+#define SWFR_FLAG_LINEAR_PIXMAN 8u       /* a SWFR_FILL_LINEAR_GRADIENT becomes a SWFR_STYLE_LINEAR_PIXMAN style -- libcairo's bytes, every
+                                            spread -- instead of the float64 model (within +-1 of Cairo, pad only).  Together with
+                                            SWFR_FLAG_ANTIALIAS_NONE: swfr_create fails with SWFR_ERR_NOT_IMPLEMENTED
+                                            ("NotImplementedAliasedPixmanLinear", readable with swfr_last_error(NULL) on the same thread) */
 
 typedef struct {
     int32_t device;                      /* HIP device ordinal, or SWFR_DEVICE_HOST_ONLY */
@@ -240,7 +244,9 @@ typedef struct {
 /* ---- lifecycle / assets / render ----------------------------------------------------------- */
 int  swfr_create(uint32_t width, uint32_t height, const swfr_config *cfg, swfr_renderer **out);
 void swfr_destroy(swfr_renderer *r);
-const char *swfr_last_error(const swfr_renderer *r);
+const char *swfr_last_error(const swfr_renderer *r);   /* r == NULL: "null handle" -- or, after a swfr_create on this thread refused a combination
+                                                          of flags (SWFR_FLAG_LINEAR_PIXMAN with SWFR_FLAG_ANTIALIAS_NONE), that refusal's name, until the
+                                                          thread's next swfr_create */
 uint32_t swfr_abi_version(void);
 
 int  swfr_register_shape(swfr_renderer *r, const swfr_define_shape *tag, uint32_t *out_id);
@@ -317,7 +323,16 @@ typedef struct {
 enum { SWFR_OP_OVER = 0, SWFR_OP_MULTIPLY = 1, SWFR_OP_SCREEN = 2, SWFR_OP_LIGHTEN = 3, SWFR_OP_DARKEN = 4, SWFR_OP_DIFFERENCE = 5,
        SWFR_OP_ADD = 6, SWFR_OP_OVERLAY = 7, SWFR_OP_HARDLIGHT = 8 };
 
-enum { SWFR_STYLE_SOLID = 0, SWFR_STYLE_RADIAL = 1, SWFR_STYLE_LINEAR = 2, SWFR_STYLE_BITMAP = 3 };
+enum { SWFR_STYLE_SOLID = 0, SWFR_STYLE_RADIAL = 1, SWFR_STYLE_LINEAR = 2, SWFR_STYLE_BITMAP = 3,
+       SWFR_STYLE_LINEAR_PIXMAN = 4 };   /* 4: the linear gradient c0 -> c1 evaluated as pixman 0.40 does (linear_get_scanline), piece by
+                                            piece as cairo 1.16 composites the shape -- bit-exact, with extend 0 pad, 1 repeat, 2 reflect.
+                                            One path per style; c0 == c1 is SWFR_ERR_INVALID; a line other than a SWF fill's (-16384, 0)-(16384, 0) is
+                                            SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedLinearLine" (only that line has been held against libcairo); on a handle with SWFR_FLAG_ANTIALIAS_NONE
+                                            SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedAliasedPixmanLinear"; a rectilinear path of several
+                                            boxes, or one box off the pixel grid wider than 256 px, "NotImplementedLinearPieces"; a position
+                                            that moves by less than one 16.16 unit per pixel row without standing still,
+                                            "NotImplementedLinearRowStep"; a rectangle that leaves pixman's 16.16 range SWFR_ERR_CAPACITY,
+                                            "LinearGradientOutOfRange".  2 stays the float64 model.  DESIGN.md, "Pixman-exact linear gradients" */
 #define SWFR_MAX_STOPS 16
 
 typedef struct {
@@ -334,7 +349,7 @@ typedef struct {
                                             handle's last scene walk built (swfr_build_frame), valid on that handle until its next walk */
     uint32_t extend;                     /* bitmap: 0 none, 1 repeat, 2 pad (CAIRO_EXTEND_PAD: swfr_fill_style::pad).  Radial / linear: 0 pad, 1 repeat, 2 reflect (cairo_pattern_set_extend);
                                             any other value on a gradient style is SWFR_ERR_INVALID at upload, and 1 or 2 on a LINEAR
-                                            style SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread" */
+                                            style SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread" (a LINEAR_PIXMAN style takes all three) */
     uint32_t filter;                     /* bitmap: 0 CAIRO_FILTER_GOOD, 1 CAIRO_FILTER_NEAREST (swfr_fill_style::filter); any other value on a
                                             bitmap style is SWFR_ERR_INVALID at upload.  Ignored for every other kind.  Offset 436, in what
                                             was the struct's tail padding: the size (440) and every other offset are unchanged */

@@ -20,9 +20,11 @@ DEVICE_HOST_ONLY = -1
 FLAG_EVEN_ODD = 1
 FLAG_BANDS_CONTIGUOUS = 2
 FLAG_ANTIALIAS_NONE = 4
+FLAG_LINEAR_PIXMAN = 8
+LINEAR_MODES = ("float64", "pixman")    # how a linear gradient fill is evaluated: the float64 model (within +-1 of Cairo, pad only) or as pixman does (exact, every spread)
 ANTIALIAS_MODES = ("default", "none")   # node-canvas's ctx.antialias values this renderer knows
 PATH_TOR, PATH_BOXES = 0, 1
-STYLE_SOLID, STYLE_RADIAL, STYLE_LINEAR, STYLE_BITMAP = 0, 1, 2, 3
+STYLE_SOLID, STYLE_RADIAL, STYLE_LINEAR, STYLE_BITMAP, STYLE_LINEAR_PIXMAN = 0, 1, 2, 3, 4
 MAX_STOPS = 16
 
 EXPORTS = [
@@ -478,19 +480,25 @@ def decode_x_swf_bmp(data: bytes):
 class Renderer:
     """`new NodeCanvasRenderer(width, height)` + `Renderer{render, addBitmap}` over libswfr.so."""
 
-    def __init__(self, width, height, device=0, even_odd=False, band_index=0, band_count=0, contiguous_bands=False, antialias="default"):
+    def __init__(self, width, height, device=0, even_odd=False, band_index=0, band_count=0, contiguous_bands=False, antialias="default", linear="float64"):
         # antialias: "default" (Cairo's 15x256 antialiasing, the reference) or "none" (aliased edges: CAIRO_ANTIALIAS_NONE)
+        # linear: "float64" (linear gradient fills by the float64 model, pad only) or "pixman" (as pixman paints them: libcairo's bytes, every spread)
         if antialias not in ANTIALIAS_MODES:
             raise ValueError("antialias must be one of %r, not %r" % (ANTIALIAS_MODES, antialias))
+        if linear not in LINEAR_MODES:
+            raise ValueError("linear must be one of %r, not %r" % (LINEAR_MODES, linear))
         self.L = load_library()
         self.width, self.height = int(width), int(height)
         self.antialias = antialias
-        flags = (FLAG_EVEN_ODD if even_odd else 0) | (FLAG_BANDS_CONTIGUOUS if contiguous_bands else 0) | (FLAG_ANTIALIAS_NONE if antialias == "none" else 0)
+        self.linear = linear
+        flags = ((FLAG_EVEN_ODD if even_odd else 0) | (FLAG_BANDS_CONTIGUOUS if contiguous_bands else 0) | (FLAG_ANTIALIAS_NONE if antialias == "none" else 0) |
+                 (FLAG_LINEAR_PIXMAN if linear == "pixman" else 0))
         cfg = Config(int(device), flags, band_index, band_count)
         h = C.c_void_p()
         rc = self.L.swfr_create(self.width, self.height, C.byref(cfg), C.byref(h))
         if rc != OK:
-            raise SwfrError(rc, "swfr_create failed (no HIP device?)" if rc == ERR_NO_DEVICE else "swfr_create failed")
+            why = self.L.swfr_last_error(None).decode("utf-8", "replace") if rc == ERR_NOT_IMPLEMENTED else ""
+            raise SwfrError(rc, "swfr_create failed (no HIP device?)" if rc == ERR_NO_DEVICE else "swfr_create failed" + (": " + why if why else ""))
         self.h = h
         self._ids = {}        # id(tag) -> (registered id, tag)  [the reference's WeakMap caches]
 

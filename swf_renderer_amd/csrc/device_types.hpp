@@ -113,6 +113,9 @@ static_assert(sizeof(DevFilter) == 96, "DevFilter layout");
 // pixman-radial-gradient.c, pixman-gradient-walker.c): the 16.16 sample position as for bitmaps, the circles after Cairo's
 // fit-to-range scaling, the constant terms of the quadratic, and one single-precision colour ramp per interval between stops
 // (PAD sentinels at both ends; REPEAT and REFLECT: the stops themselves, the ramp is formed per pixel).  DevFilter::pad of the style holds its index + 1 into the handle's gradient table.
+// A SWFR_STYLE_LINEAR_PIXMAN style (host: linear_of) uses the same record: c1x, c1y = p1, dx, dy = p2 - p1 (16.16); a = (double)(dx p1.x + dy p1.y),
+// inva = 65536 / (dx^2 + dy^2), mindr = the position's step per pixel; x_min = the rectangle's left edge; pad, c1r, dr = a tor path's table of piece
+// origins in the handle's int32 table: offset + 1 (0: none), the rectangle's first row, entries per row (raster2.hip, k2_linear_pieces).
 struct DevGradient {
     int64_t base_x, base_y;
     int32_t m00, m01, m10, m11;
@@ -247,6 +250,9 @@ struct Frame2 {
     uint32_t band_first, band_stride;   // the handle's tile-rows: band_first + l * band_stride, l < n_strips / (STRIPS_PER_TILE * tiles_x)
                                         // (interleaved over the ranks: stride = ranks; one contiguous block per rank: stride = 1)
     uint32_t mono;           // 1: SWFR_FLAG_ANTIALIAS_NONE -- tor paths are converted at pixel centres by k2_rows_mono (mono.hip)
+    uint32_t n_linear_records;   // records of src.gradients k2_linear_pieces looks through: all of them in a frame with a pixman-linear tor path, else 0
+                                 // (a batch is launched with the largest count of its frames: a workgroup beyond this frame's count returns)
+    uint32_t pad_linear;
     const uint8_t* path_op;  // per path: its operator (SWFR_OP_*) | PATH_OP_* bits, read by k2_tiles<3> and <4> alone; nullptr in a frame without a blended path.
                              // The path records themselves carry lerp & 1 only -- 0 for every blended path -- so that nothing k2_bin and
                              // the row kernels derive from "lerp is not zero" (BE_LERP, opaque covers, culling) can fire for one

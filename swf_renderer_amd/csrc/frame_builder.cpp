@@ -200,7 +200,8 @@ struct FrameBuilder::Pool {
     }
 };
 
-FrameBuilder::FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased) : w_(width), h_(height), even_odd_(even_odd), aliased_(aliased) {}
+FrameBuilder::FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased, bool linear_pixman)
+    : w_(width), h_(height), even_odd_(even_odd), aliased_(aliased), linear_pixman_(linear_pixman) {}
 
 FrameBuilder::~FrameBuilder() {
     if (pool_) {
@@ -295,7 +296,7 @@ void FrameBuilder::build(const swfr_stage& stage) {
     if (!pool_) pool_.reset(new Pool);
     Pool& P = *pool_;
     while (int(P.builders.size()) < pieces) {                 // (piece k is built by builders[k-1] for k >= 1; piece 0 needs a scratch builder, too)
-        P.builders.emplace_back(new FrameBuilder(w_, h_, even_odd_, aliased_));
+        P.builders.emplace_back(new FrameBuilder(w_, h_, even_odd_, aliased_, linear_pixman_));
         P.builders.back()->parent_ = this;
         P.builders.back()->threads_ = 0;
     }
@@ -679,9 +680,10 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         // field.  A linear gradient is the float64 extension: next to a repeat seam a +-1 LSB model can land a whole colour away,
         // so a spread one is refused
         st.extend = s.spread == 1 ? 2u : s.spread == 2 ? 1u : 0u;
-        if (s.type == SWFR_FILL_LINEAR_GRADIENT && st.extend) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"};
+        // (SWFR_FLAG_LINEAR_PIXMAN: pixman's own evaluation, SWFR_STYLE_LINEAR_PIXMAN, which has every spread)
+        if (s.type == SWFR_FILL_LINEAR_GRADIENT && st.extend && !linear_pixman_) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"};
         if (s.type == SWFR_FILL_LINEAR_GRADIENT) {
-            st.kind = SWFR_STYLE_LINEAR;
+            st.kind = linear_pixman_ ? SWFR_STYLE_LINEAR_PIXMAN : SWFR_STYLE_LINEAR;
             st.c0x = -R; st.c1x = R;
         } else {
             st.kind = SWFR_STYLE_RADIAL;

@@ -48,7 +48,7 @@ bool color_transform_valid(const swfr_color_transform& ct);
 // paint into a SOURCE-rule lerp -- is marked in the paths (`lerp` = 2) and settled when the pieces are joined.
 class FrameBuilder {
 public:
-    FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased = false);   // aliased: SWFR_FLAG_ANTIALIAS_NONE
+    FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased = false, bool linear_pixman = false);   // aliased: SWFR_FLAG_ANTIALIAS_NONE
     ~FrameBuilder();
     FrameBuilder(const FrameBuilder&) = delete;
     FrameBuilder& operator=(const FrameBuilder&) = delete;
@@ -110,6 +110,7 @@ private:
     uint32_t w_, h_;
     bool even_odd_;
     bool aliased_;
+    bool linear_pixman_;     // SWFR_FLAG_LINEAR_PIXMAN: linear gradient fills become SWFR_STYLE_LINEAR_PIXMAN styles
     std::vector<DecodedShape> shapes_, morphs_;
     std::map<uint32_t, BitmapInfo> bitmaps_;
     std::vector<State> stack_;

@@ -1237,6 +1237,7 @@ __device__ __forceinline__ uint32_t shade_bitmap(uint32_t style_index, const Sou
 // its own, everything else is shade()'s as before (wave-uniform: one style per band entry)
 __device__ __forceinline__ uint32_t shade_gradient(const swfr_style* __restrict__ styles, uint32_t style, const Sources& src, int cx, int cy) {
     if (src.filters[style].extend && src.filters[style].kind == SWFR_STYLE_RADIAL && src.filters[style].pad > 0) return shade_spread(src, style, cx, cy);
+    if (src.filters[style].kind == SWFR_STYLE_LINEAR_PIXMAN) return shade_linear(src, style, cx, cy);      // (the pixman-exact linear gradient, every extend)
     return shade(styles[style], style, src, cx, cy);
 }
 template <int SHADERS>
@@ -2074,6 +2075,80 @@ void launch2_rows_slow(hipStream_t st, const Frame2* frames, uint32_t n_frames, 
         if (grid_huge) hipLaunchKernelGGL(k2_rows_huge_b, dim3(grid_huge, n_frames), dim3(HUGE_THREADS), 0, st, frames, pass);
         if (pass + 1 >= max_passes) break;
     }
+}
+// ---------------------------------------------------------------------------------------------
+// k2_linear_pieces: where libcairo starts the ramp of a pixman-linear gradient in every row of a tor path ("Pixman-exact
+// linear gradients").  libcairo's span renderer hands pixman every row of spans on its own (cairo-image-compositor.c, _inplace_spans):
+// one composite from the row's first span to its last -- cut where a span of 256 or more pixels has coverage 255 (composited alone,
+// without the mask) and where an empty span follows more than 256 gathered pixels -- and pixman's linear_get_scanline counts its
+// pixels from the composite's left edge.  The spans are those of cairo-tor-scan-converter.c, blit_a8, formed from the row's cells: one
+// wherever the raw area changes.  One workgroup per gradient record, one thread per row of the path: the row's cells (few) are walked in
+// column order by repeated minimum, the spans go through _inplace_spans' state, and the first column of every composite is written
+// to the row's list in the handle's int32 table (host: prepare_sources), which shade_linear reads.  The values follow from the scene
+// alone, so frames in flight write the same ones.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void linear_pieces_body(FramePtr FR) {
+    if (blockIdx.x >= FR->n_linear_records) return;                      // (workgroup-uniform: a batch's grid is sized for its largest frame)
+    const DevGradient* G = FR->src.gradients + blockIdx.x;
+    if (G->pad <= 0) return;                                             // (workgroup-uniform: a radial record, or a box path's)
+    int32_t* table = const_cast<int32_t*>(FR->src.fparams) + (G->pad - 1);
+    const uint32_t path = (uint32_t)table[-1];
+    if (path >= FR->n_paths) return;
+    const DevPath P = FR->paths[path];
+    const int per_row = G->dr, run = 256;
+    const int xmax = P.x_max - P.x_min;
+    for (int r = P.y_min + (int)threadIdx.x; r < P.y_max; r += (int)blockDim.x) {
+        int32_t* out = table + (size_t)(r - G->c1r) * (size_t)per_row;
+        int n_out = 0;
+        const BandSlot bs = FR->band_slots[FR->path_slots[path] + (uint32_t)(r / TILE_H - P.y_min / TILE_H)];
+        RowInfo2 ri; ri.off = 0; ri.n = 0; ri.mode = (uint16_t)ROW_FOREIGN;
+        if (bs.path == path && bs.band == (uint32_t)(r / TILE_H)) ri = FR->rows[(size_t)bs.slot * TILE_H + (uint32_t)(r & (TILE_H - 1))];
+        int n = (int)ri.n;
+        if (bs.path != path || bs.band != (uint32_t)(r / TILE_H)) n = 0;  // (no band entry: a frame that overflowed its band list has failed already)
+        if (ri.mode == ROW_FOREIGN || ri.mode == ROW_DEFER) n = 0;
+        if (ri.off > FR->cell_slice - min((uint32_t)n, FR->cell_slice)) n = 0;
+        const Cell* cp = FR->cells + ri.off;
+        // _inplace_spans over the spans blit_a8 forms; a span is known once the next one begins
+        bool have = false, first = true;
+        int sx = 0, scov = 0, x0 = 0, x1 = 0;
+        auto piece = [&](int from) { if (n_out < per_row) out[n_out] = from + P.x_min; ++n_out; };
+        auto feed = [&](int x, int raw) {                                // a span begins at column x (relative to the path) with this raw area
+            if (have) {
+                const int len = x - sx, cov = (int)(((uint32_t)(17 * scov + 256) >> 9) & 255u);
+                if (first) { x0 = x1 = sx; first = false; }
+                if (len > 1) {
+                    if (len >= run && cov == 255) { if (x1 != x0) piece(x0); piece(sx); x0 = x; }
+                    else if (cov == 0 && x1 - x0 > run) { piece(x0); x0 = x; }
+                }
+                x1 = x;
+            }
+            have = true; sx = x; scov = raw;
+        };
+        int prev_x = 0, last_x = -1, cover = 0, last_cover = 0, cur = -1;
+        for (;;) {
+            int c = 0x7fffffff;
+            for (int k = 0; k < n; ++k) { const int col = cell_col(cp[k]); if (col > cur && col < c) c = col; }
+            if (c >= xmax) break;                                        // (also: no cell left)
+            int hsum = 0, usum = 0;
+            for (int k = 0; k < n; ++k) if (cell_col(cp[k]) == c) { hsum += cell_ch(cp[k]); usum += cell_ua(cp[k]); }
+            if (c > prev_x && cover != last_cover) { feed(prev_x, cover); last_cover = cover; last_x = prev_x; }
+            cover += hsum * 512;
+            const int area = cover - usum;
+            if (area != last_cover) { feed(c, area); last_cover = area; last_x = c; }
+            prev_x = c + 1;
+            cur = c;
+        }
+        if (prev_x <= xmax && cover != last_cover) { feed(prev_x, cover); last_cover = cover; last_x = prev_x; }
+        if (last_x < xmax && last_cover) feed(xmax, 0);
+        if (!first && x1 != x0) piece(x0);
+        if (n_out > per_row) { atomicOr(&FR->counters[C2_ERROR], E2_ROW_TABLE); n_out = per_row; }
+        for (int k = n_out; k < per_row; ++k) out[k] = 0x7fffffff;
+    }
+}
+__global__ __launch_bounds__(64) void k2_linear_pieces_b(const Frame2* __restrict__ frames) { linear_pieces_body(FRAME_PTR(frames, blockIdx.y)); }
+void launch2_linear_pieces(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t n_gradients) {
+    if (!n_gradients) return;
+    hipLaunchKernelGGL(k2_linear_pieces_b, dim3(n_gradients, n_frames), dim3(64), 0, st, frames);
 }
 // fb_to: where THIS launch's pixels go instead of the descriptors' framebuffer (one frame per launch only), or nullptr
 void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_strips, uint32_t grid_cap, int shader_level, uint32_t* fb_to) {

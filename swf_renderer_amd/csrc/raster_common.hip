@@ -609,6 +609,29 @@ __device__ __forceinline__ bool radial_position(const DevGradient& G, int px, in
     }
     return false;
 }
+// pixman-linear-gradient.c, linear_get_scanline (the affine branch), for a SWFR_STYLE_LINEAR_PIXMAN style (host: linear_of): the piece of
+// the row that holds the pixel starts at column `origin` -- the rectangle's left edge for a box path; for a tor path the last entry
+// not right of the pixel in the row's list, which k2_linear_pieces (raster2.hip) has written from the row's cells -- and the
+// position of its i-th pixel is trunc(t) + trunc(inc * i): t from the 64-bit integer products at the piece's first sample, the two
+// truncations apart.  (pixman fills a scanline with the pixel at trunc(t) when trunc(inc * width) == 0; every trunc(inc * i) is then
+// zero as well, so that branch asks the walker for the same positions and needs no code here.)
+__device__ __forceinline__ int linear_origin(const DevGradient& G, const int32_t* __restrict__ fparams, int px, int py) {
+    int origin = G.x_min;
+    if (G.pad > 0) {
+        const int32_t* row = fparams + (G.pad - 1) + (size_t)(py - G.c1r) * (size_t)G.dr;
+#pragma nounroll
+        for (int k = 0; k < G.dr && row[k] <= px; ++k) origin = row[k];
+    }
+    return origin;
+}
+__device__ __forceinline__ long long linear_position(const DevGradient& G, int origin, int px, int py) {
+    const long long vx = G.base_x + (long long)origin * G.m00 + (long long)py * G.m01;
+    const long long vy = G.base_y + (long long)origin * G.m10 + (long long)py * G.m11;
+    const long long ai = (long long)G.dx * vx + (long long)G.dy * vy;
+    const double t = ((double)ai - G.a) * G.inva;
+    const double step = G.mindr * (double)(px - origin);
+    return (long long)t + (long long)step;
+}
 // pixman-gradient-walker.c under REPEAT (G.extend 1) and REFLECT (2): gradient_walker_reset at this pixel's position -- the position
 // folded into [0, 1] (mirrored in an odd period of REFLECT), the first stop beyond it, the interval mirrored back and shifted into the
 // position's own period, slope and offset of every channel in single precision FROM THOSE SHIFTED ENDS (so they differ from period to
@@ -623,11 +646,16 @@ __device__ __forceinline__ bool radial_position(const DevGradient& G, int px, in
 // rectangle -- the two agree unless the shape's first covered pixel of a run is such a sample.)
 // A shader call of its own beside shade() (raster2.hip, shade_gradient, picks per style): shade() -- the padded walker, the linear
 // extension, the bitmap filters -- stays the code it was, instruction for instruction, and keeps its registers.
-__device__ __noinline__ uint32_t shade_spread(const Sources bitmaps, uint32_t style_index, int px, int py) {
+// LINEAR: the position is linear_position's, and the scan to the left asks that, too, down to the piece's first column (where libcairo's
+// walker starts).
+template <bool LINEAR>
+__device__ __forceinline__ uint32_t spread_pixel(const Sources& bitmaps, uint32_t style_index, int px, int py) {
     const DevGradient& G = bitmaps.gradients[bitmaps.filters[style_index].pad - 1];
     if (!G.n_intervals) return 0u;
     long long pos;
-    if (!radial_position(G, px, py, pos)) return 0u;
+    int origin = G.x_min;
+    if (LINEAR) { origin = linear_origin(G, bitmaps.fparams, px, py); pos = linear_position(G, origin, px, py); }
+    else if (!radial_position(G, px, py, pos)) return 0u;
     const int low = (int)(pos & 0xffff);
     const bool odd = G.extend == 2 && (pos & 0x10000);
     const int x = odd ? 0x10000 - low : low;
@@ -641,9 +669,10 @@ __device__ __noinline__ uint32_t shade_spread(const Sources bitmaps, uint32_t st
         while (first > 1 && G.x[first - 1] == x) --first;           // the first of the stops at x: the interval that begins here (in the scanline's direction) ends at the stop before it
         const long long end = pos - low + 0x10000 - G.x[first - 1];
 #pragma nounroll
-        for (int qx = px - 1; qx >= G.x_min; --qx) {
+        for (int qx = px - 1; qx >= origin; --qx) {
             long long q;
-            if (!radial_position(G, qx, py, q) || q == pos) continue;
+            if (LINEAR) { q = linear_position(G, origin, qx, py); if (q == pos) continue; }
+            else if (!radial_position(G, qx, py, q) || q == pos) continue;
             if (q > pos && q < end) il = first - 1;
             break;
         }
@@ -667,6 +696,17 @@ __device__ __noinline__ uint32_t shade_spread(const Sources bitmaps, uint32_t st
         else out |= ((uint32_t)(fa * v + .5f) & 0xffu) << (24 - 8 * ch);
     }
     return out;
+}
+__device__ __noinline__ uint32_t shade_spread(const Sources bitmaps, uint32_t style_index, int px, int py) {
+    return spread_pixel<false>(bitmaps, style_index, px, py);
+}
+// A SWFR_STYLE_LINEAR_PIXMAN style's pixel: the padded walker or the spread one at pixman's linear position.  A shader call of its own
+// like shade_spread, for the same reason.
+__device__ __noinline__ uint32_t shade_linear(const Sources bitmaps, uint32_t style_index, int px, int py) {
+    const DevGradient& G = bitmaps.gradients[bitmaps.filters[style_index].pad - 1];
+    if (G.extend) return spread_pixel<true>(bitmaps, style_index, px, py);
+    if (!G.n_intervals) return 0u;
+    return radial_walker_pixel(G, linear_position(G, linear_origin(G, bitmaps.fparams, px, py), px, py));
 }
 __device__ __noinline__ uint32_t shade(const swfr_style& s, uint32_t style_index, const Sources bitmaps, int px, int py) {
     if (s.kind == SWFR_STYLE_RADIAL) {

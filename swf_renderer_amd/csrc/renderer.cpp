@@ -31,6 +31,7 @@ void launch2_bin(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint3
 void launch2_rows(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, bool, bool);
 void launch2_rows_slow(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, bool);
 void launch2_tiles(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, int, uint32_t*);
+void launch2_linear_pieces(hipStream_t, const Frame2*, uint32_t, uint32_t);
 void launch_unpremultiply(hipStream_t, const uint32_t*, uint32_t*, size_t);
 void launch_pack_band(hipStream_t, const uint32_t*, uint32_t*, int, int, uint32_t, uint32_t, uint32_t);
 void launch_cxform_texels(hipStream_t, const uint8_t*, uint32_t*, size_t, const uint32_t*);
@@ -182,6 +183,7 @@ struct swfr_renderer {
         size_t n_edges = 0, n_paths = 0, n_styles = 0, n_rows = 0, n_chunks = 0, n_bands = 0, chunk_rows = 64;
         bool any_shader = false;
         int shader_level = 0;
+        uint32_t linear_grid = 0;            // gradient records k2_linear_pieces looks through (0: the scene has no pixman-linear tor path)
         size_t n_incidences = 0, n_strips = 0, n_strip_slots = 0;   // (edge, pixel row) pairs: bounds the cells of a frame; k2_tiles wavefronts / launch list slots
         size_t n_slots = 0, cell_total = 0;
         uint32_t max_path_edges = 0;              // picks the row kernel's instance (edges staged in LDS per chunk)
@@ -507,7 +509,7 @@ bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths
 void validate_gradient_extend(const swfr_style* styles, size_t n_styles) {
     for (size_t i = 0; i < n_styles; ++i) {
         const swfr_style& s = styles[i];
-        if (s.kind != SWFR_STYLE_RADIAL && s.kind != SWFR_STYLE_LINEAR) continue;
+        if (s.kind != SWFR_STYLE_RADIAL && s.kind != SWFR_STYLE_LINEAR && s.kind != SWFR_STYLE_LINEAR_PIXMAN) continue;
         if (s.extend > 2) throw StatusError{SWFR_ERR_INVALID, "gradient extend must be 0 (pad), 1 (repeat) or 2 (reflect)"};
         if (s.kind == SWFR_STYLE_LINEAR && s.extend) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"};
     }
@@ -563,8 +565,14 @@ void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edg
     }
     for (size_t i = 0; i < n_styles; ++i) {
         const swfr_style& s = styles[i];
-        if (s.kind > SWFR_STYLE_BITMAP) throw StatusError{SWFR_ERR_INVALID, "unknown style kind"};
+        if (s.kind > SWFR_STYLE_LINEAR_PIXMAN) throw StatusError{SWFR_ERR_INVALID, "unknown style kind"};
         if (s.n_stops > SWFR_MAX_STOPS) throw StatusError{SWFR_ERR_INVALID, "too many gradient stops"};
+        if (s.kind == SWFR_STYLE_LINEAR_PIXMAN) {
+            // aliased, libcairo composites span by span and pixman starts the ramp anew at every span: the tile pass does not have the
+            // start of a covered run that begins left of its strip, so the combination is refused, never approximated
+            if (r->mono) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedAliasedPixmanLinear"};
+            if (s.c0x == s.c1x && s.c0y == s.c1y) throw StatusError{SWFR_ERR_INVALID, "a pixman-linear gradient needs two distinct points (c0 == c1)"};
+        }
         if (s.kind == SWFR_STYLE_BITMAP) {
             const auto& V = r->builder->variants();
             const bool known = s.bitmap >= VARIANT_BASE ? (s.bitmap - VARIANT_BASE < V.size() && r->bitmaps.count(V[s.bitmap - VARIANT_BASE].bitmap))
@@ -679,6 +687,7 @@ Affine pattern_matrix(const swfr_style& st) {
 // forms it in single precision from the interval's ends shifted into that period -- so no table can hold it: the device gets the
 // 16.16 stops with the sentinels of the repeat kind, the 16-bit colours and the left edge of the operation's rectangle, where
 // pixman starts a scanline's walker, and resets per pixel (raster_common.hip, shade_spread).
+void gradient_stops_of(const swfr_style& st, const int rect[4], DevGradient& g);
 DevGradient radial_of(const swfr_style& st, const int rect[4]) {
     DevGradient g;
     std::memset(&g, 0, sizeof g);
@@ -699,6 +708,12 @@ DevGradient radial_of(const swfr_style& st, const int rect[4]) {
     g.a = double(dx * dx + dy * dy - dr * dr);
     g.inva = g.a != 0 ? 1. * 65536 / g.a : 0;
     g.mindr = -1. * 65536 * double(f1r);
+    gradient_stops_of(st, rect, g);
+    return g;
+}
+// The walker's part of a DevGradient, the same for a radial and a pixman-linear style: 16.16 stops, 16-bit colours, the sentinels of
+// the extend, and the ramp table (pad) or the colours and the rectangle's left edge (repeat, reflect)
+void gradient_stops_of(const swfr_style& st, const int rect[4], DevGradient& g) {
     const int n = int(st.n_stops);
     g.n_intervals = n ? n + 1 : 0;
     uint16_t col[SWFR_MAX_STOPS + 2][4] = {};
@@ -723,7 +738,7 @@ DevGradient radial_of(const swfr_style& st, const int rect[4]) {
             g.x[0] = -g.x[1]; g.x[n + 1] = 0x20000 - g.x[n];
         }
         std::memcpy(g.col, col, sizeof col);
-        return g;
+        return;
     }
     for (int k = 0; k <= n && n; ++k) {
         const int64_t left_x = g.x[k], right_x = g.x[k + 1];
@@ -740,6 +755,51 @@ DevGradient radial_of(const swfr_style& st, const int rect[4]) {
             }
         }
     }
+}
+
+// A linear gradient as cairo 1.16 hands it to pixman 0.40 and as pixman evaluates it (pixman-linear-gradient.c, linear_get_scanline,
+// the affine branch): the end points scaled into +-16383 (the matrix takes the inverse factor), 16.16 points, and per scanline of a
+// PIECE -- what libcairo hands to pixman_image_composite32 as one rectangle -- with v the 16.16 sample position at the piece's left edge
+//     t = ((double)(dx v.x + dy v.y) - (double)(dx p1.x + dy p1.y)) * invden,  invden = 65536 / (double)(dx^2 + dy^2)
+//     inc = (double)(dx m00 + dy m10) * invden,   position of the i-th pixel of the piece = trunc(t) + trunc(inc * i)
+// The fields of the radial record are reused: c1x, c1y = p1; dx, dy; a = (double)(dx p1.x + dy p1.y); inva = invden; mindr = inc;
+// x_min = the rectangle's left edge (the origin of a box path's one piece); pad, c1r, dr: the table of piece origins of a tor
+// path -- offset + 1 into the handle's int32 table (0: none), the rectangle's first row, entries per row (prepare_sources).
+// Refused, never approximated: a rectangle whose corner pixels (it grown by one pixel, as pixman's analyze_extent grows it) leave
+// 16.16 -- libcairo then paints some rows or none -- and a position that moves by less than one 16.16 unit per pixel row without
+// standing still: pixman then evaluates the first scanline of a piece for all its rows (linear_gradient_is_horizontal), and which
+// rows libcairo gathers into one piece the tile pass does not know.
+DevGradient linear_of(const swfr_style& st, const int rect[4]) {
+    DevGradient g;
+    std::memset(&g, 0, sizeof g);
+    double x1 = st.c0x, y1 = st.c0y, x2 = st.c1x, y2 = st.c1y;
+    double dim = std::fabs(x1);
+    for (double v : {y1, x2, y2, x1 - x2, y1 - y2}) dim = std::max(dim, std::fabs(v));
+    Affine m = pattern_matrix(st);
+    if (dim > 16383.0) {                                            // _cairo_gradient_pattern_fit_to_range, PIXMAN_MAX_INT >> 1
+        dim = 16383.0 / dim;
+        x1 *= dim; y1 *= dim; x2 *= dim; y2 *= dim;
+        m = m.then(Affine::scale(dim, dim));
+    }
+    const PixmanPosition pos = pixman_transform_of(m, rect);
+    g.base_x = pos.base_x; g.base_y = pos.base_y; g.m00 = pos.m00; g.m01 = pos.m01; g.m10 = pos.m10; g.m11 = pos.m11;
+    const int64_t p1x = fixed_16_16(x1), p1y = fixed_16_16(y1), dx = fixed_16_16(x2) - p1x, dy = fixed_16_16(y2) - p1y;
+    const int64_t l = dx * dx + dy * dy;
+    if (l == 0) throw StatusError{SWFR_ERR_INVALID, "a pixman-linear gradient needs two distinct points (c0 == c1 in 16.16)"};
+    for (int px : {rect[0] - 1, rect[2]})
+        for (int py : {rect[1] - 1, rect[3]}) {
+            const int64_t vx = pos.base_x + int64_t(px) * pos.m00 + int64_t(py) * pos.m01, vy = pos.base_y + int64_t(px) * pos.m10 + int64_t(py) * pos.m11;
+            const int64_t lim = (int64_t(1) << 31) - 8;
+            if (vx < -lim || vx >= lim || vy < -lim || vy >= lim) throw StatusError{SWFR_ERR_CAPACITY, "LinearGradientOutOfRange"};
+        }
+    g.c1x = int32_t(p1x); g.c1y = int32_t(p1y); g.dx = int32_t(dx); g.dy = int32_t(dy);
+    g.a = double(dx * p1x + dy * p1y);
+    g.inva = 65536.0 * 65536.0 / (double(l) * 65536.0);
+    g.mindr = double(dx * pos.m00 + dy * pos.m10) * g.inva;
+    const double row_step = double(dx * pos.m01 + dy * pos.m11) * g.inva;
+    if (row_step != 0 && row_step > -1 && row_step < 1) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedLinearRowStep"};
+    gradient_stops_of(st, rect, g);
+    g.extend = int32_t(st.extend); g.x_min = rect[0]; g.pad = 0;
     return g;
 }
 
@@ -766,16 +826,33 @@ DevFilter good_filter(const swfr_style& st, const int rect[4], std::vector<int32
 }
 
 // pixman's view of every bitmap / radial-gradient style of a scene (sample positions, filter tables, colour ramps)
-void prepare_sources(const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles, std::vector<DevFilter>& filters,
+constexpr int LINEAR_RUN_LENGTH = 256;      // cairo-image-compositor.c, inplace_renderer_init: run_length of a linear or radial source
+// edges: the scene's (a pixman-linear box path is looked at); split: `paths` are the caller's, the device gets column blocks of them
+// (split_wide_paths); n_linear: how many pixman-linear styles got a table of piece origins for k2_linear_pieces to fill
+void prepare_sources(const swfr_edge* edges, bool split, size_t& n_linear, const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles, std::vector<DevFilter>& filters,
                      std::vector<DevGradient>& gradients, std::vector<int32_t>& fparams, const std::vector<DevBitmap>& bitmap_table,
                      const std::vector<DevBitmap>& variant_table) {
     filters.assign(n_styles, DevFilter{});
     // a bitmap style belongs to one drawing operation: pixman's transform is anchored at the centre of that operation's rectangle
     std::vector<int> rect(4 * n_styles, 0);
     std::vector<uint8_t> seen(n_styles, 0);
+    std::vector<uint32_t> owner(n_styles, ~0u);                   // the one path of a pixman-linear style
+    n_linear = 0;
     for (size_t i = 0; i < n_paths; ++i) {
         const swfr_path& p = paths[i];
-        if (styles[p.style].kind != SWFR_STYLE_BITMAP && styles[p.style].kind != SWFR_STYLE_RADIAL) continue;
+        if (styles[p.style].kind != SWFR_STYLE_BITMAP && styles[p.style].kind != SWFR_STYLE_RADIAL && styles[p.style].kind != SWFR_STYLE_LINEAR_PIXMAN) continue;
+        if (styles[p.style].kind == SWFR_STYLE_LINEAR_PIXMAN) {
+            // libcairo starts the ramp anew at every piece it composites: one path per style, and of a rectilinear path only what is
+            // one piece -- a single box, on whole pixels or no wider than the run length at which libcairo's span renderer splits a row
+            if (seen[p.style]) throw StatusError{SWFR_ERR_INVALID, "a pixman-linear gradient style belongs to one path"};
+            if (split) throw StatusError{SWFR_ERR_CAPACITY, "a pixman-linear gradient on a path wider than 8192 px"};
+            if (p.kind == SWFR_PATH_BOXES) {
+                bool whole = true;
+                if (p.n_edges == 1 && edges) { const swfr_edge& b = edges[p.first_edge]; whole = !((b.x1 | b.x2 | b.y1 | b.y2) & 255); }
+                if (p.n_edges > 1 || (!whole && p.x_max - p.x_min > LINEAR_RUN_LENGTH)) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedLinearPieces"};
+            }
+            owner[p.style] = uint32_t(i);
+        }
         int* q = &rect[4 * size_t(p.style)];
         if (seen[p.style] && (q[0] != p.x_min || q[1] != p.y_min || q[2] != p.x_max || q[3] != p.y_max))
             throw StatusError{SWFR_ERR_INVALID, "paths that share a bitmap or radial-gradient style must share the pixel rectangle (one drawing operation)"};
@@ -796,6 +873,24 @@ void prepare_sources(const swfr_path* paths, size_t n_paths, const swfr_style* s
             gradients.push_back(radial_of(styles[i], &rect[4 * i]));
             filters[i].pad = int32_t(gradients.size());            // index + 1 into the gradient table
         }
+        if (styles[i].kind == SWFR_STYLE_LINEAR_PIXMAN) {
+            const int* q = &rect[4 * i];
+            DevGradient g = linear_of(styles[i], q);
+            if (owner[i] != ~0u && paths[owner[i]].kind == SWFR_PATH_TOR && q[2] > q[0] && q[3] > q[1]) {
+                // a tor path: libcairo's span renderer composites every row in pieces of its own (cairo-image-compositor.c,
+                // _inplace_spans: from the row's first span on, cut at runs of 256 and more full or empty pixels), which only the
+                // row pass's cells tell.  k2_linear_pieces writes the pieces' first columns here, per row, per frame -- the same
+                // values every frame: they follow from the scene alone.  Header: the path, then `per_row` columns a row, ascending,
+                // INT32_MAX behind the last; none: the rectangle's left edge
+                const int per_row = 2 * ((q[2] - q[0]) / LINEAR_RUN_LENGTH) + 2;
+                fparams.push_back(int32_t(owner[i]));
+                g.pad = int32_t(fparams.size()) + 1; g.c1r = q[1]; g.dr = per_row;
+                fparams.resize(fparams.size() + size_t(per_row) * size_t(q[3] - q[1]), INT32_MAX);
+                ++n_linear;
+            }
+            gradients.push_back(g);
+            filters[i].pad = int32_t(gradients.size());
+        }
     }
 }
 
@@ -815,6 +910,7 @@ struct SceneLayout {
     std::vector<DevFilter> filters;
     std::vector<DevGradient> gradients;
     std::vector<int32_t> fparams;
+    size_t n_linear = 0;        // pixman-linear styles on tor paths: k2_linear_pieces runs between the row pass and the tile pass (0: not launched)
 };
 // `edges` carry their path index in `reserved`
 // src_paths: the paths as the caller drew them, when `paths` holds the column blocks of wide ones (split_wide_paths): a bitmap or
@@ -892,8 +988,8 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
     L.n_strips = size_t(local_tile_rows(r)) * tiles_x * STRIPS_PER_TILE;
     L.n_strip_slots = strip_slots(local_tile_rows(r), uint32_t(tiles_x * STRIPS_PER_TILE));
     L.filters.clear(); L.gradients.clear(); L.fparams.clear();
-    if (src_paths) prepare_sources(src_paths, n_src_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
-    else prepare_sources(paths, n_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
+    if (src_paths) prepare_sources(nullptr, true, L.n_linear, src_paths, n_src_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
+    else prepare_sources(edges, false, L.n_linear, paths, n_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
 }
 // A tor path wider than the 13-bit column field of a cell (only possible in frames wider than 8192 px) is rasterized as several
 // paths over the SAME edges, one per block of 8192 pixel columns: the scan converter clips a path's cells to its column range
@@ -954,6 +1050,7 @@ swfr_edge* push_scene(SceneArena& A, const SceneLayout& L, const swfr_edge* edge
     }
     f.src.fparams = static_cast<int32_t*>(A.push(L.fparams.data(), L.fparams.size() * sizeof(int32_t)));
     f.src.gradients = static_cast<DevGradient*>(A.push(L.gradients.data(), L.gradients.size() * sizeof(DevGradient)));
+    f.n_linear_records = L.n_linear ? uint32_t(L.gradients.size()) : 0u; f.pad_linear = 0;
     f.path_chunks = static_cast<uint32_t*>(A.push(L.chunk_base.data(), (n_paths + 1) * sizeof(uint32_t)));
     f.path_slots = static_cast<uint32_t*>(A.push(L.slot_base.data(), (n_paths + 1) * sizeof(uint32_t)));
     f.path_inc = static_cast<uint32_t*>(A.push(L.inc_base.data(), (n_paths + 1) * sizeof(uint32_t)));
@@ -1173,6 +1270,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
     else resolve_variants(r, paths, n_paths, styles, n_styles, up_stream, si == 0);
     layout_scene(r, edges, n_edges, paths, n_paths, styles, n_styles, L, src_paths, n_src_paths, faded);
     sc.n_edges = n_edges; sc.n_paths = n_paths; sc.n_styles = n_styles; sc.any_shader = L.any_shader; sc.shader_level = L.shader_level;
+    sc.linear_grid = L.n_linear ? uint32_t(L.gradients.size()) : 0u;
     sc.n_chunks = L.n_chunks; sc.chunk_rows = L.chunk_rows; sc.n_bands = L.n_bands; sc.n_rows = L.n_rows;
     sc.n_strips = L.n_strips; sc.n_strip_slots = L.n_strip_slots; sc.n_incidences = L.incidences;
     sc.n_slots = L.n_slots; sc.cell_total = L.cell_total; sc.max_path_edges = L.max_path_edges; sc.rows_wide = L.rows_wide;
@@ -1246,6 +1344,38 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
     return SWFR_OK;
 }
 
+// A scene with a SWFR_STYLE_LINEAR_PIXMAN style: everything such a style is refused for, by a host-only handle too -- an unknown kind
+// beside it, an aliased handle, c0 == c1, and what prepare_sources / linear_of find (pieces, range, row step), by a dry run of theirs.
+void validate_linear_pixman(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
+                            const swfr_style* styles, size_t n_styles) {
+    bool any = false;
+    for (size_t i = 0; i < n_styles; ++i) any = any || styles[i].kind >= SWFR_STYLE_LINEAR_PIXMAN;
+    if (!any) return;
+    for (size_t i = 0; i < n_styles; ++i) {
+        const swfr_style& s = styles[i];
+        if (s.kind > SWFR_STYLE_LINEAR_PIXMAN) throw StatusError{SWFR_ERR_INVALID, "unknown style kind"};
+        if (s.kind != SWFR_STYLE_LINEAR_PIXMAN) continue;
+        if (r->mono) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedAliasedPixmanLinear"};
+        if (s.n_stops > SWFR_MAX_STOPS) throw StatusError{SWFR_ERR_INVALID, "too many gradient stops"};
+        if (s.c0x == s.c1x && s.c0y == s.c1y) throw StatusError{SWFR_ERR_INVALID, "a pixman-linear gradient needs two distinct points (c0 == c1)"};
+        // only the line of a SWF fill, (-16384, 0)-(16384, 0), has been held against libcairo (with it Cairo's fit-to-range scaling
+        // always applies); any other line is refused, not trusted
+        if (s.c0x != -16384.0 || s.c0y != 0.0 || s.c1x != 16384.0 || s.c1y != 0.0) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedLinearLine"};
+    }
+    for (size_t i = 0; i < n_paths; ++i) {                            // (a malformed path is validate_scene's to name)
+        const swfr_path& p = paths[i];
+        if (size_t(p.first_edge) + p.n_edges > n_edges || (p.kind < SWFR_PATH_GROUP_BEGIN && p.style >= n_styles) || p.kind > SWFR_PATH_GROUP_MASK) return;
+        if (p.x_min < 0 || p.y_min < 0 || p.x_max > int(r->width) || p.y_max > int(r->height) || p.x_min > p.x_max || p.y_min > p.y_max) return;
+    }
+    std::vector<DevFilter> filters; std::vector<DevGradient> gradients; std::vector<int32_t> fparams; size_t n_linear = 0;
+    std::vector<swfr_style> only;                                     // (the other kinds need tables a host-only handle may not have)
+    only.assign(styles, styles + n_styles);
+    for (swfr_style& s : only) if (s.kind != SWFR_STYLE_LINEAR_PIXMAN) { s.kind = SWFR_STYLE_SOLID; }
+    std::vector<swfr_path> drawn;                                     // (a group marker has no style of its own before lower_groups)
+    for (size_t i = 0; i < n_paths; ++i) if (paths[i].kind < SWFR_PATH_GROUP_BEGIN) drawn.push_back(paths[i]);
+    prepare_sources(edges, false, n_linear, drawn.data(), drawn.size(), only.data(), n_styles, filters, gradients, fparams, r->bitmap_table, r->variant_table);
+}
+
 // Uploads a caller-supplied scene (validated first) into scene slot `si`; see upload2.
 int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
            const swfr_style* styles, size_t n_styles, uint32_t* fb_override = nullptr) {
@@ -1253,6 +1383,7 @@ int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size
     validate_blend_fields(paths, n_paths);                       // (a malformed blend field is refused as such even by a host-only handle)
     validate_gradient_extend(styles, n_styles);                  // (and so is a gradient's extend)
     validate_bitmap_filter(styles, n_styles);                    // (and a bitmap's filter)
+    validate_linear_pixman(r, edges, n_edges, paths, n_paths, styles, n_styles);   // (and what a pixman-linear style cannot be drawn with)
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
     validate_scene(r, edges, n_edges, paths, n_paths, styles, n_styles);
     return upload2(r, si, all_sets, edges, n_edges, paths, n_paths, styles, n_styles, fb_override, false);
@@ -1273,6 +1404,7 @@ void launch_frame(swfr_renderer* r, const swfr_renderer::Scene& sc, swfr_rendere
         launch2_rows(st, fh, 1, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
         // the queued rows (coincident edges, crowded rows): skipped once a frame of this resident scene has shown there are none
         if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, 1, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes, r->mono);
+        launch2_linear_pieces(st, fh, 1, sc.linear_grid);           // (pixman-linear tor paths: where libcairo starts each row's ramps; timed with the row pass)
         if (e) HIP_CHECK(hipEventRecord(e[2], st));
         const uint32_t grid = r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : (overlapped ? ~0u : 0x7fffffffu);   // (~0u: the default shape; any other value caps the wavefronts)
         launch2_tiles(st, fh, 1, uint32_t(sc.n_strip_slots), grid, sc.shader_level, fb);      // (fb: this frame's own target, else the descriptor's)
@@ -1417,6 +1549,7 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
             launch2_bin(st, fh, cnt, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
             launch2_rows(st, fh, cnt, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
             if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, cnt, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes, r->mono);
+            launch2_linear_pieces(st, fh, cnt, sc.linear_grid);
             launch2_tiles(st, fh, cnt, uint32_t(sc.n_strip_slots), r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : ~0u, sc.shader_level, nullptr);
             last_set = g * rb + cnt - 1;
             last_on[g * rb] = int64_t(gi);
@@ -1547,7 +1680,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             size_t arena_bytes = pad(cnt * sizeof(Frame2)) + 4096, work_bytes = 0, cls_bytes = 0;
             size_t max_e = 0, max_p = 0, max_bands = 0, max_chunks = 0, max_strips = 0;
             int shader_level = 0;
-            uint32_t max_pe = 0;
+            uint32_t max_pe = 0, linear_grid = 0;
             bool rows_wide = false;
             auto t0 = clk::now();
             for (uint32_t k = 0; k < cnt; ++k) {
@@ -1579,6 +1712,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
                 max_e = std::max(max_e, F.e.size()); max_p = std::max(max_p, F.p.size()); max_bands = std::max(max_bands, L.n_bands);
                 max_chunks = std::max(max_chunks, L.n_chunks); max_strips = std::max(max_strips, L.n_strip_slots);
                 shader_level = std::max(shader_level, L.shader_level);
+                if (L.n_linear) linear_grid = std::max(linear_grid, uint32_t(L.gradients.size()));
                 max_pe = std::max(max_pe, L.max_path_edges);
                 rows_wide = rows_wide || L.rows_wide;
             }
@@ -1634,6 +1768,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             launch2_bin(G.stream, frames_dev, cnt, uint32_t(max_e), uint32_t(max_p), uint32_t(max_bands), 1u, r->mono);
             launch2_rows(G.stream, frames_dev, cnt, uint32_t(max_chunks), max_pe, rows_wide, r->mono);
             if (max_chunks) launch2_rows_slow(G.stream, frames_dev, cnt, 256u, 64u, SLOW_PASSES, r->mono);
+            launch2_linear_pieces(G.stream, frames_dev, cnt, linear_grid);
             launch2_tiles(G.stream, frames_dev, cnt, uint32_t(max_strips), ~0u, shader_level, nullptr);
             HIP_CHECK(hipEventRecord(G.ev_end, G.stream));
             for (uint32_t k = 0; k < cnt; ++k)
@@ -1723,6 +1858,7 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
         launch2_bin(st, r->rb_frames.ptr, B, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
         launch2_rows(st, r->rb_frames.ptr, B, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
         if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, r->rb_frames.ptr, B, 256u, sc.slow_state == 2 ? 0u : 64u, sc.slow_passes, r->mono);
+        launch2_linear_pieces(st, r->rb_frames.ptr, B, sc.linear_grid);
         launch2_tiles(st, r->rb_frames.ptr, B, uint32_t(sc.n_strip_slots), ~0u, sc.shader_level, nullptr);
     };
     one_launch();                                              // warm-up: leaves a cost history for the strip order
@@ -1836,6 +1972,9 @@ int finish_read(swfr_renderer* r) {
     return SWFR_OK;
 }
 
+// (swfr_last_error(NULL): why this thread's last swfr_create refused a flag combination, if it did)
+thread_local const char* create_error = nullptr;
+
 }  // namespace
 
 extern "C" {
@@ -1843,7 +1982,7 @@ extern "C" {
 
 uint32_t swfr_abi_version(void) { return SWFR_ABI_VERSION; }
 
-const char* swfr_last_error(const swfr_renderer* r) { return r ? r->error.c_str() : "null handle"; }
+const char* swfr_last_error(const swfr_renderer* r) { return r ? r->error.c_str() : (create_error ? create_error : "null handle"); }
 
 int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_renderer** out) {
     if (!out) return SWFR_ERR_INVALID;
@@ -1856,7 +1995,10 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     if (cfg) r->cfg = *cfg;
     if (r->cfg.band_count > 1 && r->cfg.band_index >= r->cfg.band_count) return SWFR_ERR_INVALID;
     r->mono = (r->cfg.flags & SWFR_FLAG_ANTIALIAS_NONE) != 0;
-    r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono));
+    create_error = nullptr;
+    // (aliased, every span is a piece of its own for pixman's linear ramp: validate_scene)
+    if (r->mono && (r->cfg.flags & SWFR_FLAG_LINEAR_PIXMAN)) { create_error = "NotImplementedAliasedPixmanLinear"; return SWFR_ERR_NOT_IMPLEMENTED; }
+    r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono, (r->cfg.flags & SWFR_FLAG_LINEAR_PIXMAN) != 0));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
     if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 6);
