@@ -22,6 +22,7 @@
 
 #include "../../include/swfr.h"
 #include "device_types.hpp"
+#include "frame_layout.hpp"
 #include "frame_builder.hpp"
 #include "shape_decoder.hpp"
 #include "bitmap_decode.hpp"
@@ -178,14 +179,11 @@ struct swfr_renderer {
     // Resident rendering uses scene 0; swfr_render_batch keeps one scene per frame in flight.
     struct Scene {
         SceneArena arena;
-        swfr_edge* raw = nullptr; DevPath* paths = nullptr; swfr_style* styles = nullptr;
-        DevFilter* filters = nullptr; int32_t* filter_params = nullptr; DevGradient* gradients = nullptr;
-        size_t n_edges = 0, n_paths = 0, n_styles = 0, n_rows = 0, n_chunks = 0, n_bands = 0, chunk_rows = 64;
-        bool any_shader = false;
+        size_t n_edges = 0, n_paths = 0, n_slots = 0, n_rows = 0, n_chunks = 0, cell_total = 0;   // (with the strips: what FrameDims::of_scene reads)
+        size_t n_strips = 0, n_strip_slots = 0;   // k2_tiles wavefronts / launch list slots
+        size_t n_bands = 0;
         int shader_level = 0;
         uint32_t linear_grid = 0;            // gradient records k2_linear_pieces looks through (0: the scene has no pixman-linear tor path)
-        size_t n_incidences = 0, n_strips = 0, n_strip_slots = 0;   // (edge, pixel row) pairs: bounds the cells of a frame; k2_tiles wavefronts / launch list slots
-        size_t n_slots = 0, cell_total = 0;
         uint32_t max_path_edges = 0;              // picks the row kernel's instance (edges staged in LDS per chunk)
         bool rows_wide = false;                   // SWFR_ROWS_WIDE: k2_rows_wide whatever max_path_edges says
         Frame2 proto{};                           // the scene fields and sizes of a frame descriptor (per-frame buffers not filled in)
@@ -363,12 +361,6 @@ BandShare band_share(const swfr_renderer* r) {
 }
 uint32_t local_tile_rows(const swfr_renderer* r) { return band_share(r).count; }
 
-// Validate a caller-supplied scene so that no kernel can index out of bounds.
-// The class bytes of a frame and, behind them (16-byte aligned), one StripTop record per strip of the handle: both are cleared when a
-// scene is uploaded (the tile pass clears a strip's record again when it has read it).
-inline size_t cls_bytes_of(size_t n_slots, size_t tiles_x) { return (size_t(STRIPS_PER_TILE) * n_slots * tiles_x + 64 + 15) & ~size_t(15); }
-inline size_t cls_region_bytes(size_t n_slots, size_t tiles_x, size_t n_strips) { return cls_bytes_of(n_slots, tiles_x) + (n_strips + 1) * sizeof(StripTop); }
-
 // swfr_path::lerp is lerp | operator << 8: an operator is never a SOURCE lerp
 void validate_blend_fields(const swfr_path* paths, size_t n_paths) {
     for (size_t i = 0; i < n_paths; ++i) {
@@ -521,6 +513,7 @@ void validate_bitmap_filter(const swfr_style* styles, size_t n_styles) {
         if (styles[i].kind == SWFR_STYLE_BITMAP && styles[i].filter > 1) throw StatusError{SWFR_ERR_INVALID, "bitmap filter must be 0 (good) or 1 (nearest)"};
 }
 
+// Validate a caller-supplied scene so that no kernel can index out of bounds.
 void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
                     const swfr_style* styles, size_t n_styles) {
     // end points within +-32768 px (2^23 in 24.8): inside that range the int64 products of the closed-form edge evaluation cannot overflow
@@ -900,7 +893,6 @@ void prepare_sources(const swfr_edge* edges, bool split, size_t& n_linear, const
 struct SceneLayout {
     uint32_t chunk_rows = ROWS_CHUNK;
     size_t n_chunks = 0, n_slots = 0, n_rows = 0, n_bands = 0, n_strips = 0, n_strip_slots = 0, incidences = 0, cell_main = 0, cell_total = 0;
-    bool any_shader = false;
     uint32_t max_path_edges = 0;
     bool rows_wide = false;     // the row kernel's wide instance although no path has more than ROWS_STAGE edges (SWFR_ROWS_WIDE)
     int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators, 4 + isolated groups, 5 + masked groups, 6 + faded groups: picks the tile kernel's instance
@@ -936,11 +928,9 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
     //  whose rows all need sample passes runs one pass per four rows)
     if (r->force_chunk_rows == 8 || r->force_chunk_rows == 16 || r->force_chunk_rows == 32 || r->force_chunk_rows == 64) L.chunk_rows = uint32_t(r->force_chunk_rows);
     else while (L.chunk_rows > uint32_t(STRIP_H) && count_chunks(L.chunk_rows) < 1024) L.chunk_rows >>= 1;
-    L.any_shader = false; L.shader_level = 0;
-    for (size_t i = 0; i < n_styles; ++i) {
-        L.any_shader = L.any_shader || styles[i].kind != SWFR_STYLE_SOLID;
+    L.shader_level = 0;
+    for (size_t i = 0; i < n_styles; ++i)
         L.shader_level = std::max(L.shader_level, styles[i].kind == SWFR_STYLE_SOLID ? 0 : (styles[i].kind == SWFR_STYLE_BITMAP ? 1 : 2));
-    }
     uint32_t blend_bits = 0;
     for (size_t i = 0; i < n_paths; ++i) blend_bits |= paths[i].lerp;
     L.any_blend = (blend_bits >> 8) != 0u;
@@ -1221,6 +1211,24 @@ void resolve_variants(swfr_renderer* r, const swfr_path* paths, size_t n_paths, 
     }
 }
 
+// The host preparation of a frame, one for every route: isolated groups lowered (frames with a group only), paths wider than 8192 px
+// split into column blocks (frames that wide only), the colour-transformed textures resolved on the paths as drawn -- queued on `st`,
+// pinned for the resident slot -- and the layout worked out into L.  A step that does not apply copies nothing: the arrays returned are
+// the ones passed in, or live in S, which has to outlive their use.  The edges carry their path index in `reserved`.
+struct FrameArrays { const swfr_edge* edges; size_t n_edges; const swfr_path* paths; size_t n_paths; const swfr_style* styles; size_t n_styles; };
+struct FrameScratch { std::vector<swfr_edge> group_e, split_e; std::vector<swfr_path> group_p, split_p; std::vector<swfr_style> group_s; };
+FrameArrays prepare_frame(swfr_renderer* r, FrameArrays a, hipStream_t st, bool pin, FrameScratch& S, SceneLayout& L) {
+    bool faded = false;
+    if (lower_groups(a.edges, a.n_edges, a.paths, a.n_paths, a.styles, a.n_styles, S.group_e, S.group_p, S.group_s, faded))
+        a = FrameArrays{S.group_e.data(), S.group_e.size(), S.group_p.data(), S.group_p.size(), S.group_s.data(), S.group_s.size()};
+    const FrameArrays drawn = a;                                      // the paths as drawn: a style is anchored at their rectangles
+    const bool split = split_wide_paths(a.edges, a.paths, a.n_paths, S.split_e, S.split_p);
+    if (split) { a.edges = S.split_e.data(); a.n_edges = S.split_e.size(); a.paths = S.split_p.data(); a.n_paths = S.split_p.size(); }
+    resolve_variants(r, drawn.paths, drawn.n_paths, a.styles, a.n_styles, st, pin);
+    layout_scene(r, a.edges, a.n_edges, a.paths, a.n_paths, a.styles, a.n_styles, L, split ? drawn.paths : nullptr, split ? drawn.n_paths : 0, faded);
+    return a;
+}
+
 // Uploads a scene -- the raw edge list, the paths and the styles, plus the layout above -- and sizes the buffers the
 // kernels write.
 int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
@@ -1250,67 +1258,26 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
                     for (uint32_t k = 0; k < paths[i].n_edges; ++k) round_box_to_pixels(tagged[paths[i].first_edge + k]);
         edges = tagged.data();
     }
-    static thread_local std::vector<swfr_edge> group_e;
-    static thread_local std::vector<swfr_path> group_p;
-    static thread_local std::vector<swfr_style> group_s;
-    bool faded = false;
-    if (lower_groups(edges, n_edges, paths, n_paths, styles, n_styles, group_e, group_p, group_s, faded)) {   // (frames with an isolated group only)
-        edges = group_e.data(); n_edges = group_e.size(); paths = group_p.data(); n_paths = group_p.size(); styles = group_s.data(); n_styles = group_s.size();
-    }
-    static thread_local std::vector<swfr_edge> split_e;
-    static thread_local std::vector<swfr_path> split_p;
-    const swfr_path* src_paths = nullptr; size_t n_src_paths = 0;
-    if (split_wide_paths(edges, paths, n_paths, split_e, split_p)) {             // (frames wider than 8192 px only)
-        src_paths = paths; n_src_paths = n_paths;
-        edges = split_e.data(); n_edges = split_e.size(); paths = split_p.data(); n_paths = split_p.size();
-    }
-    static thread_local SceneLayout layout_scratch;        // (vectors keep their capacity from frame to frame)
-    SceneLayout& L = layout_scratch;
-    if (src_paths) resolve_variants(r, src_paths, n_src_paths, styles, n_styles, up_stream, si == 0);
-    else resolve_variants(r, paths, n_paths, styles, n_styles, up_stream, si == 0);
-    layout_scene(r, edges, n_edges, paths, n_paths, styles, n_styles, L, src_paths, n_src_paths, faded);
-    sc.n_edges = n_edges; sc.n_paths = n_paths; sc.n_styles = n_styles; sc.any_shader = L.any_shader; sc.shader_level = L.shader_level;
-    sc.linear_grid = L.n_linear ? uint32_t(L.gradients.size()) : 0u;
-    sc.n_chunks = L.n_chunks; sc.chunk_rows = L.chunk_rows; sc.n_bands = L.n_bands; sc.n_rows = L.n_rows;
-    sc.n_strips = L.n_strips; sc.n_strip_slots = L.n_strip_slots; sc.n_incidences = L.incidences;
-    sc.n_slots = L.n_slots; sc.cell_total = L.cell_total; sc.max_path_edges = L.max_path_edges; sc.rows_wide = L.rows_wide;
+    static thread_local FrameScratch scratch;              // (vectors keep their capacity from frame to frame)
+    static thread_local SceneLayout L;
+    const FrameArrays a = prepare_frame(r, FrameArrays{edges, n_edges, paths, n_paths, styles, n_styles}, up_stream, si == 0, scratch, L);
+    sc.n_edges = a.n_edges; sc.n_paths = a.n_paths; sc.n_chunks = L.n_chunks; sc.n_bands = L.n_bands; sc.n_rows = L.n_rows; sc.n_slots = L.n_slots; sc.cell_total = L.cell_total;
+    sc.n_strips = L.n_strips; sc.n_strip_slots = L.n_strip_slots; sc.max_path_edges = L.max_path_edges; sc.rows_wide = L.rows_wide;
+    sc.shader_level = L.shader_level; sc.linear_grid = L.n_linear ? uint32_t(L.gradients.size()) : 0u;
     SceneArena& A = sc.arena;
-    A.begin(scene_arena_bytes(L, n_edges, n_paths, n_styles) + SceneArena::padded(4 * sizeof(Frame2)) + 4096);
+    A.begin(scene_arena_bytes(L, a.n_edges, a.n_paths, a.n_styles) + SceneArena::padded(4 * sizeof(Frame2)) + 4096);
     Frame2 proto;
     std::memset(&proto, 0, sizeof proto);
-    push_scene(A, L, edges, n_edges, paths, n_paths, styles, n_styles, proto);
-    sc.raw = const_cast<swfr_edge*>(proto.raw); sc.paths = const_cast<DevPath*>(proto.paths); sc.styles = const_cast<swfr_style*>(proto.styles);
-    fill_frame_sizes(r, L, n_edges, n_paths, proto);
-    const size_t n_slots = L.n_slots, n_rows = L.n_rows, n_chunks = L.n_chunks;
-    // ---- per-frame (kernel-written) buffers: grow-only allocations
-    const int n_sets = std::max(1, std::min(r->in_flight, 4));
-    auto reserve_zeroed = [&](DevBuf<uint32_t>& b, size_t n) {
-        const uint32_t* before = b.ptr;
-        b.reserve(n);
-        if (b.ptr != before) HIP_CHECK(hipMemsetAsync(b.ptr, 0, b.cap * sizeof(uint32_t), up_stream));
-    };
-    for (int k = 0; k < 4; ++k) {
-        if (all_sets ? k >= n_sets : k != si) continue;
-        auto& x = r->fs[k];
-        if (!x.stream) HIP_CHECK(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
-        x.d_edges.reserve(2 * n_edges + 1); x.d_band2.reserve(n_slots); x.d_rows2.reserve(n_slots * TILE_H + 64); x.d_cells.reserve(L.cell_total);
-        x.d_slow.reserve(2 * (n_rows + 64)); x.d_huge.reserve(2 * (n_rows + 64));     // (two queues each: a pass reads one and refills the other)
-        x.d_path_flag.reserve(n_paths + 64); x.d_path_queue.reserve(n_paths + 64);
-        x.d_chunks.reserve(n_chunks + 1); x.d_band_slots.reserve(n_slots + 8); x.d_strips.reserve(L.n_strip_slots + 1);
-        reserve_zeroed(x.d_strip_cost, L.n_strips + 1);                                 // (zero between frames: the ordering workgroup clears what it has read)
-        r->d_counters.reserve(4 * COUNTER_WORDS);
-        x.counters = r->d_counters.ptr + size_t(k) * COUNTER_WORDS;
-        x.d_cls.reserve(cls_region_bytes(n_slots, tiles_x, L.n_strips));
-        // class bytes outside the paths' rectangles are never written by a kernel: cleared once per uploaded scene
-        HIP_CHECK(hipMemsetAsync(x.d_cls.ptr, 0, cls_region_bytes(n_slots, tiles_x, L.n_strips), up_stream));
-        if (!x.d_fb.ptr && !r->n_targets) {                                             // (a handle with caller targets never renders into a buffer of its own)
-            x.d_fb.reserve(size_t(r->width) * r->height);
-            HIP_CHECK(hipMemsetAsync(x.d_fb.ptr, 0, size_t(r->width) * r->height * 4, up_stream));
-        }
-    }
+    push_scene(A, L, a.edges, a.n_edges, a.paths, a.n_paths, a.styles, a.n_styles, proto);
+    fill_frame_sizes(r, L, a.n_edges, a.n_paths, proto);
     if (r->bitmap_table_dirty) r->d_bitmap_table.reserve(r->bitmap_table.size());     // (filled below; the address is what the descriptor needs)
     proto.src.bitmaps = r->d_bitmap_table.ptr;
     sc.proto = proto;
+    // ---- per-frame (kernel-written) buffers: grow-only allocations, one per buffer of the list in frame_layout.hpp, and the sets' descriptors
+    const FrameDims dims = FrameDims::of_layout(L, a.n_edges, a.n_paths);
+    const size_t cls_bytes = cls_region_bytes(dims, tiles_x);
+    const int n_sets = std::max(1, std::min(r->in_flight, 4));
+    auto hold = [](auto& buf, auto*& field, size_t n) { buf.reserve(n); field = buf.ptr; };
     Frame2 fr[4];
     std::memset(fr, 0, sizeof fr);
     for (int k = 0; k < 4; ++k) {
@@ -1318,11 +1285,24 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
         auto& x = r->fs[k];
         Frame2& f = fr[k];
         f = proto;
-        f.chunks = x.d_chunks.ptr; f.band_slots = x.d_band_slots.ptr; f.strips = x.d_strips.ptr;
-        f.strip_cost = x.d_strip_cost.ptr;
-        f.edges = x.d_edges.ptr; f.band_list = x.d_band2.ptr; f.cls = x.d_cls.ptr; f.strip_top = reinterpret_cast<StripTop*>(x.d_cls.ptr + cls_bytes_of(n_slots, tiles_x)); f.rows = x.d_rows2.ptr; f.cells = x.d_cells.ptr;
-        f.slow = x.d_slow.ptr; f.huge = x.d_huge.ptr; f.counters = x.counters;
-        f.path_flag = x.d_path_flag.ptr; f.path_queue = x.d_path_queue.ptr;
+        if (!x.stream) HIP_CHECK(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
+        hold(x.d_edges, f.edges, dims.edge_count()); hold(x.d_band2, f.band_list, dims.band_entry_count()); hold(x.d_rows2, f.rows, dims.row_count());
+        hold(x.d_cells, f.cells, dims.cell_count()); hold(x.d_slow, f.slow, dims.slow_count()); hold(x.d_huge, f.huge, dims.slow_count());
+        hold(x.d_path_flag, f.path_flag, dims.path_word_count()); hold(x.d_path_queue, f.path_queue, dims.path_word_count());
+        hold(x.d_chunks, f.chunks, dims.chunk_count()); hold(x.d_band_slots, f.band_slots, dims.band_slot_count()); hold(x.d_strips, f.strips, dims.strip_count());
+        const uint32_t* cost_before = x.d_strip_cost.ptr;
+        hold(x.d_strip_cost, f.strip_cost, dims.strip_cost_count());                    // (zero between frames: the ordering workgroup clears what it has read)
+        if (f.strip_cost != cost_before) HIP_CHECK(hipMemsetAsync(f.strip_cost, 0, x.d_strip_cost.cap * sizeof(uint32_t), up_stream));
+        r->d_counters.reserve(4 * COUNTER_WORDS);
+        f.counters = x.counters = r->d_counters.ptr + size_t(k) * COUNTER_WORDS;
+        x.d_cls.reserve(cls_bytes);
+        // class bytes outside the paths' rectangles are never written by a kernel: cleared once per uploaded scene
+        HIP_CHECK(hipMemsetAsync(x.d_cls.ptr, 0, cls_bytes, up_stream));
+        set_cls_region(f, dims, tiles_x, x.d_cls.ptr);
+        if (!x.d_fb.ptr && !r->n_targets) {                                             // (a handle with caller targets never renders into a buffer of its own)
+            x.d_fb.reserve(size_t(r->width) * r->height);
+            HIP_CHECK(hipMemsetAsync(x.d_fb.ptr, 0, size_t(r->width) * r->height * 4, up_stream));
+        }
         f.fb = (fb_override && k == si) ? fb_override : (r->n_targets ? r->targets[uint32_t(k) % r->n_targets] : x.d_fb.ptr);
     }
     sc.frames_dev = static_cast<Frame2*>(A.push(fr, sizeof fr));
@@ -1389,57 +1369,78 @@ int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size
     return upload2(r, si, all_sets, edges, n_edges, paths, n_paths, styles, n_styles, fb_override, false);
 }
 
+// What the kernels of a frame -- or of several frames per launch (blockIdx.y = frame) -- are launched with: the grids' bounds over the
+// frames of the launch, and the choices in which the routes differ.
+struct LaunchPlan {
+    uint32_t max_edges, max_paths, max_bands, slow_kernels;      // k2_bin; slow_kernels 1: it also prepares the queued-row kernels' work
+    uint32_t max_chunks, max_path_edges; bool rows_wide;         // the row pass
+    bool run_slow; uint32_t grid_slow, grid_huge, slow_passes;   // the queued-row kernels (coincident edges, crowded rows), if launched
+    uint32_t linear_grid;                                        // k2_linear_pieces (0: not launched)
+    uint32_t max_strips, tiles_grid; int shader_level;           // the tile pass; tiles_grid ~0u: the default shape, any other value caps the wavefronts
+};
+// THE launch chain: bin -> rows -> queued rows -> linear pieces -> tiles.  events (optional): four, recorded around the three passes.
+// fb_to: the one frame's own target instead of its descriptor's (swfr_render_resident_async_to), else nullptr.
+void launch_chain(swfr_renderer* r, hipStream_t st, const Frame2* frames, uint32_t n_frames, const LaunchPlan& p, hipEvent_t* events, uint32_t* fb_to) {
+    if (events) HIP_CHECK(hipEventRecord(events[0], st));
+    launch2_bin(st, frames, n_frames, p.max_edges, p.max_paths, p.max_bands, p.slow_kernels, r->mono);
+    if (events) HIP_CHECK(hipEventRecord(events[1], st));
+    launch2_rows(st, frames, n_frames, p.max_chunks, p.max_path_edges, p.rows_wide, r->mono);
+    if (p.run_slow) launch2_rows_slow(st, frames, n_frames, p.grid_slow, p.grid_huge, p.slow_passes, r->mono);
+    launch2_linear_pieces(st, frames, n_frames, p.linear_grid);    // (pixman-linear tor paths: where libcairo starts each row's ramps; timed with the row pass)
+    if (events) HIP_CHECK(hipEventRecord(events[2], st));
+    launch2_tiles(st, frames, n_frames, p.max_strips, p.tiles_grid, p.shader_level, fb_to);
+    if (events) HIP_CHECK(hipEventRecord(events[3], st));
+}
+// The plan of the resident scene's frames, as a frame launched on its own frame set gets it; the routes that differ say so where they call.
+LaunchPlan plan_of(const swfr_renderer* r, const swfr_renderer::Scene& sc) {
+    LaunchPlan p;
+    p.max_edges = uint32_t(sc.n_edges); p.max_paths = uint32_t(sc.n_paths); p.max_bands = uint32_t(sc.n_bands);
+    p.run_slow = sc.n_chunks && sc.slow_state != 1;            // the queued rows: skipped once a frame of this resident scene has shown there are none
+    p.slow_kernels = p.run_slow ? 1u : 0u;
+    p.max_chunks = uint32_t(sc.n_chunks); p.max_path_edges = sc.max_path_edges; p.rows_wide = sc.rows_wide;
+    p.grid_slow = 1024u; p.grid_huge = sc.slow_state == 2 ? 0u : 256u; p.slow_passes = sc.slow_passes;
+    p.linear_grid = sc.linear_grid; p.max_strips = uint32_t(sc.n_strip_slots); p.shader_level = sc.shader_level;
+    p.tiles_grid = r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : ~0u;
+    return p;
+}
+
 // the kernels of one frame of scene `sc` on frame set `F`, writing the framebuffer `fb`; e (optional): four events around them
 // overlapped: other frames run beside this one (several frame sets in flight) -- the tile pass is then launched in its paired shape (two
 // strips per wavefront, better for the frame rate); a frame that has the GPU to itself (a blocking swfr_render, a handle with one frame
 // in flight) gets one wavefront per strip, which finishes 2-3 us sooner ("Two strips per wavefront")
 void launch_frame(swfr_renderer* r, const swfr_renderer::Scene& sc, swfr_renderer::FrameSet& F, uint32_t* fb, hipEvent_t* e, bool overlapped) {
-    const hipStream_t st = F.stream;
-    {
-        // the frame's descriptor (scene arrays, this set's buffers, the framebuffer) was written with the scene
-        const Frame2* fh = sc.frames_dev + (&F - r->fs);        // the set's descriptor, uploaded with the scene
-        if (e) HIP_CHECK(hipEventRecord(e[0], st));
-        launch2_bin(st, fh, 1, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
-        if (e) HIP_CHECK(hipEventRecord(e[1], st));
-        launch2_rows(st, fh, 1, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
-        // the queued rows (coincident edges, crowded rows): skipped once a frame of this resident scene has shown there are none
-        if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, 1, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes, r->mono);
-        launch2_linear_pieces(st, fh, 1, sc.linear_grid);           // (pixman-linear tor paths: where libcairo starts each row's ramps; timed with the row pass)
-        if (e) HIP_CHECK(hipEventRecord(e[2], st));
-        const uint32_t grid = r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : (overlapped ? ~0u : 0x7fffffffu);   // (~0u: the default shape; any other value caps the wavefronts)
-        launch2_tiles(st, fh, 1, uint32_t(sc.n_strip_slots), grid, sc.shader_level, fb);      // (fb: this frame's own target, else the descriptor's)
-        if (e) HIP_CHECK(hipEventRecord(e[3], st));
-    }
+    LaunchPlan plan = plan_of(r, sc);
+    if (r->tiles_grid <= 0 && !overlapped) plan.tiles_grid = 0x7fffffffu;      // (a frame alone: one wavefront per strip)
+    // the frame's descriptor (scene arrays, this set's buffers, the framebuffer) was uploaded with the scene
+    launch_chain(r, F.stream, sc.frames_dev + (&F - r->fs), 1, plan, e, fb);   // (fb: this frame's own target, else the descriptor's)
 }
 
 int check_counters(swfr_renderer* r, const uint32_t* counters) {
-    {
-        const uint32_t err = counters[C2_ERROR];
-        r->stats.frames += 1; r->stats.queued_rows += counters[C2_SLOW]; r->stats.crowded_rows += counters[C2_HUGE];
-        r->stats.tie_rows += counters[C2_TIE_ROWS];
-        r->stats.pairtest_limit += counters[C2_TIE_PAIRTEST_SKIPPED] ? 1 : 0;
-        r->stats.start_group_limit += ((err & (E2_ACTIVE_EDGES | E2_START_GROUP)) || counters[C2_TIE_SORT_OVERFLOW]) ? 1 : 0;
-        r->stats.history_limit += counters[C2_TIE_DEPTH] ? 1 : 0;
-        if (err & ~(E2_ACTIVE_EDGES | E2_START_GROUP | E2_CELL_ARENA)) {
-            r->fb_valid = false;
-            return fail(r, SWFR_ERR_DEVICE, "internal consistency check failed in the raster kernels (code " + std::to_string(err) + ")");
-        }
-        if (err) {
-            r->fb_valid = false;
-            return fail(r, SWFR_ERR_CAPACITY, err & E2_CELL_ARENA ? "cell arena exhausted (uneven allocator shares)" :
-                        "a pixel row has more than 8192 active edges of one path, or more than 8192 of its edges start at one sample row (scan converter capacity)");
-        }
-        // the replay of Cairo's edge-list order for coincident edges has capacity limits; a scene that reaches one is refused,
-        // never rendered approximately
-        if (counters[C2_TIE_PAIRTEST_SKIPPED] | counters[C2_TIE_SORT_OVERFLOW] | counters[C2_TIE_DEPTH]) {
-            r->fb_valid = false;
-            return fail(r, SWFR_ERR_CAPACITY, std::string("coincident edges beyond the capacity of the list-order replay (") +
-                        (counters[C2_TIE_PAIRTEST_SKIPPED] ? "crossing test over more than 2^21 edge pairs; " : "") +
-                        (counters[C2_TIE_SORT_OVERFLOW] ? "more than 16 edges starting at one sample row; " : "") +
-                        (counters[C2_TIE_DEPTH] ? "tie history deeper than two levels; " : "") + ")");
-        }
-        return SWFR_OK;
+    const uint32_t err = counters[C2_ERROR];
+    r->stats.frames += 1; r->stats.queued_rows += counters[C2_SLOW]; r->stats.crowded_rows += counters[C2_HUGE];
+    r->stats.tie_rows += counters[C2_TIE_ROWS];
+    r->stats.pairtest_limit += counters[C2_TIE_PAIRTEST_SKIPPED] ? 1 : 0;
+    r->stats.start_group_limit += ((err & (E2_ACTIVE_EDGES | E2_START_GROUP)) || counters[C2_TIE_SORT_OVERFLOW]) ? 1 : 0;
+    r->stats.history_limit += counters[C2_TIE_DEPTH] ? 1 : 0;
+    if (err & ~(E2_ACTIVE_EDGES | E2_START_GROUP | E2_CELL_ARENA)) {
+        r->fb_valid = false;
+        return fail(r, SWFR_ERR_DEVICE, "internal consistency check failed in the raster kernels (code " + std::to_string(err) + ")");
     }
+    if (err) {
+        r->fb_valid = false;
+        return fail(r, SWFR_ERR_CAPACITY, err & E2_CELL_ARENA ? "cell arena exhausted (uneven allocator shares)" :
+                    "a pixel row has more than 8192 active edges of one path, or more than 8192 of its edges start at one sample row (scan converter capacity)");
+    }
+    // the replay of Cairo's edge-list order for coincident edges has capacity limits; a scene that reaches one is refused,
+    // never rendered approximately
+    if (counters[C2_TIE_PAIRTEST_SKIPPED] | counters[C2_TIE_SORT_OVERFLOW] | counters[C2_TIE_DEPTH]) {
+        r->fb_valid = false;
+        return fail(r, SWFR_ERR_CAPACITY, std::string("coincident edges beyond the capacity of the list-order replay (") +
+                    (counters[C2_TIE_PAIRTEST_SKIPPED] ? "crossing test over more than 2^21 edge pairs; " : "") +
+                    (counters[C2_TIE_SORT_OVERFLOW] ? "more than 16 edges starting at one sample row; " : "") +
+                    (counters[C2_TIE_DEPTH] ? "tie history deeper than two levels; " : "") + ")");
+    }
+    return SWFR_OK;
 }
 
 // One frame of the resident scene on frame set F as a graph launch: the set's kernels (with the queued-row kernels the scene is
@@ -1541,16 +1542,11 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
     int64_t last_on[4] = {-1, -1, -1, -1};                 // per frame set's stream: the last launch of this call it carries (none: -1)
     if (batched) {
         const uint32_t groups = n_sets / rb;
+        const LaunchPlan plan = plan_of(r, sc);                // (as a frame of its own, with the tile pass in its default shape unless SWFR_TILES_GRID caps it)
         uint32_t gi = 0;
         for (uint32_t f = 0; f < frames; f += rb, ++gi) {
             const uint32_t g = gi % groups, cnt = std::min(rb, frames - f);
-            const hipStream_t st = r->fs[g * rb].stream;
-            const Frame2* fh = sc.frames_dev + g * rb;
-            launch2_bin(st, fh, cnt, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
-            launch2_rows(st, fh, cnt, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
-            if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, fh, cnt, 1024u, sc.slow_state == 2 ? 0u : 256u, sc.slow_passes, r->mono);
-            launch2_linear_pieces(st, fh, cnt, sc.linear_grid);
-            launch2_tiles(st, fh, cnt, uint32_t(sc.n_strip_slots), r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : ~0u, sc.shader_level, nullptr);
+            launch_chain(r, r->fs[g * rb].stream, sc.frames_dev + g * rb, cnt, plan, nullptr, nullptr);
             last_set = g * rb + cnt - 1;
             last_on[g * rb] = int64_t(gi);
         }
@@ -1637,7 +1633,8 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
 // batch of small frames -- the 256 ratios of a morph shape -- fills the GPU instead of paying a launch chain per frame.  Two groups
 // alternate: the host builds group g + 1 (scene walk, flattening, layout) while the GPU rasterizes group g.
 int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* device_dst, size_t frame_stride) {
-    struct FrameData { std::vector<swfr_edge> e; std::vector<swfr_path> p; std::vector<swfr_style> s; SceneLayout L; };
+    // a frame of the group being built: the builder's arrays (the builder goes on to the next frame), what prepare_frame made of them
+    struct FrameData { std::vector<swfr_edge> e; std::vector<swfr_path> p; std::vector<swfr_style> s; FrameScratch scratch; SceneLayout L; FrameArrays a; FrameDims dims; };
     static thread_local std::vector<FrameData> fd;
     // frames per group: SWFR_BATCH_FRAMES at most; a call with fewer frames is still cut into four groups, so that building group
     // g + 1 overlaps rasterizing group g, as long as a group keeps enough pixels (32 Mpx: four 4K frames, thirty-two 1024x1024 ones)
@@ -1645,7 +1642,6 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
     const uint32_t fill = uint32_t((size_t(32) << 20) / std::max<size_t>(size_t(r->width) * r->height, 1)) + 1;
     const uint32_t B = std::min(uint32_t(std::max(1, r->batch_frames)), std::max((n + 3) / 4, fill));
     const uint32_t tiles_x = (r->width + TILE_W - 1) / TILE_W;
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
     double t_build = 0, t_wait = 0, t_stage = 0, t_launch = 0;
@@ -1677,45 +1673,28 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             if (!G.stream) HIP_CHECK(hipStreamCreateWithFlags(&G.stream, hipStreamNonBlocking));
             // ---- host: build the group's frames (the other group is being rasterized meanwhile)
             if (fd.size() < cnt) fd.resize(cnt);
-            size_t arena_bytes = pad(cnt * sizeof(Frame2)) + 4096, work_bytes = 0, cls_bytes = 0;
-            size_t max_e = 0, max_p = 0, max_bands = 0, max_chunks = 0, max_strips = 0;
-            int shader_level = 0;
-            uint32_t max_pe = 0, linear_grid = 0;
-            bool rows_wide = false;
+            size_t arena_bytes = pad256(cnt * sizeof(Frame2)) + 4096, work_bytes = 0, cls_bytes = 0;
+            // the group's plan: the running maximum over its frames' layouts.  Nothing renders a frame of a batch again: k2_bin always prepares the queued rows, their kernels run
+            // -- in the grids of frames that share the GPU, with every pass -- whenever a frame has row chunks; the tile pass keeps its default shape whatever SWFR_TILES_GRID says
+            LaunchPlan plan{};
+            plan.slow_kernels = 1u; plan.grid_slow = 256u; plan.grid_huge = 64u; plan.slow_passes = SLOW_PASSES; plan.tiles_grid = ~0u;
             auto t0 = clk::now();
             for (uint32_t k = 0; k < cnt; ++k) {
                 FrameData& F = fd[k];
                 r->builder->build(stages[first + k]);
                 F.e = r->builder->edges(); F.p = r->builder->paths(); F.s = r->builder->styles();
                 validate_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size());
-                bool faded = false;
-                {
-                    std::vector<swfr_edge> ge; std::vector<swfr_path> gp; std::vector<swfr_style> gs;
-                    if (lower_groups(F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), ge, gp, gs, faded)) { F.e.swap(ge); F.p.swap(gp); F.s.swap(gs); }
-                }
-                resolve_variants(r, F.p.data(), F.p.size(), F.s.data(), F.s.size(), G.stream, false);
-                {
-                    std::vector<swfr_edge> se; std::vector<swfr_path> sp;
-                    if (split_wide_paths(F.e.data(), F.p.data(), F.p.size(), se, sp)) {
-                        const std::vector<swfr_path> orig = F.p;
-                        F.e.swap(se); F.p.swap(sp);
-                        layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L, orig.data(), orig.size(), faded);
-                    } else layout_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), F.L, nullptr, 0, faded);
-                }
-                arena_bytes += scene_arena_bytes(F.L, F.e.size(), F.p.size(), F.s.size());
+                F.a = prepare_frame(r, FrameArrays{F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size()}, G.stream, false, F.scratch, F.L);
                 const SceneLayout& L = F.L;
-                work_bytes += pad((2 * F.e.size() + 1) * sizeof(DevEdge)) + pad(L.n_slots * sizeof(BandEntry2)) + pad((L.n_slots * TILE_H + 64) * sizeof(RowInfo2)) +
-                              pad(L.cell_total * sizeof(Cell)) + 2 * pad(2 * (L.n_rows + 64) * sizeof(SlowRow)) + 2 * pad((F.p.size() + 64) * sizeof(uint32_t)) +
-                              pad((L.n_chunks + 1) * sizeof(ChunkInfo)) + pad((L.n_slots + 8) * sizeof(BandSlot)) + pad((L.n_strip_slots + 1) * sizeof(StripDesc)) +
-                              pad((L.n_strips + 1) * sizeof(uint32_t)) + pad(COUNTER_WORDS * sizeof(uint32_t));
-                cls_bytes += pad(cls_region_bytes(L.n_slots, tiles_x, L.n_strips));
-                max_e = std::max(max_e, F.e.size()); max_p = std::max(max_p, F.p.size()); max_bands = std::max(max_bands, L.n_bands);
-                max_chunks = std::max(max_chunks, L.n_chunks); max_strips = std::max(max_strips, L.n_strip_slots);
-                shader_level = std::max(shader_level, L.shader_level);
-                if (L.n_linear) linear_grid = std::max(linear_grid, uint32_t(L.gradients.size()));
-                max_pe = std::max(max_pe, L.max_path_edges);
-                rows_wide = rows_wide || L.rows_wide;
+                F.dims = FrameDims::of_layout(L, F.a.n_edges, F.a.n_paths);
+                arena_bytes += scene_arena_bytes(L, F.a.n_edges, F.a.n_paths, F.a.n_styles);
+                work_bytes += frame_work_bytes(F.dims); cls_bytes += pad256(cls_region_bytes(F.dims, tiles_x));
+                plan.max_edges = std::max(plan.max_edges, uint32_t(F.a.n_edges)); plan.max_paths = std::max(plan.max_paths, uint32_t(F.a.n_paths)); plan.max_bands = std::max(plan.max_bands, uint32_t(L.n_bands));
+                plan.max_chunks = std::max(plan.max_chunks, uint32_t(L.n_chunks)); plan.max_path_edges = std::max(plan.max_path_edges, L.max_path_edges); plan.rows_wide = plan.rows_wide || L.rows_wide;
+                if (L.n_linear) plan.linear_grid = std::max(plan.linear_grid, uint32_t(L.gradients.size()));
+                plan.max_strips = std::max(plan.max_strips, uint32_t(L.n_strip_slots)); plan.shader_level = std::max(plan.shader_level, L.shader_level);
             }
+            plan.run_slow = plan.max_chunks != 0;
             t_build += ms_since(t0); t0 = clk::now();
             // ---- this group's previous use must be over before its staging and device buffers are rewritten
             finish_group(g);
@@ -1732,32 +1711,17 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
                 G.h_counters_cap = B;
             }
             std::vector<Frame2> fr(cnt);
-            uint8_t* w = G.work.ptr;
-            uint8_t* c = G.cls.ptr;
-            auto carve = [&](size_t bytes) { uint8_t* q = w; w += pad(bytes); return q; };
+            uint8_t *w = G.work.ptr, *c = G.cls.ptr;
             for (uint32_t k = 0; k < cnt; ++k) {
-                FrameData& F = fd[k];
-                const SceneLayout& L = F.L;
+                const FrameData& F = fd[k];
                 Frame2& f = fr[k];
                 std::memset(&f, 0, sizeof f);
-                push_scene(G.arena, L, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size(), f);
-                fill_frame_sizes(r, L, F.e.size(), F.p.size(), f);
+                push_scene(G.arena, F.L, F.a.edges, F.a.n_edges, F.a.paths, F.a.n_paths, F.a.styles, F.a.n_styles, f);
+                fill_frame_sizes(r, F.L, F.a.n_edges, F.a.n_paths, f);
                 f.src.bitmaps = r->d_bitmap_table.ptr;
-                f.edges = reinterpret_cast<DevEdge*>(carve((2 * F.e.size() + 1) * sizeof(DevEdge)));
-                f.band_list = reinterpret_cast<BandEntry2*>(carve(L.n_slots * sizeof(BandEntry2)));
-                f.rows = reinterpret_cast<RowInfo2*>(carve((L.n_slots * TILE_H + 64) * sizeof(RowInfo2)));
-                f.cells = reinterpret_cast<Cell*>(carve(L.cell_total * sizeof(Cell)));
-                f.slow = reinterpret_cast<SlowRow*>(carve(2 * (L.n_rows + 64) * sizeof(SlowRow)));
-                f.huge = reinterpret_cast<SlowRow*>(carve(2 * (L.n_rows + 64) * sizeof(SlowRow)));
-                f.path_flag = reinterpret_cast<uint32_t*>(carve((F.p.size() + 64) * sizeof(uint32_t)));
-                f.path_queue = reinterpret_cast<uint32_t*>(carve((F.p.size() + 64) * sizeof(uint32_t)));
-                f.chunks = reinterpret_cast<ChunkInfo*>(carve((L.n_chunks + 1) * sizeof(ChunkInfo)));
-                f.band_slots = reinterpret_cast<BandSlot*>(carve((L.n_slots + 8) * sizeof(BandSlot)));
-                f.strips = reinterpret_cast<StripDesc*>(carve((L.n_strip_slots + 1) * sizeof(StripDesc)));
-                f.strip_cost = reinterpret_cast<uint32_t*>(carve((L.n_strips + 1) * sizeof(uint32_t)));
-                f.counters = reinterpret_cast<uint32_t*>(carve(COUNTER_WORDS * sizeof(uint32_t)));
-                f.cls = c; f.strip_top = reinterpret_cast<StripTop*>(c + cls_bytes_of(L.n_slots, tiles_x)); c += pad(cls_region_bytes(L.n_slots, tiles_x, L.n_strips));
-                f.strip_order = 0;                              // (a frame's buffers held another frame before: no cost history to order by)
+                w = carve_frame(f, F.dims, w);
+                set_cls_region(f, F.dims, tiles_x, c); c += pad256(cls_region_bytes(F.dims, tiles_x));
+                f.strip_order = 0;                             // (a frame's buffers held another frame before: no cost history to order by)
                 f.fb = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(device_dst) + size_t(first + k) * frame_stride);
             }
             const Frame2* frames_dev = static_cast<Frame2*>(G.arena.push(fr.data(), cnt * sizeof(Frame2)));
@@ -1765,11 +1729,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             t_stage += ms_since(t0); t0 = clk::now();
             if (!G.ev_begin) { HIP_CHECK(hipEventCreate(&G.ev_begin)); HIP_CHECK(hipEventCreate(&G.ev_end)); }
             HIP_CHECK(hipEventRecord(G.ev_begin, G.stream));
-            launch2_bin(G.stream, frames_dev, cnt, uint32_t(max_e), uint32_t(max_p), uint32_t(max_bands), 1u, r->mono);
-            launch2_rows(G.stream, frames_dev, cnt, uint32_t(max_chunks), max_pe, rows_wide, r->mono);
-            if (max_chunks) launch2_rows_slow(G.stream, frames_dev, cnt, 256u, 64u, SLOW_PASSES, r->mono);
-            launch2_linear_pieces(G.stream, frames_dev, cnt, linear_grid);
-            launch2_tiles(G.stream, frames_dev, cnt, uint32_t(max_strips), ~0u, shader_level, nullptr);
+            launch_chain(r, G.stream, frames_dev, cnt, plan, nullptr, nullptr);
             HIP_CHECK(hipEventRecord(G.ev_end, G.stream));
             for (uint32_t k = 0; k < cnt; ++k)
                 HIP_CHECK(hipMemcpyAsync(G.h_counters + size_t(k) * COUNTER_WORDS, fr[k].counters, COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, G.stream));
@@ -1813,13 +1773,9 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     if (!r->scn[0].slow_verified) { const int rc = render_resident(r, 1); if (rc != SWFR_OK) return rc; }
     const swfr_renderer::Scene& sc = r->scn[0];
     const uint32_t B = per_launch, tiles_x = (r->width + TILE_W - 1) / TILE_W;
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t n_px = size_t(r->width) * r->height;
-    const size_t work_one = pad((2 * sc.n_edges + 1) * sizeof(DevEdge)) + pad(sc.n_slots * sizeof(BandEntry2)) + pad((sc.n_slots * TILE_H + 64) * sizeof(RowInfo2)) +
-                            pad(sc.cell_total * sizeof(Cell)) + 2 * pad(2 * (sc.n_rows + 64) * sizeof(SlowRow)) + 2 * pad((sc.n_paths + 64) * sizeof(uint32_t)) +
-                            pad((sc.n_chunks + 1) * sizeof(ChunkInfo)) + pad((sc.n_slots + 8) * sizeof(BandSlot)) + pad((sc.n_strip_slots + 1) * sizeof(StripDesc)) +
-                            pad((sc.n_strips + 1) * sizeof(uint32_t)) + pad(COUNTER_WORDS * sizeof(uint32_t));
-    const size_t cls_one = pad(cls_region_bytes(sc.n_slots, tiles_x, sc.n_strips));
+    const FrameDims dims = FrameDims::of_scene(sc);
+    const size_t work_one = frame_work_bytes(dims), cls_one = pad256(cls_region_bytes(dims, tiles_x));
     const hipStream_t st = r->stream;
     r->fb_valid = false;                                       // (fb_cur may point into a buffer the next lines reallocate; set again below)
     r->fb_cur = nullptr;
@@ -1831,39 +1787,22 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     HIP_CHECK(hipMemsetAsync(r->rb_cls.ptr, 0, cls_one * B, st));
     std::vector<Frame2> fr(B);
     uint8_t* w = r->rb_work.ptr;
-    auto carve = [&](size_t bytes) { uint8_t* q = w; w += pad(bytes); return q; };
     for (uint32_t k = 0; k < B; ++k) {
         Frame2& f = fr[k];
         f = sc.proto;
-        f.edges = reinterpret_cast<DevEdge*>(carve((2 * sc.n_edges + 1) * sizeof(DevEdge)));
-        f.band_list = reinterpret_cast<BandEntry2*>(carve(sc.n_slots * sizeof(BandEntry2)));
-        f.rows = reinterpret_cast<RowInfo2*>(carve((sc.n_slots * TILE_H + 64) * sizeof(RowInfo2)));
-        f.cells = reinterpret_cast<Cell*>(carve(sc.cell_total * sizeof(Cell)));
-        f.slow = reinterpret_cast<SlowRow*>(carve(2 * (sc.n_rows + 64) * sizeof(SlowRow)));
-        f.huge = reinterpret_cast<SlowRow*>(carve(2 * (sc.n_rows + 64) * sizeof(SlowRow)));
-        f.path_flag = reinterpret_cast<uint32_t*>(carve((sc.n_paths + 64) * sizeof(uint32_t)));
-        f.path_queue = reinterpret_cast<uint32_t*>(carve((sc.n_paths + 64) * sizeof(uint32_t)));
-        f.chunks = reinterpret_cast<ChunkInfo*>(carve((sc.n_chunks + 1) * sizeof(ChunkInfo)));
-        f.band_slots = reinterpret_cast<BandSlot*>(carve((sc.n_slots + 8) * sizeof(BandSlot)));
-        f.strips = reinterpret_cast<StripDesc*>(carve((sc.n_strip_slots + 1) * sizeof(StripDesc)));
-        f.strip_cost = reinterpret_cast<uint32_t*>(carve((sc.n_strips + 1) * sizeof(uint32_t)));
-        f.counters = reinterpret_cast<uint32_t*>(carve(COUNTER_WORDS * sizeof(uint32_t)));
-        f.cls = r->rb_cls.ptr + cls_one * k; f.strip_top = reinterpret_cast<StripTop*>(f.cls + cls_bytes_of(sc.n_slots, tiles_x));
+        w = carve_frame(f, dims, w);
+        set_cls_region(f, dims, tiles_x, r->rb_cls.ptr + cls_one * k);
         f.fb = r->rb_fb.ptr + n_px * k;
     }
     HIP_CHECK(hipMemcpyAsync(r->rb_frames.ptr, fr.data(), B * sizeof(Frame2), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));                       // (fr is a local)
     if (!r->rb_ev[0]) { HIP_CHECK(hipEventCreate(&r->rb_ev[0])); HIP_CHECK(hipEventCreate(&r->rb_ev[1])); }
-    auto one_launch = [&]() {
-        launch2_bin(st, r->rb_frames.ptr, B, uint32_t(sc.n_edges), uint32_t(sc.n_paths), uint32_t(sc.n_bands), (sc.n_chunks && sc.slow_state != 1) ? 1u : 0u, r->mono);
-        launch2_rows(st, r->rb_frames.ptr, B, uint32_t(sc.n_chunks), sc.max_path_edges, sc.rows_wide, r->mono);
-        if (sc.n_chunks && sc.slow_state != 1) launch2_rows_slow(st, r->rb_frames.ptr, B, 256u, sc.slow_state == 2 ? 0u : 64u, sc.slow_passes, r->mono);
-        launch2_linear_pieces(st, r->rb_frames.ptr, B, sc.linear_grid);
-        launch2_tiles(st, r->rb_frames.ptr, B, uint32_t(sc.n_strip_slots), ~0u, sc.shader_level, nullptr);
-    };
-    one_launch();                                              // warm-up: leaves a cost history for the strip order
+    // as a frame of its own, but the queued-row kernels in the grids of frames that share the GPU, and the tile pass in its default shape whatever SWFR_TILES_GRID says
+    LaunchPlan plan = plan_of(r, sc);
+    plan.grid_slow = 256u; plan.grid_huge = sc.slow_state == 2 ? 0u : 64u; plan.tiles_grid = ~0u;
+    launch_chain(r, st, r->rb_frames.ptr, B, plan, nullptr, nullptr);      // warm-up: leaves a cost history for the strip order
     HIP_CHECK(hipEventRecord(r->rb_ev[0], st));
-    for (uint32_t l = 0; l < launches; ++l) one_launch();
+    for (uint32_t l = 0; l < launches; ++l) launch_chain(r, st, r->rb_frames.ptr, B, plan, nullptr, nullptr);
     HIP_CHECK(hipEventRecord(r->rb_ev[1], st));
     HIP_CHECK(hipGetLastError());
     std::vector<uint32_t> hc(size_t(B) * COUNTER_WORDS);
@@ -1893,7 +1832,6 @@ int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* d
     if (device_dst && r->batch_frames > 1) return render_batch2(r, stages, n, device_dst, frame_stride);
     order_frames_behind_pending_read(r);                       // (frames without a device_dst land in the frame sets' own framebuffers)
     const uint32_t n_sets = uint32_t(std::max(1, std::min(r->in_flight, 4)));
-    std::vector<uint32_t*> pinned_counters;
     uint32_t* hc = nullptr;
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hc), size_t(n) * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
     int rc = SWFR_OK;
@@ -1913,10 +1851,9 @@ int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* d
             r->scn[k].slow_state = 0; r->scn[k].slow_passes = SLOW_PASSES;
             swfr_renderer::FrameSet& F = r->fs[k];
             if (k > 0 && i < n_sets) HIP_CHECK(hipStreamSynchronize(r->stream));   // first use of the set: bitmap table etc. are in place
-            uint32_t* fb = device_dst ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(device_dst) + size_t(i) * frame_stride) : F.d_fb.ptr;
-            launch_frame(r, r->scn[k], F, nullptr, nullptr, n_sets > 1 && n > 1);     // (the descriptor carries fb)
+            launch_frame(r, r->scn[k], F, nullptr, nullptr, n_sets > 1 && n > 1);     // (the descriptor carries the frame's target)
             HIP_CHECK(hipMemcpyAsync(hc + size_t(i) * COUNTER_WORDS, F.counters, COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, F.stream));
-            r->fb_cur = fb;
+            r->fb_cur = fb_dst ? fb_dst : F.d_fb.ptr;
         }
         HIP_CHECK(hipGetLastError());
         for (uint32_t k = 0; k < n_sets; ++k)
@@ -1970,6 +1907,32 @@ int finish_read(swfr_renderer* r) {
     HIP_CHECK(hipEventSynchronize(r->read_done));
     r->read_pending = false;
     return SWFR_OK;
+}
+
+// One frame of the resident scene queued on the next frame set in rotation and not waited for (swfr_wait): into the set's own target, or
+// -- block_target, always launched as a frame that shares the GPU -- into the caller's block of the handle's tile-rows.
+int render_resident_async(swfr_renderer* r, void* block_target, uint32_t* out_set) {
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    if (!r->scene_ready) return fail(r, SWFR_ERR_INVALID, "no scene uploaded");
+    const BandShare bs = band_share(r);
+    if (block_target && bs.stride != 1) return fail(r, SWFR_ERR_INVALID, "a block target needs a handle that owns one contiguous block of tile-rows");
+    return guarded(r, [&]() {
+        uint32_t n_sets = 1;
+        while (n_sets < uint32_t(std::min(r->in_flight, 4)) && n_sets < r->sets_ready && r->fs[n_sets].stream && r->fs[n_sets].d_cells.ptr) ++n_sets;
+        const uint32_t k = r->async_next++ % n_sets;
+        r->async_used |= 1u << k;
+        if (!r->scn[0].slow_verified) { r->scn[0].slow_state = 0; r->scn[0].slow_passes = SLOW_PASSES; }   // (nothing checks an async frame's queues: launch everything unless a blocking frame of this scene has shown what it needs)
+        // row y of the frame is row y - (first tile-row) * 16 of the block: the kernels address the frame, so they get the block's
+        // address moved up by the rows above it (only the handle's own rows are ever written)
+        uint32_t* fb_to = block_target ? static_cast<uint32_t*>(block_target) - size_t(bs.first) * TILE_H * r->width : nullptr;
+        order_frames_behind_pending_read(r);
+        launch_frame(r, r->scn[0], r->fs[k], fb_to, nullptr, block_target || n_sets > 1);
+        HIP_CHECK(hipGetLastError());
+        r->fb_cur = block_target ? nullptr : (r->n_targets ? r->targets[k % r->n_targets] : r->fs[k].d_fb.ptr);
+        if (block_target) r->fb_valid = false;                 // (the frame is the caller's: nothing to read back from the handle)
+        if (out_set) *out_set = k;
+        return int(SWFR_OK);
+    });
 }
 
 // (swfr_last_error(NULL): why this thread's last swfr_create refused a flag combination, if it did)
@@ -2407,48 +2370,11 @@ int swfr_set_targets(swfr_renderer* r, void* const* device_targets, uint32_t n_t
 }
 
 int swfr_render_resident_async(swfr_renderer* r, uint32_t* out_set) {
-    if (!r) return SWFR_ERR_INVALID;
-    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
-    if (!r->scene_ready) return fail(r, SWFR_ERR_INVALID, "no scene uploaded");
-    return guarded(r, [&]() {
-        uint32_t n_sets = 1;
-        while (n_sets < uint32_t(std::min(r->in_flight, 4)) && n_sets < r->sets_ready && r->fs[n_sets].stream && r->fs[n_sets].d_cells.ptr) ++n_sets;
-        const uint32_t k = r->async_next++ % n_sets;
-        r->async_used |= 1u << k;
-        swfr_renderer::FrameSet& F = r->fs[k];
-        if (!r->scn[0].slow_verified) { r->scn[0].slow_state = 0; r->scn[0].slow_passes = SLOW_PASSES; }   // (nothing checks an async frame's queues: launch everything unless a blocking frame of this scene has shown what it needs)
-        order_frames_behind_pending_read(r);
-        launch_frame(r, r->scn[0], F, nullptr, nullptr, n_sets > 1);
-        HIP_CHECK(hipGetLastError());
-        r->fb_cur = r->n_targets ? r->targets[k % r->n_targets] : F.d_fb.ptr;
-        if (out_set) *out_set = k;
-        return int(SWFR_OK);
-    });
+    return r ? render_resident_async(r, nullptr, out_set) : SWFR_ERR_INVALID;
 }
 
 int swfr_render_resident_async_to(swfr_renderer* r, void* block_target, uint32_t* out_set) {
-    if (!r || !block_target) return SWFR_ERR_INVALID;
-    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
-    if (!r->scene_ready) return fail(r, SWFR_ERR_INVALID, "no scene uploaded");
-    const BandShare bs = band_share(r);
-    if (bs.stride != 1) return fail(r, SWFR_ERR_INVALID, "a block target needs a handle that owns one contiguous block of tile-rows");
-    return guarded(r, [&]() {
-        uint32_t n_sets = 1;
-        while (n_sets < uint32_t(std::min(r->in_flight, 4)) && n_sets < r->sets_ready && r->fs[n_sets].stream && r->fs[n_sets].d_cells.ptr) ++n_sets;
-        const uint32_t k = r->async_next++ % n_sets;
-        r->async_used |= 1u << k;
-        swfr_renderer::FrameSet& F = r->fs[k];
-        if (!r->scn[0].slow_verified) { r->scn[0].slow_state = 0; r->scn[0].slow_passes = SLOW_PASSES; }
-        // row y of the frame is row y - (first tile-row) * 16 of the block: the kernels address the frame, so they get the block's
-        // address moved up by the rows above it (only the handle's own rows are ever written)
-        uint32_t* fb = static_cast<uint32_t*>(block_target) - size_t(bs.first) * TILE_H * r->width;
-        order_frames_behind_pending_read(r);
-        launch_frame(r, r->scn[0], F, fb, nullptr, true);
-        HIP_CHECK(hipGetLastError());
-        r->fb_cur = nullptr; r->fb_valid = false;              // (the frame is the caller's: nothing to read back from the handle)
-        if (out_set) *out_set = k;
-        return int(SWFR_OK);
-    });
+    return r && block_target ? render_resident_async(r, block_target, out_set) : SWFR_ERR_INVALID;
 }
 
 int swfr_render_resident_group_to(swfr_renderer* r, void* const* block_targets, uint32_t n_frames, uint32_t* sets_used) {

@@ -232,6 +232,38 @@ def test_every_route_gives_the_same_frame(gpu):
         r.close()
 
 
+@pytest.mark.gpu
+def test_frames_per_launch_with_queued_rows(gpu, monkeypatch):
+    """The two routes that launch several frames per kernel -- render_resident_batched and render_resident in groups of frame sets
+    (SWFR_RESIDENT_BATCH=2, no per-kernel events) -- on an aliased handle whose scene has queued rows (a comb of 80 edges per row):
+    every read-back equals the blocking render_edges frame of the same handle, and no capacity limit was reached."""
+    import swf_renderer_amd as S
+    from swf_renderer_amd import api
+    from helpers import crowded_rows_scene
+    monkeypatch.setenv("SWFR_RESIDENT_BATCH", "2")
+    monkeypatch.setenv("SWFR_EVENT_STRIDE", "1000")
+    sc = crowded_rows_scene(40, False)
+    w, h = sc["width"], sc["height"]
+    assert w <= 256 and h <= 192
+    host = S.Renderer(w, h, device=api.DEVICE_HOST_ONLY, antialias="none")
+    frame = host.build_frame(sc["stage"])
+    host.close()
+    r = S.Renderer(w, h, antialias="none")
+    try:
+        r.render_edges(*frame)
+        want = r.read_image(premultiplied=True).copy()
+        assert want[..., 3].any()
+        r.render_resident_batched(3, 2)
+        assert (r.read_image(premultiplied=True) == want).all()
+        r.render_resident(6)
+        assert (r.read_image(premultiplied=True) == want).all()
+        st = r.stats()
+        assert st["queued_rows"] > 0
+        assert (st["pairtest_limit"], st["start_group_limit"], st["history_limit"]) == (0, 0, 0)
+    finally:
+        r.close()
+
+
 def _owned(h, rank, world, contiguous):
     tile_rows = (h + 15) // 16
     t = np.arange(h) // 16
