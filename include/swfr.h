@@ -461,7 +461,8 @@ int  swfr_wait(swfr_renderer *r);
 
 /* Diagnostics (tools/soak_case.py): copies an intermediate buffer of the last rendered frame to the host.
    what = 0: row headers (8 bytes per (band list entry, row of its tile-row): first cell u32, cells u16, mode u16);
-   1: cells (4 bytes each: column relative to the path's x_min << 19 | covered height (5 bits signed) << 14 | uncovered area (14 bits signed)).
+   1: cells (4 bytes each: column relative to the path's x_min << 19 | covered height (5 bits signed) << 14 | uncovered area (14 bits signed));
+   2: one uint32, the workgroup size of the k2_bin instance the last launch chain ran (256 or 1024; tests/test_bin_instances_gpu.py).
    Returns the number of bytes copied (at most `bytes`), or a negative SWFR_ERR_*. */
 long swfr_debug_copy(swfr_renderer *r, int what, void *dst, size_t bytes);
 /* Measurement (tools/cxform_bench.py): the texel pass of colour transforms (cxform.hip) over registered bitmap `bitmap_id` under

@@ -220,6 +220,9 @@ constexpr uint32_t XCDS = 8;            // a launch's workgroups go round-robin 
 // everything the strips of one tile-row read (its band list, class bytes, row headers, cells) is fetched into ONE L2; the classes
 // are padded to the size of the largest (slots without a strip: wg = ~0u)
 inline uint32_t strip_slots(uint32_t local_tile_rows, uint32_t strips_per_row) { return XCDS * ((local_tile_rows + XCDS - 1) / XCDS) * strips_per_row; }
+// k2_bin's two instances by workgroup size (raster2.hip, bin_body), and the most paths a frame may have for the launch plan to
+// choose the small one by itself: what ONE round of its tile-row step tests (16 paths per thread)
+constexpr uint32_t BIN_THREADS_LARGE = 1024, BIN_THREADS_SMALL = 256, BIN_SMALL_PATHS = 16 * BIN_THREADS_SMALL;
 
 struct Frame2 {
     // the scene (read-only)

@@ -184,7 +184,7 @@ __device__ __forceinline__ uint32_t alloc_cells(FramePtr FR, uint32_t n, int lan
 //             band entries, (path, tile-row) -> entry table, class bytes of boxes paths; one thread per edge: the scan converter's
 //             constants (A.5 make_edge); one thread per path: its row chunks; counters cleared
 //   k2_rows   (below) also adds, per (tile, path) pair with a boundary in it, the boundary rows to the cost of the tile's strips
-//             ... and the last workgroup of k2_bin sorts the strips by the costs of the previous frame rendered with the same buffers
+//             ... and eight workgroups of k2_bin order the strips by the costs of the previous frame rendered with the same buffers
 //             (counting sort): the launch list of the tile pass, heaviest strips first
 // The host contributes the LAYOUT of the tables only -- prefix sums over the paths' rectangles (chunks, band slots) and row spans
 // (cells), and over the tile-rows (band list offsets): O(paths) additions, no per-row, per-edge-row or per-tile work.
@@ -214,23 +214,41 @@ __device__ __forceinline__ uint32_t path_chunk_count(const DevPath& P, uint32_t 
     return ((uint32_t)P.y_max - a0 + chunk_rows - 1) / chunk_rows;
 }
 
-__device__ __forceinline__ void order_body(FramePtr F, uint32_t xcd_class);
-constexpr uint32_t BIN_THREADS = 1024;
+// Two instances, by the workgroup's thread count BIN_THREADS (the launch plan chooses: renderer.cpp, bin_threads_of):
+//   1024  a round of the tile-row step covers 16 384 paths, a round of the ordering step 16 384 strips of a class; 26.7 KB of LDS
+//    256  4 096 paths, 4 096 strips, 8.1 KB -- for frames of up to BIN_SMALL_PATHS paths that run beside other frames: a workgroup of
+//         sixteen wavefronts starts only where four wave slots and 224 VGPRs are free on every SIMD of one CU at once, which the
+//         row and tile passes of the frames beside it (480 of a SIMD's 512 VGPRs held, every freed slot refilled) grant only as
+//         they drain; one of four wavefronts needs a single slot per SIMD.  Of a 1 000-path frame's tile-row workgroup only 63
+//         threads have paths to test: the 1024-thread instance parks fifteen idle wavefronts beside the working one.
+// Either instance is exact for any scene: more paths, hits or strips than a round holds take more rounds (windows).
+template <uint32_t BIN_THREADS> __device__ __forceinline__ void order_body(FramePtr F, uint32_t xcd_class);
 constexpr uint32_t BAND_PER_THREAD = 16;                                  // paths a thread tests per round
-constexpr uint32_t BAND_LIST = 4096;                                      // hits of a round staged at a time
-__device__ __forceinline__ void bin_body(FramePtr F, uint32_t slow_kernels) {
+// ORDER_FIRST: the eight ordering workgroups -- the kernel's longest -- are the first of the grid and not the last; per instance
+#ifndef BIN_ORDER_FIRST_SMALL
+#define BIN_ORDER_FIRST_SMALL 1
+#endif
+#ifndef BIN_ORDER_FIRST_LARGE
+#define BIN_ORDER_FIRST_LARGE 0        // (measured: S2's overlapping frames lose 2 % with them in front, DESIGN.md 6.1 "k2_bin sized to the scene")
+#endif
+template <uint32_t BIN_THREADS, bool ORDER_FIRST> __device__ __forceinline__ void bin_body(FramePtr F, uint32_t slow_kernels) {
+    constexpr uint32_t BAND_LIST = 4 * BIN_THREADS;                       // hits of a round staged at a time (4 096 / 1 024)
+    static_assert(BIN_THREADS % 64 == 0 && BIN_THREADS >= (uint32_t)C2_WORDS, "whole wavefronts; block 0 clears the counters in one step");
     __shared__ uint32_t wave_cnt[BIN_THREADS / 64];
     __shared__ uint32_t band_hits[BAND_LIST];                // a tile-row's hits of one round, in painter's order
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (blockIdx.x == 0 && tid < C2_WORDS) F->counters[tid] = 0;
-    if (blockIdx.x >= gridDim.x - XCDS) { order_body(F, blockIdx.x - (gridDim.x - XCDS)); return; }   // the last eight workgroups: the tile pass's launch list
-    if (blockIdx.x < F->n_bands) {
+    // eight workgroups, the first or the last of the grid: the tile pass's launch list
+    const uint32_t order_at = ORDER_FIRST ? 0u : gridDim.x - XCDS;
+    if (blockIdx.x - order_at < XCDS) { order_body<BIN_THREADS>(F, blockIdx.x - order_at); return; }
+    const uint32_t block = blockIdx.x - (ORDER_FIRST ? XCDS : 0u);       // tile-rows' workgroups, then the edge and the path workgroups
+    if (block < F->n_bands) {
         // ---- the paths that touch tile-row `band`, in painter's order
-        const int band = (int)blockIdx.x;
+        const int band = (int)block;
         const uint32_t b0 = F->band_off[band], n_b = F->band_off[band + 1] - b0;
-        // Two steps per round of BAND_PER_THREAD * 1024 paths (one round for a scene of up to 16 384 paths).  Step 1: every thread tests
+        // Two steps per round of BAND_PER_THREAD * BIN_THREADS paths (one round for a scene of up to 16 384 / 4 096 paths).  Step 1: every thread tests
         // sixteen consecutive paths against the host's table of tile-row spans (four bytes a path, 64 contiguous bytes a thread) and
-        // the hits are compacted in painter's order into an LDS list: per-thread counts, one wavefront scan, sixteen wavefront totals.
+        // the hits are compacted in painter's order into an LDS list: per-thread counts, one wavefront scan, the wavefronts' totals.
         // Step 2: one thread per HIT fetches the path and its style and writes the band entry -- every hit's chain of dependent loads
         // runs side by side (round 4, before: four paths per thread and three rounds of the whole chain for S2's 10 000 paths, 22 us).
         uint32_t n = 0;
@@ -255,7 +273,7 @@ __device__ __forceinline__ void bin_body(FramePtr F, uint32_t slow_kernels) {
             uint32_t before = 0, total = 0;
             for (int w = 0; w < (int)(BIN_THREADS / 64); ++w) { const uint32_t t = wave_cnt[w]; if (w < wave) before += t; total += t; }
             const uint32_t first = before + incl - cnt;                  // this thread's first hit among the round's
-            for (uint32_t lo = 0; lo < total; lo += BAND_LIST) {         // (workgroup-uniform; one window unless a tile-row has more than 4 096 hits in a round)
+            for (uint32_t lo = 0; lo < total; lo += BAND_LIST) {         // (workgroup-uniform; one window unless a tile-row has more than BAND_LIST hits in a round)
                 uint32_t m = mask, idx = first;
                 while (m) {
                     const uint32_t bit = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
@@ -321,7 +339,7 @@ __device__ __forceinline__ void bin_body(FramePtr F, uint32_t slow_kernels) {
     // side (round 4: the workgroup that did both was the kernel's long pole) -- one thread per path
     // (batched launches: a frame with fewer tile-rows, edges or paths leaves blocks idle)
     // (an aliased frame has no edge workgroups: its row pass reads the raw edges)
-    const uint32_t rel = blockIdx.x - F->n_bands, edge_blocks = F->mono ? 0u : (F->n_edges + BIN_THREADS - 1) / BIN_THREADS;
+    const uint32_t rel = block - F->n_bands, edge_blocks = F->mono ? 0u : (F->n_edges + BIN_THREADS - 1) / BIN_THREADS;
     const bool path_block = rel >= edge_blocks;
     const uint32_t i = path_block ? ~0u : rel * BIN_THREADS + (uint32_t)tid;
     // ---- one thread per edge: scan converter constants
@@ -385,7 +403,7 @@ __device__ __forceinline__ void bin_body(FramePtr F, uint32_t slow_kernels) {
 // tile-row % XCDS -- the hardware deals a launch's workgroups round-robin over the XCDs, so all strips of a tile-row run on one XCD
 // and share its L2.  Ranks: heaviest first by the cost k2_rows added up during the PREVIOUS frame rendered with these buffers (a
 // scheduling hint only -- a scene's first frame runs in row-major order); the costs are cleared for this frame's k2_rows.
-// One 1024-thread workgroup per XCD class (the last XCDS workgroups of the k2_bin launch).  Round 4: a stable partition into eight
+// One workgroup per XCD class (XCDS workgroups of the k2_bin launch: the first of the small instance's grid, the last of the large one's).  Round 4: a stable partition into eight
 // cost ranges -- one round of loads, per-wavefront counts (eight byte counters in two words, one DPP scan each) in LDS, one scan by one
 // wavefront, two barriers -- instead of
 // a 128-bucket counting sort with returning LDS atomics (these workgroups were k2_bin's long pole: 9-11 us beside the others' 3-4).
@@ -393,10 +411,10 @@ constexpr uint32_t ORDER_RANGES = 8;
 __device__ __forceinline__ uint32_t order_range(uint32_t cost) {          // 0 = heaviest
     return cost >= 48u ? 0u : cost >= 32u ? 1u : cost >= 24u ? 2u : cost >= 16u ? 3u : cost >= 8u ? 4u : cost >= 4u ? 5u : cost >= 1u ? 6u : 7u;
 }
-constexpr uint32_t ORDER_U = 16;                                           // strips per thread and round: 16 384 strips of a class per round
-__device__ __forceinline__ void order_body(FramePtr F, uint32_t x) {
+constexpr uint32_t ORDER_U = 16;                                           // strips per thread and round: 16 384 / 4 096 strips of a class per round
+template <uint32_t BIN_THREADS> __device__ __forceinline__ void order_body(FramePtr F, uint32_t x) {
     __shared__ uint2 rowinfo[256];                         // per tile-row of the class: {first band list entry, entries}
-    __shared__ uint32_t cnt[ORDER_RANGES][ORDER_U][BIN_THREADS / 64];      // strips per (cost range, round of 1024, wavefront); then their exclusive prefix
+    __shared__ uint32_t cnt[ORDER_RANGES][ORDER_U][BIN_THREADS / 64];      // strips per (cost range, round of BIN_THREADS, wavefront); then their exclusive prefix
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t n_strips = F->n_strips, bc = F->band_stride, bi = F->band_first;
     const uint32_t per_row = STRIPS_PER_TILE * (uint32_t)F->tiles_x;
@@ -415,13 +433,13 @@ __device__ __forceinline__ void order_body(FramePtr F, uint32_t x) {
             F->strips[(size_t)(n_mine + j) * XCDS + x] = sd;
         }
     __syncthreads();                                       // rowinfo is complete
-    // strip i of the class: tile-row x + 8 * (i / per_row), position i % per_row in it.  A thread's strips are 1024 apart: one division
-    // per thread and round, then (row, position) advance by the (workgroup-uniform) quotient and remainder of 1024 / per_row
+    // strip i of the class: tile-row x + 8 * (i / per_row), position i % per_row in it.  A thread's strips are BIN_THREADS apart: one division
+    // per thread and round, then (row, position) advance by the (workgroup-uniform) quotient and remainder of BIN_THREADS / per_row
     // (three divisions per strip made these workgroups k2_bin's long pole on S2: 18.6 us of the kernel's 19.4).
     const uint32_t dq = BIN_THREADS / per_row, dr = BIN_THREADS - dq * per_row;
     auto advance = [&](uint32_t& j, uint32_t& pos) { j += dq; pos += dr; if (pos >= per_row) { pos -= per_row; ++j; } };
     auto strip_at = [&](uint32_t j, uint32_t pos) { return (x + j * XCDS) * per_row + pos; };
-    for (uint32_t base = 0; base < n_mine; base += ORDER_U * BIN_THREADS) {                // (one round unless a class has more than 16 384 strips)
+    for (uint32_t base = 0; base < n_mine; base += ORDER_U * BIN_THREADS) {                // (one round unless a class has more than ORDER_U * BIN_THREADS strips)
         const uint32_t n_round = min(n_mine - base, ORDER_U * BIN_THREADS), U = (n_round + BIN_THREADS - 1) / BIN_THREADS;   // workgroup-uniform
         unsigned long long ranges = 0;                     // this thread's strips' cost ranges, three bits each
         uint32_t behind[ORDER_U];                          // strips of the same range before this one in its wavefront
@@ -462,7 +480,7 @@ __device__ __forceinline__ void order_body(FramePtr F, uint32_t x) {
                 uint32_t* flat = &cnt[0][0][0];
                 uint32_t carry = 0;
                 for (uint32_t q = 0; q < ORDER_RANGES; ++q)
-                    for (uint32_t e0 = 0; e0 < U * (BIN_THREADS / 64); e0 += 64) {       // (the rounds in use: U * 16 counts per range, contiguous)
+                    for (uint32_t e0 = 0; e0 < U * (BIN_THREADS / 64); e0 += 64) {       // (the rounds in use: U counts per wavefront and range, contiguous)
                         const uint32_t e = e0 + (uint32_t)tid, lim = U * (BIN_THREADS / 64);
                         const uint32_t v = e < lim ? flat[q * ORDER_U * (BIN_THREADS / 64) + e] : 0u;
                         const uint32_t incl = (uint32_t)wave_scan_incl((int)v);
@@ -497,7 +515,9 @@ __device__ __forceinline__ void order_body(FramePtr F, uint32_t x) {
 // At most 80 SGPRs: the hardware hands a wavefront its SGPRs in blocks of 16 plus 16 (MI355X_MICROARCH.md, "Occupancy API one block/CU
 // high"), so 81-96 leave room for 7 wavefronts per SIMD -- ONE 1024-thread workgroup per CU instead of two, and a frame with more
 // than 256 of them (S2: 386) ran k2_bin in two rounds (r04y: 44.6 us; its edge and path workgroups entered when the tile-rows' left).
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) void k2_bin_b(const Frame2* __restrict__ frames, uint32_t slow_kernels) { TRACE_DECL; TRACE_NOWAIT(0); bin_body(FRAME_PTR(frames, blockIdx.y), slow_kernels); TRACE(7); TRACE_OUT(0, blockIdx.x); }
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) void k2_bin_b(const Frame2* __restrict__ frames, uint32_t slow_kernels) { TRACE_DECL; TRACE_NOWAIT(0); bin_body<BIN_THREADS_LARGE, BIN_ORDER_FIRST_LARGE != 0>(FRAME_PTR(frames, blockIdx.y), slow_kernels); TRACE(7); TRACE_OUT(0, blockIdx.x); }
+// (no SGPR cap: at its 102 SGPRs seven of these four-wavefront workgroups fit a CU -- the cap above is what lets TWO sixteen-wavefront ones fit; not tried here)
+__global__ __launch_bounds__(256) void k2_bin_small_b(const Frame2* __restrict__ frames, uint32_t slow_kernels) { TRACE_DECL; TRACE_NOWAIT(0); bin_body<BIN_THREADS_SMALL, BIN_ORDER_FIRST_SMALL != 0>(FRAME_PTR(frames, blockIdx.y), slow_kernels); TRACE(7); TRACE_OUT(0, blockIdx.x); }
 
 // ---------------------------------------------------------------------------------------------
 // k2_rows
@@ -2053,10 +2073,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAY
 // ---------------------------------------------------------------------------------------------
 // slow_kernels: 0 when the queued-row kernels will not be launched behind this k2_bin (their DevEdge records are then not written)
 // mono: the frames are aliased (Frame2::mono) -- k2_bin has no edge workgroups, the row pass is k2_rows_mono (+ k2_rows_mono_huge)
-void launch2_bin(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_edges, uint32_t max_paths, uint32_t max_bands, uint32_t slow_kernels, bool mono) {
+// bin_threads: the instance (BIN_THREADS_SMALL or BIN_THREADS_LARGE; the plan chooses)
+void launch2_bin(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_edges, uint32_t max_paths, uint32_t max_bands, uint32_t slow_kernels, bool mono, uint32_t bin_threads) {
     // tile-rows' workgroups, edge workgroups, path workgroups (a frame's own follow its own edge workgroups), + the eight that order the strips
-    const uint32_t g = max_bands + (mono ? 0u : (max_edges + BIN_THREADS - 1) / BIN_THREADS) + (max_paths + BIN_THREADS - 1) / BIN_THREADS + XCDS;
-    hipLaunchKernelGGL(k2_bin_b, dim3(g, n_frames), dim3(BIN_THREADS), 0, st, frames, slow_kernels);
+    const uint32_t T = bin_threads == BIN_THREADS_SMALL ? BIN_THREADS_SMALL : BIN_THREADS_LARGE;
+    const uint32_t g = XCDS + max_bands + (mono ? 0u : (max_edges + T - 1) / T) + (max_paths + T - 1) / T;
+    if (T == BIN_THREADS_SMALL) hipLaunchKernelGGL(k2_bin_small_b, dim3(g, n_frames), dim3(BIN_THREADS_SMALL), 0, st, frames, slow_kernels);
+    else hipLaunchKernelGGL(k2_bin_b, dim3(g, n_frames), dim3(BIN_THREADS_LARGE), 0, st, frames, slow_kernels);
 }
 // wide: k2_rows_wide even when no path has more than ROWS_STAGE edges (the SWFR_ROWS_WIDE test knob)
 void launch2_rows(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_chunks, uint32_t max_path_edges, bool wide, bool mono) {

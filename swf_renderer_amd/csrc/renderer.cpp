@@ -28,7 +28,7 @@
 #include "bitmap_decode.hpp"
 
 namespace swfr {
-void launch2_bin(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, bool);
+void launch2_bin(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, bool, uint32_t);
 void launch2_rows(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, bool, bool);
 void launch2_rows_slow(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, bool);
 void launch2_tiles(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, int, uint32_t*);
@@ -256,6 +256,8 @@ struct swfr_renderer {
     bool mono = false;                      // SWFR_FLAG_ANTIALIAS_NONE: boxes rounded to pixels, tor paths by k2_rows_mono (Frame2::mono)
     int fast_limit = 16;                    // rows with more active edges go to k2_rows_slow; the row kernel's instance caps it at its 8 or 16 slots (SWFR_FAST_LIMIT: test knob)
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
+    int bin_threads = 0;                    // SWFR_BIN_THREADS: 256 or 1024 forces that instance of k2_bin (0 = the launch plan's rule; tests and sweeps)
+    uint32_t last_bin_threads = 0;          // the instance of the last launch chain (swfr_debug_copy, what = 2)
     int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups, 5 masked groups, 6 faded groups; test knob)
     bool rows_wide = false;                 // SWFR_ROWS_WIDE=1: every frame with tor paths runs k2_rows_wide (test knob; aliased frames keep k2_rows_mono)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
@@ -1373,6 +1375,7 @@ int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size
 // frames of the launch, and the choices in which the routes differ.
 struct LaunchPlan {
     uint32_t max_edges, max_paths, max_bands, slow_kernels;      // k2_bin; slow_kernels 1: it also prepares the queued-row kernels' work
+    uint32_t bin_threads;                                        // k2_bin's instance: BIN_THREADS_SMALL or BIN_THREADS_LARGE (bin_threads_of)
     uint32_t max_chunks, max_path_edges; bool rows_wide;         // the row pass
     bool run_slow; uint32_t grid_slow, grid_huge, slow_passes;   // the queued-row kernels (coincident edges, crowded rows), if launched
     uint32_t linear_grid;                                        // k2_linear_pieces (0: not launched)
@@ -1382,7 +1385,8 @@ struct LaunchPlan {
 // fb_to: the one frame's own target instead of its descriptor's (swfr_render_resident_async_to), else nullptr.
 void launch_chain(swfr_renderer* r, hipStream_t st, const Frame2* frames, uint32_t n_frames, const LaunchPlan& p, hipEvent_t* events, uint32_t* fb_to) {
     if (events) HIP_CHECK(hipEventRecord(events[0], st));
-    launch2_bin(st, frames, n_frames, p.max_edges, p.max_paths, p.max_bands, p.slow_kernels, r->mono);
+    r->last_bin_threads = p.bin_threads;
+    launch2_bin(st, frames, n_frames, p.max_edges, p.max_paths, p.max_bands, p.slow_kernels, r->mono, p.bin_threads);
     if (events) HIP_CHECK(hipEventRecord(events[1], st));
     launch2_rows(st, frames, n_frames, p.max_chunks, p.max_path_edges, p.rows_wide, r->mono);
     if (p.run_slow) launch2_rows_slow(st, frames, n_frames, p.grid_slow, p.grid_huge, p.slow_passes, r->mono);
@@ -1391,12 +1395,22 @@ void launch_chain(swfr_renderer* r, hipStream_t st, const Frame2* frames, uint32
     launch2_tiles(st, frames, n_frames, p.max_strips, p.tiles_grid, p.shader_level, fb_to);
     if (events) HIP_CHECK(hipEventRecord(events[3], st));
 }
+// k2_bin's instance for a launch whose frames have up to max_paths paths: SWFR_BIN_THREADS when set, else the small one where no frame
+// needs a second round of its tile-row step and other frames run beside the launch (`overlapped`, as in launch_frame): its
+// four-wavefront workgroups start in the slots the other frames' row and tile passes free one at a time, where a sixteen-wavefront
+// workgroup waits for half a CU ("k2_bin sized to the scene").  A frame that has the GPU to itself keeps the
+// large instance: its ordering workgroups have four times the threads for the same strips.
+uint32_t bin_threads_of(const swfr_renderer* r, uint32_t max_paths, bool overlapped) {
+    if (r->bin_threads) return uint32_t(r->bin_threads);
+    return overlapped && max_paths <= BIN_SMALL_PATHS ? BIN_THREADS_SMALL : BIN_THREADS_LARGE;
+}
 // The plan of the resident scene's frames, as a frame launched on its own frame set gets it; the routes that differ say so where they call.
 LaunchPlan plan_of(const swfr_renderer* r, const swfr_renderer::Scene& sc) {
     LaunchPlan p;
     p.max_edges = uint32_t(sc.n_edges); p.max_paths = uint32_t(sc.n_paths); p.max_bands = uint32_t(sc.n_bands);
     p.run_slow = sc.n_chunks && sc.slow_state != 1;            // the queued rows: skipped once a frame of this resident scene has shown there are none
     p.slow_kernels = p.run_slow ? 1u : 0u;
+    p.bin_threads = bin_threads_of(r, p.max_paths, true);
     p.max_chunks = uint32_t(sc.n_chunks); p.max_path_edges = sc.max_path_edges; p.rows_wide = sc.rows_wide;
     p.grid_slow = 1024u; p.grid_huge = sc.slow_state == 2 ? 0u : 256u; p.slow_passes = sc.slow_passes;
     p.linear_grid = sc.linear_grid; p.max_strips = uint32_t(sc.n_strip_slots); p.shader_level = sc.shader_level;
@@ -1411,6 +1425,7 @@ LaunchPlan plan_of(const swfr_renderer* r, const swfr_renderer::Scene& sc) {
 void launch_frame(swfr_renderer* r, const swfr_renderer::Scene& sc, swfr_renderer::FrameSet& F, uint32_t* fb, hipEvent_t* e, bool overlapped) {
     LaunchPlan plan = plan_of(r, sc);
     if (r->tiles_grid <= 0 && !overlapped) plan.tiles_grid = 0x7fffffffu;      // (a frame alone: one wavefront per strip)
+    plan.bin_threads = bin_threads_of(r, plan.max_paths, overlapped);
     // the frame's descriptor (scene arrays, this set's buffers, the framebuffer) was uploaded with the scene
     launch_chain(r, F.stream, sc.frames_dev + (&F - r->fs), 1, plan, e, fb);   // (fb: this frame's own target, else the descriptor's)
 }
@@ -1695,6 +1710,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
                 plan.max_strips = std::max(plan.max_strips, uint32_t(L.n_strip_slots)); plan.shader_level = std::max(plan.shader_level, L.shader_level);
             }
             plan.run_slow = plan.max_chunks != 0;
+            plan.bin_threads = bin_threads_of(r, plan.max_paths, true);     // (over the frames of the launch; the other group's launch runs beside it)
             t_build += ms_since(t0); t0 = clk::now();
             // ---- this group's previous use must be over before its staging and device buffers are rewritten
             finish_group(g);
@@ -1800,6 +1816,7 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     // as a frame of its own, but the queued-row kernels in the grids of frames that share the GPU, and the tile pass in its default shape whatever SWFR_TILES_GRID says
     LaunchPlan plan = plan_of(r, sc);
     plan.grid_slow = 256u; plan.grid_huge = sc.slow_state == 2 ? 0u : 64u; plan.tiles_grid = ~0u;
+    plan.bin_threads = bin_threads_of(r, plan.max_paths, B > 1);
     launch_chain(r, st, r->rb_frames.ptr, B, plan, nullptr, nullptr);      // warm-up: leaves a cost history for the strip order
     HIP_CHECK(hipEventRecord(r->rb_ev[0], st));
     for (uint32_t l = 0; l < launches; ++l) launch_chain(r, st, r->rb_frames.ptr, B, plan, nullptr, nullptr);
@@ -1964,6 +1981,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono, (r->cfg.flags & SWFR_FLAG_LINEAR_PIXMAN) != 0));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
+    if (const char* bt = std::getenv("SWFR_BIN_THREADS")) { const int v = std::atoi(bt); r->bin_threads = v == int(BIN_THREADS_SMALL) || v == int(BIN_THREADS_LARGE) ? v : 0; }
     if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 6);
     if (const char* rw = std::getenv("SWFR_ROWS_WIDE")) r->rows_wide = std::atoi(rw) != 0;
     if (const char* bf = std::getenv("SWFR_BATCH_FRAMES")) r->batch_frames = std::max(1, std::atoi(bf));
@@ -2420,6 +2438,11 @@ int swfr_wait(swfr_renderer* r) {
 long swfr_debug_copy(swfr_renderer* r, int what, void* dst, size_t bytes) {
     if (!r || !dst) return -long(SWFR_ERR_INVALID);
     if (!r->has_device) return -long(SWFR_ERR_NO_DEVICE);
+    if (what == 2) {                                       // (no device buffer: what the last launch chain chose)
+        if (bytes < sizeof(uint32_t)) return 0;
+        std::memcpy(dst, &r->last_bin_threads, sizeof(uint32_t));
+        return long(sizeof(uint32_t));
+    }
     const swfr_renderer::FrameSet& F = r->fs[0];
     const void* src = what == 0 ? static_cast<const void*>(F.d_rows2.ptr) : static_cast<const void*>(F.d_cells.ptr);
     const size_t have = what == 0 ? F.d_rows2.cap * sizeof(RowInfo2) : F.d_cells.cap * sizeof(Cell);

@@ -60,14 +60,18 @@ for k, name in enumerate(("k2_bin", "k2_rows", "k2_tiles")):
     print("%s: %d workgroups, starts at %.2f us, span %.2f us; workgroup duration us: p10 %.2f p50 %.2f p90 %.2f max %.2f; entries spread over %.2f us" %
           (name, len(b), (t0 - t_all0) * 0.01, (t1 - t0) * 0.01, *np.percentile(dur, [10, 50, 90]), dur.max(), (b[:, 0].max() - t0) * 0.01))
     if name == "k2_bin":
-        # which workgroups are the long ones: tile-row workgroups first, then the edge / path workgroups, the last eight order the strips
+        # which workgroups are the long ones: tile-row workgroups, then the edge / path workgroups; the eight that order the strips are the
+        # LAST of the 1024-thread instance's grid (a frame alone, as here) and the FIRST of the 256-thread one's (SWFR_BIN_THREADS=256)
+        order_first = os.environ.get("SWFR_BIN_THREADS") == "256"
         used_idx = np.nonzero(used)[0]
         worst = np.argsort(-dur)[:10]
-        print("   slowest workgroups (blockIdx: us): " + ", ".join("%d: %.1f" % (int(used_idx[i]), dur[i]) for i in worst) + "; the last eight blockIdx are the ordering workgroups (grid %d)" % (int(used_idx.max()) + 1))
-        # entry time and duration along blockIdx (tile-rows' workgroups, edge workgroups, path workgroups, the ordering eight)
-        ent = (b[:, 0] - t0) * 0.01
         g = int(used_idx.max()) + 1
-        cuts = sorted(set(list(range(0, g - 8, max((g - 8) // 12, 1))) + [g - 8, g]))
+        print("   slowest workgroups (blockIdx: us): " + ", ".join("%d: %.1f" % (int(used_idx[i]), dur[i]) for i in worst) +
+              "; blockIdx %d..%d are the ordering workgroups (grid %d)" % ((0, 7, g) if order_first else (g - 8, g - 1, g)))
+        # entry time and duration along blockIdx (tile-rows' workgroups, edge workgroups, path workgroups; the ordering eight before or behind them)
+        ent = (b[:, 0] - t0) * 0.01
+        lo0, hi0 = (8, g) if order_first else (0, g - 8)
+        cuts = sorted(set([0, g] + list(range(lo0, hi0, max((g - 8) // 12, 1))) + [hi0]))
         for lo, hi in zip(cuts[:-1], cuts[1:]):
             m = (used_idx >= lo) & (used_idx < hi)
             if m.any(): print("   blockIdx %4d..%4d: entry %.2f..%.2f us, duration mean %.2f max %.2f us" % (lo, hi - 1, ent[m].min(), ent[m].max(), dur[m].mean(), dur[m].max()))
