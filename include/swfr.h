@@ -155,7 +155,8 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
                                             surface of the frame's size, which is then composited onto the parent as ONE layer with the
                                             operator of the SWF blend-mode number in `id` -- cairo_push_group; the children;
                                             cairo_pop_group_to_source; cairo_set_operator; cairo_paint.  0, 1, 2 (normal, layer): OVER;
-                                            3..8, 13, 14: the mode's operator; 9..12: SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode";
+                                            3..8, 13, 14: the mode's operator; 9..12: SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode"
+                                            (11 and 12 are accepted on a handle with SWFR_FLAG_ALPHA_MODES: SWFR_BLEND_*, below);
                                             above 14: SWFR_ERR_INVALID.  A SWFR_OBJECT_BLEND_MODE in force around the layer still applies
                                             per path inside it, against the layer's own pixels.  Layers nest up to SWFR_MAX_LAYER_DEPTH
                                             deep: deeper is SWFR_ERR_CAPACITY, "LayerDepth".  (Masks: SWFR_OBJECT_MASKED_LAYER.)  A colour
@@ -188,7 +189,15 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
 /* SWF blend-mode numbers (PlaceObject3, swf-tree BlendMode).  0, 1: OVER.  3..8, 13, 14: the Cairo operator of the same name
    (CAIRO_OPERATOR_MULTIPLY, SCREEN, LIGHTEN, DARKEN, DIFFERENCE, ADD, OVERLAY, HARD_LIGHT).  SUBTRACT, INVERT, ALPHA, ERASE have no
    Cairo operator or act on a parent layer's alpha, and LAYER means nothing for a SWFR_OBJECT_BLEND_MODE (it is SWFR_OBJECT_LAYER's
-   OVER): SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode".  Above 14: SWFR_ERR_INVALID. */
+   OVER): SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlendMode".  Above 14: SWFR_ERR_INVALID.
+   On a handle with SWFR_FLAG_ALPHA_MODES two of the four are accepted ("Erase and alpha modes"):
+   ERASE (12) is CAIRO_OPERATOR_DEST_OUT, d' = mul_un8(d, 255 - sa) in every channel: as a SWFR_OBJECT_BLEND_MODE (per path) and as the
+   mode of the three layer types (the group, masked or faded as ever, is the source of one DEST_OUT composite);
+   ALPHA (11) is CAIRO_OPERATOR_DEST_IN, d' = mul_un8(d, sa): as the mode of the three layer types only.  Like canvas
+   "destination-in" it is unbounded: the parent surface is cleared wherever the layer is transparent, outside the layer's own bounds
+   too (Flash Player confines it to them).  As a SWFR_OBJECT_BLEND_MODE it stays "NotImplementedBlendMode": per path every single
+   fill or stroke would clear the surface outside itself.  Neither mode needs a "layer" parent: outside any layer the surface is the
+   frame.  SUBTRACT and INVERT stay refused. */
 enum { SWFR_BLEND_NORMAL0 = 0, SWFR_BLEND_NORMAL = 1, SWFR_BLEND_LAYER = 2, SWFR_BLEND_MULTIPLY = 3, SWFR_BLEND_SCREEN = 4,
        SWFR_BLEND_LIGHTEN = 5, SWFR_BLEND_DARKEN = 6, SWFR_BLEND_DIFFERENCE = 7, SWFR_BLEND_ADD = 8, SWFR_BLEND_SUBTRACT = 9,
        SWFR_BLEND_INVERT = 10, SWFR_BLEND_ALPHA = 11, SWFR_BLEND_ERASE = 12, SWFR_BLEND_OVERLAY = 13, SWFR_BLEND_HARDLIGHT = 14 };
@@ -230,6 +239,9 @@ int swfr_set_color_transform(swfr_renderer *r, uint32_t slot, const swfr_color_t
                                             spread -- instead of the float64 model (within +-1 of Cairo, pad only).  Together with
                                             SWFR_FLAG_ANTIALIAS_NONE: swfr_create fails with SWFR_ERR_NOT_IMPLEMENTED
                                             ("NotImplementedAliasedPixmanLinear", readable with swfr_last_error(NULL) on the same thread) */
+#define SWFR_FLAG_ALPHA_MODES 16u        /* the blend modes ERASE (12) and ALPHA (11) are accepted (SWFR_BLEND_*, above) and so are the path
+                                            operators SWFR_OP_ERASE and SWFR_OP_ALPHA at swfr_upload_edges.  Without the flag every
+                                            refusal and every byte is what it was */
 
 typedef struct {
     int32_t device;                      /* HIP device ordinal, or SWFR_DEVICE_HOST_ONLY */
@@ -321,7 +333,15 @@ typedef struct {
 /* The operator of a path (swfr_path::lerp >> 8): pixman's unified combiner of that name applied to mul_un8(source pixel, coverage).
    Of a SWFR_PATH_GROUP_END: the same combiner applied to the group's pixel itself (no coverage). */
 enum { SWFR_OP_OVER = 0, SWFR_OP_MULTIPLY = 1, SWFR_OP_SCREEN = 2, SWFR_OP_LIGHTEN = 3, SWFR_OP_DARKEN = 4, SWFR_OP_DIFFERENCE = 5,
-       SWFR_OP_ADD = 6, SWFR_OP_OVERLAY = 7, SWFR_OP_HARDLIGHT = 8 };
+       SWFR_OP_ADD = 6, SWFR_OP_OVERLAY = 7, SWFR_OP_HARDLIGHT = 8,
+       /* on a handle with SWFR_FLAG_ALPHA_MODES only (without it: SWFR_ERR_INVALID as every value above 8).  With s the source as above
+          and sa its alpha byte, per channel, alpha included, pixman's 0x80 rounding:
+          ERASE, CAIRO_OPERATOR_DEST_OUT: d' = mul_un8(d, 255 - sa).  On an ordinary path (lerp bits 0) and on a GROUP_END.
+          ALPHA, CAIRO_OPERATOR_DEST_IN: d' = mul_un8(d, sa).  On a GROUP_END only (an ordinary path: SWFR_ERR_INVALID).  The operator
+          is unbounded -- where the group is transparent the parent surface becomes clear -- so an ALPHA GROUP_END and its BEGIN (and
+          MASK) must carry a rectangle that contains the rectangle of every path since the enclosing surface began (the enclosing
+          GROUP_BEGIN, or the frame's start): outside it the parent is clear anyway.  SWFR_ERR_INVALID otherwise */
+       SWFR_OP_ERASE = 9, SWFR_OP_ALPHA = 10 };
 
 enum { SWFR_STYLE_SOLID = 0, SWFR_STYLE_RADIAL = 1, SWFR_STYLE_LINEAR = 2, SWFR_STYLE_BITMAP = 3,
        SWFR_STYLE_LINEAR_PIXMAN = 4 };   /* 4: the linear gradient c0 -> c1 evaluated as pixman 0.40 does (linear_get_scanline), piece by

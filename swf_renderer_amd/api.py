@@ -21,6 +21,7 @@ FLAG_EVEN_ODD = 1
 FLAG_BANDS_CONTIGUOUS = 2
 FLAG_ANTIALIAS_NONE = 4
 FLAG_LINEAR_PIXMAN = 8
+FLAG_ALPHA_MODES = 16
 LINEAR_MODES = ("float64", "pixman")    # how a linear gradient fill is evaluated: the float64 model (within +-1 of Cairo, pad only) or as pixman does (exact, every spread)
 ANTIALIAS_MODES = ("default", "none")   # node-canvas's ctx.antialias values this renderer knows
 PATH_TOR, PATH_BOXES = 0, 1
@@ -49,6 +50,9 @@ BLEND_MODES = {"normal": 1, "layer": 2, "multiply": 3, "screen": 4, "lighten": 5
                "subtract": 9, "invert": 10, "alpha": 11, "erase": 12, "overlay": 13, "hardlight": 14}
 # operators of a low-level path (swfr_path::lerp >> 8, swfr.h SWFR_OP_*)
 PATH_OPERATORS = {"over": 0, "multiply": 1, "screen": 2, "lighten": 3, "darken": 4, "difference": 5, "add": 6, "overlay": 7, "hardlight": 8}
+# the two more of a handle created with alpha_modes=True (SWFR_FLAG_ALPHA_MODES; swfr.h SWFR_OP_ERASE, SWFR_OP_ALPHA): Cairo's DEST_OUT,
+# on a path or a GROUP_END, and DEST_IN, on a GROUP_END only
+ALPHA_MODE_OPERATORS = {"erase": 9, "alpha": 10}
 
 
 def blend_mode_number(mode) -> int:
@@ -480,7 +484,9 @@ def decode_x_swf_bmp(data: bytes):
 class Renderer:
     """`new NodeCanvasRenderer(width, height)` + `Renderer{render, addBitmap}` over libswfr.so."""
 
-    def __init__(self, width, height, device=0, even_odd=False, band_index=0, band_count=0, contiguous_bands=False, antialias="default", linear="float64"):
+    def __init__(self, width, height, device=0, even_odd=False, band_index=0, band_count=0, contiguous_bands=False, antialias="default", linear="float64", alpha_modes=False):
+        # alpha_modes: the blend modes "erase" (per path and as a layer's mode) and "alpha" (as a layer's mode) are accepted: Cairo's
+        # DEST_OUT and DEST_IN (SWFR_FLAG_ALPHA_MODES); without it they are refused with NotImplementedBlendMode, as subtract and invert always are
         # antialias: "default" (Cairo's 15x256 antialiasing, the reference) or "none" (aliased edges: CAIRO_ANTIALIAS_NONE)
         # linear: "float64" (linear gradient fills by the float64 model, pad only) or "pixman" (as pixman paints them: libcairo's bytes, every spread)
         if antialias not in ANTIALIAS_MODES:
@@ -492,7 +498,8 @@ class Renderer:
         self.antialias = antialias
         self.linear = linear
         flags = ((FLAG_EVEN_ODD if even_odd else 0) | (FLAG_BANDS_CONTIGUOUS if contiguous_bands else 0) | (FLAG_ANTIALIAS_NONE if antialias == "none" else 0) |
-                 (FLAG_LINEAR_PIXMAN if linear == "pixman" else 0))
+                 (FLAG_LINEAR_PIXMAN if linear == "pixman" else 0) | (FLAG_ALPHA_MODES if alpha_modes else 0))
+        self.alpha_modes = bool(alpha_modes)
         cfg = Config(int(device), flags, band_index, band_count)
         h = C.c_void_p()
         rc = self.L.swfr_create(self.width, self.height, C.byref(cfg), C.byref(h))

@@ -42,7 +42,9 @@ Css morph_color(const swfr_rgba8& s, const swfr_rgba8& e, bool morph, double rat
 
 // SWF blend-mode number -> path operator ("Blend modes"): the eight modes Cairo has an operator for; the others need an
 // isolated group (layer, alpha, erase) or have no Cairo operator (subtract, invert)
-uint32_t blend_operator(uint32_t mode) {
+// (SWFR_FLAG_ALPHA_MODES: erase is DEST_OUT, per path too; alpha -- DEST_IN, unbounded -- is a layer's mode only: layer_operator)
+uint32_t blend_operator(uint32_t mode, bool alpha_modes) {
+    if (alpha_modes && mode == SWFR_BLEND_ERASE) return SWFR_OP_ERASE;
     switch (mode) {
         case SWFR_BLEND_NORMAL0: case SWFR_BLEND_NORMAL: return SWFR_OP_OVER;
         case SWFR_BLEND_MULTIPLY: return SWFR_OP_MULTIPLY;
@@ -59,7 +61,10 @@ uint32_t blend_operator(uint32_t mode) {
     throw StatusError{SWFR_ERR_INVALID, "InvalidBlendMode"};
 }
 // the operator an isolated layer (SWFR_OBJECT_LAYER) is composited with: OVER also for "layer", the mode whose whole meaning is the group
-uint32_t layer_operator(uint32_t mode) { return mode == SWFR_BLEND_LAYER ? uint32_t(SWFR_OP_OVER) : blend_operator(mode); }
+uint32_t layer_operator(uint32_t mode, bool alpha_modes) {
+    if (alpha_modes && mode == SWFR_BLEND_ALPHA) return SWFR_OP_ALPHA;
+    return mode == SWFR_BLEND_LAYER ? uint32_t(SWFR_OP_OVER) : blend_operator(mode, alpha_modes);
+}
 // a path's blend field once it is known whether the surface was still clear when it was drawn: "2" (a lerp only because nothing was
 // painted yet -- an OVER or an ADD path) becomes the SOURCE lerp, or what the path is otherwise: OVER, or its operator
 inline uint32_t settle_lerp(uint32_t lerp, bool clear) { return (lerp & 0xffu) == 2u ? (clear ? 1u : (lerp & ~0xffu)) : lerp; }
@@ -200,8 +205,8 @@ struct FrameBuilder::Pool {
     }
 };
 
-FrameBuilder::FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased, bool linear_pixman)
-    : w_(width), h_(height), even_odd_(even_odd), aliased_(aliased), linear_pixman_(linear_pixman) {}
+FrameBuilder::FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased, bool linear_pixman, bool alpha_modes)
+    : w_(width), h_(height), even_odd_(even_odd), aliased_(aliased), linear_pixman_(linear_pixman), alpha_modes_(alpha_modes) {}
 
 FrameBuilder::~FrameBuilder() {
     if (pool_) {
@@ -221,6 +226,7 @@ void FrameBuilder::build_range(const std::vector<const swfr_display_object*>& wr
     failed_ = false;
     group_depth_ = 0;
     surface_clear_ = true;  // clearRect over the whole canvas (canvas-renderer.ts:70-71); a later piece learns the truth when joined
+    drawn_ = PixelRect{};
     State s;
     s.ctm = Affine::scale(1.0 / 20.0, 1.0 / 20.0);  // twips -> px (:74)
     s.inv = Affine::scale(1.0 / (1.0 / 20.0), 1.0 / (1.0 / 20.0));  // cairo_scale: ctm_inverse *= scale(1/sx, 1/sy)
@@ -235,7 +241,7 @@ void FrameBuilder::build_range(const std::vector<const swfr_display_object*>& wr
                 if (it == store()->cxforms_.end()) throw StatusError{SWFR_ERR_NOT_FOUND, "ColorTransformNotFound"};
                 stack_.back().lut = compose(stack_.back().lut, it->second);
             }
-            if (w->type == SWFR_OBJECT_BLEND_MODE) stack_.back().op = blend_operator(w->id);
+            if (w->type == SWFR_OBJECT_BLEND_MODE) stack_.back().op = blend_operator(w->id, alpha_modes_);
         }
         for (uint32_t i = lo; i < hi; ++i) draw(kids[i], int(wraps.size()));
     } catch (const StatusError& e) {
@@ -285,8 +291,9 @@ void FrameBuilder::build(const swfr_stage& stage) {
         n_kids = kids[0].n_children;
         kids = kids[0].children;
     }
-    // pieces of at least 64 display objects each
-    const int pieces = int(std::min<uint32_t>(uint32_t(std::max(want, 1)), n_kids / 64));
+    // pieces of at least 64 display objects each.  (SWFR_FLAG_ALPHA_MODES: one walk -- an ALPHA layer's rectangle takes in every path
+    // drawn on its surface before it, which a piece does not know of the pieces before it)
+    const int pieces = alpha_modes_ ? 1 : int(std::min<uint32_t>(uint32_t(std::max(want, 1)), n_kids / 64));
     if (pieces < 2) {
         build_range({}, stage.children, 0, stage.n_children);
         if (failed_) throw failure_;
@@ -296,7 +303,7 @@ void FrameBuilder::build(const swfr_stage& stage) {
     if (!pool_) pool_.reset(new Pool);
     Pool& P = *pool_;
     while (int(P.builders.size()) < pieces) {                 // (piece k is built by builders[k-1] for k >= 1; piece 0 needs a scratch builder, too)
-        P.builders.emplace_back(new FrameBuilder(w_, h_, even_odd_, aliased_, linear_pixman_));
+        P.builders.emplace_back(new FrameBuilder(w_, h_, even_odd_, aliased_, linear_pixman_, alpha_modes_));
         P.builders.back()->parent_ = this;
         P.builders.back()->threads_ = 0;
     }
@@ -361,7 +368,7 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
             break;
         }
         case SWFR_OBJECT_BLEND_MODE:
-            stack_.back().op = blend_operator(obj.id);
+            stack_.back().op = blend_operator(obj.id, alpha_modes_);
             for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
             break;
         case SWFR_OBJECT_LAYER:
@@ -398,9 +405,10 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
 // With an opacity below 255 (SWFR_OBJECT_FADED_LAYER; DESIGN.md, "Layer opacity") the last call is cairo_paint_with_alpha(opacity / 255.0):
 // the END marker carries the fade 255 - opacity in bits 24..31 of its `lerp`.
 void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth, uint32_t mode, uint32_t opacity) {
-    const uint32_t op = layer_operator(mode);
+    const uint32_t op = layer_operator(mode, alpha_modes_);
     if (group_depth_ >= SWFR_MAX_LAYER_DEPTH) throw StatusError{SWFR_ERR_CAPACITY, "LayerDepth"};
     const bool parent_clear = surface_clear_;
+    const PixelRect parent_drawn = drawn_;
     const size_t begin = paths_.size(), begin_edges = edges_.size(), begin_styles = styles_.size();
     swfr_path m;
     std::memset(&m, 0, sizeof m);
@@ -408,37 +416,71 @@ void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth, uint32_
     m.first_edge = uint32_t(edges_.size());
     paths_.push_back(m);
     surface_clear_ = true;
+    drawn_ = PixelRect{};
     ++group_depth_;
     for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);      // (a throw ends the whole build: nothing to unwind)
     --group_depth_;
     const bool group_clear = surface_clear_;
+    drawn_ = parent_drawn;
     // libcairo: painting a still-clear group with OVER or ADD is NOTHING_TO_DO and leaves the parent's "still clear" state alone; under
     // any other operator, and whenever the group was drawn on (even if every pixel of it is zero), the parent counts as drawn
     surface_clear_ = parent_clear && group_clear && (op == SWFR_OP_OVER || op == SWFR_OP_ADD);
-    if (opacity == 0u) {
-        // libcairo: cairo_paint_with_alpha(0) returns at once under all nine operators (each is bounded by the mask): no pixel changes
-        // and the parent's "still clear" state survives even behind a group that was drawn on.  Nothing is emitted
+    if (opacity == 0u && op != SWFR_OP_ALPHA) {
+        // libcairo: cairo_paint_with_alpha(0) returns at once under the nine operators and under ERASE (each is bounded by the mask): no
+        // pixel changes and the parent's "still clear" state survives even behind a group that was drawn on.  Nothing is emitted
         surface_clear_ = parent_clear;
         paths_.resize(begin);
         edges_.resize(begin_edges);
         styles_.resize(begin_styles);
         return;
     }
-    if (paths_.size() == begin + 1) {                         // no path survived: a transparent group changes no pixel under any operator
+    if (op == SWFR_OP_ALPHA && (opacity == 0u || paths_.size() == begin + 1)) {
+        // ALPHA (DEST_IN) is not bounded by its mask or its source: at opacity 0, and with a group no path of which survived, the source
+        // is transparent everywhere and the parent surface becomes clear
+        paths_.resize(begin);
+        edges_.resize(begin_edges);
+        styles_.resize(begin_styles);
+        emit_clearing_group();
+        return;
+    }
+    if (paths_.size() == begin + 1) {                         // no path survived: a transparent group changes no pixel under these operators
         paths_.pop_back();
         return;
     }
     swfr_path& b = paths_[begin];
-    b.x_min = b.y_min = INT32_MAX; b.x_max = b.y_max = INT32_MIN;
-    for (size_t i = begin + 1; i < paths_.size(); ++i) {
-        const swfr_path& p = paths_[i];
-        b.x_min = std::min(b.x_min, p.x_min); b.y_min = std::min(b.y_min, p.y_min);
-        b.x_max = std::max(b.x_max, p.x_max); b.y_max = std::max(b.y_max, p.y_max);
-    }
+    group_rectangle(b, begin, paths_.size(), op);
     m = b;
     m.kind = SWFR_PATH_GROUP_END;
     m.first_edge = uint32_t(edges_.size());
     m.lerp = (op << 8) | ((255u - opacity) << 24);            // (0 < opacity < 255: libcairo's bookkeeping is the plain layer's, above)
+    paths_.push_back(m);
+}
+
+// The rectangle of a group's markers: the union of the rectangles of paths_[begin + 1 .. end) (the MASK marker among them has none yet:
+// all zero, skipped by its kind).  ALPHA ("Erase and alpha modes") takes in everything drawn on the parent surface so far:
+// the composite clears the parent wherever the group is transparent, and outside this rectangle the parent is clear already.  The
+// parent surface has then been drawn on inside the markers' rectangle, whatever the operator.
+void FrameBuilder::group_rectangle(swfr_path& b, size_t begin, size_t end, uint32_t op) {
+    PixelRect u;
+    for (size_t i = begin + 1; i < end; ++i)
+        if (paths_[i].kind != SWFR_PATH_GROUP_MASK) u.add(paths_[i].x_min, paths_[i].y_min, paths_[i].x_max, paths_[i].y_max);
+    if (op == SWFR_OP_ALPHA) u.add(drawn_);
+    b.x_min = u.x0; b.y_min = u.y0; b.x_max = u.x1; b.y_max = u.y1;
+    drawn_.add(u);
+}
+
+// An ALPHA layer whose source is transparent everywhere: an empty group over everything drawn on the surface so far, which its END
+// clears.  Nothing was drawn: nothing to clear, nothing is emitted (the surface counts as drawn on all the same: the caller)
+void FrameBuilder::emit_clearing_group() {
+    if (drawn_.empty()) return;
+    swfr_path m;
+    std::memset(&m, 0, sizeof m);
+    m.kind = SWFR_PATH_GROUP_BEGIN;
+    m.first_edge = uint32_t(edges_.size());
+    m.x_min = drawn_.x0; m.y_min = drawn_.y0; m.x_max = drawn_.x1; m.y_max = drawn_.y1;
+    paths_.push_back(m);
+    m.kind = SWFR_PATH_GROUP_END;
+    m.lerp = uint32_t(SWFR_OP_ALPHA) << 8;
     paths_.push_back(m);
 }
 
@@ -447,10 +489,11 @@ void FrameBuilder::draw_layer(const swfr_display_object& obj, int depth, uint32_
 // MASK; the mask's paths; END(operator), the three markers sharing the union of all member rectangles.  Each half is a group surface of
 // its own that starts clear; the pair takes two levels of SWFR_MAX_LAYER_DEPTH from its BEGIN on.
 void FrameBuilder::draw_masked_layer(const swfr_display_object& obj, int depth) {
-    const uint32_t op = layer_operator(obj.id);
+    const uint32_t op = layer_operator(obj.id, alpha_modes_);
     if (obj.n_children == 0) throw StatusError{SWFR_ERR_INVALID, "MaskedLayerWithoutMask"};
     if (group_depth_ + 2 > SWFR_MAX_LAYER_DEPTH) throw StatusError{SWFR_ERR_CAPACITY, "LayerDepth"};
     const bool parent_clear = surface_clear_;
+    const PixelRect parent_drawn = drawn_;
     const size_t begin = paths_.size(), begin_edges = edges_.size(), begin_styles = styles_.size();
     swfr_path m;
     std::memset(&m, 0, sizeof m);
@@ -459,6 +502,7 @@ void FrameBuilder::draw_masked_layer(const swfr_display_object& obj, int depth) 
     paths_.push_back(m);
     group_depth_ += 2;
     surface_clear_ = true;
+    drawn_ = PixelRect{};
     for (uint32_t i = 1; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);
     const bool content_clear = surface_clear_;
     const size_t mask_at = paths_.size();
@@ -466,28 +510,27 @@ void FrameBuilder::draw_masked_layer(const swfr_display_object& obj, int depth) 
     m.first_edge = uint32_t(edges_.size());
     paths_.push_back(m);
     surface_clear_ = true;
+    drawn_ = PixelRect{};
     draw(obj.children[0], depth + 1);
     const bool mask_clear = surface_clear_;
     group_depth_ -= 2;
-    // libcairo: a still-clear mask is NOTHING_TO_DO under every operator, a still-clear content under OVER and ADD only; the parent's
-    // "still clear" state survives exactly then.  Otherwise -- both drawn on, even with every pixel zero -- the parent counts as drawn
-    const bool nothing_to_do = mask_clear || (content_clear && (op == SWFR_OP_OVER || op == SWFR_OP_ADD));
+    drawn_ = parent_drawn;
+    // libcairo: a still-clear mask is NOTHING_TO_DO under every operator that is bounded by its mask, a still-clear content under OVER
+    // and ADD only; the parent's "still clear" state survives exactly then.  Otherwise -- both drawn on, even with every pixel zero --
+    // the parent counts as drawn.  ALPHA is not bounded by its mask: never nothing to do
+    const bool nothing_to_do = op != SWFR_OP_ALPHA && (mask_clear || (content_clear && (op == SWFR_OP_OVER || op == SWFR_OP_ADD)));
     surface_clear_ = parent_clear && nothing_to_do;
-    // a half without a surviving path is transparent: the product mul_un8(C, Ma) is, and changes no pixel under any operator
+    // a half without a surviving path is transparent: the product mul_un8(C, Ma) is, and changes no pixel under any operator -- but
+    // ALPHA, under which the parent surface becomes clear
     if (nothing_to_do || mask_at == begin + 1 || paths_.size() == mask_at + 1) {
         paths_.resize(begin);
         edges_.resize(begin_edges);
         styles_.resize(begin_styles);
+        if (op == SWFR_OP_ALPHA) emit_clearing_group();
         return;
     }
     swfr_path& b = paths_[begin];
-    b.x_min = b.y_min = INT32_MAX; b.x_max = b.y_max = INT32_MIN;
-    for (size_t i = begin + 1; i < paths_.size(); ++i) {
-        if (i == mask_at) continue;
-        const swfr_path& p = paths_[i];
-        b.x_min = std::min(b.x_min, p.x_min); b.y_min = std::min(b.y_min, p.y_min);
-        b.x_max = std::max(b.x_max, p.x_max); b.y_max = std::max(b.y_max, p.y_max);
-    }
+    group_rectangle(b, begin, paths_.size(), op);
     swfr_path& k = paths_[mask_at];
     k.x_min = b.x_min; k.y_min = b.y_min; k.x_max = b.x_max; k.y_max = b.y_max;
     m = b;
@@ -631,6 +674,7 @@ void FrameBuilder::emit_polygon(Polygon& poly, bool rectilinear, uint32_t style,
     if (p.n_edges) {
         for (uint32_t k = p.first_edge; k < p.first_edge + p.n_edges; ++k) edges_[k].reserved = int32_t(paths_.size());   // owning path: the device bins by it
         paths_.push_back(p);
+        drawn_.add(p.x_min, p.y_min, p.x_max, p.y_max);
     } else edges_.resize(p.first_edge);
 }
 

@@ -39,6 +39,17 @@ struct TextureVariant {
 };
 constexpr uint32_t VARIANT_BASE = 65536;         // (registered bitmap ids are below it)
 
+// A union of pixel rectangles; empty until the first is added
+struct PixelRect {
+    int32_t x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
+    bool empty() const { return x0 >= x1 || y0 >= y1; }
+    void add(int32_t ax0, int32_t ay0, int32_t ax1, int32_t ay1) {
+        if (ax0 >= ax1 || ay0 >= ay1) return;                  // (an empty rectangle holds no pixel)
+        x0 = ax0 < x0 ? ax0 : x0; y0 = ay0 < y0 ? ay0 : y0; x1 = ax1 > x1 ? ax1 : x1; y1 = ay1 > y1 ? ay1 : y1;
+    }
+    void add(const PixelRect& r) { add(r.x0, r.y0, r.x1, r.y1); }
+};
+
 // swfr_set_color_transform's check: eight values in the int16 range
 bool color_transform_valid(const swfr_color_transform& ct);
 
@@ -48,7 +59,7 @@ bool color_transform_valid(const swfr_color_transform& ct);
 // paint into a SOURCE-rule lerp -- is marked in the paths (`lerp` = 2) and settled when the pieces are joined.
 class FrameBuilder {
 public:
-    FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased = false, bool linear_pixman = false);   // aliased: SWFR_FLAG_ANTIALIAS_NONE
+    FrameBuilder(uint32_t width, uint32_t height, bool even_odd, bool aliased = false, bool linear_pixman = false, bool alpha_modes = false);   // aliased: SWFR_FLAG_ANTIALIAS_NONE
     ~FrameBuilder();
     FrameBuilder(const FrameBuilder&) = delete;
     FrameBuilder& operator=(const FrameBuilder&) = delete;
@@ -79,6 +90,8 @@ private:
     void draw(const swfr_display_object& obj, int depth);
     void draw_layer(const swfr_display_object& obj, int depth, uint32_t mode, uint32_t opacity);
     void draw_masked_layer(const swfr_display_object& obj, int depth);
+    void group_rectangle(swfr_path& b, size_t begin, size_t end, uint32_t op);   // the markers' rectangle of the group paths_[begin .. end)
+    void emit_clearing_group();                                // an ALPHA layer with a transparent source: the surface drawn so far becomes clear
     void draw_path(const StyledPath& p, bool morph, double ratio);
     void trace(const StyledPath& p, bool morph, double ratio);
     void emit_fill(const OwnedFill& f, bool morph, double ratio);
@@ -116,6 +129,8 @@ private:
     std::vector<State> stack_;
     DevicePath path_;
     Polygon poly_;
+    bool alpha_modes_;       // SWFR_FLAG_ALPHA_MODES: the blend modes erase and alpha are accepted (SWFR_OP_ERASE, SWFR_OP_ALPHA)
+    PixelRect drawn_;        // of the surface being drawn on: the union of the rectangles of the paths and group markers emitted onto it
     bool surface_clear_ = true;   // of the surface being drawn on: the frame's, or inside a SWFR_OBJECT_LAYER the innermost group's
     int group_depth_ = 0;         // open layers (at most SWFR_MAX_LAYER_DEPTH)
     std::vector<swfr_edge> edges_;

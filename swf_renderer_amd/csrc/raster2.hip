@@ -1506,11 +1506,23 @@ __device__ __forceinline__ void op_pixels4(uint32_t (&px)[4], const uint32_t (&s
 #pragma unroll
     for (int i = 0; i < 4; ++i) px[i] = op_pixel<OP>(sp[i], px[i]);
 }
+// SWFR_OP_ERASE and SWFR_OP_ALPHA (k2_tiles<7>; DESIGN.md, "Erase and alpha modes"): CAIRO_OPERATOR_DEST_OUT and DEST_IN, the destination times
+// 255 - sa, or times sa, per channel, alpha included, pixman's 0x80 rounding: mask_group's arithmetic with a factor per pixel.  At
+// s = 0 ERASE returns d; ALPHA returns 0, which is why it is a GROUP_END's operator only
+template <bool ERASE>
+__device__ __forceinline__ void alpha_pixels4(uint32_t (&px)[4], const uint32_t (&sp)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t a = ERASE ? 255u - (sp[i] >> 24) : sp[i] >> 24;
+        px[i] = mul8x2_80_24(px[i] & 0xff00ffu, a) | (mul8x2_80_24((px[i] >> 8) & 0xff00ffu, a) << 8);
+    }
+}
 // The strip's eight pixels of one lane under a blended entry, one row half (a lane's four pixels of a row) at a time: the source
 // pixels (the colour, or the bitmap / gradient sample of the pixels with coverage) times the coverage, then ONE operator's code for
 // the four -- `op` is wave-uniform, the switch is a scalar branch.  No coverage-255 shortcut and no queue: an operator needs the
 // destination at every pixel of the path.  A pixel without coverage (s = 0) is left as it is by every operator, so a row half in which
 // no lane of the wavefront has coverage (rows outside the path's rectangle, the empty rows of a partial pair) is skipped as a whole.
+template <bool ALPHA_MODES>
 __device__ __forceinline__ void blend8_op(uint32_t (&px)[8], const uint32_t (&al)[8], uint32_t op, uint32_t eflags, uint32_t solid,
                                           const swfr_style* __restrict__ styles, uint32_t style, const Sources& src, int cx0, int cy0) {
 #pragma unroll
@@ -1530,7 +1542,8 @@ __device__ __forceinline__ void blend8_op(uint32_t (&px)[8], const uint32_t (&al
                 sp[i] = mul_un8_24(c, a);
             }
         }
-        switch (op) {
+        if (ALPHA_MODES && op == SWFR_OP_ERASE) alpha_pixels4<true>(p4, sp);      // (instance 7 only; upload refuses ALPHA on a path)
+        else switch (op) {
             case SWFR_OP_MULTIPLY: op_pixels4<SWFR_OP_MULTIPLY>(p4, sp); break;
             case SWFR_OP_SCREEN: op_pixels4<SWFR_OP_SCREEN>(p4, sp); break;
             case SWFR_OP_LIGHTEN: op_pixels4<SWFR_OP_LIGHTEN>(p4, sp); break;
@@ -1560,13 +1573,16 @@ __device__ __forceinline__ uint32_t* layer_stack() {
 }
 // GROUP_END: the group's pixels `px` composited onto the strip as it was at GROUP_BEGIN (`d`), pixman's UNMASKED combiner -- the source
 // is the group pixel itself, no coverage.  A transparent group pixel leaves the destination as it is under every operator.
+template <bool ALPHA_MODES>
 __device__ __forceinline__ void composite_group(uint32_t (&px)[8], const uint32_t* __restrict__ d, uint32_t op) {
 #pragma unroll 1
     for (int h = 0; h < 2; ++h) {
         uint32_t sp[4], p4[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { sp[i] = h ? px[4 + i] : px[i]; p4[i] = d[(4 * h + i) * 64]; }
-        switch (op) {
+        if (ALPHA_MODES && op == SWFR_OP_ERASE) alpha_pixels4<true>(p4, sp);      // (instance 7 only)
+        else if (ALPHA_MODES && op == SWFR_OP_ALPHA) alpha_pixels4<false>(p4, sp);
+        else switch (op) {
             case SWFR_OP_OVER:
 #pragma unroll
                 for (int i = 0; i < 4; ++i) p4[i] = over_pixel(sp[i], p4[i]);
@@ -1808,8 +1824,8 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                             if (op & PATH_OP_GROUP_BEGIN) ++sp;     // (also a MASK: the mask's surface is a group opened above the content's)
                             else if (sp > 0) {
                                 [[maybe_unused]] bool fade_end = false;
-                                if constexpr (SHADERS == 6) {
-                                    // (instance 6 only: instance 5 stays the code it was, frames with a fade never run it)
+                                if constexpr (SHADERS >= 6) {
+                                    // (instances 6 and 7 only: instance 5 stays the code it was, frames with a fade never run it)
                                     // the END of a faded group (its entry's solid word is the fade, 255 - opacity; a masked END's is
                                     // 0): the group's pixels times the opacity, then the END.  Only where they were set aside in this
                                     // strip: otherwise px holds the parent's pixels, the group is transparent here and changes nothing
@@ -1832,7 +1848,13 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                                 }
                                 if (mat == sp) {
                                     --mat;
-                                    if (mat < SWFR_MAX_LAYER_DEPTH) composite_group(px, layer_stack() + mat * (8 * 64) + lane, op & PATH_OP_MASK);
+                                    if (mat < SWFR_MAX_LAYER_DEPTH) composite_group<SHADERS == 7>(px, layer_stack() + mat * (8 * 64) + lane, op & PATH_OP_MASK);
+                                } else if (SHADERS == 7 && mat == sp - 1 && (op & PATH_OP_MASK) == SWFR_OP_ALPHA) {
+                                    // (instance 7 only) an ALPHA END in a strip where the group -- masked or faded, the same -- was never
+                                    // set aside: the group is transparent here, and px, the pixels of the surface it is composited onto,
+                                    // become clear.  (mat < sp - 1: that surface was not set aside either -- it is clear, and px is not its)
+#pragma unroll
+                                    for (int j = 0; j < 8; ++j) px[j] = 0u;
                                 }
                                 --sp;
                             }
@@ -1995,7 +2017,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                     for (int j = 0; j < 8; ++j) px[j] = al[j] == 255u ? solid : px[j];
 #else
                     if constexpr (SHADERS >= 3) {
-                        if (op) { blend8_op(px, al, op, eflags, solid, styles, style, bitmaps, cx0, cy0); continue; }   // (wave-uniform)
+                        if (op) { blend8_op<SHADERS == 7>(px, al, op, eflags, solid, styles, style, bitmaps, cx0, cy0); continue; }   // (wave-uniform)
                     }
                     blend8<SHADERS>(px, al, eflags, solid, styles, style, bitmaps, cx0, cy0, bq, lane);
 #endif
@@ -2067,6 +2089,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAY
 // frames with a faded group (a fade in its GROUP_END): everything the mask instance does, plus the fade step at a faded group's END.  An
 // instance of its own so that frames with masked groups run the code they ran before
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAYER))) void k2_tiles_fade_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<6>(FRAME_PTR(frames, blockIdx.y), fb_to); }
+// frames with an ERASE or ALPHA operator (SWFR_FLAG_ALPHA_MODES): everything the fade instance does, plus the two combiners and the ALPHA END of a
+// strip its group does not reach.  An instance of its own: instances 0 to 6 stay the code they were (profiles/alpha_modes_kernel_resources.txt)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(T2_WAVES_LAYER))) void k2_tiles_alpha_b(const Frame2* __restrict__ frames, uint32_t* fb_to) { tiles3_body<7>(FRAME_PTR(frames, blockIdx.y), fb_to); }
 
 // ---------------------------------------------------------------------------------------------
 // launchers: `frames` is a device array of n_frames descriptors, blockIdx.y picks one
@@ -2182,7 +2207,8 @@ void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint
     // smaller frames do not fill the GPU and keep one wavefront per strip.
     uint32_t g = max_strips < grid_cap ? max_strips : grid_cap;
     if (grid_cap == ~0u && max_strips > T3_PAIR_FROM) g = (max_strips + 1u) / 2u;
-    if (shader_level >= 6) hipLaunchKernelGGL(k2_tiles_fade_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    if (shader_level >= 7) hipLaunchKernelGGL(k2_tiles_alpha_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
+    else if (shader_level == 6) hipLaunchKernelGGL(k2_tiles_fade_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 5) hipLaunchKernelGGL(k2_tiles_mask_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 4) hipLaunchKernelGGL(k2_tiles_layer_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);
     else if (shader_level == 3) hipLaunchKernelGGL(k2_tiles_blend_b, dim3(g, n_frames), dim3(64), 0, st, frames, fb_to);

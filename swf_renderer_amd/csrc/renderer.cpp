@@ -258,7 +258,7 @@ struct swfr_renderer {
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
     int bin_threads = 0;                    // SWFR_BIN_THREADS: 256 or 1024 forces that instance of k2_bin (0 = the launch plan's rule; tests and sweeps)
     uint32_t last_bin_threads = 0;          // the instance of the last launch chain (swfr_debug_copy, what = 2)
-    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups, 5 masked groups, 6 faded groups; test knob)
+    int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups, 5 masked groups, 6 faded groups, 7 erase and alpha operators; test knob)
     bool rows_wide = false;                 // SWFR_ROWS_WIDE=1: every frame with tor paths runs k2_rows_wide (test knob; aliased frames keep k2_rows_mono)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
     // the host builds one while the GPU works on the other
@@ -364,10 +364,13 @@ BandShare band_share(const swfr_renderer* r) {
 uint32_t local_tile_rows(const swfr_renderer* r) { return band_share(r).count; }
 
 // swfr_path::lerp is lerp | operator << 8: an operator is never a SOURCE lerp
-void validate_blend_fields(const swfr_path* paths, size_t n_paths) {
+// (alpha_modes, SWFR_FLAG_ALPHA_MODES: SWFR_OP_ERASE is an operator like the eight; SWFR_OP_ALPHA, which is unbounded, is a GROUP_END's only)
+void validate_blend_fields(const swfr_path* paths, size_t n_paths, bool alpha_modes) {
     for (size_t i = 0; i < n_paths; ++i) {
         const uint32_t v = paths[i].lerp;
         if (paths[i].kind >= SWFR_PATH_GROUP_BEGIN) continue;      // (validate_groups)
+        if (alpha_modes && (v >> 8) == SWFR_OP_ALPHA) throw StatusError{SWFR_ERR_INVALID, "path blend field: SWFR_OP_ALPHA is the operator of a GROUP_END only"};
+        if (alpha_modes && v == uint32_t(SWFR_OP_ERASE) << 8) continue;
         if ((v & 0xffu) > 1u || (v >> 8) > SWFR_OP_HARDLIGHT || ((v >> 8) != 0u && (v & 0xffu) != 0u))
             throw StatusError{SWFR_ERR_INVALID, "path blend field: lerp must be 0 or 1, the operator at most 8, and lerp 0 with an operator"};
     }
@@ -378,8 +381,13 @@ void validate_blend_fields(const swfr_path* paths, size_t n_paths) {
 // rectangle, the lerp bits zero, END's operator one of SWFR_OP_*, at most one MASK per group and none outside one.  Bits 24..31 of an
 // END's lerp are the group's fade (255 - opacity, swfr.h): on a group without a MASK only, and on no other path (a BEGIN's and a MASK's
 // lerp is 0 as a whole; an ordinary path's is refused by validate_blend_fields)
-void validate_groups(const swfr_path* paths, size_t n_paths) {
+// alpha_modes (SWFR_FLAG_ALPHA_MODES): END's operator may be SWFR_OP_ERASE or SWFR_OP_ALPHA, and the rectangle of an ALPHA group
+// contains the rectangle of every path drawn since the surface the group is composited onto began -- its enclosing GROUP_BEGIN (or
+// GROUP_MASK: the mask's surface), or the frame's start: the composite clears that surface wherever the group is transparent
+void validate_groups(const swfr_path* paths, size_t n_paths, bool alpha_modes) {
     auto bad = [](const char* what) { throw StatusError{SWFR_ERR_INVALID, what}; };
+    const uint32_t max_op = alpha_modes ? uint32_t(SWFR_OP_ALPHA) : uint32_t(SWFR_OP_HARDLIGHT);
+    PixelRect seen[SWFR_MAX_LAYER_DEPTH + 1];                    // per open surface: the union of the rectangles drawn onto it so far
     // which BEGINs open a masked group (a MASK belongs to the innermost group open where it stands)
     static thread_local std::vector<size_t> opened;
     static thread_local std::vector<uint8_t> masked;
@@ -415,18 +423,24 @@ void validate_groups(const swfr_path* paths, size_t n_paths) {
             if (levels + need > SWFR_MAX_LAYER_DEPTH) bad("group markers nest deeper than SWFR_MAX_LAYER_DEPTH");
             levels += need;
             open[depth++] = i;
+            seen[depth] = PixelRect{};
         } else if (p.kind == SWFR_PATH_GROUP_END) {
             if (!depth) bad("GROUP_END without a GROUP_BEGIN");
             const swfr_path& g = paths[open[--depth]];
             levels -= any_mask && masked[open[depth]] ? 2 : 1;
-            if (p.n_edges != 0u || (p.lerp & 0xffu) != 0u || ((p.lerp >> 8) & 0xffffu) > SWFR_OP_HARDLIGHT) bad("GROUP_END: n_edges and lerp bits 0..7 and 16..23 must be 0, the operator at most 8");
+            if (p.n_edges != 0u || (p.lerp & 0xffu) != 0u || ((p.lerp >> 8) & 0xffffu) > max_op) bad("GROUP_END: n_edges and lerp bits 0..7 and 16..23 must be 0, the operator at most 8");
             if ((p.lerp >> 24) != 0u && any_mask && masked[open[depth]]) bad("GROUP_END: a fade on a group with a GROUP_MASK");
             if (p.x_min != g.x_min || p.y_min != g.y_min || p.x_max != g.x_max || p.y_max != g.y_max) bad("group markers: the rectangles of GROUP_BEGIN and GROUP_END differ");
+            const PixelRect& u = seen[depth];
+            if (((p.lerp >> 8) & 0xffu) == SWFR_OP_ALPHA && !u.empty() && (u.x0 < p.x_min || u.y0 < p.y_min || u.x1 > p.x_max || u.y1 > p.y_max))
+                bad("an ALPHA group's rectangle must contain every path drawn on its parent surface before it");
+            seen[depth].add(p.x_min, p.y_min, p.x_max, p.y_max);
         } else if (p.kind == SWFR_PATH_GROUP_MASK) {
             const swfr_path& g = paths[open[depth - 1]];                  // (inside a group: checked above)
             if (p.n_edges != 0u || p.lerp != 0u) bad("GROUP_MASK: n_edges and lerp must be 0");
             if (p.x_min != g.x_min || p.y_min != g.y_min || p.x_max != g.x_max || p.y_max != g.y_max) bad("group markers: the rectangles of GROUP_BEGIN and GROUP_MASK differ");
-        }
+            seen[depth] = PixelRect{};                                   // (the mask's surface starts clear)
+        } else seen[depth].add(p.x_min, p.y_min, p.x_max, p.y_max);
     }
     if (depth) bad("GROUP_BEGIN without a GROUP_END");
 }
@@ -897,7 +911,7 @@ struct SceneLayout {
     size_t n_chunks = 0, n_slots = 0, n_rows = 0, n_bands = 0, n_strips = 0, n_strip_slots = 0, incidences = 0, cell_main = 0, cell_total = 0;
     uint32_t max_path_edges = 0;
     bool rows_wide = false;     // the row kernel's wide instance although no path has more than ROWS_STAGE edges (SWFR_ROWS_WIDE)
-    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators, 4 + isolated groups, 5 + masked groups, 6 + faded groups: picks the tile kernel's instance
+    int shader_level = 0;       // 0 solid colours only, 1 + bitmap fills, 2 + gradients, 3 + blend operators, 4 + isolated groups, 5 + masked groups, 6 + faded groups, 7 + the erase and alpha operators: picks the tile kernel's instance
     bool any_blend = false;     // some path carries an operator byte (swfr_path::lerp >> 8; lower_groups): the arena gets the path_op table
     std::vector<uint32_t> chunk_base, slot_base, inc_base, band_off;
     std::vector<uint32_t> band_span;     // per path: first tile-row | last tile-row << 16 of its rectangle (0xffff | 0 << 16: none); padded to a multiple of 16 paths
@@ -934,10 +948,12 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
     for (size_t i = 0; i < n_styles; ++i)
         L.shader_level = std::max(L.shader_level, styles[i].kind == SWFR_STYLE_SOLID ? 0 : (styles[i].kind == SWFR_STYLE_BITMAP ? 1 : 2));
     uint32_t blend_bits = 0;
-    for (size_t i = 0; i < n_paths; ++i) blend_bits |= paths[i].lerp;
+    bool alpha_ops = false;                                      // SWFR_OP_ERASE or SWFR_OP_ALPHA on a path or an END: the instance that has them
+    for (size_t i = 0; i < n_paths; ++i) { blend_bits |= paths[i].lerp; alpha_ops = alpha_ops || ((paths[i].lerp >> 8) & PATH_OP_MASK) >= uint32_t(SWFR_OP_ERASE); }
     L.any_blend = (blend_bits >> 8) != 0u;
     if (L.any_blend) L.shader_level = (blend_bits >> 8) & PATH_OP_MASKED ? 5 : ((blend_bits >> 8) & (PATH_OP_GROUP_BEGIN | PATH_OP_GROUP_END) ? 4 : 3);
     if (faded) L.shader_level = 6;                               // (lower_groups met a faded END: the instance that fades)
+    if (alpha_ops) L.shader_level = 7;                           // (instance 6 plus the two combiners and the ALPHA END rule)
     // (the test knobs: a higher instance than the frame needs -- with the style table in its full format -- and the wide row kernel)
     L.shader_level = std::max(L.shader_level, r->tiles_shaders);
     L.rows_wide = r->rows_wide;
@@ -1361,8 +1377,9 @@ void validate_linear_pixman(const swfr_renderer* r, const swfr_edge* edges, size
 // Uploads a caller-supplied scene (validated first) into scene slot `si`; see upload2.
 int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
            const swfr_style* styles, size_t n_styles, uint32_t* fb_override = nullptr) {
-    validate_groups(paths, n_paths);
-    validate_blend_fields(paths, n_paths);                       // (a malformed blend field is refused as such even by a host-only handle)
+    const bool alpha_modes = (r->cfg.flags & SWFR_FLAG_ALPHA_MODES) != 0;
+    validate_groups(paths, n_paths, alpha_modes);
+    validate_blend_fields(paths, n_paths, alpha_modes);                       // (a malformed blend field is refused as such even by a host-only handle)
     validate_gradient_extend(styles, n_styles);                  // (and so is a gradient's extend)
     validate_bitmap_filter(styles, n_styles);                    // (and a bitmap's filter)
     validate_linear_pixman(r, edges, n_edges, paths, n_paths, styles, n_styles);   // (and what a pixman-linear style cannot be drawn with)
@@ -1978,11 +1995,12 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     create_error = nullptr;
     // (aliased, every span is a piece of its own for pixman's linear ramp: validate_scene)
     if (r->mono && (r->cfg.flags & SWFR_FLAG_LINEAR_PIXMAN)) { create_error = "NotImplementedAliasedPixmanLinear"; return SWFR_ERR_NOT_IMPLEMENTED; }
-    r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono, (r->cfg.flags & SWFR_FLAG_LINEAR_PIXMAN) != 0));
+    r->builder.reset(new FrameBuilder(width, height, (r->cfg.flags & SWFR_FLAG_EVEN_ODD) != 0, r->mono, (r->cfg.flags & SWFR_FLAG_LINEAR_PIXMAN) != 0,
+                                        (r->cfg.flags & SWFR_FLAG_ALPHA_MODES) != 0));
     if (const char* fl = std::getenv("SWFR_FAST_LIMIT")) r->fast_limit = std::atoi(fl);
     if (const char* tg = std::getenv("SWFR_TILES_GRID")) r->tiles_grid = std::atoi(tg);
     if (const char* bt = std::getenv("SWFR_BIN_THREADS")) { const int v = std::atoi(bt); r->bin_threads = v == int(BIN_THREADS_SMALL) || v == int(BIN_THREADS_LARGE) ? v : 0; }
-    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 6);
+    if (const char* ts = std::getenv("SWFR_TILES_SHADERS")) r->tiles_shaders = std::min(std::max(std::atoi(ts), 0), 7);
     if (const char* rw = std::getenv("SWFR_ROWS_WIDE")) r->rows_wide = std::atoi(rw) != 0;
     if (const char* bf = std::getenv("SWFR_BATCH_FRAMES")) r->batch_frames = std::max(1, std::atoi(bf));
     if (const char* cr = std::getenv("SWFR_CHUNK_ROWS")) r->force_chunk_rows = std::atoi(cr);
