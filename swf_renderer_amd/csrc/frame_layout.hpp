@@ -18,9 +18,6 @@ struct FrameDims {
     static FrameDims of_layout(const Layout& L, size_t n_edges, size_t n_paths) {
         return FrameDims{n_edges, n_paths, L.n_slots, L.n_rows, L.n_chunks, L.n_strips, L.n_strip_slots, L.cell_total};
     }
-    // from an uploaded scene (swfr_renderer::Scene), which keeps the eight numbers under the same names
-    template <class Scene>
-    static FrameDims of_scene(const Scene& s) { return of_layout(s, s.n_edges, s.n_paths); }
 
     size_t edge_count() const { return 2 * n_edges + 1; }
     size_t band_entry_count() const { return n_slots; }

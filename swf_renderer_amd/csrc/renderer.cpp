@@ -59,15 +59,7 @@ template <class T>
 struct DevBuf {
     T* ptr = nullptr;
     size_t cap = 0;
-    bool view = false;                       // points into the handle's scene arena: not owned
-    void set_view(void* p) {
-        if (ptr && !view) (void)hipFree(ptr);
-        ptr = static_cast<T*>(p);
-        cap = 0;
-        view = true;
-    }
     void reserve(size_t n) {
-        if (view) { ptr = nullptr; view = false; cap = 0; }
         if (n <= cap) return;
         if (ptr) HIP_CHECK(hipFree(ptr));
         ptr = nullptr;
@@ -78,11 +70,25 @@ struct DevBuf {
         cap = want;
     }
     void release() {
-        if (ptr && !view) (void)hipFree(ptr);
+        if (ptr) (void)hipFree(ptr);
         ptr = nullptr;
         cap = 0;
-        view = false;
     }
+};
+
+// A scene as every host function sees it: the three arrays of the C ABI (swfr_upload_edges) or of the frame builder, or what
+// prepare_frame made of them.  A view: it owns nothing.
+struct SceneView { const swfr_edge* edges; size_t n_edges; const swfr_path* paths; size_t n_paths; const swfr_style* styles; size_t n_styles; };
+
+// What the kernels of a frame -- or of several frames per launch (blockIdx.y = frame) -- are launched with: the grids' bounds over the
+// frames of the launch (plan_bounds, merge_bounds), and the choices in which the routes differ.
+struct LaunchPlan {
+    uint32_t max_edges, max_paths, max_bands, slow_kernels;      // k2_bin; slow_kernels 1: it also prepares the queued-row kernels' work
+    uint32_t bin_threads;                                        // k2_bin's instance: BIN_THREADS_SMALL or BIN_THREADS_LARGE (bin_threads_of)
+    uint32_t max_chunks, max_path_edges; bool rows_wide;         // the row pass
+    bool run_slow; uint32_t grid_slow, grid_huge, slow_passes;   // the queued-row kernels (coincident edges, crowded rows), if launched
+    uint32_t linear_grid;                                        // k2_linear_pieces (0: not launched)
+    uint32_t max_strips, tiles_grid; int shader_level;           // the tile pass; tiles_grid ~0u: the default shape, any other value caps the wavefronts
 };
 
 // The read-only arrays of an uploaded scene live in one device allocation and are filled by one H2D copy from one pinned
@@ -179,13 +185,8 @@ struct swfr_renderer {
     // Resident rendering uses scene 0; swfr_render_batch keeps one scene per frame in flight.
     struct Scene {
         SceneArena arena;
-        size_t n_edges = 0, n_paths = 0, n_slots = 0, n_rows = 0, n_chunks = 0, cell_total = 0;   // (with the strips: what FrameDims::of_scene reads)
-        size_t n_strips = 0, n_strip_slots = 0;   // k2_tiles wavefronts / launch list slots
-        size_t n_bands = 0;
-        int shader_level = 0;
-        uint32_t linear_grid = 0;            // gradient records k2_linear_pieces looks through (0: the scene has no pixman-linear tor path)
-        uint32_t max_path_edges = 0;              // picks the row kernel's instance (edges staged in LDS per chunk)
-        bool rows_wide = false;                   // SWFR_ROWS_WIDE: k2_rows_wide whatever max_path_edges says
+        FrameDims dims;                           // what the sizes of a frame's kernel-written buffers follow from (frame_layout.hpp)
+        LaunchPlan bounds{};                      // the grids' bounds of a frame of the scene (plan_bounds); plan_of adds what a launch chooses
         Frame2 proto{};                           // the scene fields and sizes of a frame descriptor (per-frame buffers not filled in)
         Frame2* frames_dev = nullptr;            // one descriptor per frame set (contiguous, in the arena)
         uint32_t slow_passes = SLOW_PASSES;      // passes of the slow-row kernels the scene needs (known after a frame of a resident scene)
@@ -197,19 +198,10 @@ struct swfr_renderer {
     // frames rotate over n sets, so the front of frame f+1 overlaps the tail of frame f (every frame recomputes everything).
     struct FrameSet {
         hipStream_t stream = nullptr;
-        DevBuf<DevEdge> d_edges;
-        DevBuf<uint8_t> d_cls;
+        DevBuf<uint8_t> work, cls;               // the kernel-written buffers of one frame, carved like a batch group's (place_frame)
+        DevBuf<uint32_t> strip_cost;             // ... but the strip costs, which stay where they are from scene to scene (upload2)
         uint32_t* counters = nullptr;            // this set's COUNTER_WORDS of swfr_renderer::d_counters (one buffer: one copy brings all sets' back)
         DevBuf<uint32_t> d_fb;
-        DevBuf<BandEntry2> d_band2;
-        DevBuf<RowInfo2> d_rows2;
-        DevBuf<Cell> d_cells;
-        DevBuf<SlowRow> d_slow, d_huge;
-        DevBuf<uint32_t> d_path_flag, d_path_queue;
-        DevBuf<ChunkInfo> d_chunks;
-        DevBuf<BandSlot> d_band_slots;
-        DevBuf<StripDesc> d_strips;
-        DevBuf<uint32_t> d_strip_cost;
         // the kernels of one frame of the resident scene on this set, captured once per uploaded scene: a frame is then ONE
         // hipGraphLaunch for the host instead of three to twelve kernel launches
         hipGraph_t graph = nullptr;
@@ -278,7 +270,6 @@ struct swfr_renderer {
     DevBuf<uint8_t> rb_work, rb_cls;
     DevBuf<Frame2> rb_frames;
     DevBuf<uint32_t> rb_fb;
-    uint32_t rb_count = 0;
     hipEvent_t rb_ev[2] = {nullptr, nullptr};
     // swfr_read_image: pinned staging (a pageable destination costs 7x the copy time), swfr_read_image_async: the copy in flight
     uint8_t* h_image = nullptr; size_t h_image_cap = 0;
@@ -296,9 +287,7 @@ struct swfr_renderer {
             if (read_done) (void)hipEventDestroy(read_done);
             for (int k = 0; k < 4; ++k) {
                 FrameSet& x = fs[k];
-                x.d_edges.release(); x.d_cls.release(); x.d_fb.release();
-                x.d_band2.release(); x.d_rows2.release(); x.d_cells.release(); x.d_slow.release(); x.d_huge.release(); x.d_path_flag.release(); x.d_path_queue.release(); x.d_chunks.release(); x.d_band_slots.release(); x.d_strips.release();
-                x.d_strip_cost.release();
+                x.work.release(); x.cls.release(); x.strip_cost.release(); x.d_fb.release();
                 if (x.graph_exec) (void)hipGraphExecDestroy(x.graph_exec);
                 if (x.graph) (void)hipGraphDestroy(x.graph);
                 if (k > 0 && x.stream) (void)hipStreamDestroy(x.stream);
@@ -349,6 +338,12 @@ int guarded(swfr_renderer* r, F&& f) {
     }
 }
 
+// the frame builder's last frame (its edges carry their path index in `reserved`)
+SceneView builder_view(const swfr_renderer* r) {
+    const auto& e = r->builder->edges(); const auto& p = r->builder->paths(); const auto& s = r->builder->styles();
+    return SceneView{e.data(), e.size(), p.data(), p.size(), s.data(), s.size()};
+}
+
 // the handle's share of the frame's tile-rows: local tile-row l is frame tile-row first + l * stride, l < count; `padded` = the
 // share of the best-served rank (slabs are gathered at that common size)
 struct BandShare { uint32_t first, stride, count, padded; };
@@ -365,10 +360,10 @@ uint32_t local_tile_rows(const swfr_renderer* r) { return band_share(r).count; }
 
 // swfr_path::lerp is lerp | operator << 8: an operator is never a SOURCE lerp
 // (alpha_modes, SWFR_FLAG_ALPHA_MODES: SWFR_OP_ERASE is an operator like the eight; SWFR_OP_ALPHA, which is unbounded, is a GROUP_END's only)
-void validate_blend_fields(const swfr_path* paths, size_t n_paths, bool alpha_modes) {
-    for (size_t i = 0; i < n_paths; ++i) {
-        const uint32_t v = paths[i].lerp;
-        if (paths[i].kind >= SWFR_PATH_GROUP_BEGIN) continue;      // (validate_groups)
+void validate_blend_fields(const SceneView& sv, bool alpha_modes) {
+    for (size_t i = 0; i < sv.n_paths; ++i) {
+        const uint32_t v = sv.paths[i].lerp;
+        if (sv.paths[i].kind >= SWFR_PATH_GROUP_BEGIN) continue;      // (validate_groups)
         if (alpha_modes && (v >> 8) == SWFR_OP_ALPHA) throw StatusError{SWFR_ERR_INVALID, "path blend field: SWFR_OP_ALPHA is the operator of a GROUP_END only"};
         if (alpha_modes && v == uint32_t(SWFR_OP_ERASE) << 8) continue;
         if ((v & 0xffu) > 1u || (v >> 8) > SWFR_OP_HARDLIGHT || ((v >> 8) != 0u && (v & 0xffu) != 0u))
@@ -384,8 +379,9 @@ void validate_blend_fields(const swfr_path* paths, size_t n_paths, bool alpha_mo
 // alpha_modes (SWFR_FLAG_ALPHA_MODES): END's operator may be SWFR_OP_ERASE or SWFR_OP_ALPHA, and the rectangle of an ALPHA group
 // contains the rectangle of every path drawn since the surface the group is composited onto began -- its enclosing GROUP_BEGIN (or
 // GROUP_MASK: the mask's surface), or the frame's start: the composite clears that surface wherever the group is transparent
-void validate_groups(const swfr_path* paths, size_t n_paths, bool alpha_modes) {
-    auto bad = [](const char* what) { throw StatusError{SWFR_ERR_INVALID, what}; };
+void validate_groups(const SceneView& sv, bool alpha_modes) {
+    const swfr_path* const paths = sv.paths; const size_t n_paths = sv.n_paths;
+    auto bad =[](const char* what) { throw StatusError{SWFR_ERR_INVALID, what}; };
     const uint32_t max_op = alpha_modes ? uint32_t(SWFR_OP_ALPHA) : uint32_t(SWFR_OP_HARDLIGHT);
     PixelRect seen[SWFR_MAX_LAYER_DEPTH + 1];                    // per open surface: the union of the rectangles drawn onto it so far
     // which BEGINs open a masked group (a MASK belongs to the innermost group open where it stands)
@@ -458,8 +454,8 @@ void validate_groups(const swfr_path* paths, size_t n_paths, bool alpha_modes) {
 // solid word is 0, a faded END's is not: that tells the two steps apart (upload refuses a fade on a masked group).  `faded` says
 // whether the scene has such an END: layout_scene then picks k2_tiles<6>.
 // Returns false when the scene has no marker (nothing is copied).
-bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles,
-                  std::vector<swfr_edge>& out_e, std::vector<swfr_path>& out_p, std::vector<swfr_style>& out_s, bool& faded) {
+bool lower_groups(const SceneView& sv, std::vector<swfr_edge>& out_e, std::vector<swfr_path>& out_p, std::vector<swfr_style>& out_s, bool& faded) {
+    const auto [edges, n_edges, paths, n_paths, styles, n_styles] = sv;
     faded = false;
     bool any = false;
     for (size_t i = 0; i < n_paths && !any; ++i) any = paths[i].kind >= SWFR_PATH_GROUP_BEGIN;
@@ -514,9 +510,9 @@ bool lower_groups(const swfr_edge* edges, size_t n_edges, const swfr_path* paths
 }
 
 // swfr_style::extend of a gradient style: 0 pad, 1 repeat, 2 reflect; a linear gradient -- the float64 extension -- pads only
-void validate_gradient_extend(const swfr_style* styles, size_t n_styles) {
-    for (size_t i = 0; i < n_styles; ++i) {
-        const swfr_style& s = styles[i];
+void validate_gradient_extend(const SceneView& sv) {
+    for (size_t i = 0; i < sv.n_styles; ++i) {
+        const swfr_style& s = sv.styles[i];
         if (s.kind != SWFR_STYLE_RADIAL && s.kind != SWFR_STYLE_LINEAR && s.kind != SWFR_STYLE_LINEAR_PIXMAN) continue;
         if (s.extend > 2) throw StatusError{SWFR_ERR_INVALID, "gradient extend must be 0 (pad), 1 (repeat) or 2 (reflect)"};
         if (s.kind == SWFR_STYLE_LINEAR && s.extend) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread"};
@@ -524,14 +520,14 @@ void validate_gradient_extend(const swfr_style* styles, size_t n_styles) {
 }
 
 // swfr_style::filter of a bitmap style: 0 CAIRO_FILTER_GOOD, 1 CAIRO_FILTER_NEAREST; every other kind ignores the field
-void validate_bitmap_filter(const swfr_style* styles, size_t n_styles) {
-    for (size_t i = 0; i < n_styles; ++i)
-        if (styles[i].kind == SWFR_STYLE_BITMAP && styles[i].filter > 1) throw StatusError{SWFR_ERR_INVALID, "bitmap filter must be 0 (good) or 1 (nearest)"};
+void validate_bitmap_filter(const SceneView& sv) {
+    for (size_t i = 0; i < sv.n_styles; ++i)
+        if (sv.styles[i].kind == SWFR_STYLE_BITMAP && sv.styles[i].filter > 1) throw StatusError{SWFR_ERR_INVALID, "bitmap filter must be 0 (good) or 1 (nearest)"};
 }
 
 // Validate a caller-supplied scene so that no kernel can index out of bounds.
-void validate_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
-                    const swfr_style* styles, size_t n_styles) {
+void validate_scene(const swfr_renderer* r, const SceneView& sv) {
+    const auto [edges, n_edges, paths, n_paths, styles, n_styles] = sv;
     // end points within +-32768 px (2^23 in 24.8): inside that range the int64 products of the closed-form edge evaluation cannot overflow
     for (size_t i = 0; i < n_edges; ++i) {
         const swfr_edge& e = edges[i];
@@ -836,11 +832,11 @@ DevFilter good_filter(const swfr_style& st, const int rect[4], std::vector<int32
 
 // pixman's view of every bitmap / radial-gradient style of a scene (sample positions, filter tables, colour ramps)
 constexpr int LINEAR_RUN_LENGTH = 256;      // cairo-image-compositor.c, inplace_renderer_init: run_length of a linear or radial source
-// edges: the scene's (a pixman-linear box path is looked at); split: `paths` are the caller's, the device gets column blocks of them
+// sv: the scene as drawn (the edges of a pixman-linear box path are looked at); split: the device gets column blocks of its paths
 // (split_wide_paths); n_linear: how many pixman-linear styles got a table of piece origins for k2_linear_pieces to fill
-void prepare_sources(const swfr_edge* edges, bool split, size_t& n_linear, const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles, std::vector<DevFilter>& filters,
-                     std::vector<DevGradient>& gradients, std::vector<int32_t>& fparams, const std::vector<DevBitmap>& bitmap_table,
-                     const std::vector<DevBitmap>& variant_table) {
+void prepare_sources(const SceneView& sv, bool split, size_t& n_linear, std::vector<DevFilter>& filters, std::vector<DevGradient>& gradients,
+                     std::vector<int32_t>& fparams, const std::vector<DevBitmap>& bitmap_table, const std::vector<DevBitmap>& variant_table) {
+    const auto [edges, n_edges, paths, n_paths, styles, n_styles] = sv;
     filters.assign(n_styles, DevFilter{});
     // a bitmap style belongs to one drawing operation: pixman's transform is anchored at the centre of that operation's rectangle
     std::vector<int> rect(4 * n_styles, 0);
@@ -920,11 +916,12 @@ struct SceneLayout {
     std::vector<int32_t> fparams;
     size_t n_linear = 0;        // pixman-linear styles on tor paths: k2_linear_pieces runs between the row pass and the tile pass (0: not launched)
 };
-// `edges` carry their path index in `reserved`
-// src_paths: the paths as the caller drew them, when `paths` holds the column blocks of wide ones (split_wide_paths): a bitmap or
+// sv: the scene as the device gets it; its edges carry their path index in `reserved`
+// drawn: the scene as the caller drew it, when sv holds the column blocks of wide paths (split_wide_paths): a bitmap or
 // gradient style is anchored at the rectangle of its drawing operation, not of a block
-void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
-                  const swfr_style* styles, size_t n_styles, SceneLayout& L, const swfr_path* src_paths = nullptr, size_t n_src_paths = 0, bool faded = false) {
+void layout_scene(const swfr_renderer* r, const SceneView& sv, SceneLayout& L, const SceneView* drawn = nullptr, bool faded = false) {
+    const swfr_edge* const edges = sv.edges; const swfr_path* const paths = sv.paths; const swfr_style* const styles = sv.styles;
+    const size_t n_edges = sv.n_edges, n_paths = sv.n_paths, n_styles = sv.n_styles;
     L.n_bands = (r->height + TILE_H - 1) / TILE_H;
     const uint32_t tiles_x = (r->width + TILE_W - 1) / TILE_W;
     // rows per k2_rows wavefront: 64 when that already gives the GPU a thousand wavefronts, fewer (whole tile-rows) for scenes made
@@ -996,8 +993,7 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
     L.n_strips = size_t(local_tile_rows(r)) * tiles_x * STRIPS_PER_TILE;
     L.n_strip_slots = strip_slots(local_tile_rows(r), uint32_t(tiles_x * STRIPS_PER_TILE));
     L.filters.clear(); L.gradients.clear(); L.fparams.clear();
-    if (src_paths) prepare_sources(nullptr, true, L.n_linear, src_paths, n_src_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
-    else prepare_sources(edges, false, L.n_linear, paths, n_paths, styles, n_styles, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
+    prepare_sources(drawn ? *drawn : sv, drawn != nullptr, L.n_linear, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
 }
 // A tor path wider than the 13-bit column field of a cell (only possible in frames wider than 8192 px) is rasterized as several
 // paths over the SAME edges, one per block of 8192 pixel columns: the scan converter clips a path's cells to its column range
@@ -1005,7 +1001,8 @@ void layout_scene(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges
 // dropped -- so the blocks' pixels are the pixels of the whole path, and the blocks do not overlap.  (A bitmap or gradient style stays
 // anchored at the rectangle of the unsplit path: layout_scene gets the original paths for that.)  Returns false when the scene
 // has no such path; otherwise the new edge list (tagged with the owning path) and path table.
-bool split_wide_paths(const swfr_edge* edges, const swfr_path* paths, size_t n_paths, std::vector<swfr_edge>& out_e, std::vector<swfr_path>& out_p) {
+bool split_wide_paths(const SceneView& sv, std::vector<swfr_edge>& out_e, std::vector<swfr_path>& out_p) {
+    const swfr_edge* const edges = sv.edges; const swfr_path* const paths = sv.paths; const size_t n_paths = sv.n_paths;
     bool any = false;
     for (size_t i = 0; i < n_paths && !any; ++i) any = paths[i].kind == SWFR_PATH_TOR && paths[i].x_max - paths[i].x_min > MAX_PATH_WIDTH;
     if (!any) return false;
@@ -1030,17 +1027,17 @@ bool split_wide_paths(const swfr_edge* edges, const swfr_path* paths, size_t n_p
 }
 
 // bytes of the scene's read-only part in an arena (raw arrays + layout prefixes + sources), each piece padded
-size_t scene_arena_bytes(const SceneLayout& L, size_t n_edges, size_t n_paths, size_t n_styles) {
+size_t scene_arena_bytes(const SceneLayout& L, const SceneView& sv) {
     auto P = SceneArena::padded;
+    const size_t n_edges = sv.n_edges, n_paths = sv.n_paths, n_styles = sv.n_styles;
     // (a scene of solid colours only: the styles' {kind, pixel} heads, no filter records)
     return P(n_edges * sizeof(swfr_edge)) + P(n_paths * sizeof(swfr_path)) + (L.shader_level == 0 ? P(n_styles * 8) : P(n_styles * sizeof(swfr_style)) + P(n_styles * sizeof(DevFilter))) +
            P(L.fparams.size() * sizeof(int32_t)) + P(L.gradients.size() * sizeof(DevGradient)) + 3 * P((n_paths + 1) * sizeof(uint32_t)) +
            P((L.n_bands + 2) * sizeof(uint32_t)) + P(L.band_span.size() * sizeof(uint32_t)) + (L.any_blend ? P(n_paths + 64) : 0);
 }
-// pushes that part and fills the descriptor's scene fields; the edge array's host staging copy is returned (for tagging)
-swfr_edge* push_scene(SceneArena& A, const SceneLayout& L, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
-                      const swfr_style* styles, size_t n_styles, Frame2& f) {
-    swfr_edge* staged = reinterpret_cast<swfr_edge*>(A.host + A.used);
+// pushes that part and fills the descriptor's scene fields
+void push_scene(SceneArena& A, const SceneLayout& L, const SceneView& sv, Frame2& f) {
+    const auto [edges, n_edges, paths, n_paths, styles, n_styles] = sv;
     f.raw = static_cast<swfr_edge*>(A.push(edges, n_edges * sizeof(swfr_edge)));
     f.paths = static_cast<DevPath*>(A.push(paths, n_paths * sizeof(swfr_path)));
     static_assert(offsetof(swfr_style, kind) == 0 && offsetof(swfr_style, pixel) == 4, "the head of a style is {kind, pixel}");
@@ -1074,10 +1071,9 @@ swfr_edge* push_scene(SceneArena& A, const SceneLayout& L, const swfr_edge* edge
         std::memset(ops + n_paths, 0, 64);
         f.path_op = static_cast<const uint8_t*>(A.push(nullptr, n_paths + 64));
     }
-    return staged;
 }
-void fill_frame_sizes(const swfr_renderer* r, const SceneLayout& L, size_t n_edges, size_t n_paths, Frame2& f) {
-    f.n_edges = uint32_t(n_edges); f.n_paths = uint32_t(n_paths); f.n_chunks = uint32_t(L.n_chunks);
+void fill_frame_sizes(const swfr_renderer* r, const SceneLayout& L, const SceneView& sv, Frame2& f) {
+    f.n_edges = uint32_t(sv.n_edges); f.n_paths = uint32_t(sv.n_paths); f.n_chunks = uint32_t(L.n_chunks);
     f.n_bands = uint32_t(L.n_bands); f.n_strips = uint32_t(L.n_strips); f.n_strip_slots = uint32_t(L.n_strip_slots); f.cell_slice = uint32_t(L.cell_total); f.slow_cap = uint32_t(L.n_rows + 64);
     f.width = int32_t(r->width); f.height = int32_t(r->height); f.tiles_x = int32_t((r->width + TILE_W - 1) / TILE_W);
     f.fast_limit = uint32_t(std::min(std::max(r->fast_limit, 0), 16));       // (the row kernel's instance caps it at its own slots: 8 or 16)
@@ -1161,7 +1157,8 @@ CxVariant cx_make_room(swfr_renderer* r, size_t bytes) {
 // The textures a scene's colour-transformed bitmap styles sample (swfr_style::bitmap = VARIANT_BASE + k, k into the builder's
 // variants()): from the cache, or made by the texel pass queued on `st` ahead of the frame.  Fills r->variant_table for
 // prepare_sources.  pin: the scene goes to the resident slot -- its textures stay until the next scene replaces it there.
-void resolve_variants(swfr_renderer* r, const swfr_path* paths, size_t n_paths, const swfr_style* styles, size_t n_styles, hipStream_t st, bool pin) {
+void resolve_variants(swfr_renderer* r, const SceneView& sv, hipStream_t st, bool pin) {
+    const auto [edges, n_edges, paths, n_paths, styles, n_styles] = sv;
     r->variant_table.clear();
     if (pin) {
         for (const std::string& key : r->cx_pins) {
@@ -1233,24 +1230,44 @@ void resolve_variants(swfr_renderer* r, const swfr_path* paths, size_t n_paths, 
 // split into column blocks (frames that wide only), the colour-transformed textures resolved on the paths as drawn -- queued on `st`,
 // pinned for the resident slot -- and the layout worked out into L.  A step that does not apply copies nothing: the arrays returned are
 // the ones passed in, or live in S, which has to outlive their use.  The edges carry their path index in `reserved`.
-struct FrameArrays { const swfr_edge* edges; size_t n_edges; const swfr_path* paths; size_t n_paths; const swfr_style* styles; size_t n_styles; };
 struct FrameScratch { std::vector<swfr_edge> group_e, split_e; std::vector<swfr_path> group_p, split_p; std::vector<swfr_style> group_s; };
-FrameArrays prepare_frame(swfr_renderer* r, FrameArrays a, hipStream_t st, bool pin, FrameScratch& S, SceneLayout& L) {
+SceneView prepare_frame(swfr_renderer* r, SceneView a, hipStream_t st, bool pin, FrameScratch& S, SceneLayout& L) {
     bool faded = false;
-    if (lower_groups(a.edges, a.n_edges, a.paths, a.n_paths, a.styles, a.n_styles, S.group_e, S.group_p, S.group_s, faded))
-        a = FrameArrays{S.group_e.data(), S.group_e.size(), S.group_p.data(), S.group_p.size(), S.group_s.data(), S.group_s.size()};
-    const FrameArrays drawn = a;                                      // the paths as drawn: a style is anchored at their rectangles
-    const bool split = split_wide_paths(a.edges, a.paths, a.n_paths, S.split_e, S.split_p);
+    if (lower_groups(a, S.group_e, S.group_p, S.group_s, faded))
+        a = SceneView{S.group_e.data(), S.group_e.size(), S.group_p.data(), S.group_p.size(), S.group_s.data(), S.group_s.size()};
+    const SceneView drawn = a;                                        // the paths as drawn: a style is anchored at their rectangles
+    const bool split = split_wide_paths(a, S.split_e, S.split_p);
     if (split) { a.edges = S.split_e.data(); a.n_edges = S.split_e.size(); a.paths = S.split_p.data(); a.n_paths = S.split_p.size(); }
-    resolve_variants(r, drawn.paths, drawn.n_paths, a.styles, a.n_styles, st, pin);
-    layout_scene(r, a.edges, a.n_edges, a.paths, a.n_paths, a.styles, a.n_styles, L, split ? drawn.paths : nullptr, split ? drawn.n_paths : 0, faded);
+    resolve_variants(r, drawn, st, pin);
+    layout_scene(r, a, L, split ? &drawn : nullptr, faded);
     return a;
+}
+
+// The bounds part of a launch plan -- what the grids of the kernels are sized by -- of one laid-out frame: every other field is zero
+LaunchPlan plan_bounds(const SceneLayout& L, size_t n_edges, size_t n_paths) {
+    LaunchPlan p{};
+    p.max_edges = uint32_t(n_edges); p.max_paths = uint32_t(n_paths); p.max_bands = uint32_t(L.n_bands);
+    p.max_chunks = uint32_t(L.n_chunks); p.max_path_edges = L.max_path_edges; p.rows_wide = L.rows_wide;
+    p.linear_grid = L.n_linear ? uint32_t(L.gradients.size()) : 0u;
+    p.max_strips = uint32_t(L.n_strip_slots); p.shader_level = L.shader_level;
+    return p;
+}
+// ... of several frames in one launch: the maxima of theirs (the wide row kernel when one of them asks for it)
+void merge_bounds(LaunchPlan& p, const LaunchPlan& q) {
+    p.max_edges = std::max(p.max_edges, q.max_edges); p.max_paths = std::max(p.max_paths, q.max_paths); p.max_bands = std::max(p.max_bands, q.max_bands);
+    p.max_chunks = std::max(p.max_chunks, q.max_chunks); p.max_path_edges = std::max(p.max_path_edges, q.max_path_edges); p.rows_wide = p.rows_wide || q.rows_wide;
+    p.linear_grid = std::max(p.linear_grid, q.linear_grid); p.max_strips = std::max(p.max_strips, q.max_strips); p.shader_level = std::max(p.shader_level, q.shader_level);
+}
+// Points a frame's descriptor at its share of a work and a cls allocation (frame_layout.hpp) and moves w and c on to the next frame's
+void place_frame(Frame2& f, const FrameDims& d, size_t tiles_x, uint8_t*& w, uint8_t*& c) {
+    w = carve_frame(f, d, w);
+    set_cls_region(f, d, tiles_x, c);
+    c += pad256(cls_region_bytes(d, tiles_x));
 }
 
 // Uploads a scene -- the raw edge list, the paths and the styles, plus the layout above -- and sizes the buffers the
 // kernels write.
-int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
-            const swfr_style* styles, size_t n_styles, uint32_t* fb_override, bool edges_tagged) {
+int upload2(swfr_renderer* r, int si, bool all_sets, SceneView sv, uint32_t* fb_override, bool edges_tagged) {
     swfr_renderer::Scene& sc = r->scn[si];
     if (si == 0) r->scene_ready = false;
     if (r->async_used) {
@@ -1266,36 +1283,33 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
     const uint32_t tiles_x = (r->width + TILE_W - 1) / TILE_W;
     std::vector<swfr_edge> tagged;
     if (!edges_tagged) {
-        tagged.assign(edges, edges + n_edges);
-        for (size_t i = 0; i < n_paths; ++i)
-            for (uint32_t k = 0; k < paths[i].n_edges; ++k) tagged[paths[i].first_edge + k].reserved = int32_t(i);
+        tagged.assign(sv.edges, sv.edges + sv.n_edges);
+        for (size_t i = 0; i < sv.n_paths; ++i)
+            for (uint32_t k = 0; k < sv.paths[i].n_edges; ++k) tagged[sv.paths[i].first_edge + k].reserved = int32_t(i);
         // an aliased handle paints a caller's boxes as the frame builder makes them: rounded to whole pixels (a box that rounds away covers nothing)
         if (r->mono)
-            for (size_t i = 0; i < n_paths; ++i)
-                if (paths[i].kind == SWFR_PATH_BOXES)
-                    for (uint32_t k = 0; k < paths[i].n_edges; ++k) round_box_to_pixels(tagged[paths[i].first_edge + k]);
-        edges = tagged.data();
+            for (size_t i = 0; i < sv.n_paths; ++i)
+                if (sv.paths[i].kind == SWFR_PATH_BOXES)
+                    for (uint32_t k = 0; k < sv.paths[i].n_edges; ++k) round_box_to_pixels(tagged[sv.paths[i].first_edge + k]);
+        sv.edges = tagged.data();
     }
     static thread_local FrameScratch scratch;              // (vectors keep their capacity from frame to frame)
     static thread_local SceneLayout L;
-    const FrameArrays a = prepare_frame(r, FrameArrays{edges, n_edges, paths, n_paths, styles, n_styles}, up_stream, si == 0, scratch, L);
-    sc.n_edges = a.n_edges; sc.n_paths = a.n_paths; sc.n_chunks = L.n_chunks; sc.n_bands = L.n_bands; sc.n_rows = L.n_rows; sc.n_slots = L.n_slots; sc.cell_total = L.cell_total;
-    sc.n_strips = L.n_strips; sc.n_strip_slots = L.n_strip_slots; sc.max_path_edges = L.max_path_edges; sc.rows_wide = L.rows_wide;
-    sc.shader_level = L.shader_level; sc.linear_grid = L.n_linear ? uint32_t(L.gradients.size()) : 0u;
+    const SceneView a = prepare_frame(r, sv, up_stream, si == 0, scratch, L);
+    const FrameDims dims = sc.dims = FrameDims::of_layout(L, a.n_edges, a.n_paths);
+    sc.bounds = plan_bounds(L, a.n_edges, a.n_paths);
     SceneArena& A = sc.arena;
-    A.begin(scene_arena_bytes(L, a.n_edges, a.n_paths, a.n_styles) + SceneArena::padded(4 * sizeof(Frame2)) + 4096);
+    A.begin(scene_arena_bytes(L, a) + SceneArena::padded(4 * sizeof(Frame2)) + 4096);
     Frame2 proto;
     std::memset(&proto, 0, sizeof proto);
-    push_scene(A, L, a.edges, a.n_edges, a.paths, a.n_paths, a.styles, a.n_styles, proto);
-    fill_frame_sizes(r, L, a.n_edges, a.n_paths, proto);
+    push_scene(A, L, a, proto);
+    fill_frame_sizes(r, L, a, proto);
     if (r->bitmap_table_dirty) r->d_bitmap_table.reserve(r->bitmap_table.size());     // (filled below; the address is what the descriptor needs)
     proto.src.bitmaps = r->d_bitmap_table.ptr;
     sc.proto = proto;
-    // ---- per-frame (kernel-written) buffers: grow-only allocations, one per buffer of the list in frame_layout.hpp, and the sets' descriptors
-    const FrameDims dims = FrameDims::of_layout(L, a.n_edges, a.n_paths);
+    // ---- per-frame (kernel-written) buffers: two grow-only allocations per frame set, carved by the list in frame_layout.hpp, and the sets' descriptors
     const size_t cls_bytes = cls_region_bytes(dims, tiles_x);
     const int n_sets = std::max(1, std::min(r->in_flight, 4));
-    auto hold = [](auto& buf, auto*& field, size_t n) { buf.reserve(n); field = buf.ptr; };
     Frame2 fr[4];
     std::memset(fr, 0, sizeof fr);
     for (int k = 0; k < 4; ++k) {
@@ -1304,19 +1318,20 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
         Frame2& f = fr[k];
         f = proto;
         if (!x.stream) HIP_CHECK(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
-        hold(x.d_edges, f.edges, dims.edge_count()); hold(x.d_band2, f.band_list, dims.band_entry_count()); hold(x.d_rows2, f.rows, dims.row_count());
-        hold(x.d_cells, f.cells, dims.cell_count()); hold(x.d_slow, f.slow, dims.slow_count()); hold(x.d_huge, f.huge, dims.slow_count());
-        hold(x.d_path_flag, f.path_flag, dims.path_word_count()); hold(x.d_path_queue, f.path_queue, dims.path_word_count());
-        hold(x.d_chunks, f.chunks, dims.chunk_count()); hold(x.d_band_slots, f.band_slots, dims.band_slot_count()); hold(x.d_strips, f.strips, dims.strip_count());
-        const uint32_t* cost_before = x.d_strip_cost.ptr;
-        hold(x.d_strip_cost, f.strip_cost, dims.strip_cost_count());                    // (zero between frames: the ordering workgroup clears what it has read)
-        if (f.strip_cost != cost_before) HIP_CHECK(hipMemsetAsync(f.strip_cost, 0, x.d_strip_cost.cap * sizeof(uint32_t), up_stream));
+        x.work.reserve(frame_work_bytes(dims)); x.cls.reserve(cls_bytes);
+        uint8_t *w = x.work.ptr, *c = x.cls.ptr;
+        place_frame(f, dims, tiles_x, w, c);
+        // two buffers keep places of their own instead of the carved ones.  The strip costs: the next scene's sizes would move them, and
+        // the costs one frame leaves order the strips of the next whatever scene that is (zero between frames: the ordering workgroup
+        // clears what it has read; cleared here on fresh memory only).  The counters: one copy brings all sets' back
+        const uint32_t* cost_before = x.strip_cost.ptr;
+        x.strip_cost.reserve(dims.strip_cost_count());
+        if (x.strip_cost.ptr != cost_before) HIP_CHECK(hipMemsetAsync(x.strip_cost.ptr, 0, x.strip_cost.cap * sizeof(uint32_t), up_stream));
+        f.strip_cost = x.strip_cost.ptr;
         r->d_counters.reserve(4 * COUNTER_WORDS);
         f.counters = x.counters = r->d_counters.ptr + size_t(k) * COUNTER_WORDS;
-        x.d_cls.reserve(cls_bytes);
         // class bytes outside the paths' rectangles are never written by a kernel: cleared once per uploaded scene
-        HIP_CHECK(hipMemsetAsync(x.d_cls.ptr, 0, cls_bytes, up_stream));
-        set_cls_region(f, dims, tiles_x, x.d_cls.ptr);
+        HIP_CHECK(hipMemsetAsync(x.cls.ptr, 0, cls_bytes, up_stream));
         if (!x.d_fb.ptr && !r->n_targets) {                                             // (a handle with caller targets never renders into a buffer of its own)
             x.d_fb.reserve(size_t(r->width) * r->height);
             HIP_CHECK(hipMemsetAsync(x.d_fb.ptr, 0, size_t(r->width) * r->height * 4, up_stream));
@@ -1344,8 +1359,8 @@ int upload2(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, siz
 
 // A scene with a SWFR_STYLE_LINEAR_PIXMAN style: everything such a style is refused for, by a host-only handle too -- an unknown kind
 // beside it, an aliased handle, c0 == c1, and what prepare_sources / linear_of find (pieces, range, row step), by a dry run of theirs.
-void validate_linear_pixman(const swfr_renderer* r, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
-                            const swfr_style* styles, size_t n_styles) {
+void validate_linear_pixman(const swfr_renderer* r, const SceneView& sv) {
+    const auto [edges, n_edges, paths, n_paths, styles, n_styles] = sv;
     bool any = false;
     for (size_t i = 0; i < n_styles; ++i) any = any || styles[i].kind >= SWFR_STYLE_LINEAR_PIXMAN;
     if (!any) return;
@@ -1371,33 +1386,22 @@ void validate_linear_pixman(const swfr_renderer* r, const swfr_edge* edges, size
     for (swfr_style& s : only) if (s.kind != SWFR_STYLE_LINEAR_PIXMAN) { s.kind = SWFR_STYLE_SOLID; }
     std::vector<swfr_path> drawn;                                     // (a group marker has no style of its own before lower_groups)
     for (size_t i = 0; i < n_paths; ++i) if (paths[i].kind < SWFR_PATH_GROUP_BEGIN) drawn.push_back(paths[i]);
-    prepare_sources(edges, false, n_linear, drawn.data(), drawn.size(), only.data(), n_styles, filters, gradients, fparams, r->bitmap_table, r->variant_table);
+    prepare_sources(SceneView{edges, n_edges, drawn.data(), drawn.size(), only.data(), n_styles}, false, n_linear, filters, gradients, fparams, r->bitmap_table, r->variant_table);
 }
 
-// Uploads a caller-supplied scene (validated first) into scene slot `si`; see upload2.
-int upload(swfr_renderer* r, int si, bool all_sets, const swfr_edge* edges, size_t n_edges, const swfr_path* paths, size_t n_paths,
-           const swfr_style* styles, size_t n_styles, uint32_t* fb_override = nullptr) {
+// Everything a caller-supplied scene is refused for before it is uploaded (swfr_upload_edges).  The order is behaviour: it decides which
+// refusal a scene with several faults gets, and what a host-only handle still names before it refuses to rasterize
+void validate_upload(const swfr_renderer* r, const SceneView& sv) {
     const bool alpha_modes = (r->cfg.flags & SWFR_FLAG_ALPHA_MODES) != 0;
-    validate_groups(paths, n_paths, alpha_modes);
-    validate_blend_fields(paths, n_paths, alpha_modes);                       // (a malformed blend field is refused as such even by a host-only handle)
-    validate_gradient_extend(styles, n_styles);                  // (and so is a gradient's extend)
-    validate_bitmap_filter(styles, n_styles);                    // (and a bitmap's filter)
-    validate_linear_pixman(r, edges, n_edges, paths, n_paths, styles, n_styles);   // (and what a pixman-linear style cannot be drawn with)
-    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
-    validate_scene(r, edges, n_edges, paths, n_paths, styles, n_styles);
-    return upload2(r, si, all_sets, edges, n_edges, paths, n_paths, styles, n_styles, fb_override, false);
+    validate_groups(sv, alpha_modes);
+    validate_blend_fields(sv, alpha_modes);                      // (a malformed blend field is refused as such even by a host-only handle)
+    validate_gradient_extend(sv);                                // (and so is a gradient's extend)
+    validate_bitmap_filter(sv);                                  // (and a bitmap's filter)
+    validate_linear_pixman(r, sv);                               // (and what a pixman-linear style cannot be drawn with)
+    if (!r->has_device) throw StatusError{SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize"};
+    validate_scene(r, sv);
 }
 
-// What the kernels of a frame -- or of several frames per launch (blockIdx.y = frame) -- are launched with: the grids' bounds over the
-// frames of the launch, and the choices in which the routes differ.
-struct LaunchPlan {
-    uint32_t max_edges, max_paths, max_bands, slow_kernels;      // k2_bin; slow_kernels 1: it also prepares the queued-row kernels' work
-    uint32_t bin_threads;                                        // k2_bin's instance: BIN_THREADS_SMALL or BIN_THREADS_LARGE (bin_threads_of)
-    uint32_t max_chunks, max_path_edges; bool rows_wide;         // the row pass
-    bool run_slow; uint32_t grid_slow, grid_huge, slow_passes;   // the queued-row kernels (coincident edges, crowded rows), if launched
-    uint32_t linear_grid;                                        // k2_linear_pieces (0: not launched)
-    uint32_t max_strips, tiles_grid; int shader_level;           // the tile pass; tiles_grid ~0u: the default shape, any other value caps the wavefronts
-};
 // THE launch chain: bin -> rows -> queued rows -> linear pieces -> tiles.  events (optional): four, recorded around the three passes.
 // fb_to: the one frame's own target instead of its descriptor's (swfr_render_resident_async_to), else nullptr.
 void launch_chain(swfr_renderer* r, hipStream_t st, const Frame2* frames, uint32_t n_frames, const LaunchPlan& p, hipEvent_t* events, uint32_t* fb_to) {
@@ -1423,14 +1427,11 @@ uint32_t bin_threads_of(const swfr_renderer* r, uint32_t max_paths, bool overlap
 }
 // The plan of the resident scene's frames, as a frame launched on its own frame set gets it; the routes that differ say so where they call.
 LaunchPlan plan_of(const swfr_renderer* r, const swfr_renderer::Scene& sc) {
-    LaunchPlan p;
-    p.max_edges = uint32_t(sc.n_edges); p.max_paths = uint32_t(sc.n_paths); p.max_bands = uint32_t(sc.n_bands);
-    p.run_slow = sc.n_chunks && sc.slow_state != 1;            // the queued rows: skipped once a frame of this resident scene has shown there are none
+    LaunchPlan p = sc.bounds;
+    p.run_slow = p.max_chunks && sc.slow_state != 1;           // the queued rows: skipped once a frame of this resident scene has shown there are none
     p.slow_kernels = p.run_slow ? 1u : 0u;
     p.bin_threads = bin_threads_of(r, p.max_paths, true);
-    p.max_chunks = uint32_t(sc.n_chunks); p.max_path_edges = sc.max_path_edges; p.rows_wide = sc.rows_wide;
     p.grid_slow = 1024u; p.grid_huge = sc.slow_state == 2 ? 0u : 256u; p.slow_passes = sc.slow_passes;
-    p.linear_grid = sc.linear_grid; p.max_strips = uint32_t(sc.n_strip_slots); p.shader_level = sc.shader_level;
     p.tiles_grid = r->tiles_grid > 0 ? uint32_t(r->tiles_grid) : ~0u;
     return p;
 }
@@ -1519,8 +1520,7 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
     if (frames == 0) frames = 1;
     if (frames > 1 && r->scene_from_builder && r->sets_ready < uint32_t(std::max(1, std::min(r->in_flight, 4)))) {
         // swfr_render prepared one frame set for its one frame; several frames of the same scene rotate over all of them
-        const auto& e = r->builder->edges(); const auto& p = r->builder->paths(); const auto& st = r->builder->styles();
-        const int rc = upload2(r, 0, true, e.data(), e.size(), p.data(), p.size(), st.data(), st.size(), nullptr, true);
+        const int rc = upload2(r, 0, true, builder_view(r), nullptr, true);
         if (rc != SWFR_OK) return rc;
     }
     if (frames > 1 && r->use_graphs && !r->scn[0].slow_verified) {
@@ -1628,7 +1628,7 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
     for (uint32_t k = 1; k < used_sets; ++k)               // (set 0's counts, every set's error and limit flags)
         for (uint32_t w : {uint32_t(C2_ERROR), uint32_t(C2_TIE_PAIRTEST_SKIPPED), uint32_t(C2_TIE_SORT_OVERFLOW), uint32_t(C2_TIE_DEPTH)})
             counters[w] |= r->h_counters[k * COUNTER_WORDS + w];
-    r->timing = swfr_timing{total_ms, setup_ms, rows_ms, tiles_ms, frames, sc.n_edges, sc.n_paths, sc.n_rows, 0, timed_frames};
+    r->timing = swfr_timing{total_ms, setup_ms, rows_ms, tiles_ms, frames, sc.dims.n_edges, sc.dims.n_paths, sc.dims.n_rows, 0, timed_frames};
     r->fb_valid = true;
     {
         uint32_t slow = 0, huge = 0;
@@ -1666,7 +1666,7 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
 // alternate: the host builds group g + 1 (scene walk, flattening, layout) while the GPU rasterizes group g.
 int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* device_dst, size_t frame_stride) {
     // a frame of the group being built: the builder's arrays (the builder goes on to the next frame), what prepare_frame made of them
-    struct FrameData { std::vector<swfr_edge> e; std::vector<swfr_path> p; std::vector<swfr_style> s; FrameScratch scratch; SceneLayout L; FrameArrays a; FrameDims dims; };
+    struct FrameData { std::vector<swfr_edge> e; std::vector<swfr_path> p; std::vector<swfr_style> s; FrameScratch scratch; SceneLayout L; SceneView a; FrameDims dims; };
     static thread_local std::vector<FrameData> fd;
     // frames per group: SWFR_BATCH_FRAMES at most; a call with fewer frames is still cut into four groups, so that building group
     // g + 1 overlaps rasterizing group g, as long as a group keeps enough pixels (32 Mpx: four 4K frames, thirty-two 1024x1024 ones)
@@ -1714,17 +1714,13 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             for (uint32_t k = 0; k < cnt; ++k) {
                 FrameData& F = fd[k];
                 r->builder->build(stages[first + k]);
+                validate_scene(r, builder_view(r));
                 F.e = r->builder->edges(); F.p = r->builder->paths(); F.s = r->builder->styles();
-                validate_scene(r, F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size());
-                F.a = prepare_frame(r, FrameArrays{F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size()}, G.stream, false, F.scratch, F.L);
-                const SceneLayout& L = F.L;
-                F.dims = FrameDims::of_layout(L, F.a.n_edges, F.a.n_paths);
-                arena_bytes += scene_arena_bytes(L, F.a.n_edges, F.a.n_paths, F.a.n_styles);
+                F.a = prepare_frame(r, SceneView{F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size()}, G.stream, false, F.scratch, F.L);
+                F.dims = FrameDims::of_layout(F.L, F.a.n_edges, F.a.n_paths);
+                arena_bytes += scene_arena_bytes(F.L, F.a);
                 work_bytes += frame_work_bytes(F.dims); cls_bytes += pad256(cls_region_bytes(F.dims, tiles_x));
-                plan.max_edges = std::max(plan.max_edges, uint32_t(F.a.n_edges)); plan.max_paths = std::max(plan.max_paths, uint32_t(F.a.n_paths)); plan.max_bands = std::max(plan.max_bands, uint32_t(L.n_bands));
-                plan.max_chunks = std::max(plan.max_chunks, uint32_t(L.n_chunks)); plan.max_path_edges = std::max(plan.max_path_edges, L.max_path_edges); plan.rows_wide = plan.rows_wide || L.rows_wide;
-                if (L.n_linear) plan.linear_grid = std::max(plan.linear_grid, uint32_t(L.gradients.size()));
-                plan.max_strips = std::max(plan.max_strips, uint32_t(L.n_strip_slots)); plan.shader_level = std::max(plan.shader_level, L.shader_level);
+                merge_bounds(plan, plan_bounds(F.L, F.a.n_edges, F.a.n_paths));
             }
             plan.run_slow = plan.max_chunks != 0;
             plan.bin_threads = bin_threads_of(r, plan.max_paths, true);     // (over the frames of the launch; the other group's launch runs beside it)
@@ -1749,11 +1745,10 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
                 const FrameData& F = fd[k];
                 Frame2& f = fr[k];
                 std::memset(&f, 0, sizeof f);
-                push_scene(G.arena, F.L, F.a.edges, F.a.n_edges, F.a.paths, F.a.n_paths, F.a.styles, F.a.n_styles, f);
-                fill_frame_sizes(r, F.L, F.a.n_edges, F.a.n_paths, f);
+                push_scene(G.arena, F.L, F.a, f);
+                fill_frame_sizes(r, F.L, F.a, f);
                 f.src.bitmaps = r->d_bitmap_table.ptr;
-                w = carve_frame(f, F.dims, w);
-                set_cls_region(f, F.dims, tiles_x, c); c += pad256(cls_region_bytes(F.dims, tiles_x));
+                place_frame(f, F.dims, tiles_x, w, c);
                 f.strip_order = 0;                             // (a frame's buffers held another frame before: no cost history to order by)
                 f.fb = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(device_dst) + size_t(first + k) * frame_stride);
             }
@@ -1807,7 +1802,7 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     const swfr_renderer::Scene& sc = r->scn[0];
     const uint32_t B = per_launch, tiles_x = (r->width + TILE_W - 1) / TILE_W;
     const size_t n_px = size_t(r->width) * r->height;
-    const FrameDims dims = FrameDims::of_scene(sc);
+    const FrameDims& dims = sc.dims;
     const size_t work_one = frame_work_bytes(dims), cls_one = pad256(cls_region_bytes(dims, tiles_x));
     const hipStream_t st = r->stream;
     r->fb_valid = false;                                       // (fb_cur may point into a buffer the next lines reallocate; set again below)
@@ -1819,12 +1814,11 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     HIP_CHECK(hipMemsetAsync(r->rb_work.ptr, 0, work_one * B, st));           // (strip costs start at zero; class bytes outside the paths' rectangles)
     HIP_CHECK(hipMemsetAsync(r->rb_cls.ptr, 0, cls_one * B, st));
     std::vector<Frame2> fr(B);
-    uint8_t* w = r->rb_work.ptr;
+    uint8_t *w = r->rb_work.ptr, *c = r->rb_cls.ptr;
     for (uint32_t k = 0; k < B; ++k) {
         Frame2& f = fr[k];
         f = sc.proto;
-        w = carve_frame(f, dims, w);
-        set_cls_region(f, dims, tiles_x, r->rb_cls.ptr + cls_one * k);
+        place_frame(f, dims, tiles_x, w, c);
         f.fb = r->rb_fb.ptr + n_px * k;
     }
     HIP_CHECK(hipMemcpyAsync(r->rb_frames.ptr, fr.data(), B * sizeof(Frame2), hipMemcpyHostToDevice, st));
@@ -1846,7 +1840,6 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     float ms = 0;
     HIP_CHECK(hipEventElapsedTime(&ms, r->rb_ev[0], r->rb_ev[1]));
     if (ms_out) *ms_out = ms;
-    r->rb_count = B;
     r->fb_cur = fr[B - 1].fb;
     r->fb_valid = true;
     int rc = SWFR_OK;
@@ -1873,12 +1866,9 @@ int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* d
         for (uint32_t i = 0; i < n; ++i) {
             const int k = int(i % n_sets);
             r->builder->build(stages[i]);
-            const auto& e = r->builder->edges();
-            const auto& p = r->builder->paths();
-            const auto& s = r->builder->styles();
             uint32_t* fb_dst = device_dst ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(device_dst) + size_t(i) * frame_stride) : nullptr;
-            validate_scene(r, e.data(), e.size(), p.data(), p.size(), s.data(), s.size());
-            rc = upload2(r, k, false, e.data(), e.size(), p.data(), p.size(), s.data(), s.size(), fb_dst, true);   // (the builder's edges carry their path index)
+            validate_scene(r, builder_view(r));
+            rc = upload2(r, k, false, builder_view(r), fb_dst, true);   // (the builder's edges carry their path index)
             if (rc != SWFR_OK) break;
             // nothing renders a frame of a batch again: every frame launches all the queued-row kernels (upload2 seeds set 0 with what
             // the previous scene needed, a guess only render_resident checks against the frame's counters)
@@ -1952,7 +1942,7 @@ int render_resident_async(swfr_renderer* r, void* block_target, uint32_t* out_se
     if (block_target && bs.stride != 1) return fail(r, SWFR_ERR_INVALID, "a block target needs a handle that owns one contiguous block of tile-rows");
     return guarded(r, [&]() {
         uint32_t n_sets = 1;
-        while (n_sets < uint32_t(std::min(r->in_flight, 4)) && n_sets < r->sets_ready && r->fs[n_sets].stream && r->fs[n_sets].d_cells.ptr) ++n_sets;
+        while (n_sets < uint32_t(std::min(r->in_flight, 4)) && n_sets < r->sets_ready && r->fs[n_sets].stream && r->fs[n_sets].work.ptr) ++n_sets;
         const uint32_t k = r->async_next++ % n_sets;
         r->async_used |= 1u << k;
         if (!r->scn[0].slow_verified) { r->scn[0].slow_state = 0; r->scn[0].slow_passes = SLOW_PASSES; }   // (nothing checks an async frame's queues: launch everything unless a blocking frame of this scene has shown what it needs)
@@ -2206,7 +2196,11 @@ int swfr_upload_edges(swfr_renderer* r, const swfr_edge* edges, size_t n_edges, 
                       const swfr_style* styles, size_t n_styles) {
     if (!r || (n_edges && !edges) || (n_paths && !paths) || (n_styles && !styles)) return fail(r, SWFR_ERR_INVALID, "null argument");
     ++r->cx_epoch;
-    return guarded(r, [&]() { return upload(r, 0, true, edges, n_edges, paths, n_paths, styles, n_styles); });
+    return guarded(r, [&]() {
+        const SceneView sv{edges, n_edges, paths, n_paths, styles, n_styles};
+        validate_upload(r, sv);
+        return upload2(r, 0, true, sv, nullptr, false);
+    });
 }
 
 int swfr_render_resident(swfr_renderer* r, uint32_t frames) {
@@ -2231,12 +2225,9 @@ int swfr_render(swfr_renderer* r, const swfr_stage* stage) {
         const auto t0 = clk::now();
         r->builder->build(*stage);
         const auto t1 = clk::now();
-        const auto& e = r->builder->edges();
-        const auto& p = r->builder->paths();
-        const auto& s = r->builder->styles();
-        validate_scene(r, e.data(), e.size(), p.data(), p.size(), s.data(), s.size());
+        validate_scene(r, builder_view(r));
         // (one frame set: this frame is rendered alone; the builder's edges carry their path index)
-        int rc = upload2(r, 0, false, e.data(), e.size(), p.data(), p.size(), s.data(), s.size(), nullptr, true);
+        int rc = upload2(r, 0, false, builder_view(r), nullptr, true);
         const auto t2 = clk::now();
         if (rc != SWFR_OK) return rc;
         rc = render_resident(r, 1);
@@ -2461,11 +2452,14 @@ long swfr_debug_copy(swfr_renderer* r, int what, void* dst, size_t bytes) {
         std::memcpy(dst, &r->last_bin_threads, sizeof(uint32_t));
         return long(sizeof(uint32_t));
     }
-    const swfr_renderer::FrameSet& F = r->fs[0];
-    const void* src = what == 0 ? static_cast<const void*>(F.d_rows2.ptr) : static_cast<const void*>(F.d_cells.ptr);
-    const size_t have = what == 0 ? F.d_rows2.cap * sizeof(RowInfo2) : F.d_cells.cap * sizeof(Cell);
-    const size_t n = std::min(bytes, have);
-    if (!src || !n) return 0;
+    if (!r->fs[0].work.ptr) return 0;
+    // frame set 0's descriptor as upload2 carved it (scene slot 0's sizes), and the bytes its row headers and cells take
+    const FrameDims& d = r->scn[0].dims;
+    Frame2 f{};
+    carve_frame(f, d, r->fs[0].work.ptr);
+    const void* src = what == 0 ? static_cast<const void*>(f.rows) : static_cast<const void*>(f.cells);
+    const size_t n = std::min(bytes, what == 0 ? d.row_count() * sizeof(RowInfo2) : d.cell_count() * sizeof(Cell));
+    if (!n) return 0;
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return -long(SWFR_ERR_DEVICE);
     return long(n);
 }
