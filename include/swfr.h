@@ -145,7 +145,7 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
        SWFR_OBJECT_COLOR_TRANSFORM = 3   /* a container (matrix + children) whose `id` names a colour-transform slot (swfr_set_color_transform):
                                             the slot's value at the time of the render call applies to everything below it.  Beyond the
                                             reference, whose display objects carry a matrix and a ratio only */,
-       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10, 12 and 14 and above) */
+       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10, 12, 14, 15 and 17 and above) */
        SWFR_OBJECT_BLEND_MODE = 5,       /* a container (matrix + children) whose `id` is an SWF blend-mode number (SWFR_BLEND_*): every path
                                             drawn below it is composited, each on its own, with the mode's Cairo operator -- what
                                             CanvasRenderer would do if it set ctx.globalCompositeOperation before drawing the object.  It
@@ -183,8 +183,31 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
                                             mode an SWF blend-mode number, accepted exactly as SWFR_OBJECT_LAYER accepts it, the opacity
                                             0..255; id >= 0x10000: SWFR_ERR_INVALID.  Opacity 255 is SWFR_OBJECT_LAYER byte for byte,
                                             opacity 0 draws nothing.  One level of SWFR_MAX_LAYER_DEPTH; nests with the other two layer
-                                            types.  DESIGN.md, "Layer opacity" */ };
+                                            types.  DESIGN.md, "Layer opacity" */,
+       /* 14 and 15 are not display-object types */
+       SWFR_OBJECT_BLURRED_LAYER = 16    /* a blurred layer: a container (matrix + children) whose children are drawn onto a transparent
+                                            surface of the frame's size, which is box-blurred and then composited onto the parent as ONE
+                                            layer -- cairo_push_group; the children; cairo_pop_group; the blur on the group's surface;
+                                            cairo_set_source; cairo_set_operator; cairo_paint.  `id` is mode | blur_x << 8 | blur_y << 16 |
+                                            passes << 24: the mode an SWF blend-mode number, accepted exactly as SWFR_OBJECT_LAYER accepts
+                                            it; blur_x, blur_y 0..255 the box widths in device pixels (0 and 1: that axis is left alone),
+                                            not scaled by any matrix; passes 1..15 (0 or more: SWFR_ERR_INVALID, "InvalidBlur").  The blur
+                                            (blur_x, blur_y, passes) is `passes` times a horizontal pass of width max(1, blur_x), then a
+                                            vertical pass of width max(1, blur_y); one pass of width w is what pixman 0.40 computes for a
+                                            PIXMAN_FILTER_CONVOLUTION of w equal taps (swfr_blur_bitmap).  What the children draw outside the
+                                            frame is gone before the blur.  The children are built into a sub-frame of their own
+                                            (swfr_built_layer) which swfr_render renders, captures and blurs on the device before the
+                                            parent frame; in the parent the object is one SWFR_PATH_BOXES path over the whole frame with a
+                                            nearest-filtered SWFR_STYLE_BITMAP style naming texture SWFR_BLUR_BASE + k.  A blurred layer
+                                            below another: SWFR_ERR_NOT_IMPLEMENTED, "NestedBlur"; more than SWFR_MAX_BLUR_LAYERS in a
+                                            frame: SWFR_ERR_CAPACITY, "BlurLayers".  The other layer types may sit inside and around it; the
+                                            sub-frame counts its own SWFR_MAX_LAYER_DEPTH.  Only swfr_render draws it: swfr_render_batch,
+                                            swfr_render_sequence and swfr_render_sequence_readback answer SWFR_ERR_NOT_IMPLEMENTED,
+                                            "NotImplementedBlurRoute", a handle with band_count > 1 "NotImplementedBlurBands".
+                                            DESIGN.md, "Blurred layers" */ };
 #define SWFR_MAX_LAYER_DEPTH 4
+#define SWFR_MAX_BLUR_LAYERS 8
+#define SWFR_BLUR_BASE 131072            /* swfr_style::bitmap of the k-th blurred layer of a frame: SWFR_BLUR_BASE + k */
 
 /* SWF blend-mode numbers (PlaceObject3, swf-tree BlendMode).  0, 1: OVER.  3..8, 13, 14: the Cairo operator of the same name
    (CAIRO_OPERATOR_MULTIPLY, SCREEN, LIGHTEN, DARKEN, DIFFERENCE, ADD, OVERLAY, HARD_LIGHT).  SUBTRACT, INVERT, ALPHA, ERASE have no
@@ -275,6 +298,20 @@ int  swfr_register_bitmap_tag(swfr_renderer *r, uint32_t id, const char *media_t
    caller's buffer of rgba_cap bytes (SWFR_ERR_CAPACITY when it is too small; call with NULL first to size it). */
 int  swfr_decode_x_swf_bmp(const uint8_t *data, size_t len, uint32_t *width, uint32_t *height, uint8_t *rgba, size_t rgba_cap);
 int  swfr_render(swfr_renderer *r, const swfr_stage *stage);               /* blocking */
+/* The last rendered frame becomes registered bitmap `bitmap_id` (< 65536), of the frame's size: its premultiplied pixels, device to
+   device, no host copy.  Blocking; queued on the handle's stream behind everything pending on every frame set.  No frame yet:
+   SWFR_ERR_INVALID; a host-only handle: SWFR_ERR_NO_DEVICE; a handle with band_count > 1, which holds only its own rows:
+   SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlurBands".  A captured bitmap has no straight texels: a colour transform over a fill that
+   samples it is refused with SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedCapturedBitmapTransform". */
+int  swfr_capture_bitmap(swfr_renderer *r, uint32_t bitmap_id);
+/* Registered bitmap `bitmap_id` box-blurred in place on the device (ping-pong with a scratch texture the handle keeps): `passes`
+   (1..15) times a horizontal pass of box width max(1, blur_x), then a vertical pass of width max(1, blur_y); blur_x, blur_y 0..255;
+   anything else SWFR_ERR_INVALID, "InvalidBlur"; an unknown id SWFR_ERR_NOT_FOUND.  One pass of width w >= 2 over the premultiplied
+   ARGB texels, per channel, alpha included: out = min(255, (f * S + 0x8000) >> 16) with f = (65536 + w / 2) / w and S the sum over
+   the window [x - w / 2, x - w / 2 + w - 1], texels outside the image reading 0 -- pixman 0.40's PIXMAN_FILTER_CONVOLUTION with w
+   equal taps, byte for byte; w = 1 is the identity.  The bitmap's generation is bumped and it counts as captured from then on.
+   Blocking, ordered like swfr_capture_bitmap. */
+int  swfr_blur_bitmap(swfr_renderer *r, uint32_t bitmap_id, uint32_t blur_x, uint32_t blur_y, uint32_t passes);
 int  swfr_read_image(swfr_renderer *r, uint8_t *dst, size_t dst_stride, int premultiplied);
 /* Mapped read-back in two halves (HeadlessGfxRenderer::get_image maps its staging buffer the same way:
    rs/src/headless_renderer.rs:725-868): _async queues the device-to-host copy of the last frame into the handle's PINNED staging
@@ -366,7 +403,9 @@ typedef struct {
     float stop_offset[SWFR_MAX_STOPS];
     float stop_rgba[SWFR_MAX_STOPS][4];  /* straight, 0..1 */
     uint32_t bitmap;                     /* registered bitmap id; 65536 + k: texture k of the colour-transformed bitmaps of the frame the
-                                            handle's last scene walk built (swfr_build_frame), valid on that handle until its next walk */
+                                            handle's last scene walk built (swfr_build_frame), valid on that handle until its next walk;
+                                            131072 + k (SWFR_BLUR_BASE): the texture of the frame's k-th blurred layer, which only swfr_render
+                                            makes -- at swfr_upload_edges SWFR_ERR_NOT_FOUND */
     uint32_t extend;                     /* bitmap: 0 none, 1 repeat, 2 pad (CAIRO_EXTEND_PAD: swfr_fill_style::pad).  Radial / linear: 0 pad, 1 repeat, 2 reflect (cairo_pattern_set_extend);
                                             any other value on a gradient style is SWFR_ERR_INVALID at upload, and 1 or 2 on a LINEAR
                                             style SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedGradientSpread" (a LINEAR_PIXMAN style takes all three) */
@@ -395,6 +434,16 @@ int  swfr_build_frame(swfr_renderer *r, const swfr_stage *stage,
                       const swfr_edge **edges, size_t *n_edges,
                       const swfr_path **paths, size_t *n_paths,
                       const swfr_style **styles, size_t *n_styles);
+
+/* The sub-frames of the blurred layers (SWFR_OBJECT_BLURRED_LAYER) of the frame the handle's last scene walk built: how many, and the
+   k-th one's arrays -- what swfr_render renders, captures and blurs into texture SWFR_BLUR_BASE + k before the parent frame -- with its
+   blur.  Owned by the handle until its next walk; any out-parameter may be NULL.  k out of range: SWFR_ERR_NOT_FOUND. */
+uint32_t swfr_built_layers(const swfr_renderer *r);
+int  swfr_built_layer(swfr_renderer *r, uint32_t k,
+                      const swfr_edge **edges, size_t *n_edges,
+                      const swfr_path **paths, size_t *n_paths,
+                      const swfr_style **styles, size_t *n_styles,
+                      uint32_t *blur_x, uint32_t *blur_y, uint32_t *passes);
 
 /* Decoded paths of a registered (morph) shape as JSON text in the format of the reference's
    decode goldens (tests/<set>/<name>/shape.ts.json).  String owned by the handle. */
@@ -425,7 +474,9 @@ int  swfr_last_timing(swfr_renderer *r, swfr_timing *out);
 /* Where the time of the last swfr_render went (the reference's calling pattern: one blocking call per frame). */
 typedef struct {
     double build_ms;                     /* host: Stage -> edge list (scene walk, flattening, stroking, clipping) */
-    double upload_host_ms;               /* host: staging copy + table layout (prefix sums over the paths) */
+    double upload_host_ms;               /* host: staging copy + table layout (prefix sums over the paths); for a frame with blurred
+                                            layers also everything done for their sub-frames before the parent is uploaded -- each one
+                                            uploaded, rendered, captured, blurred and waited for (device time included) */
     double h2d_ms;                       /* the scene's one host-to-device copy (HIP events) */
     double device_ms;                    /* first kernel start -> last kernel end (HIP events) */
     double total_ms;                     /* wall clock of the whole call, synchronisation included */
@@ -489,6 +540,10 @@ long swfr_debug_copy(swfr_renderer *r, int what, void *dst, size_t bytes);
    `ct`, `reps` times back to back into a scratch texture, then `reps` device-to-device copies of the same bytes; HIP-event time per
    pass and per copy in *pass_ms / *copy_ms.  Touches no frame and no cache. */
 int  swfr_debug_time_cxform(swfr_renderer *r, uint32_t bitmap_id, const swfr_color_transform *ct, uint32_t reps, float *pass_ms, float *copy_ms);
+/* Measurement (tools/blur_bench.py): one horizontal and one vertical pass of box width `w` (2..255) over a width x height texture of
+   the handle's own, `reps` times each, back to back, then `reps` device-to-device copies of the same bytes; HIP-event time per pass
+   and per copy.  Touches no frame and no bitmap. */
+int  swfr_debug_time_blur(swfr_renderer *r, uint32_t width, uint32_t height, uint32_t w, uint32_t reps, float *h_ms, float *v_ms, float *copy_ms);
 /* Device pointer of the premultiplied RGBA8 framebuffer (width*height*4 bytes, tight rows). */
 void *swfr_device_framebuffer(swfr_renderer *r);
 

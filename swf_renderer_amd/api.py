@@ -37,13 +37,17 @@ EXPORTS = [
     "swfr_render_resident_batched", "swfr_read_image_async", "swfr_read_image_wait", "swfr_render_sequence_readback",
     "swfr_register_bitmap_tag", "swfr_decode_x_swf_bmp", "swfr_render_resident_async_to", "swfr_render_resident_group_to",
     "swfr_set_color_transform", "swfr_debug_time_cxform",
+    "swfr_capture_bitmap", "swfr_blur_bitmap", "swfr_built_layers", "swfr_built_layer", "swfr_debug_time_blur",
 ]
 OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
 OBJECT_BLEND_MODE = 5
 OBJECT_LAYER = 8                        # an isolated group (swfr.h SWFR_OBJECT_LAYER); `id` is the blend mode it is composited with
 OBJECT_MASKED_LAYER = 11                # a masked layer (swfr.h SWFR_OBJECT_MASKED_LAYER): children[0] the mask, children[1..] the content; `id` the blend mode
 OBJECT_FADED_LAYER = 13                 # a layer with an opacity (swfr.h SWFR_OBJECT_FADED_LAYER): `id` is the blend mode | opacity << 8
+OBJECT_BLURRED_LAYER = 16               # a blurred layer (swfr.h SWFR_OBJECT_BLURRED_LAYER): `id` is the blend mode | blur_x << 8 | blur_y << 16 | passes << 24
 MAX_LAYER_DEPTH = 4                     # (a masked layer takes two levels)
+MAX_BLUR_LAYERS = 8                     # blurred layers in one frame
+BLUR_BASE = 131072                      # a bitmap style's `bitmap` at or above it names the texture of a blurred layer of the frame
 PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END, PATH_GROUP_MASK = 0, 1, 2, 3, 4
 # SWF blend-mode numbers under swf-tree's names (BlendMode); what the library does with each is swfr.h's SWFR_BLEND_* comment
 BLEND_MODES = {"normal": 1, "layer": 2, "multiply": 3, "screen": 4, "lighten": 5, "darken": 6, "difference": 7, "add": 8,
@@ -65,6 +69,20 @@ def blend_mode_number(mode) -> int:
     if isinstance(mode, bool) or int(mode) != mode or not 0 <= int(mode) < 2 ** 32:
         raise SwfrError(ERR_INVALID, "InvalidBlendMode: %r" % (mode,))
     return int(mode)
+
+
+def blur_values(blur):
+    """the (x, y, passes) of a "blur" value: a dict with integer "x" and "y" (box widths in device pixels, 0..255; absent: 0) and
+    "passes" (1..15; absent: 1).  A value out of range still goes to the library, to be refused there, when it fits the encoding."""
+    if not isinstance(blur, dict):
+        raise SwfrError(ERR_INVALID, "InvalidBlur: %r" % (blur,))
+    v = []
+    for key, default, top in (("x", 0, 255), ("y", 0, 255), ("passes", 1, 255)):
+        n = blur.get(key, default)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= top:
+            raise SwfrError(ERR_INVALID, "InvalidBlur: %r" % (blur,))
+        v.append(int(n))
+    return tuple(v)
 
 
 def layer_mode_number(layer) -> int:
@@ -276,6 +294,17 @@ def load_library():
     L.swfr_set_color_transform.argtypes = [P, U, C.POINTER(ColorTransform)]
     L.swfr_debug_time_cxform.restype = I
     L.swfr_debug_time_cxform.argtypes = [P, U, C.POINTER(ColorTransform), U, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.swfr_capture_bitmap.restype = I
+    L.swfr_capture_bitmap.argtypes = [P, U]
+    L.swfr_blur_bitmap.restype = I
+    L.swfr_blur_bitmap.argtypes = [P, U, U, U, U]
+    L.swfr_built_layers.restype = U
+    L.swfr_built_layers.argtypes = [P]
+    L.swfr_built_layer.restype = I
+    L.swfr_built_layer.argtypes = [P, U, C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(P), C.POINTER(C.c_size_t),
+                                   C.POINTER(U), C.POINTER(U), C.POINTER(U)]
+    L.swfr_debug_time_blur.restype = I
+    L.swfr_debug_time_blur.argtypes = [P, U, U, U, U, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     if L.swfr_abi_version() != 1:
         raise ImportError("libswfr.so ABI mismatch")
     _LIB = L
@@ -547,6 +576,37 @@ class Renderer:
         buf = (C.c_uint8 * len(rgba_straight)).from_buffer_copy(rgba_straight)
         self._check(self.L.swfr_register_bitmap(self.h, bitmap_id, width, height, C.cast(buf, C.c_void_p), width * 4))
 
+    def capture_bitmap(self, bitmap_id):
+        """swfr_capture_bitmap: the last rendered frame becomes registered bitmap `bitmap_id`, of the frame's size, on the device."""
+        self._check(self.L.swfr_capture_bitmap(self.h, bitmap_id))
+
+    def blur_bitmap(self, bitmap_id, x, y, passes=1):
+        """swfr_blur_bitmap: registered bitmap `bitmap_id` box-blurred in place on the device: `passes` times a horizontal pass of
+        width max(1, x), then a vertical pass of width max(1, y), each as pixman's convolution filter computes it."""
+        for v in (x, y, passes):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 32:
+                raise SwfrError(ERR_INVALID, "InvalidBlur")
+        self._check(self.L.swfr_blur_bitmap(self.h, bitmap_id, int(x), int(y), int(passes)))
+
+    def built_layers(self):
+        """The sub-frames of the blurred layers of the frame the last scene walk built (build_frame, render): a list of
+        (edges, paths, styles, (x, y, passes)), in painter's order -- what render() draws, captures and blurs before the frame."""
+        out = []
+        for k in range(self.L.swfr_built_layers(self.h)):
+            pe, pp, ps = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            ne, npth, ns = C.c_size_t(), C.c_size_t(), C.c_size_t()
+            bx, by, passes = C.c_uint32(), C.c_uint32(), C.c_uint32()
+            self._check(self.L.swfr_built_layer(self.h, k, C.byref(pe), C.byref(ne), C.byref(pp), C.byref(npth), C.byref(ps), C.byref(ns),
+                                                C.byref(bx), C.byref(by), C.byref(passes)))
+            out.append(self._arrays(pe, ne, pp, npth, ps, ns) + ((bx.value, by.value, passes.value),))
+        return out
+
+    def debug_time_blur(self, width, height, w, reps=20):
+        """swfr_debug_time_blur: HIP-event milliseconds of one horizontal pass, one vertical pass and one device-to-device copy."""
+        h, v, c = C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.swfr_debug_time_blur(self.h, width, height, w, reps, C.byref(h), C.byref(v), C.byref(c)))
+        return h.value, v.value, c.value
+
     def set_color_transform(self, slot, ct):
         """swfr_set_color_transform: `ct` a swf-tree ColorTransformWithAlpha dict, or None to clear the slot.  (render() and the
         other stage calls assign slots 0.. to the transforms of their own stages and set them; this is for callers that build
@@ -606,6 +666,21 @@ class Renderer:
             inner = {k: v for k, v in obj.items() if k not in ("mask", "layer")}
             kids = arena.array(DisplayObject, [self._object(arena, {"type": "container", "children": list(obj["mask"])}), self._object(arena, inner)])
             w.n_children, w.children = 2, C.cast(kids, C.POINTER(DisplayObject))
+            return w
+        if obj.get("blur") is not None:
+            # the object inside a type-16 wrapper, where the type-8 wrapper would sit: drawn as an isolated group, box-blurred, and
+            # composited as one layer with the mode of "layer" (absent: normal).  With "mask" or "opacity" those wrappers, above, go
+            # around this one and take the mode: a filter applies before mask and fade, as in Flash Player
+            bx, by, passes = blur_values(obj["blur"])
+            w = DisplayObject()
+            layer = obj.get("layer")
+            mode = BLEND_MODES["normal"] if layer is None or layer is False else layer_mode_number(layer)
+            if not 0 <= mode <= 255:
+                raise SwfrError(ERR_INVALID, "InvalidBlendMode: %r" % (layer,))
+            w.type, w.id = OBJECT_BLURRED_LAYER, mode | bx << 8 | by << 16 | passes << 24
+            inner = {k: v for k, v in obj.items() if k not in ("blur", "layer")}
+            kids = arena.array(DisplayObject, [self._object(arena, inner)])
+            w.n_children, w.children = 1, C.cast(kids, C.POINTER(DisplayObject))
             return w
         if obj.get("layer") is not None and obj.get("layer") is not False:
             # the object inside a type-8 wrapper, outside its blend-mode and colour-transform wrappers: the object is drawn as an
@@ -722,6 +797,11 @@ class Renderer:
         ne, npth, ns = C.c_size_t(), C.c_size_t(), C.c_size_t()
         self._check(self.L.swfr_build_frame(self.h, C.byref(s), C.byref(pe), C.byref(ne), C.byref(pp), C.byref(npth),
                                             C.byref(ps), C.byref(ns)))
+        return self._arrays(pe, ne, pp, npth, ps, ns)
+
+    @staticmethod
+    def _arrays(pe, ne, pp, npth, ps, ns):
+        """copies of the three arrays a scene walk handed out"""
         edges = np.frombuffer((C.c_char * (ne.value * EDGE_DTYPE.itemsize)).from_address(pe.value), dtype=EDGE_DTYPE).copy() \
             if ne.value else np.zeros(0, EDGE_DTYPE)
         paths = np.frombuffer((C.c_char * (npth.value * PATH_DTYPE.itemsize)).from_address(pp.value), dtype=PATH_DTYPE).copy() \

@@ -69,6 +69,10 @@ uint32_t layer_operator(uint32_t mode, bool alpha_modes) {
 // painted yet -- an OVER or an ADD path) becomes the SOURCE lerp, or what the path is otherwise: OVER, or its operator
 inline uint32_t settle_lerp(uint32_t lerp, bool clear) { return (lerp & 0xffu) == 2u ? (clear ? 1u : (lerp & ~0xffu)) : lerp; }
 
+// a worker builder met a blurred layer: sub-frames are built by one walk only, so build() walks the stage again on its own (never
+// leaves the builder)
+constexpr int BLUR_IN_PIECE = -16;
+
 }  // namespace
 
 bool color_transform_valid(const swfr_color_transform& ct) {
@@ -225,6 +229,8 @@ void FrameBuilder::build_range(const std::vector<const swfr_display_object*>& wr
     luts_.clear(); lut_index_.clear(); compose_memo_.clear(); variant_index_.clear(); variants_.clear();
     failed_ = false;
     group_depth_ = 0;
+    layers_.clear();
+    in_blur_ = false;
     surface_clear_ = true;  // clearRect over the whole canvas (canvas-renderer.ts:70-71); a later piece learns the truth when joined
     drawn_ = PixelRect{};
     State s;
@@ -274,6 +280,8 @@ void FrameBuilder::copy_piece(FrameBuilder& dst, size_t edge_off, size_t path_of
 }
 
 void FrameBuilder::build(const swfr_stage& stage) {
+    layers_.clear();          // (a build in pieces never runs build_range on this builder: the last frame's sub-frames go here)
+    in_blur_ = false;
     int want = threads_;
     if (want < 0) {
         const char* env = std::getenv("SWFR_BUILD_THREADS");
@@ -314,6 +322,14 @@ void FrameBuilder::build(const swfr_stage& stage) {
     auto lo_of = [&](int k) { return uint32_t(uint64_t(n_kids) * uint64_t(k) / uint64_t(pieces)); };
     // ---- phase A: every piece into its own builder
     P.run(pieces, [&](int k) { P.builders[k]->build_range(wraps, kids, lo_of(k), lo_of(k + 1)); });
+    for (int k = 0; k < pieces; ++k)
+        if (P.builders[k]->failed_ && P.builders[k]->failure_.code == BLUR_IN_PIECE) {
+            // a frame with a blurred layer: one walk, which keeps the layers' sub-frames and numbers them in painter's order
+            build_range({}, stage.children, 0, stage.n_children);
+            if (failed_) throw failure_;
+            for (swfr_path& p : paths_) p.lerp = settle_lerp(p.lerp, true);
+            return;
+        }
     size_t ne = 0, np = 0, ns = 0;
     std::vector<size_t> eo(pieces), po(pieces), so(pieces);
     std::vector<char> clear_at(pieces);
@@ -380,6 +396,9 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
             break;
         case SWFR_OBJECT_MASKED_LAYER:
             draw_masked_layer(obj, depth);
+            break;
+        case SWFR_OBJECT_BLURRED_LAYER:
+            draw_blurred_layer(obj, depth);
             break;
         case SWFR_OBJECT_SHAPE: {
             const DecodedShape* sh = shape(obj.id, false);
@@ -538,6 +557,72 @@ void FrameBuilder::draw_masked_layer(const swfr_display_object& obj, int depth) 
     m.first_edge = uint32_t(edges_.size());
     m.lerp = op << 8;
     paths_.push_back(m);
+}
+
+// A blurred layer ("Blurred layers"): cairo_push_group; the children; cairo_pop_group; the blur on the group's surface;
+// cairo_set_source; cairo_set_operator; cairo_paint.  The children are built -- under the matrix, colour-transform chain and blend
+// mode in force -- into a sub-frame of their own: a surface of the frame's size that starts clear, with its own layer depth.  In the
+// parent the object is one box path over the whole frame whose bitmap style names the sub-frame's blurred texture, BLUR_BASE + k: a
+// nearest fetch at 1:1 under full coverage, composited with the operator, is the group paint.  The parent surface counts as drawn on
+// behind it (the blurred surface is dirty to Cairo whatever it holds).  ALPHA is a group's operator only in the tile pass: the path
+// then sits in a group of its own over the whole frame, which the END composites with it.
+void FrameBuilder::draw_blurred_layer(const swfr_display_object& obj, int depth) {
+    const uint32_t mode = obj.id & 0xffu, blur_x = (obj.id >> 8) & 0xffu, blur_y = (obj.id >> 16) & 0xffu, passes = obj.id >> 24;
+    const uint32_t op = layer_operator(mode, alpha_modes_);
+    if (passes == 0u || passes > 15u) throw StatusError{SWFR_ERR_INVALID, "InvalidBlur"};
+    if (in_blur_) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NestedBlur"};
+    if (parent_) throw StatusError{BLUR_IN_PIECE, "blurred layer in a build piece"};
+    if (layers_.size() >= SWFR_MAX_BLUR_LAYERS) throw StatusError{SWFR_ERR_CAPACITY, "BlurLayers"};
+    if (op == SWFR_OP_ALPHA && group_depth_ >= SWFR_MAX_LAYER_DEPTH) throw StatusError{SWFR_ERR_CAPACITY, "LayerDepth"};
+    // ---- the sub-frame: the walk goes on into fresh arrays
+    std::vector<swfr_edge> parent_edges; std::vector<swfr_path> parent_paths; std::vector<swfr_style> parent_styles;
+    parent_edges.swap(edges_); parent_paths.swap(paths_); parent_styles.swap(styles_);
+    const PixelRect parent_drawn = drawn_;
+    const int parent_depth = group_depth_;
+    surface_clear_ = true; drawn_ = PixelRect{}; group_depth_ = 0; in_blur_ = true;
+    for (uint32_t i = 0; i < obj.n_children; ++i) draw(obj.children[i], depth + 1);      // (a throw ends the whole build: nothing to unwind)
+    for (swfr_path& p : paths_) p.lerp = settle_lerp(p.lerp, true);
+    layers_.emplace_back();
+    BlurLayer& L = layers_.back();
+    L.edges.swap(edges_); L.paths.swap(paths_); L.styles.swap(styles_);
+    L.blur_x = blur_x; L.blur_y = blur_y; L.passes = passes;
+    edges_.swap(parent_edges); paths_.swap(parent_paths); styles_.swap(parent_styles);
+    drawn_ = parent_drawn; group_depth_ = parent_depth; in_blur_ = false;
+    // ---- the parent's path
+    const int32_t w = int32_t(w_), h = int32_t(h_);
+    swfr_path m;
+    std::memset(&m, 0, sizeof m);
+    m.x_max = w; m.y_max = h;
+    if (op == SWFR_OP_ALPHA) {
+        m.kind = SWFR_PATH_GROUP_BEGIN;
+        m.first_edge = uint32_t(edges_.size());
+        paths_.push_back(m);
+    }
+    swfr_style st;
+    std::memset(&st, 0, sizeof st);
+    st.kind = SWFR_STYLE_BITMAP;
+    st.inv[0] = 1.0; st.inv[3] = 1.0;
+    st.bitmap = BLUR_BASE + uint32_t(layers_.size() - 1);
+    st.extend = 0; st.filter = 1;
+    styles_.push_back(st);
+    swfr_path p = m;
+    p.kind = SWFR_PATH_BOXES;
+    p.first_edge = uint32_t(edges_.size()); p.n_edges = 1;
+    p.style = uint32_t(styles_.size() - 1);
+    p.lerp = op == SWFR_OP_ALPHA ? 0u : op << 8;
+    swfr_edge b;
+    std::memset(&b, 0, sizeof b);
+    b.x2 = w * 256; b.y2 = h * 256; b.bottom = b.y2; b.dir = 1; b.reserved = int32_t(paths_.size());
+    edges_.push_back(b);
+    paths_.push_back(p);
+    if (op == SWFR_OP_ALPHA) {
+        m.kind = SWFR_PATH_GROUP_END;
+        m.first_edge = uint32_t(edges_.size());
+        m.lerp = op << 8;
+        paths_.push_back(m);
+    }
+    surface_clear_ = false;
+    drawn_.add(0, 0, w, h);
 }
 
 bool FrameBuilder::transform(const Affine& m) {
@@ -701,6 +786,7 @@ void FrameBuilder::emit_fill(const OwnedFill& f, bool morph, double ratio) {
         const double m[6] = {inv.xx, inv.yx, inv.xy, inv.yy, inv.x0, inv.y0};
         std::memcpy(st.inv, m, sizeof m);
         const int32_t lut = stack_.back().lut;
+        if (lut >= 0 && it->second.captured) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedCapturedBitmapTransform"};
         st.bitmap = lut < 0 ? s.bitmap_id : VARIANT_BASE + variant_of(s.bitmap_id, lut);
         st.extend = s.pad ? 2 : s.repeating ? 1 : 0;               // (pad and repeating together are refused when the shape is registered)
         st.filter = s.filter;                                      // 0 CAIRO_FILTER_GOOD, 1 CAIRO_FILTER_NEAREST (above 1: refused with the shape)

@@ -21,7 +21,18 @@ namespace swfr {
 
 struct BitmapInfo {
     uint32_t width = 0, height = 0;
+    bool captured = false;                           // made on the device (swfr_capture_bitmap, swfr_blur_bitmap): no straight texels to transform
 };
+
+// The sub-frame of a blurred layer (SWFR_OBJECT_BLURRED_LAYER): what its children build as a frame of their own, and its blur.  The
+// parent frame samples the rendered, blurred sub-frame as texture BLUR_BASE + k, k the layer's index in FrameBuilder::layers().
+struct BlurLayer {
+    std::vector<swfr_edge> edges;
+    std::vector<swfr_path> paths;
+    std::vector<swfr_style> styles;
+    uint32_t blur_x = 0, blur_y = 0, passes = 0;
+};
+constexpr uint32_t BLUR_BASE = SWFR_BLUR_BASE;
 
 struct StatusError {
     int code;
@@ -77,6 +88,8 @@ public:
     const std::vector<swfr_path>& paths() const { return paths_; }
     const std::vector<swfr_style>& styles() const { return styles_; }
     const std::vector<TextureVariant>& variants() const { return variants_; }   // textures VARIANT_BASE + k of the bitmap styles, first-use order
+    const std::vector<BlurLayer>& layers() const { return layers_; }            // the sub-frames of the frame's blurred layers, in painter's order
+    void set_bitmap_captured(uint32_t id) { const auto it = bitmaps_.find(id); if (it != bitmaps_.end()) it->second.captured = true; }
 
 private:
     struct State {
@@ -90,6 +103,7 @@ private:
     void draw(const swfr_display_object& obj, int depth);
     void draw_layer(const swfr_display_object& obj, int depth, uint32_t mode, uint32_t opacity);
     void draw_masked_layer(const swfr_display_object& obj, int depth);
+    void draw_blurred_layer(const swfr_display_object& obj, int depth);
     void group_rectangle(swfr_path& b, size_t begin, size_t end, uint32_t op);   // the markers' rectangle of the group paths_[begin .. end)
     void emit_clearing_group();                                // an ALPHA layer with a transparent source: the surface drawn so far becomes clear
     void draw_path(const StyledPath& p, bool morph, double ratio);
@@ -136,6 +150,8 @@ private:
     std::vector<swfr_edge> edges_;
     std::vector<swfr_path> paths_;
     std::vector<swfr_style> styles_;
+    std::vector<BlurLayer> layers_;   // blurred layers met so far (at most SWFR_MAX_BLUR_LAYERS); always built by one walk (build)
+    bool in_blur_ = false;            // the walk is inside a blurred layer: edges_, paths_ and styles_ are the sub-frame's
     // colour transforms: the slots (set on the handle's builder), the chains of this walk (deduplicated by content) and the
     // textures its bitmap styles ask for (deduplicated by (bitmap, chain))
     std::map<uint32_t, swfr_color_transform> cxforms_;

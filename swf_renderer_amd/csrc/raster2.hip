@@ -2218,6 +2218,7 @@ void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint
 }
 
 #include "cxform.hip"
+#include "blur.hip"
 
 }  // namespace swfr
 

@@ -36,6 +36,8 @@ void launch2_linear_pieces(hipStream_t, const Frame2*, uint32_t, uint32_t);
 void launch_unpremultiply(hipStream_t, const uint32_t*, uint32_t*, size_t);
 void launch_pack_band(hipStream_t, const uint32_t*, uint32_t*, int, int, uint32_t, uint32_t, uint32_t);
 void launch_cxform_texels(hipStream_t, const uint8_t*, uint32_t*, size_t, const uint32_t*);
+void launch_blur_capture(hipStream_t, const uint32_t*, uint32_t*, size_t);
+void launch_blur_pass(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, bool);
 }  // namespace swfr
 
 using namespace swfr;
@@ -149,6 +151,7 @@ struct DeviceBitmap {
     hipEvent_t straight_ready = nullptr;     // recorded behind that upload, on straight_stream
     hipStream_t straight_stream = nullptr;
     bool straight_done = false;              // the upload is known to have completed
+    bool captured = false;                   // made on the device (swfr_capture_bitmap, swfr_blur_bitmap): premultiplied texels only, no `straight`
 };
 
 // A colour-transformed texture (cxform.hip): premultiplied ARGB of one (bitmap, generation, chain), made by the texel pass on `stream`
@@ -237,6 +240,11 @@ struct swfr_renderer {
     uint64_t cx_epoch = 0, cx_tick = 0, cx_synced_epoch = ~uint64_t(0);
     std::vector<std::string> cx_pins;      // the resident scene's textures
     std::vector<DevBitmap> variant_table;  // textures VARIANT_BASE + k of the scene being laid out
+    // blurred layers ("Blurred layers"): texture BLUR_BASE + k of the frame swfr_render is drawing -- a grow-only pool, of the
+    // frame's size each, valid until the handle's next scene walk -- and the scratch texture the passes alternate with
+    DevBuf<uint32_t> blur_tex[SWFR_MAX_BLUR_LAYERS];
+    DevBuf<uint32_t> blur_scratch;
+    std::vector<DevBitmap> blur_table;
     bool bitmap_table_dirty = false, bitmap_table_dirty_copied = false;
     bool scene_ready = false, fb_valid = false;
     swfr_timing timing{};
@@ -282,6 +290,8 @@ struct swfr_renderer {
             (void)hipSetDevice(cfg.device);
             d_bitmap_table.release(); d_tmp.release(); d_counters.release();
             rb_work.release(); rb_cls.release(); rb_frames.release(); rb_fb.release();
+            for (auto& t : blur_tex) t.release();
+            blur_scratch.release();
             for (auto& e : rb_ev) if (e) (void)hipEventDestroy(e);
             if (h_image) (void)hipHostFree(h_image);
             if (read_done) (void)hipEventDestroy(read_done);
@@ -526,7 +536,8 @@ void validate_bitmap_filter(const SceneView& sv) {
 }
 
 // Validate a caller-supplied scene so that no kernel can index out of bounds.
-void validate_scene(const swfr_renderer* r, const SceneView& sv) {
+// blur_ok: the scene is a frame swfr_render is drawing, whose blurred layers' textures (BLUR_BASE + k) have been made
+void validate_scene(const swfr_renderer* r, const SceneView& sv, bool blur_ok = false) {
     const auto [edges, n_edges, paths, n_paths, styles, n_styles] = sv;
     // end points within +-32768 px (2^23 in 24.8): inside that range the int64 products of the closed-form edge evaluation cannot overflow
     for (size_t i = 0; i < n_edges; ++i) {
@@ -580,7 +591,8 @@ void validate_scene(const swfr_renderer* r, const SceneView& sv) {
         }
         if (s.kind == SWFR_STYLE_BITMAP) {
             const auto& V = r->builder->variants();
-            const bool known = s.bitmap >= VARIANT_BASE ? (s.bitmap - VARIANT_BASE < V.size() && r->bitmaps.count(V[s.bitmap - VARIANT_BASE].bitmap))
+            const bool known = s.bitmap >= BLUR_BASE ? (blur_ok && s.bitmap - BLUR_BASE < r->blur_table.size() && r->blur_table[s.bitmap - BLUR_BASE].pixels != nullptr)
+                               : s.bitmap >= VARIANT_BASE ? (s.bitmap - VARIANT_BASE < V.size() && r->bitmaps.count(V[s.bitmap - VARIANT_BASE].bitmap))
                                                         : r->bitmaps.count(s.bitmap) != 0;
             if (!known) throw StatusError{SWFR_ERR_NOT_FOUND, "BitmapNotFound"};
         }
@@ -835,7 +847,8 @@ constexpr int LINEAR_RUN_LENGTH = 256;      // cairo-image-compositor.c, inplace
 // sv: the scene as drawn (the edges of a pixman-linear box path are looked at); split: the device gets column blocks of its paths
 // (split_wide_paths); n_linear: how many pixman-linear styles got a table of piece origins for k2_linear_pieces to fill
 void prepare_sources(const SceneView& sv, bool split, size_t& n_linear, std::vector<DevFilter>& filters, std::vector<DevGradient>& gradients,
-                     std::vector<int32_t>& fparams, const std::vector<DevBitmap>& bitmap_table, const std::vector<DevBitmap>& variant_table) {
+                     std::vector<int32_t>& fparams, const std::vector<DevBitmap>& bitmap_table, const std::vector<DevBitmap>& variant_table,
+                     const std::vector<DevBitmap>& blur_table) {
     const auto [edges, n_edges, paths, n_paths, styles, n_styles] = sv;
     filters.assign(n_styles, DevFilter{});
     // a bitmap style belongs to one drawing operation: pixman's transform is anchored at the centre of that operation's rectangle
@@ -870,7 +883,8 @@ void prepare_sources(const SceneView& sv, bool split, size_t& n_linear, std::vec
         if (styles[i].kind == SWFR_STYLE_BITMAP) {
             // (a colour-transformed bitmap samples its texture from the texel pass: resolve_variants)
             const uint32_t b = styles[i].bitmap;
-            const DevBitmap* bm = b >= VARIANT_BASE ? (b - VARIANT_BASE < variant_table.size() ? &variant_table[b - VARIANT_BASE] : nullptr)
+            const DevBitmap* bm = b >= BLUR_BASE ? (b - BLUR_BASE < blur_table.size() ? &blur_table[b - BLUR_BASE] : nullptr)
+                                  : b >= VARIANT_BASE ? (b - VARIANT_BASE < variant_table.size() ? &variant_table[b - VARIANT_BASE] : nullptr)
                                                     : (b < bitmap_table.size() ? &bitmap_table[b] : nullptr);
             if (bm) { filters[i].pixels = bm->pixels; filters[i].width = bm->width; filters[i].height = bm->height; }
         }
@@ -993,7 +1007,7 @@ void layout_scene(const swfr_renderer* r, const SceneView& sv, SceneLayout& L, c
     L.n_strips = size_t(local_tile_rows(r)) * tiles_x * STRIPS_PER_TILE;
     L.n_strip_slots = strip_slots(local_tile_rows(r), uint32_t(tiles_x * STRIPS_PER_TILE));
     L.filters.clear(); L.gradients.clear(); L.fparams.clear();
-    prepare_sources(drawn ? *drawn : sv, drawn != nullptr, L.n_linear, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table);
+    prepare_sources(drawn ? *drawn : sv, drawn != nullptr, L.n_linear, L.filters, L.gradients, L.fparams, r->bitmap_table, r->variant_table, r->blur_table);
 }
 // A tor path wider than the 13-bit column field of a cell (only possible in frames wider than 8192 px) is rasterized as several
 // paths over the SAME edges, one per block of 8192 pixel columns: the scan converter clips a path's cells to its column range
@@ -1168,17 +1182,19 @@ void resolve_variants(swfr_renderer* r, const SceneView& sv, hipStream_t st, boo
         r->cx_pins.clear();
     }
     bool any = false;
-    for (size_t i = 0; i < n_styles && !any; ++i) any = styles[i].kind == SWFR_STYLE_BITMAP && styles[i].bitmap >= VARIANT_BASE;
+    for (size_t i = 0; i < n_styles && !any; ++i) any = styles[i].kind == SWFR_STYLE_BITMAP && styles[i].bitmap >= VARIANT_BASE && styles[i].bitmap < BLUR_BASE;
     if (!any) return;                                             // (a scene without colour-transformed bitmaps: nothing at all)
     const auto& V = r->builder->variants();
     r->variant_table.assign(V.size(), DevBitmap{nullptr, 0, 0});
     for (size_t i = 0; i < n_paths; ++i) {
         const swfr_style& s = styles[paths[i].style];
-        if (s.kind != SWFR_STYLE_BITMAP || s.bitmap < VARIANT_BASE) continue;
+        if (s.kind != SWFR_STYLE_BITMAP || s.bitmap < VARIANT_BASE || s.bitmap >= BLUR_BASE) continue;
         const uint32_t k = s.bitmap - VARIANT_BASE;               // (validate_scene: k < V.size(), the bitmap is registered)
         if (r->variant_table[k].pixels) continue;
         const TextureVariant& tv = V[k];
         DeviceBitmap& bm = r->bitmaps.at(tv.bitmap);
+        // (arrays built before the bitmap was captured or blurred: it has no straight texels for the texel pass any more)
+        if (bm.captured) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedCapturedBitmapTransform"};
         std::string key(sizeof(uint32_t) + sizeof(uint64_t) + sizeof(ColorLut), '\0');
         std::memcpy(&key[0], &tv.bitmap, sizeof(uint32_t));
         std::memcpy(&key[sizeof(uint32_t)], &bm.gen, sizeof(uint64_t));
@@ -1386,7 +1402,7 @@ void validate_linear_pixman(const swfr_renderer* r, const SceneView& sv) {
     for (swfr_style& s : only) if (s.kind != SWFR_STYLE_LINEAR_PIXMAN) { s.kind = SWFR_STYLE_SOLID; }
     std::vector<swfr_path> drawn;                                     // (a group marker has no style of its own before lower_groups)
     for (size_t i = 0; i < n_paths; ++i) if (paths[i].kind < SWFR_PATH_GROUP_BEGIN) drawn.push_back(paths[i]);
-    prepare_sources(SceneView{edges, n_edges, drawn.data(), drawn.size(), only.data(), n_styles}, false, n_linear, filters, gradients, fparams, r->bitmap_table, r->variant_table);
+    prepare_sources(SceneView{edges, n_edges, drawn.data(), drawn.size(), only.data(), n_styles}, false, n_linear, filters, gradients, fparams, r->bitmap_table, r->variant_table, r->blur_table);
 }
 
 // Everything a caller-supplied scene is refused for before it is uploaded (swfr_upload_edges).  The order is behaviour: it decides which
@@ -1512,6 +1528,48 @@ void order_frames_behind_pending_read(swfr_renderer* r) {
     if (!r->read_pending || !r->read_done) return;
     for (int k = 1; k < 4; ++k)
         if (r->fs[k].stream) HIP_CHECK(hipStreamWaitEvent(r->fs[k].stream, r->read_done, 0));
+}
+
+// ---- blurred layers ("Blurred layers")
+// the routes that do not draw a blurred layer refuse the frame by name (swfr.h, SWFR_OBJECT_BLURRED_LAYER): never drawn unblurred
+void refuse_blur_route(const swfr_renderer* r) {
+    if (!r->builder->layers().empty()) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute"};
+}
+// everything queued on any stream of the handle has finished: what swfr_capture_bitmap and swfr_blur_bitmap are ordered behind
+void wait_all_streams(swfr_renderer* r) {
+    for (auto& x : r->fs) if (x.stream) HIP_CHECK(hipStreamSynchronize(x.stream));
+    for (auto& g : r->groups) if (g.stream) HIP_CHECK(hipStreamSynchronize(g.stream));
+}
+// the box passes of a blur that do something: a width of 0 or 1 leaves its axis alone
+uint32_t blur_steps(uint32_t blur_x, uint32_t blur_y, uint32_t passes) { return passes * ((blur_x > 1u ? 1u : 0u) + (blur_y > 1u ? 1u : 0u)); }
+// The blur (blur_x, blur_y, passes) of the width x height image at `a`, the passes alternating between `a` and `b`, queued on `st`:
+// returns where the result lies -- `a` after an even number of steps (blur_steps), `b` after an odd one
+uint32_t* blur_image(hipStream_t st, uint32_t* a, uint32_t* b, uint32_t width, uint32_t height, uint32_t blur_x, uint32_t blur_y, uint32_t passes) {
+    for (uint32_t p = 0; p < passes; ++p)
+        for (int vertical = 0; vertical < 2; ++vertical) {
+            const uint32_t w = vertical ? blur_y : blur_x;
+            if (w <= 1u) continue;
+            launch_blur_pass(st, a, b, width, height, w, vertical != 0);
+            std::swap(a, b);
+        }
+    HIP_CHECK(hipGetLastError());
+    return a;
+}
+// drops what a bitmap slot holds before it gets new texels: its device memory, and the colour-transformed textures made from it
+void release_bitmap_slot(swfr_renderer* r, uint32_t id, DeviceBitmap& slot) {
+    if (slot.pixels) HIP_CHECK(hipFree(slot.pixels));
+    if (slot.d_straight) HIP_CHECK(hipFree(slot.d_straight));
+    if (slot.straight_ready) HIP_CHECK(hipEventDestroy(slot.straight_ready));
+    slot = DeviceBitmap{};
+    for (auto it = r->cx_cache.begin(); it != r->cx_cache.end();) {
+        if (it->second.bitmap == id && !it->second.pinned) {
+            cx_quiesce(r);
+            (void)hipFree(it->second.pixels);
+            if (it->second.ready) (void)hipEventDestroy(it->second.ready);
+            r->cx_bytes -= it->second.bytes;
+            it = r->cx_cache.erase(it);
+        } else ++it;
+    }
 }
 
 int render_resident(swfr_renderer* r, uint32_t frames) {
@@ -1656,6 +1714,82 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
     return check_counters(r, counters);
 }
 
+// The blurred layers of the frame the builder has just built, before the frame itself (swfr_render): sub-frame k is validated, uploaded
+// and rendered as an ordinary frame, its framebuffer captured as ARGB texels and blurred into texture k of the pool.  The capture goes
+// to the texture or to the scratch, whichever makes the last pass land in the texture.  Everything runs on the handle's stream, behind
+// the sub-frame's kernels (render_resident returns with every stream idle), and is waited for: the builder's arrays and the
+// framebuffer are free for the next sub-frame, and for the parent.
+int render_blur_layers(swfr_renderer* r) {
+    const auto& layers = r->builder->layers();
+    if (r->cfg.band_count > 1) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlurBands"};
+    const size_t n = size_t(r->width) * r->height;
+    r->blur_table.assign(layers.size(), DevBitmap{nullptr, 0, 0});
+    // scene slot 0 and the framebuffer are about to hold sub-frames: neither is "the scene" or "the frame" until the parent is up,
+    // whichever way this function is left (upload2 and render_resident set the flags again for each sub-frame: cleared behind them)
+    struct Invalidate { swfr_renderer* r; ~Invalidate() { r->scene_ready = false; r->fb_valid = false; r->scene_from_builder = false; } } invalidate{r};
+    r->scene_ready = false; r->fb_valid = false;
+    for (size_t k = 0; k < layers.size(); ++k) {
+        const BlurLayer& B = layers[k];
+        const SceneView sv{B.edges.data(), B.edges.size(), B.paths.data(), B.paths.size(), B.styles.data(), B.styles.size()};
+        r->blur_tex[k].reserve(n);
+        uint32_t* const tex = r->blur_tex[k].ptr;
+        if (B.paths.empty()) {                                 // nothing drawn: the group is clear, and so is its blur
+            HIP_CHECK(hipMemsetAsync(tex, 0, n * 4, r->stream));
+        } else {
+            validate_scene(r, sv);
+            int rc = upload2(r, 0, false, sv, nullptr, true);
+            if (rc == SWFR_OK) rc = render_resident(r, 1);
+            if (rc != SWFR_OK) return rc;
+            const uint32_t steps = blur_steps(B.blur_x, B.blur_y, B.passes);
+            if (steps) r->blur_scratch.reserve(n);                 // (a box of 1 x 1 runs no pass: the capture is the texture)
+            uint32_t* const tmp = r->blur_scratch.ptr;
+            const bool odd = (steps & 1u) != 0u;
+            launch_blur_capture(r->stream, r->fb_cur ? r->fb_cur : r->fs[0].d_fb.ptr, odd ? tmp : tex, n);
+            blur_image(r->stream, odd ? tmp : tex, odd ? tex : tmp, r->width, r->height, B.blur_x, B.blur_y, B.passes);
+        }
+        HIP_CHECK(hipStreamSynchronize(r->stream));
+        r->blur_table[k] = DevBitmap{tex, r->width, r->height};
+    }
+    return SWFR_OK;
+}
+
+// swfr_render; allow_blur: the route draws blurred layers (the sequence entries refuse them)
+int render_stage(swfr_renderer* r, const swfr_stage* stage, bool allow_blur) {
+    if (!r || !stage) return fail(r, SWFR_ERR_INVALID, "null argument");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    ++r->cx_epoch;
+    return guarded(r, [&]() {
+        using clk = std::chrono::steady_clock;
+        auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        const auto t0 = clk::now();
+        r->builder->build(*stage);
+        const auto tb = clk::now();
+        r->blur_table.clear();
+        const bool blurred = !r->builder->layers().empty();
+        if (blurred) {
+            if (!allow_blur) refuse_blur_route(r);
+            const int rc = render_blur_layers(r);
+            if (rc != SWFR_OK) return rc;
+        }
+        validate_scene(r, builder_view(r), blurred);
+        // (one frame set: this frame is rendered alone; the builder's edges carry their path index)
+        int rc = upload2(r, 0, false, builder_view(r), nullptr, true);
+        const auto t2 = clk::now();
+        if (rc != SWFR_OK) return rc;
+        rc = render_resident(r, 1);
+        const auto t3 = clk::now();
+        swfr_path_timing& pt = r->path_timing;
+        // (upload_host_ms takes in the blurred layers' sub-frames, rendered above: swfr.h)
+        pt.build_ms = ms(t0, tb); pt.upload_host_ms = ms(tb, t2); pt.device_ms = r->timing.total_ms; pt.total_ms = ms(t0, t3);
+        pt.h2d_bytes = r->scn[0].arena.used; pt.h2d_ms = 0;
+        if (r->scn[0].arena.copy_begin) {
+            float h = 0;
+            if (hipEventElapsedTime(&h, r->scn[0].arena.copy_begin, r->scn[0].arena.copy_end) == hipSuccess) pt.h2d_ms = h;
+        }
+        return rc;
+    });
+}
+
 // A batch of different frames (BASELINE config 3: 256 morph ratios): frame i is built on the host, uploaded into the scene slot
 // of frame set i mod n and rasterized on that set's stream straight into device_dst + i * frame_stride, while the host already
 // builds frame i+1.  Nothing waits for the GPU until the end (a scene slot's pinned staging buffer is reused only after its
@@ -1714,6 +1848,7 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             for (uint32_t k = 0; k < cnt; ++k) {
                 FrameData& F = fd[k];
                 r->builder->build(stages[first + k]);
+                refuse_blur_route(r);
                 validate_scene(r, builder_view(r));
                 F.e = r->builder->edges(); F.p = r->builder->paths(); F.s = r->builder->styles();
                 F.a = prepare_frame(r, SceneView{F.e.data(), F.e.size(), F.p.data(), F.p.size(), F.s.data(), F.s.size()}, G.stream, false, F.scratch, F.L);
@@ -1866,6 +2001,7 @@ int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* d
         for (uint32_t i = 0; i < n; ++i) {
             const int k = int(i % n_sets);
             r->builder->build(stages[i]);
+            refuse_blur_route(r);
             uint32_t* fb_dst = device_dst ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(device_dst) + size_t(i) * frame_stride) : nullptr;
             validate_scene(r, builder_view(r));
             rc = upload2(r, k, false, builder_view(r), fb_dst, true);   // (the builder's edges carry their path index)
@@ -2093,22 +2229,10 @@ int swfr_register_bitmap(swfr_renderer* r, uint32_t id, uint32_t width, uint32_t
             }
         }
         DeviceBitmap& slot = r->bitmaps[id];
-        if (slot.pixels) HIP_CHECK(hipFree(slot.pixels));
-        if (slot.d_straight) HIP_CHECK(hipFree(slot.d_straight));
-        if (slot.straight_ready) HIP_CHECK(hipEventDestroy(slot.straight_ready));
-        slot = DeviceBitmap{};
+        release_bitmap_slot(r, id, slot);
         slot.gen = ++r->bitmap_gen;                             // (the colour-transformed textures of the previous generation are stale)
         slot.straight.resize(size_t(width) * height * 4);
         for (uint32_t y = 0; y < height; ++y) std::memcpy(&slot.straight[size_t(y) * width * 4], rgba + size_t(y) * stride, size_t(width) * 4);
-        for (auto it = r->cx_cache.begin(); it != r->cx_cache.end();) {
-            if (it->second.bitmap == id && !it->second.pinned) {
-                cx_quiesce(r);
-                (void)hipFree(it->second.pixels);
-                if (it->second.ready) (void)hipEventDestroy(it->second.ready);
-                r->cx_bytes -= it->second.bytes;
-                it = r->cx_cache.erase(it);
-            } else ++it;
-        }
         HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&slot.pixels), argb.size() * 4));
         HIP_CHECK(hipMemcpy(slot.pixels, argb.data(), argb.size() * 4, hipMemcpyHostToDevice));
         slot.width = width;
@@ -2182,12 +2306,131 @@ int swfr_build_frame(swfr_renderer* r, const swfr_stage* stage, const swfr_edge*
     return guarded(r, [&]() {
         r->scene_from_builder = false;                          // (the builder's arrays are about to hold another frame than scene 0)
         r->builder->build(*stage);
+        r->blur_table.clear();                                  // (the walk's blurred layers have no textures: only swfr_render makes them)
         if (edges) *edges = r->builder->edges().data();
         if (n_edges) *n_edges = r->builder->edges().size();
         if (paths) *paths = r->builder->paths().data();
         if (n_paths) *n_paths = r->builder->paths().size();
         if (styles) *styles = r->builder->styles().data();
         if (n_styles) *n_styles = r->builder->styles().size();
+        return int(SWFR_OK);
+    });
+}
+
+uint32_t swfr_built_layers(const swfr_renderer* r) { return r ? uint32_t(r->builder->layers().size()) : 0u; }
+
+int swfr_built_layer(swfr_renderer* r, uint32_t k, const swfr_edge** edges, size_t* n_edges, const swfr_path** paths, size_t* n_paths,
+                     const swfr_style** styles, size_t* n_styles, uint32_t* blur_x, uint32_t* blur_y, uint32_t* passes) {
+    if (!r) return SWFR_ERR_INVALID;
+    const auto& layers = r->builder->layers();
+    if (k >= layers.size()) return fail(r, SWFR_ERR_NOT_FOUND, "no such blurred layer in the last built frame");
+    const BlurLayer& B = layers[k];
+    if (edges) *edges = B.edges.data();
+    if (n_edges) *n_edges = B.edges.size();
+    if (paths) *paths = B.paths.data();
+    if (n_paths) *n_paths = B.paths.size();
+    if (styles) *styles = B.styles.data();
+    if (n_styles) *n_styles = B.styles.size();
+    if (blur_x) *blur_x = B.blur_x;
+    if (blur_y) *blur_y = B.blur_y;
+    if (passes) *passes = B.passes;
+    return SWFR_OK;
+}
+
+int swfr_capture_bitmap(swfr_renderer* r, uint32_t bitmap_id) {
+    if (!r) return SWFR_ERR_INVALID;
+    if (bitmap_id > 65535) return fail(r, SWFR_ERR_INVALID, "bitmap id out of range");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle has no image");
+    if (r->cfg.band_count > 1) return fail(r, SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlurBands");
+    if (!r->fb_valid) return fail(r, SWFR_ERR_INVALID, "nothing rendered yet");
+    return guarded(r, [&]() {
+        wait_all_streams(r);
+        const uint32_t* fb = r->fb_cur ? r->fb_cur : r->fs[0].d_fb.ptr;
+        const size_t n = size_t(r->width) * r->height;
+        DeviceBitmap& slot = r->bitmaps[bitmap_id];
+        release_bitmap_slot(r, bitmap_id, slot);
+        slot.gen = ++r->bitmap_gen;
+        slot.captured = true;
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&slot.pixels), n * 4));
+        slot.width = r->width; slot.height = r->height;
+        launch_blur_capture(r->stream, fb, slot.pixels, n);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(r->stream));
+        BitmapInfo info{r->width, r->height};
+        info.captured = true;
+        r->builder->add_bitmap(bitmap_id, info);
+        if (r->bitmap_table.size() <= bitmap_id) r->bitmap_table.resize(bitmap_id + 1, DevBitmap{nullptr, 0, 0});
+        r->bitmap_table[bitmap_id] = DevBitmap{slot.pixels, slot.width, slot.height};
+        r->bitmap_table_dirty = true;
+        return int(SWFR_OK);
+    });
+}
+
+int swfr_blur_bitmap(swfr_renderer* r, uint32_t bitmap_id, uint32_t blur_x, uint32_t blur_y, uint32_t passes) {
+    if (!r) return SWFR_ERR_INVALID;
+    if (blur_x > 255u || blur_y > 255u || passes == 0u || passes > 15u) return fail(r, SWFR_ERR_INVALID, "InvalidBlur");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle has no bitmaps on a device");
+    return guarded(r, [&]() {
+        const auto bit = r->bitmaps.find(bitmap_id);
+        if (bit == r->bitmaps.end() || !bit->second.pixels) return fail(r, SWFR_ERR_NOT_FOUND, "BitmapNotFound");
+        DeviceBitmap& bm = bit->second;
+        wait_all_streams(r);
+        const size_t n = size_t(bm.width) * bm.height;
+        if (blur_steps(blur_x, blur_y, passes)) r->blur_scratch.reserve(n);
+        const uint32_t* at = blur_image(r->stream, bm.pixels, r->blur_scratch.ptr, bm.width, bm.height, blur_x, blur_y, passes);
+        if (at != bm.pixels) HIP_CHECK(hipMemcpyAsync(bm.pixels, at, n * 4, hipMemcpyDeviceToDevice, r->stream));
+        HIP_CHECK(hipStreamSynchronize(r->stream));
+        // the texels are no longer the registered ones: a new generation (stale colour-transformed variants go), and no straight texels
+        uint32_t* const pixels = bm.pixels;
+        const uint32_t w = bm.width, h = bm.height;
+        bm.pixels = nullptr;
+        release_bitmap_slot(r, bitmap_id, bm);
+        bm.pixels = pixels; bm.width = w; bm.height = h;
+        bm.gen = ++r->bitmap_gen;
+        bm.captured = true;
+        r->builder->set_bitmap_captured(bitmap_id);
+        return int(SWFR_OK);
+    });
+}
+
+int swfr_debug_time_blur(swfr_renderer* r, uint32_t width, uint32_t height, uint32_t w, uint32_t reps, float* h_ms, float* v_ms, float* copy_ms) {
+    if (!r || !h_ms || !v_ms || !copy_ms || reps == 0 || width == 0 || height == 0 || width > 32768 || height > 32768 || w < 2 || w > 255)
+        return fail(r, SWFR_ERR_INVALID, "bad argument");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    return guarded(r, [&]() {
+        const size_t bytes = size_t(width) * height * 4;
+        uint32_t *a = nullptr, *b = nullptr;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        std::exception_ptr failure;
+        try {
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&a), bytes));
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b), bytes));
+            HIP_CHECK(hipMemsetAsync(a, 0x5a, bytes, r->stream));
+            for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
+            launch_blur_pass(r->stream, a, b, width, height, w, false);                            // (warm-up of both kernels and the copy)
+            launch_blur_pass(r->stream, a, b, width, height, w, true);
+            HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream));
+            HIP_CHECK(hipEventRecord(e[0], r->stream));
+            for (uint32_t i = 0; i < reps; ++i) launch_blur_pass(r->stream, a, b, width, height, w, false);
+            HIP_CHECK(hipEventRecord(e[1], r->stream));
+            for (uint32_t i = 0; i < reps; ++i) launch_blur_pass(r->stream, a, b, width, height, w, true);
+            HIP_CHECK(hipEventRecord(e[2], r->stream));
+            for (uint32_t i = 0; i < reps; ++i) HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream));
+            HIP_CHECK(hipEventRecord(e[3], r->stream));
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipEventSynchronize(e[3]));
+            HIP_CHECK(hipEventElapsedTime(h_ms, e[0], e[1]));
+            HIP_CHECK(hipEventElapsedTime(v_ms, e[1], e[2]));
+            HIP_CHECK(hipEventElapsedTime(copy_ms, e[2], e[3]));
+            *h_ms /= float(reps); *v_ms /= float(reps); *copy_ms /= float(reps);
+        } catch (...) {
+            failure = std::current_exception();
+        }
+        (void)hipStreamSynchronize(r->stream);
+        if (a) (void)hipFree(a);
+        if (b) (void)hipFree(b);
+        for (auto& x : e) if (x) (void)hipEventDestroy(x);
+        if (failure) std::rethrow_exception(failure);
         return int(SWFR_OK);
     });
 }
@@ -2215,33 +2458,7 @@ int swfr_render_edges(swfr_renderer* r, const swfr_edge* edges, size_t n_edges, 
     return swfr_render_resident(r, 1);
 }
 
-int swfr_render(swfr_renderer* r, const swfr_stage* stage) {
-    if (!r || !stage) return fail(r, SWFR_ERR_INVALID, "null argument");
-    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
-    ++r->cx_epoch;
-    return guarded(r, [&]() {
-        using clk = std::chrono::steady_clock;
-        auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        const auto t0 = clk::now();
-        r->builder->build(*stage);
-        const auto t1 = clk::now();
-        validate_scene(r, builder_view(r));
-        // (one frame set: this frame is rendered alone; the builder's edges carry their path index)
-        int rc = upload2(r, 0, false, builder_view(r), nullptr, true);
-        const auto t2 = clk::now();
-        if (rc != SWFR_OK) return rc;
-        rc = render_resident(r, 1);
-        const auto t3 = clk::now();
-        swfr_path_timing& pt = r->path_timing;
-        pt.build_ms = ms(t0, t1); pt.upload_host_ms = ms(t1, t2); pt.device_ms = r->timing.total_ms; pt.total_ms = ms(t0, t3);
-        pt.h2d_bytes = r->scn[0].arena.used; pt.h2d_ms = 0;
-        if (r->scn[0].arena.copy_begin) {
-            float h = 0;
-            if (hipEventElapsedTime(&h, r->scn[0].arena.copy_begin, r->scn[0].arena.copy_end) == hipSuccess) pt.h2d_ms = h;
-        }
-        return rc;
-    });
-}
+int swfr_render(swfr_renderer* r, const swfr_stage* stage) { return render_stage(r, stage, true); }
 
 int swfr_last_path_timing(swfr_renderer* r, swfr_path_timing* out) {
     if (!r || !out) return SWFR_ERR_INVALID;
@@ -2255,7 +2472,7 @@ int swfr_render_sequence(swfr_renderer* r, const swfr_stage* stages, uint32_t n_
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t rep = 0; rep < repeat; ++rep)
         for (uint32_t i = 0; i < n_stages; ++i) {
-            const int rc = swfr_render(r, &stages[i]);
+            const int rc = render_stage(r, &stages[i], false);
             if (rc != SWFR_OK) return rc;
             const swfr_path_timing& pt = r->path_timing;
             acc.build_ms += pt.build_ms; acc.upload_host_ms += pt.upload_host_ms; acc.h2d_ms += pt.h2d_ms; acc.device_ms += pt.device_ms;
@@ -2280,7 +2497,7 @@ int swfr_render_sequence_readback(swfr_renderer* r, const swfr_stage* stages, ui
     const size_t mid = (size_t(r->height / 2) * r->width + r->width / 2) * 4;
     for (uint32_t rep = 0; rep < repeat; ++rep)
         for (uint32_t i = 0; i < n_stages; ++i) {
-            int rc = swfr_render(r, &stages[i]);
+            int rc = render_stage(r, &stages[i], false);
             if (rc != SWFR_OK) return rc;
             if (pending) { rc = swfr_read_image_wait(r, &data, nullptr); if (rc != SWFR_OK) return rc; sum += data[mid] + data[mid + 3]; pending = false; }
             rc = swfr_read_image_async(r, premultiplied);
