@@ -1287,6 +1287,7 @@ __device__ __forceinline__ uint32_t blend2(uint32_t dst, uint32_t a, uint32_t ef
 #define T3_UNITS 32                    // units (a lane's four pixels of a row) of one (path, strip) blended in compacted form per round
 #define T3_PAIR_FROM 8192u            // strips per frame from which a frame's wavefronts paint two strips each
 #define T3_CLS_PRE 2                   // x 64 class bytes of a strip fetched up front
+#define T3_CLS_PRE_SOLID 1             // ... in the solid instance: a strip whose walk reaches entries >= 64 fetches that chunk when it gets there (T2_WAVES)
 
 // The rounded products of the compacted blends: two 8-bit channels in the 0x00ff00ff layout times an 8-bit factor, in packed 16-bit
 // arithmetic (raster_common.hip): multiply-add, shift, add, shift -- four full-rate instructions and no mask between them, because
@@ -1652,16 +1653,15 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     // SIMD: the solid one.  The others read them where they are used, as before: pinned, each of them spills vector registers.
     // `strips` and `strip_top` are read where they are used in every instance: off the strip's critical path (the descriptor of the
     // strip after next, the next strip's record, the record's clear).  Held too, they were two scalar registers more than the solid
-    // instance has -- two lanes of an 81st vector register, the one register above six wavefronts per SIMD (T2_WAVES).
+    // instance had at six wavefronts per SIMD.  At seven (T2_WAVES: 72 vector and 96 scalar registers) `cls` and `cell_slice` are read
+    // where they are used as well -- held, they were four spilled scalar registers -- and one chunk of class bytes is fetched up front,
+    // not two (CLS_PRE: a vector register of the next strip and one of this strip): with that the instance has no spilled register.
     constexpr bool PIN = SHADERS == 0;
-    [[maybe_unused]] SWFR_GLOBAL_PTR(const uint8_t) p_cls = nullptr;
+    constexpr int CLS_PRE = SHADERS == 0 ? T3_CLS_PRE_SOLID : T3_CLS_PRE;
     [[maybe_unused]] SWFR_GLOBAL_PTR(const BandEntry2) p_band_list = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(const RowInfo2) p_rows = nullptr; [[maybe_unused]] SWFR_GLOBAL_PTR(const Cell) p_cells = nullptr;
-    [[maybe_unused]] uint32_t p_cell_slice = 0u;
     if constexpr (PIN) {
-        p_cls = (SWFR_GLOBAL_PTR(const uint8_t))FR->cls;
         p_band_list = (SWFR_GLOBAL_PTR(const BandEntry2))FR->band_list; p_rows = (SWFR_GLOBAL_PTR(const RowInfo2))FR->rows; p_cells = (SWFR_GLOBAL_PTR(const Cell))FR->cells;
-        p_cell_slice = FR->cell_slice;
-        SWFR_PIN_SGPR(p_cls); SWFR_PIN_SGPR(p_band_list); SWFR_PIN_SGPR(p_rows); SWFR_PIN_SGPR(p_cells); SWFR_PIN_SGPR(p_cell_slice);
+        SWFR_PIN_SGPR(p_band_list); SWFR_PIN_SGPR(p_rows); SWFR_PIN_SGPR(p_cells);
     }
 #define T3_FIELD(name) (PIN ? (decltype(FR->name))p_##name : FR->name)
     uint32_t acc_clean = 0u;                               // the accumulators are zeroed before the first partial path needs them (many strips have none)
@@ -1679,12 +1679,12 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
     };
     uint32_t n_wg = ~0u, n_band_begin = 0u, n_nb = 0u;                    // the next strip (wave-uniform) ...
     int n_tcol = 0, n_ty0 = 0;
-    uint32_t n_top = 0u, n_cls[T3_CLS_PRE];                              // ... and, on their way: its StripTop (lanes 0..3), its first class bytes
+    uint32_t n_top = 0u, n_cls[CLS_PRE];                                 // ... and, on their way: its StripTop (lanes 0..3), its first class bytes
     auto prepare = [&](uint32_t dv) {
         n_wg = (uint32_t)__builtin_amdgcn_readlane((int)dv, 0); n_band_begin = (uint32_t)__builtin_amdgcn_readlane((int)dv, 1); n_nb = (uint32_t)__builtin_amdgcn_readlane((int)dv, 2);
         n_top = 0u; n_tcol = 0; n_ty0 = height;
 #pragma unroll
-        for (int u = 0; u < T3_CLS_PRE; ++u) n_cls[u] = 0u;
+        for (int u = 0; u < CLS_PRE; ++u) n_cls[u] = 0u;
         if (n_wg == ~0u) return;                                         // a padding slot of the launch list, or the list's end
         const uint32_t where = (uint32_t)__builtin_amdgcn_readlane((int)dv, 3);        // tile column | local tile-row << 16 (k2_bin's launch list)
         const int strip = (int)(n_wg % STRIPS_PER_TILE);
@@ -1693,9 +1693,9 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         n_ty0 = trow * TILE_H + strip * STRIP_H;
         // what the row pass knows about the strip as a whole (StripTop), and the strip's class byte per band entry
         if (lane < 4) n_top = reinterpret_cast<const uint32_t*>(FR->strip_top + n_wg)[lane];
-        const uint8_t* cl = T3_FIELD(cls) + (size_t)STRIPS_PER_TILE * tiles_x * n_band_begin + (size_t)(n_tcol * STRIPS_PER_TILE + strip) * n_nb;
+        const uint8_t* cl = FR->cls + (size_t)STRIPS_PER_TILE * tiles_x * n_band_begin + (size_t)(n_tcol * STRIPS_PER_TILE + strip) * n_nb;
 #pragma unroll
-        for (int u = 0; u < T3_CLS_PRE; ++u) if ((uint32_t)(u * 64 + lane) < n_nb) n_cls[u] = (uint32_t)cl[u * 64 + lane];
+        for (int u = 0; u < CLS_PRE; ++u) if ((uint32_t)(u * 64 + lane) < n_nb) n_cls[u] = (uint32_t)cl[u * 64 + lane];
     };
     uint32_t dv2;
     {
@@ -1710,9 +1710,9 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         StripTop top;
         top.any = (uint32_t)__builtin_amdgcn_readlane((int)n_top, 0); top.pad = 0u;
         top.cover = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)n_top, 3) << 32) | (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)n_top, 2);
-        uint32_t cpre[T3_CLS_PRE];
+        uint32_t cpre[CLS_PRE];
 #pragma unroll
-        for (int u = 0; u < T3_CLS_PRE; ++u) cpre[u] = n_cls[u];
+        for (int u = 0; u < CLS_PRE; ++u) cpre[u] = n_cls[u];
         prepare(dv2);
         dv2 = fetch_desc(w + 2u * G);
         if (wg == ~0u) continue;                                         // a padding slot of the launch list
@@ -1727,12 +1727,12 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
         [[maybe_unused]] int sp = 0, mat = 0;                             // open groups of this strip's walk, and how many of them have had the
                                                                          // strip's pixels set aside for them (wave-uniform; instances 4 to 6 only)
 
-        const uint8_t* mycls = T3_FIELD(cls) + (size_t)STRIPS_PER_TILE * tiles_x * band_begin + (size_t)(tcol * STRIPS_PER_TILE + strip) * n_b;   // this strip's class byte per band entry
+        const uint8_t* mycls = FR->cls + (size_t)STRIPS_PER_TILE * tiles_x * band_begin + (size_t)(tcol * STRIPS_PER_TILE + strip) * n_b;   // this strip's class byte per band entry
         auto cls_chunk = [&](uint32_t c0) -> uint32_t {               // the class bytes of entries c0 .. c0 + 63 (c0 a multiple of 64, wave-uniform)
-            if (c0 < 64u * T3_CLS_PRE) {
+            if (c0 < 64u * CLS_PRE) {
                 uint32_t f = cpre[0];
 #pragma unroll
-                for (int u = 1; u < T3_CLS_PRE; ++u) if (c0 == 64u * (uint32_t)u) f = cpre[u];
+                for (int u = 1; u < CLS_PRE; ++u) if (c0 == 64u * (uint32_t)u) f = cpre[u];
                 return f;
             }
             return c0 + lane < n_b ? (uint32_t)mycls[c0 + lane] : 0u;
@@ -1929,7 +1929,7 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
                         if (cr >= row_lo && cr < row_hi) {                   // (a row outside the path's rows gets no cells: alpha 0)
                             const uint2 hq = *reinterpret_cast<const uint2*>(&hdr[li][2 * cr]);
                             off = hq.x; n_c = (int)(hq.y & 0xffffu);
-                            if (off > T3_FIELD(cell_slice) - min((uint32_t)n_c, T3_FIELD(cell_slice))) { atomicOr(&FR->counters[C2_ERROR], E2_CELL_RANGE); n_c = 0; }   // off + n_c > cell_slice
+                            if (off > FR->cell_slice - min((uint32_t)n_c, FR->cell_slice)) { atomicOr(&FR->counters[C2_ERROR], E2_CELL_RANGE); n_c = 0; }   // off + n_c > cell_slice
                         }
                         const Cell* __restrict__ cp = T3_FIELD(cells) + off;
                         // the first sixteen cells of every row in one round trip, the rest (long shallow edges) eight per round
@@ -2068,8 +2068,9 @@ __device__ __forceinline__ void tiles3_body(FramePtr FR, uint32_t* fb_to) {
 
 
 #ifndef T2_WAVES
-#define T2_WAVES 6                    // the solid instance: at most 80 VGPRs, no scratch, no spilled register (tests/test_wave_budget.py): six wavefronts per SIMD
-                                      // (the kernel's time follows its resident wavefronts: DESIGN.md 6.1 "Six wavefronts per SIMD")
+#define T2_WAVES 7                    // the solid instance: at most 72 VGPRs (7 x 72 = 504 of a SIMD's 512) and 96 SGPRs, no scratch, no spilled register
+                                      // (tests/test_wave_budget_seven.py): seven wavefronts per SIMD, 28 x 4 992 B of a CU's 160 KB of LDS
+                                      // (the kernel's time follows its resident wavefronts: DESIGN.md 6.1 "Seven wavefronts per SIMD")
 #endif
 // (two entry points per kernel: one frame, its descriptor passed by value -- the fields arrive with the kernel arguments, no memory
 //  round trip -- and a batch of frames, blockIdx.y indexing an array of descriptors in device memory)

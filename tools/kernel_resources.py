@@ -15,7 +15,17 @@ sys.path.insert(0, ROOT)
 FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
 
 
+_LISTING = None                                                        # (one compile per process, however many callers)
+
+
 def listing():
+    global _LISTING
+    if _LISTING is None:
+        _LISTING = _compile_listing()
+    return list(_LISTING)
+
+
+def _compile_listing():
     from swf_renderer_amd import build as b
     src = os.path.join(b.CSRC, "raster2.hip")
     with tempfile.TemporaryDirectory() as tmp:
