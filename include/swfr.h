@@ -145,7 +145,7 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
        SWFR_OBJECT_COLOR_TRANSFORM = 3   /* a container (matrix + children) whose `id` names a colour-transform slot (swfr_set_color_transform):
                                             the slot's value at the time of the render call applies to everything below it.  Beyond the
                                             reference, whose display objects carry a matrix and a ratio only */,
-       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10, 12, 14, 15 and 17 and above) */
+       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10, 12, 14, 15, 17, 18 and 20 and above) */
        SWFR_OBJECT_BLEND_MODE = 5,       /* a container (matrix + children) whose `id` is an SWF blend-mode number (SWFR_BLEND_*): every path
                                             drawn below it is composited, each on its own, with the mode's Cairo operator -- what
                                             CanvasRenderer would do if it set ctx.globalCompositeOperation before drawing the object.  It
@@ -204,9 +204,22 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
                                             sub-frame counts its own SWFR_MAX_LAYER_DEPTH.  Only swfr_render draws it: swfr_render_batch,
                                             swfr_render_sequence and swfr_render_sequence_readback answer SWFR_ERR_NOT_IMPLEMENTED,
                                             "NotImplementedBlurRoute", a handle with band_count > 1 "NotImplementedBlurBands".
-                                            DESIGN.md, "Blurred layers" */ };
+                                            DESIGN.md, "Blurred layers" */,
+       /* 17 and 18 are not display-object types */
+       SWFR_OBJECT_SHADOWED_LAYER = 19   /* a shadowed layer (drop shadow, glow): a container (matrix + children) whose children are drawn
+                                            onto a transparent surface of the frame's size, as a blurred layer's are; the surface with its
+                                            shadow (swfr_shadow, below: the group's alpha shifted, box-blurred, multiplied, tinted, and the
+                                            group over it, cut out of it, or left out) is composited onto the parent as ONE layer.  `id` is
+                                            mode | slot << 8: the mode an SWF blend-mode number, accepted exactly as SWFR_OBJECT_LAYER
+                                            accepts it; the slot (< 65536) one set with swfr_set_shadow, whose value at the scene walk is
+                                            the shadow -- an unset slot: SWFR_ERR_NOT_FOUND, "ShadowNotFound".  Built, numbered, limited and
+                                            refused together with blurred layers: a sub-frame of its own (swfr_built_layer,
+                                            swfr_built_layer_shadow), one box path in the parent naming texture SWFR_BLUR_BASE + k, at most
+                                            SWFR_MAX_BLUR_LAYERS of both kinds in a frame ("BlurLayers"), neither kind below either
+                                            ("NestedBlur"), drawn by swfr_render only ("NotImplementedBlurRoute", "NotImplementedBlurBands").
+                                            DESIGN.md, "Shadowed layers" */ };
 #define SWFR_MAX_LAYER_DEPTH 4
-#define SWFR_MAX_BLUR_LAYERS 8
+#define SWFR_MAX_BLUR_LAYERS 8           /* blurred and shadowed layers in one frame, together */
 #define SWFR_BLUR_BASE 131072            /* swfr_style::bitmap of the k-th blurred layer of a frame: SWFR_BLUR_BASE + k */
 
 /* SWF blend-mode numbers (PlaceObject3, swf-tree BlendMode).  0, 1: OVER.  3..8, 13, 14: the Cairo operator of the same name
@@ -250,6 +263,29 @@ typedef struct { int32_t mult[4], add[4]; } swfr_color_transform;
 /* Sets slot `slot` (< 65536) of the handle, or clears it (ct == NULL).  Out-of-range values: SWFR_ERR_INVALID.  A display object of
    type SWFR_OBJECT_COLOR_TRANSFORM naming an unset slot makes the render call fail with SWFR_ERR_NOT_FOUND ("ColorTransformNotFound"). */
 int swfr_set_color_transform(swfr_renderer *r, uint32_t slot, const swfr_color_transform *ct);
+
+/* ---- shadows (drop shadow and glow; DESIGN.md, "Shadowed layers") -----------------------------------------------------------
+   The shadow of a group surface G (premultiplied, of the frame's size) as a libcairo 1.16 / pixman 0.40 call sequence, byte for byte:
+     S   clear; cairo_set_source_rgba(0, 0, 0, 1); cairo_mask_surface(G, dx, dy):  S(x, y) = Ga(x - dx, y - dy) << 24, 0 where that
+         pixel lies outside the frame -- dx, dy whole device pixels;
+     S   box-blurred as swfr_blur_bitmap blurs (blur_x, blur_y, passes); the colour channels stay 0;
+     T   clear; `strength` times CAIRO_OPERATOR_ADD paints S:  Ta = min(255, strength * Sa);
+     Tc  clear; cairo_set_source_rgba(color / 255); cairo_mask_surface(T, 0, 0):  Tc = mul_un8(cp, Ta) in every channel, cp the colour's
+         premultiplied pixel as Cairo makes it (each of a, r * a, g * a, b * a in doubles, * 65535 + 0.5 to 16 bits, >> 8);
+     R   SWFR_SHADOW_HIDE_OBJECT: Tc.  SWFR_SHADOW_KNOCKOUT: CAIRO_OPERATOR_DEST_OUT paint of G, R = mul_un8(Tc, 255 - Ga).  Neither:
+         OVER paint of G, R = G + mul_un8(Tc, 255 - Ga), saturating.  Both: invalid.
+   A glow is a shadow with dx = dy = 0.  Not Flash Player's DropShadowFilter / GlowFilter: the box and the offset are whole device
+   pixels that no matrix scales (a caller rounds distance * (cos, sin)(angle) itself), the strength is whole (Flash: 8.8 fixed), there
+   is no inner shadow and no quality beyond `passes`, the surface is cut to the frame before the shadow is made, an even box sits
+   where pixman puts it, and a colour transform around the object recolours what is drawn inside, not the shadow.
+   Ranges: blur_x, blur_y 0..255; passes 1..15; dx, dy -32768..32767; strength 1..255; flags of the two below, not both; anything
+   else is SWFR_ERR_INVALID, "InvalidShadow". */
+#define SWFR_SHADOW_HIDE_OBJECT 1u
+#define SWFR_SHADOW_KNOCKOUT 2u
+typedef struct { uint32_t blur_x, blur_y, passes; int32_t dx, dy; swfr_rgba8 color; uint32_t strength, flags; } swfr_shadow;
+/* Sets shadow slot `slot` (< 65536) of the handle, or clears it (shadow == NULL), as swfr_set_color_transform does for its slots.  A
+   value out of range: SWFR_ERR_INVALID, "InvalidShadow".  SWFR_OBJECT_SHADOWED_LAYER names a slot. */
+int swfr_set_shadow(swfr_renderer *r, uint32_t slot, const swfr_shadow *shadow);
 
 /* ---- configuration ------------------------------------------------------------------------ */
 #define SWFR_DEVICE_HOST_ONLY (-1)       /* decode + geometry only; swfr_render fails with NO_DEVICE */
@@ -312,6 +348,11 @@ int  swfr_capture_bitmap(swfr_renderer *r, uint32_t bitmap_id);
    equal taps, byte for byte; w = 1 is the identity.  The bitmap's generation is bumped and it counts as captured from then on.
    Blocking, ordered like swfr_capture_bitmap. */
 int  swfr_blur_bitmap(swfr_renderer *r, uint32_t bitmap_id, uint32_t blur_x, uint32_t blur_y, uint32_t passes);
+/* Registered bitmap `src_id` plays the group G of a shadow (swfr_shadow, above); the final surface R becomes registered bitmap `dst_id`
+   (< 65536; it may be src_id), of the same size: its generation is bumped and it counts as captured.  The alpha pass, the box passes
+   and the finish pass run on the device (scratch textures the handle keeps).  `shadow` out of range: SWFR_ERR_INVALID,
+   "InvalidShadow"; an unknown src_id: SWFR_ERR_NOT_FOUND.  Blocking, ordered like swfr_blur_bitmap. */
+int  swfr_shadow_bitmap(swfr_renderer *r, uint32_t dst_id, uint32_t src_id, const swfr_shadow *shadow);
 int  swfr_read_image(swfr_renderer *r, uint8_t *dst, size_t dst_stride, int premultiplied);
 /* Mapped read-back in two halves (HeadlessGfxRenderer::get_image maps its staging buffer the same way:
    rs/src/headless_renderer.rs:725-868): _async queues the device-to-host copy of the last frame into the handle's PINNED staging
@@ -404,7 +445,7 @@ typedef struct {
     float stop_rgba[SWFR_MAX_STOPS][4];  /* straight, 0..1 */
     uint32_t bitmap;                     /* registered bitmap id; 65536 + k: texture k of the colour-transformed bitmaps of the frame the
                                             handle's last scene walk built (swfr_build_frame), valid on that handle until its next walk;
-                                            131072 + k (SWFR_BLUR_BASE): the texture of the frame's k-th blurred layer, which only swfr_render
+                                            131072 + k (SWFR_BLUR_BASE): the texture of the frame's k-th blurred or shadowed layer, which only swfr_render
                                             makes -- at swfr_upload_edges SWFR_ERR_NOT_FOUND */
     uint32_t extend;                     /* bitmap: 0 none, 1 repeat, 2 pad (CAIRO_EXTEND_PAD: swfr_fill_style::pad).  Radial / linear: 0 pad, 1 repeat, 2 reflect (cairo_pattern_set_extend);
                                             any other value on a gradient style is SWFR_ERR_INVALID at upload, and 1 or 2 on a LINEAR
@@ -444,6 +485,9 @@ int  swfr_built_layer(swfr_renderer *r, uint32_t k,
                       const swfr_path **paths, size_t *n_paths,
                       const swfr_style **styles, size_t *n_styles,
                       uint32_t *blur_x, uint32_t *blur_y, uint32_t *passes);
+/* Whether the k-th sub-frame is a shadowed layer's (SWFR_OBJECT_SHADOWED_LAYER) and, if so, its shadow as the scene walk read it from
+   the slot; swfr_built_layer reports that shadow's box.  Either out-parameter may be NULL.  k out of range: SWFR_ERR_NOT_FOUND. */
+int  swfr_built_layer_shadow(swfr_renderer *r, uint32_t k, int *has_shadow, swfr_shadow *out);
 
 /* Decoded paths of a registered (morph) shape as JSON text in the format of the reference's
    decode goldens (tests/<set>/<name>/shape.ts.json).  String owned by the handle. */
@@ -544,6 +588,10 @@ int  swfr_debug_time_cxform(swfr_renderer *r, uint32_t bitmap_id, const swfr_col
    the handle's own, `reps` times each, back to back, then `reps` device-to-device copies of the same bytes; HIP-event time per pass
    and per copy.  Touches no frame and no bitmap. */
 int  swfr_debug_time_blur(swfr_renderer *r, uint32_t width, uint32_t height, uint32_t w, uint32_t reps, float *h_ms, float *v_ms, float *copy_ms);
+/* Measurement (tools/shadow_bench.py): the two passes of shadow.hip over width x height textures of the handle's own -- the alpha pass
+   with offset (dx, dy), the finish pass with a framebuffer-ordered group, in place --, `reps` times each, back to back, then `reps`
+   device-to-device copies of the same bytes; HIP-event time per pass and per copy.  Touches no frame and no bitmap. */
+int  swfr_debug_time_shadow(swfr_renderer *r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float *alpha_ms, float *finish_ms, float *copy_ms);
 /* Device pointer of the premultiplied RGBA8 framebuffer (width*height*4 bytes, tight rows). */
 void *swfr_device_framebuffer(swfr_renderer *r);
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "swfr_register_bitmap_tag", "swfr_decode_x_swf_bmp", "swfr_render_resident_async_to", "swfr_render_resident_group_to",
     "swfr_set_color_transform", "swfr_debug_time_cxform",
     "swfr_capture_bitmap", "swfr_blur_bitmap", "swfr_built_layers", "swfr_built_layer", "swfr_debug_time_blur",
+    "swfr_set_shadow", "swfr_shadow_bitmap", "swfr_built_layer_shadow", "swfr_debug_time_shadow",
 ]
 OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
 OBJECT_BLEND_MODE = 5
@@ -45,8 +46,10 @@ OBJECT_LAYER = 8                        # an isolated group (swfr.h SWFR_OBJECT_
 OBJECT_MASKED_LAYER = 11                # a masked layer (swfr.h SWFR_OBJECT_MASKED_LAYER): children[0] the mask, children[1..] the content; `id` the blend mode
 OBJECT_FADED_LAYER = 13                 # a layer with an opacity (swfr.h SWFR_OBJECT_FADED_LAYER): `id` is the blend mode | opacity << 8
 OBJECT_BLURRED_LAYER = 16               # a blurred layer (swfr.h SWFR_OBJECT_BLURRED_LAYER): `id` is the blend mode | blur_x << 8 | blur_y << 16 | passes << 24
+OBJECT_SHADOWED_LAYER = 19              # a shadowed layer (swfr.h SWFR_OBJECT_SHADOWED_LAYER): `id` is the blend mode | shadow slot << 8
+SHADOW_HIDE_OBJECT, SHADOW_KNOCKOUT = 1, 2
 MAX_LAYER_DEPTH = 4                     # (a masked layer takes two levels)
-MAX_BLUR_LAYERS = 8                     # blurred layers in one frame
+MAX_BLUR_LAYERS = 8                     # blurred and shadowed layers in one frame
 BLUR_BASE = 131072                      # a bitmap style's `bitmap` at or above it names the texture of a blurred layer of the frame
 PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END, PATH_GROUP_MASK = 0, 1, 2, 3, 4
 # SWF blend-mode numbers under swf-tree's names (BlendMode); what the library does with each is swfr.h's SWFR_BLEND_* comment
@@ -83,6 +86,35 @@ def blur_values(blur):
             raise SwfrError(ERR_INVALID, "InvalidBlur: %r" % (blur,))
         v.append(int(n))
     return tuple(v)
+
+
+def shadow_values(shadow):
+    """the (x, y, passes, dx, dy, r, g, b, a, strength, flags) of a "shadow" value: a dict with "color" ((r, g, b, a), straight bytes) and the
+    integers "dx", "dy" (the offset in device pixels), "x", "y" (the box; all four absent: 0), "passes", "strength" (absent: 1) and the
+    booleans "hide_object", "knockout".  A value out of the library's range still goes there, to be refused by name, when it fits the struct."""
+    bad = SwfrError(ERR_INVALID, "InvalidShadow: %r" % (shadow,))
+    if not isinstance(shadow, dict) or set(shadow) - {"color", "dx", "dy", "x", "y", "passes", "strength", "hide_object", "knockout"}:
+        raise bad
+    color = shadow.get("color")
+    if not isinstance(color, (tuple, list)) or len(color) != 4:
+        raise bad
+    v = []
+    for n, lo, hi in [(shadow.get("x", 0), 0, 2 ** 32 - 1), (shadow.get("y", 0), 0, 2 ** 32 - 1), (shadow.get("passes", 1), 0, 2 ** 32 - 1),
+                      (shadow.get("dx", 0), -2 ** 31, 2 ** 31 - 1), (shadow.get("dy", 0), -2 ** 31, 2 ** 31 - 1)] + [(c, 0, 255) for c in color] + \
+                     [(shadow.get("strength", 1), 0, 2 ** 32 - 1)]:
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= n <= hi:
+            raise bad
+        v.append(int(n))
+    flags = 0
+    for key, bit in (("hide_object", SHADOW_HIDE_OBJECT), ("knockout", SHADOW_KNOCKOUT)):
+        if not isinstance(shadow.get(key, False), (bool, np.bool_)):
+            raise bad
+        flags |= bit if shadow.get(key, False) else 0
+    return tuple(v) + (flags,)
+
+
+def _shadow_struct(v):
+    return Shadow(v[0], v[1], v[2], v[3], v[4], Rgba8(*v[5:9]), v[9], v[10])
 
 
 def layer_mode_number(layer) -> int:
@@ -157,6 +189,12 @@ DisplayObject._fields_ = [("type", C.c_uint32), ("id", C.c_uint32), ("has_matrix
 
 class ColorTransform(C.Structure):
     _fields_ = [("mult", C.c_int32 * 4), ("add", C.c_int32 * 4)]
+
+
+class Shadow(C.Structure):
+    """swfr_shadow"""
+    _fields_ = [("blur_x", C.c_uint32), ("blur_y", C.c_uint32), ("passes", C.c_uint32), ("dx", C.c_int32), ("dy", C.c_int32), ("color", Rgba8),
+                ("strength", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class Stage(C.Structure):
@@ -303,6 +341,14 @@ def load_library():
     L.swfr_built_layer.restype = I
     L.swfr_built_layer.argtypes = [P, U, C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(P), C.POINTER(C.c_size_t),
                                    C.POINTER(U), C.POINTER(U), C.POINTER(U)]
+    L.swfr_set_shadow.restype = I
+    L.swfr_set_shadow.argtypes = [P, U, C.POINTER(Shadow)]
+    L.swfr_shadow_bitmap.restype = I
+    L.swfr_shadow_bitmap.argtypes = [P, U, U, C.POINTER(Shadow)]
+    L.swfr_built_layer_shadow.restype = I
+    L.swfr_built_layer_shadow.argtypes = [P, U, C.POINTER(I), C.POINTER(Shadow)]
+    L.swfr_debug_time_shadow.restype = I
+    L.swfr_debug_time_shadow.argtypes = [P, U, U, C.c_int32, C.c_int32, U, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.swfr_debug_time_blur.restype = I
     L.swfr_debug_time_blur.argtypes = [P, U, U, U, U, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     if L.swfr_abi_version() != 1:
@@ -344,11 +390,13 @@ def _filter(v):
 
 
 class _Arena:
-    """Keeps every ctypes object referenced by pointer alive for the duration of one call; collects the call's colour transforms."""
+    """Keeps every ctypes object referenced by pointer alive for the duration of one call; collects the call's colour transforms and
+    shadows."""
 
     def __init__(self):
         self.keep = []
         self.cxforms = {}     # the eight values -> slot: one slot per distinct transform of the call (all of its stages)
+        self.shadows = {}     # shadow_values -> slot, likewise
 
     def array(self, ctype, items):
         arr = (ctype * max(len(items), 1))(*items)
@@ -589,8 +637,9 @@ class Renderer:
         self._check(self.L.swfr_blur_bitmap(self.h, bitmap_id, int(x), int(y), int(passes)))
 
     def built_layers(self):
-        """The sub-frames of the blurred layers of the frame the last scene walk built (build_frame, render): a list of
-        (edges, paths, styles, (x, y, passes)), in painter's order -- what render() draws, captures and blurs before the frame."""
+        """The sub-frames of the blurred and shadowed layers of the frame the last scene walk built (build_frame, render): a list of
+        (edges, paths, styles, (x, y, passes)), in painter's order -- what render() draws, captures and blurs before the frame.  A
+        shadowed layer's tuple has a fifth member, its shadow as a dict with every key of a "shadow" value."""
         out = []
         for k in range(self.L.swfr_built_layers(self.h)):
             pe, pp, ps = C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -598,8 +647,35 @@ class Renderer:
             bx, by, passes = C.c_uint32(), C.c_uint32(), C.c_uint32()
             self._check(self.L.swfr_built_layer(self.h, k, C.byref(pe), C.byref(ne), C.byref(pp), C.byref(npth), C.byref(ps), C.byref(ns),
                                                 C.byref(bx), C.byref(by), C.byref(passes)))
-            out.append(self._arrays(pe, ne, pp, npth, ps, ns) + ((bx.value, by.value, passes.value),))
+            layer = self._arrays(pe, ne, pp, npth, ps, ns) + ((bx.value, by.value, passes.value),)
+            has, sh = C.c_int(), Shadow()
+            self._check(self.L.swfr_built_layer_shadow(self.h, k, C.byref(has), C.byref(sh)))
+            if has.value:
+                layer += ({"color": (sh.color.r, sh.color.g, sh.color.b, sh.color.a), "dx": sh.dx, "dy": sh.dy, "x": sh.blur_x, "y": sh.blur_y,
+                           "passes": sh.passes, "strength": sh.strength, "hide_object": bool(sh.flags & SHADOW_HIDE_OBJECT),
+                           "knockout": bool(sh.flags & SHADOW_KNOCKOUT)},)
+            out.append(layer)
         return out
+
+    def set_shadow(self, slot, shadow):
+        """swfr_set_shadow: `shadow` a "shadow" value (shadow_values), or None to clear the slot.  (render() and the other stage calls
+        assign slots 0.. to the shadows of their own stages and set them; this is for callers that build type-19 display objects
+        themselves.)"""
+        if shadow is None:
+            self._check(self.L.swfr_set_shadow(self.h, slot, None))
+            return
+        self._check(self.L.swfr_set_shadow(self.h, slot, C.byref(_shadow_struct(shadow_values(shadow)))))
+
+    def shadow_bitmap(self, dst_id, src_id, shadow):
+        """swfr_shadow_bitmap: registered bitmap `src_id` as the group, its final surface with the shadow (a "shadow" value) becomes
+        registered bitmap `dst_id`, which may be `src_id`, on the device."""
+        self._check(self.L.swfr_shadow_bitmap(self.h, dst_id, src_id, C.byref(_shadow_struct(shadow_values(shadow)))))
+
+    def debug_time_shadow(self, width, height, dx=0, dy=0, reps=20):
+        """swfr_debug_time_shadow: HIP-event milliseconds of one alpha pass, one finish pass and one device-to-device copy."""
+        a, f, c = C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.swfr_debug_time_shadow(self.h, width, height, dx, dy, reps, C.byref(a), C.byref(f), C.byref(c)))
+        return a.value, f.value, c.value
 
     def debug_time_blur(self, width, height, w, reps=20):
         """swfr_debug_time_blur: HIP-event milliseconds of one horizontal pass, one vertical pass and one device-to-device copy."""
@@ -630,10 +706,13 @@ class Renderer:
         return arena.cxforms.setdefault(v, len(arena.cxforms))
 
     def _apply_cxforms(self, arena):
-        """Sets the handle's colour-transform slots to this call's transforms (slots 0..n-1, by first appearance)."""
+        """Sets the handle's colour-transform slots to this call's transforms (slots 0..n-1, by first appearance), and its shadow slots
+        to this call's shadows in the same way."""
         for v, slot in arena.cxforms.items():
             ct = ColorTransform((C.c_int32 * 4)(*v[:4]), (C.c_int32 * 4)(*v[4:]))
             self._check(self.L.swfr_set_color_transform(self.h, slot, C.byref(ct)))
+        for v, slot in arena.shadows.items():
+            self._check(self.L.swfr_set_shadow(self.h, slot, C.byref(_shadow_struct(v))))
 
     def _object(self, arena, obj):
         d = DisplayObject()
@@ -666,6 +745,23 @@ class Renderer:
             inner = {k: v for k, v in obj.items() if k not in ("mask", "layer")}
             kids = arena.array(DisplayObject, [self._object(arena, {"type": "container", "children": list(obj["mask"])}), self._object(arena, inner)])
             w.n_children, w.children = 2, C.cast(kids, C.POINTER(DisplayObject))
+            return w
+        if obj.get("shadow") is not None:
+            # the object inside a type-19 wrapper, where the type-16 wrapper would sit, and composited like it; the shadow's values go to a
+            # slot of this call's (as a colour transform's do).  A filter list is ordered and this pair of keys is not: both together
+            # are refused
+            if obj.get("blur") is not None:
+                raise SwfrError(ERR_NOT_IMPLEMENTED, "NotImplementedFilterChain")
+            v = shadow_values(obj["shadow"])
+            w = DisplayObject()
+            layer = obj.get("layer")
+            mode = BLEND_MODES["normal"] if layer is None or layer is False else layer_mode_number(layer)
+            if not 0 <= mode <= 255:
+                raise SwfrError(ERR_INVALID, "InvalidBlendMode: %r" % (layer,))
+            w.type, w.id = OBJECT_SHADOWED_LAYER, mode | arena.shadows.setdefault(v, len(arena.shadows)) << 8
+            inner = {k: v for k, v in obj.items() if k not in ("shadow", "layer")}
+            kids = arena.array(DisplayObject, [self._object(arena, inner)])
+            w.n_children, w.children = 1, C.cast(kids, C.POINTER(DisplayObject))
             return w
         if obj.get("blur") is not None:
             # the object inside a type-16 wrapper, where the type-8 wrapper would sit: drawn as an isolated group, box-blurred, and

@@ -2220,6 +2220,7 @@ void launch2_tiles(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint
 
 #include "cxform.hip"
 #include "blur.hip"
+#include "shadow.hip"
 
 }  // namespace swfr
 

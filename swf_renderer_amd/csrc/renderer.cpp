@@ -38,6 +38,8 @@ void launch_pack_band(hipStream_t, const uint32_t*, uint32_t*, int, int, uint32_
 void launch_cxform_texels(hipStream_t, const uint8_t*, uint32_t*, size_t, const uint32_t*);
 void launch_blur_capture(hipStream_t, const uint32_t*, uint32_t*, size_t);
 void launch_blur_pass(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, bool);
+void launch_shadow_alpha(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, int32_t, int32_t);
+void launch_shadow_finish(hipStream_t, const uint32_t*, const uint32_t*, bool, uint32_t*, size_t, uint32_t, uint32_t, uint32_t);
 }  // namespace swfr
 
 using namespace swfr;
@@ -244,6 +246,7 @@ struct swfr_renderer {
     // frame's size each, valid until the handle's next scene walk -- and the scratch texture the passes alternate with
     DevBuf<uint32_t> blur_tex[SWFR_MAX_BLUR_LAYERS];
     DevBuf<uint32_t> blur_scratch;
+    DevBuf<uint32_t> shadow_scratch;       // swfr_shadow_bitmap: the alpha surface, which alternates with blur_scratch
     std::vector<DevBitmap> blur_table;
     bool bitmap_table_dirty = false, bitmap_table_dirty_copied = false;
     bool scene_ready = false, fb_valid = false;
@@ -291,7 +294,7 @@ struct swfr_renderer {
             d_bitmap_table.release(); d_tmp.release(); d_counters.release();
             rb_work.release(); rb_cls.release(); rb_frames.release(); rb_fb.release();
             for (auto& t : blur_tex) t.release();
-            blur_scratch.release();
+            blur_scratch.release(); shadow_scratch.release();
             for (auto& e : rb_ev) if (e) (void)hipEventDestroy(e);
             if (h_image) (void)hipHostFree(h_image);
             if (read_done) (void)hipEventDestroy(read_done);
@@ -1718,7 +1721,8 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
 // and rendered as an ordinary frame, its framebuffer captured as ARGB texels and blurred into texture k of the pool.  The capture goes
 // to the texture or to the scratch, whichever makes the last pass land in the texture.  Everything runs on the handle's stream, behind
 // the sub-frame's kernels (render_resident returns with every stream idle), and is waited for: the builder's arrays and the
-// framebuffer are free for the next sub-frame, and for the parent.
+// framebuffer are free for the next sub-frame, and for the parent.  A shadowed layer's sub-frame ("Shadowed layers") takes the
+// same way with the alpha pass in the capture's place and the finish pass behind the blur.
 int render_blur_layers(swfr_renderer* r) {
     const auto& layers = r->builder->layers();
     if (r->cfg.band_count > 1) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlurBands"};
@@ -1744,8 +1748,18 @@ int render_blur_layers(swfr_renderer* r) {
             if (steps) r->blur_scratch.reserve(n);                 // (a box of 1 x 1 runs no pass: the capture is the texture)
             uint32_t* const tmp = r->blur_scratch.ptr;
             const bool odd = (steps & 1u) != 0u;
-            launch_blur_capture(r->stream, r->fb_cur ? r->fb_cur : r->fs[0].d_fb.ptr, odd ? tmp : tex, n);
-            blur_image(r->stream, odd ? tmp : tex, odd ? tex : tmp, r->width, r->height, B.blur_x, B.blur_y, B.passes);
+            const uint32_t* const fb = r->fb_cur ? r->fb_cur : r->fs[0].d_fb.ptr;
+            if (B.has_shadow) {
+                // the group's alpha, shifted, instead of the capture; behind the box passes, which leave it in the texture, the finish
+                // pass in place: the sub-frame's framebuffer is still the group
+                launch_shadow_alpha(r->stream, fb, odd ? tmp : tex, r->width, r->height, B.shadow.dx, B.shadow.dy);
+                blur_image(r->stream, odd ? tmp : tex, odd ? tex : tmp, r->width, r->height, B.blur_x, B.blur_y, B.passes);
+                launch_shadow_finish(r->stream, tex, fb, true, tex, n, B.shadow_pixel, B.shadow.strength, B.shadow.flags);
+                HIP_CHECK(hipGetLastError());
+            } else {
+                launch_blur_capture(r->stream, fb, odd ? tmp : tex, n);
+                blur_image(r->stream, odd ? tmp : tex, odd ? tex : tmp, r->width, r->height, B.blur_x, B.blur_y, B.passes);
+            }
         }
         HIP_CHECK(hipStreamSynchronize(r->stream));
         r->blur_table[k] = DevBitmap{tex, r->width, r->height};
@@ -2252,6 +2266,14 @@ int swfr_set_color_transform(swfr_renderer* r, uint32_t slot, const swfr_color_t
     return SWFR_OK;
 }
 
+int swfr_set_shadow(swfr_renderer* r, uint32_t slot, const swfr_shadow* shadow) {
+    if (!r) return SWFR_ERR_INVALID;
+    if (slot > 65535) return fail(r, SWFR_ERR_INVALID, "shadow slot out of range (0..65535)");
+    if (shadow && !shadow_valid(*shadow)) return fail(r, SWFR_ERR_INVALID, "InvalidShadow");
+    r->builder->set_shadow(slot, shadow);
+    return SWFR_OK;
+}
+
 int swfr_debug_time_cxform(swfr_renderer* r, uint32_t bitmap_id, const swfr_color_transform* ct, uint32_t reps, float* pass_ms, float* copy_ms) {
     if (!r || !ct || !pass_ms || !copy_ms || reps == 0) return fail(r, SWFR_ERR_INVALID, "null argument");
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
@@ -2337,6 +2359,15 @@ int swfr_built_layer(swfr_renderer* r, uint32_t k, const swfr_edge** edges, size
     return SWFR_OK;
 }
 
+int swfr_built_layer_shadow(swfr_renderer* r, uint32_t k, int* has_shadow, swfr_shadow* out) {
+    if (!r) return SWFR_ERR_INVALID;
+    const auto& layers = r->builder->layers();
+    if (k >= layers.size()) return fail(r, SWFR_ERR_NOT_FOUND, "no such blurred layer in the last built frame");
+    if (has_shadow) *has_shadow = layers[k].has_shadow ? 1 : 0;
+    if (out && layers[k].has_shadow) *out = layers[k].shadow;
+    return SWFR_OK;
+}
+
 int swfr_capture_bitmap(swfr_renderer* r, uint32_t bitmap_id) {
     if (!r) return SWFR_ERR_INVALID;
     if (bitmap_id > 65535) return fail(r, SWFR_ERR_INVALID, "bitmap id out of range");
@@ -2389,6 +2420,99 @@ int swfr_blur_bitmap(swfr_renderer* r, uint32_t bitmap_id, uint32_t blur_x, uint
         bm.gen = ++r->bitmap_gen;
         bm.captured = true;
         r->builder->set_bitmap_captured(bitmap_id);
+        return int(SWFR_OK);
+    });
+}
+
+int swfr_shadow_bitmap(swfr_renderer* r, uint32_t dst_id, uint32_t src_id, const swfr_shadow* shadow) {
+    if (!r) return SWFR_ERR_INVALID;
+    if (!shadow || !shadow_valid(*shadow)) return fail(r, SWFR_ERR_INVALID, "InvalidShadow");
+    if (dst_id > 65535) return fail(r, SWFR_ERR_INVALID, "bitmap id out of range");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle has no bitmaps on a device");
+    return guarded(r, [&]() {
+        const auto sit = r->bitmaps.find(src_id);
+        if (sit == r->bitmaps.end() || !sit->second.pixels) return fail(r, SWFR_ERR_NOT_FOUND, "BitmapNotFound");
+        wait_all_streams(r);
+        const uint32_t w = sit->second.width, h = sit->second.height;
+        const size_t n = size_t(w) * h;
+        // the alpha surface in one scratch texture, the box passes between the two, the finish pass into the destination's texels: a
+        // new allocation, or the source's own -- the pass is pointwise
+        r->shadow_scratch.reserve(n);
+        if (blur_steps(shadow->blur_x, shadow->blur_y, shadow->passes)) r->blur_scratch.reserve(n);
+        uint32_t* fresh = nullptr;
+        if (dst_id != src_id) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fresh), std::max<size_t>(n, 1) * 4));
+        const uint32_t* const group = sit->second.pixels;
+        uint32_t* const out = fresh ? fresh : sit->second.pixels;
+        launch_shadow_alpha(r->stream, group, r->shadow_scratch.ptr, w, h, shadow->dx, shadow->dy);
+        const uint32_t* at = blur_image(r->stream, r->shadow_scratch.ptr, r->blur_scratch.ptr, w, h, shadow->blur_x, shadow->blur_y, shadow->passes);
+        launch_shadow_finish(r->stream, at, group, false, out, n, shadow_color_pixel(shadow->color), shadow->strength, shadow->flags);
+        const hipError_t launched = hipGetLastError(), done = hipStreamSynchronize(r->stream);
+        if (launched != hipSuccess || done != hipSuccess) {
+            if (fresh) (void)hipFree(fresh);
+            HIP_CHECK(launched);
+            HIP_CHECK(done);
+        }
+        // the destination's texels are new: a new generation (stale colour-transformed variants go), and no straight texels
+        DeviceBitmap& bm = r->bitmaps[dst_id];                  // (src_id's own slot when the two are one)
+        if (!fresh) bm.pixels = nullptr;                        // (kept: release_bitmap_slot frees what the slot holds)
+        release_bitmap_slot(r, dst_id, bm);
+        bm.pixels = out; bm.width = w; bm.height = h;
+        bm.gen = ++r->bitmap_gen;
+        bm.captured = true;
+        BitmapInfo info{w, h};
+        info.captured = true;
+        r->builder->add_bitmap(dst_id, info);
+        if (r->bitmap_table.size() <= dst_id) r->bitmap_table.resize(dst_id + 1, DevBitmap{nullptr, 0, 0});
+        r->bitmap_table[dst_id] = DevBitmap{bm.pixels, w, h};
+        r->bitmap_table_dirty = true;
+        return int(SWFR_OK);
+    });
+}
+
+int swfr_debug_time_shadow(swfr_renderer* r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float* alpha_ms, float* finish_ms, float* copy_ms) {
+    if (!r || !alpha_ms || !finish_ms || !copy_ms || reps == 0 || width == 0 || height == 0 || width > 32768 || height > 32768 || dx < -32768 ||
+        dx > 32767 || dy < -32768 || dy > 32767)
+        return fail(r, SWFR_ERR_INVALID, "bad argument");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    return guarded(r, [&]() {
+        const size_t n = size_t(width) * height, bytes = n * 4;
+        uint32_t *a = nullptr, *b = nullptr, *c = nullptr;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        std::exception_ptr failure;
+        try {
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&a), bytes));
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b), bytes));
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c), bytes));
+            HIP_CHECK(hipMemsetAsync(a, 0x5a, bytes, r->stream));
+            HIP_CHECK(hipMemsetAsync(c, 0x5a, bytes, r->stream));
+            for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
+            const uint32_t cp = 0x80402010u;
+            launch_shadow_alpha(r->stream, a, b, width, height, dx, dy);                           // (warm-up of both kernels and the copy)
+            launch_shadow_finish(r->stream, b, a, true, b, n, cp, 1u, 0u);
+            HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream));
+            HIP_CHECK(hipEventRecord(e[0], r->stream));
+            for (uint32_t i = 0; i < reps; ++i) launch_shadow_alpha(r->stream, a, b, width, height, dx, dy);
+            HIP_CHECK(hipEventRecord(e[1], r->stream));
+            // (in place over the alpha words, as swfr_render runs it: a result's alpha byte is the next repetition's input, whatever it is)
+            for (uint32_t i = 0; i < reps; ++i) launch_shadow_finish(r->stream, b, c, true, b, n, cp, 1u, 0u);
+            HIP_CHECK(hipEventRecord(e[2], r->stream));
+            for (uint32_t i = 0; i < reps; ++i) HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream));
+            HIP_CHECK(hipEventRecord(e[3], r->stream));
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipEventSynchronize(e[3]));
+            HIP_CHECK(hipEventElapsedTime(alpha_ms, e[0], e[1]));
+            HIP_CHECK(hipEventElapsedTime(finish_ms, e[1], e[2]));
+            HIP_CHECK(hipEventElapsedTime(copy_ms, e[2], e[3]));
+            *alpha_ms /= float(reps); *finish_ms /= float(reps); *copy_ms /= float(reps);
+        } catch (...) {
+            failure = std::current_exception();
+        }
+        (void)hipStreamSynchronize(r->stream);
+        if (a) (void)hipFree(a);
+        if (b) (void)hipFree(b);
+        if (c) (void)hipFree(c);
+        for (auto& x : e) if (x) (void)hipEventDestroy(x);
+        if (failure) std::rethrow_exception(failure);
         return int(SWFR_OK);
     });
 }
