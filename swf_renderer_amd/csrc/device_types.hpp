@@ -223,6 +223,8 @@ inline uint32_t strip_slots(uint32_t local_tile_rows, uint32_t strips_per_row) {
 // k2_bin's two instances by workgroup size (raster2.hip, bin_body), and the most paths a frame may have for the launch plan to
 // choose the small one by itself: what ONE round of its tile-row step tests (16 paths per thread)
 constexpr uint32_t BIN_THREADS_LARGE = 1024, BIN_THREADS_SMALL = 256, BIN_SMALL_PATHS = 16 * BIN_THREADS_SMALL;
+// ... and the one-wavefront instance at the front of k2_rows_ahead_b's grid, which bins a frame set's next frame
+constexpr uint32_t BIN_THREADS_AHEAD = 64;
 
 struct Frame2 {
     // the scene (read-only)

@@ -31,14 +31,22 @@ struct FrameDims {
     size_t strip_cost_count() const { return n_strips + 1; }
 };
 
-// THE list of a frame's kernel-written buffers: v(member of f, element count) once per buffer, in the order they are carved.
-// Every sum of sizes and every carve goes through here, so the two cannot disagree.
+// THE list of a frame's kernel-written buffers: v(member of f, element count, per parity) once per buffer, in the order they are
+// carved.  Every sum of sizes and every carve goes through here, so the two cannot disagree.
+// per parity: k2_bin writes or clears the buffer.  A frame set that bins its next frame beside the row pass of the one before
+// (k2_rows_ahead_b) has two descriptors, parity 0 and 1, with a copy of their own of each such buffer; what only the row and tile
+// passes write -- rows, cells, the two row queues, path_queue -- is one buffer both descriptors point to (carve_frame_ahead).
+template <class V>
+void for_each_frame_buffer_parity(Frame2& f, const FrameDims& d, V&& v) {
+    v(f.edges, d.edge_count(), true); v(f.band_list, d.band_entry_count(), true); v(f.rows, d.row_count(), false); v(f.cells, d.cell_count(), false);
+    v(f.slow, d.slow_count(), false); v(f.huge, d.slow_count(), false); v(f.path_flag, d.path_word_count(), true); v(f.path_queue, d.path_word_count(), false);
+    v(f.chunks, d.chunk_count(), true); v(f.band_slots, d.band_slot_count(), true); v(f.strips, d.strip_count(), true); v(f.strip_cost, d.strip_cost_count(), true);
+    v(f.counters, size_t(C2_WORDS), true);
+}
+// ... as v(member of f, element count)
 template <class V>
 void for_each_frame_buffer(Frame2& f, const FrameDims& d, V&& v) {
-    v(f.edges, d.edge_count()); v(f.band_list, d.band_entry_count()); v(f.rows, d.row_count()); v(f.cells, d.cell_count());
-    v(f.slow, d.slow_count()); v(f.huge, d.slow_count()); v(f.path_flag, d.path_word_count()); v(f.path_queue, d.path_word_count());
-    v(f.chunks, d.chunk_count()); v(f.band_slots, d.band_slot_count()); v(f.strips, d.strip_count()); v(f.strip_cost, d.strip_cost_count());
-    v(f.counters, size_t(C2_WORDS));
+    for_each_frame_buffer_parity(f, d, [&](auto*& p, size_t n, bool) { v(p, n); });
 }
 // points f's buffers into the bytes from `base` on and returns their end: the next frame's base
 inline uint8_t* carve_frame(Frame2& f, const FrameDims& d, uint8_t* base) {
@@ -50,6 +58,22 @@ inline size_t frame_work_bytes(const FrameDims& d) {
     Frame2 f{};
     size_t bytes = 0;
     for_each_frame_buffer(f, d, [&](auto* p, size_t n) { bytes += pad256(n * sizeof(*p)); });
+    return bytes;
+}
+
+// The other parity's descriptor of a frame set.  f is a copy of the parity-0 descriptor: its per-parity buffers are pointed into the
+// bytes from `base` on (the end is returned), the shared ones stay where parity 0 has them.
+inline uint8_t* carve_frame_ahead(Frame2& f, const FrameDims& d, uint8_t* base) {
+    for_each_frame_buffer_parity(f, d, [&](auto*& p, size_t n, bool per_parity) {
+        if (per_parity) { p = reinterpret_cast<decltype(p + 0)>(base); base += pad256(n * sizeof(*p)); }
+    });
+    return base;
+}
+// bytes of the other parity's own buffers: what carve_frame_ahead advances by
+inline size_t frame_ahead_bytes(const FrameDims& d) {
+    Frame2 f{};
+    size_t bytes = 0;
+    for_each_frame_buffer_parity(f, d, [&](auto* p, size_t n, bool per_parity) { if (per_parity) bytes += pad256(n * sizeof(*p)); });
     return bytes;
 }
 

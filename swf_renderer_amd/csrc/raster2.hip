@@ -221,7 +221,9 @@ __device__ __forceinline__ uint32_t path_chunk_count(const DevPath& P, uint32_t 
 //         row and tile passes of the frames beside it (480 of a SIMD's 512 VGPRs held, every freed slot refilled) grant only as
 //         they drain; one of four wavefronts needs a single slot per SIMD.  Of a 1 000-path frame's tile-row workgroup only 63
 //         threads have paths to test: the 1024-thread instance parks fifteen idle wavefronts beside the working one.
-// Either instance is exact for any scene: more paths, hits or strips than a round holds take more rounds (windows).
+//     64  1 024 paths, 1 024 strips, 256 staged hits, 1.8 KB -- BIN_THREADS_AHEAD, the workgroups at the front of k2_rows_ahead_b's grid: the
+//         NEXT frame of a frame set is binned beside the row pass of the one before, one wavefront per workgroup like the row pass's own
+// Every instance is exact for any scene: more paths, hits or strips than a round holds take more rounds (windows).
 template <uint32_t BIN_THREADS> __device__ __forceinline__ void order_body(FramePtr F, uint32_t xcd_class);
 constexpr uint32_t BAND_PER_THREAD = 16;                                  // paths a thread tests per round
 // ORDER_FIRST: the eight ordering workgroups -- the kernel's longest -- are the first of the grid and not the last; per instance
@@ -413,7 +415,8 @@ __device__ __forceinline__ uint32_t order_range(uint32_t cost) {          // 0 =
 }
 constexpr uint32_t ORDER_U = 16;                                           // strips per thread and round: 16 384 / 4 096 strips of a class per round
 template <uint32_t BIN_THREADS> __device__ __forceinline__ void order_body(FramePtr F, uint32_t x) {
-    __shared__ uint2 rowinfo[256];                         // per tile-row of the class: {first band list entry, entries}
+    constexpr uint32_t ROWINFO = BIN_THREADS >= BIN_THREADS_SMALL ? 256u : 32u;    // (the one-wavefront instance shares its workgroup's LDS with the row pass: k2_rows_ahead_b)
+    __shared__ uint2 rowinfo[ROWINFO];                     // per tile-row of the class: {first band list entry, entries}; a class with more tile-rows reads the others' from band_off
     __shared__ uint32_t cnt[ORDER_RANGES][ORDER_U][BIN_THREADS / 64];      // strips per (cost range, round of BIN_THREADS, wavefront); then their exclusive prefix
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t n_strips = F->n_strips, bc = F->band_stride, bi = F->band_first;
@@ -422,7 +425,7 @@ template <uint32_t BIN_THREADS> __device__ __forceinline__ void order_body(Frame
     const uint32_t rows_x = (n_local + XCDS - 1 - x) / XCDS, max_rows = (n_local + XCDS - 1) / XCDS;     // tile-rows x, x + 8, ... of this class
     const uint32_t n_mine = rows_x * per_row;
     const bool by_cost = F->strip_order != 0u;
-    for (uint32_t j = (uint32_t)tid; j < rows_x && j < 256u; j += BIN_THREADS) {
+    for (uint32_t j = (uint32_t)tid; j < rows_x && j < ROWINFO; j += BIN_THREADS) {
         const uint32_t trow = (x + j * XCDS) * bc + bi, b0 = F->band_off[trow];
         rowinfo[j] = make_uint2(b0, F->band_off[trow + 1] - b0);
     }
@@ -502,7 +505,7 @@ template <uint32_t BIN_THREADS> __device__ __forceinline__ void order_body(Frame
                 uint32_t rank = i;                                           // row-major inside the class
                 if (by_cost) rank = base + cnt[(uint32_t)(ranges >> (3 * u)) & 7u][u][wave] + behind[u];
                 uint2 ri;
-                if (j < 256u) ri = rowinfo[j]; else { const uint32_t trow = (x + j * XCDS) * bc + bi, b0 = F->band_off[trow]; ri = make_uint2(b0, F->band_off[trow + 1] - b0); }
+                if (j < ROWINFO) ri = rowinfo[j]; else { const uint32_t trow = (x + j * XCDS) * bc + bi, b0 = F->band_off[trow]; ri = make_uint2(b0, F->band_off[trow + 1] - b0); }
                 // (the strip's tile column and local tile-row travel with it: k2_tiles divides nothing)
                 StripDesc sd; sd.wg = strip_at(j, pos); sd.band_begin = ri.x; sd.n_b = ri.y; sd.pad = (pos / STRIPS_PER_TILE) | ((x + j * XCDS) << 16);
                 F->strips[(size_t)rank * XCDS + x] = sd;
@@ -553,6 +556,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R2_WIDE_WAVE
     FramePtr FR = FRAME_PTR(frames, blockIdx.y);
     if (blockIdx.x >= FR->n_chunks) return;
     rows3_chunk_body<ROWS_STAGE_WIDE, ROWS_FAST_WIDE>(FR, blockIdx.x);
+}
+// k2_rows_b with the k2_bin of the frame set's NEXT frame at the front of its grid ("k2_bin of the next frame in the row
+// launch"): workgroups [0, n_ahead) run the one-wavefront bin body on ahead[blockIdx.y] -- the same frame set's descriptor of the other
+// parity, so nothing they write or clear is read by this launch's row pass or by the tile pass behind it (frame_layout.hpp) -- the
+// ordering workgroups first; the others are k2_rows_b's, chunk blockIdx.x - n_ahead of frames[blockIdx.y].  The branch is on blockIdx
+// alone and no workgroup waits for another: the next launch on the stream is what orders the binned frame behind its binning.
+// ahead_frames: the frames the next row launch of the frame set has (a call's last launches may have fewer than this one).
+// (no queued rows behind a fused launch: slow_kernels = 0, the 64-bit edge records are neither computed nor written)
+__global__ __launch_bounds__(64) R2_ATTR void k2_rows_ahead_b(const Frame2* __restrict__ frames, const Frame2* __restrict__ ahead, uint32_t n_ahead, uint32_t ahead_frames) {
+    if (blockIdx.x < n_ahead) {
+        if (blockIdx.y >= ahead_frames) return;
+        TRACE_DECL; TRACE_NOWAIT(0);
+        bin_body<BIN_THREADS_AHEAD, true>(FRAME_PTR(ahead, blockIdx.y), 0u);
+        TRACE(7); TRACE_OUT(0, blockIdx.x);
+        return;
+    }
+    FramePtr FR = FRAME_PTR(frames, blockIdx.y);
+    const uint32_t chunk = blockIdx.x - n_ahead;
+    if (chunk >= FR->n_chunks) return;
+    rows3_chunk_body<ROWS_STAGE, ROWS_FAST_N>(FR, chunk);
 }
 
 #include "mono.hip"
@@ -2108,11 +2131,19 @@ void launch2_bin(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32
     else hipLaunchKernelGGL(k2_bin_b, dim3(g, n_frames), dim3(BIN_THREADS_LARGE), 0, st, frames, slow_kernels);
 }
 // wide: k2_rows_wide even when no path has more than ROWS_STAGE edges (the SWFR_ROWS_WIDE test knob)
+bool rows_wide_instance(uint32_t max_path_edges, bool wide) { return wide || max_path_edges > ROWS_STAGE; }
 void launch2_rows(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t max_chunks, uint32_t max_path_edges, bool wide, bool mono) {
     if (!max_chunks) return;
     if (mono) { hipLaunchKernelGGL(k2_rows_mono_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames); return; }
-    if (wide || max_path_edges > ROWS_STAGE) hipLaunchKernelGGL(k2_rows_wide_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames);
+    if (rows_wide_instance(max_path_edges, wide)) hipLaunchKernelGGL(k2_rows_wide_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames);
     else hipLaunchKernelGGL(k2_rows_b, dim3(max_chunks, n_frames), dim3(64), 0, st, frames);
+}
+// k2_rows_b of `frames` with k2_bin of `ahead` (the frame set's other parity; its first ahead_frames frames) in front: the grid of
+// launch2_bin's one-wavefront instance, then max_chunks row workgroups.  Neither wide nor aliased frames, no queued rows behind it.
+void launch2_rows_ahead(hipStream_t st, const Frame2* frames, const Frame2* ahead, uint32_t n_frames, uint32_t ahead_frames, uint32_t max_edges, uint32_t max_paths, uint32_t max_bands, uint32_t max_chunks) {
+    constexpr uint32_t T = BIN_THREADS_AHEAD;
+    const uint32_t n_ahead = XCDS + max_bands + (max_edges + T - 1) / T + (max_paths + T - 1) / T;
+    hipLaunchKernelGGL(k2_rows_ahead_b, dim3(n_ahead + max_chunks, n_frames), dim3(64), 0, st, frames, ahead, n_ahead, ahead_frames);
 }
 void launch2_rows_slow(hipStream_t st, const Frame2* frames, uint32_t n_frames, uint32_t grid_slow, uint32_t grid_huge, uint32_t max_passes, bool mono) {
     // an aliased frame's queued rows need no order replay and no second pass (mono.hip): grid_huge workgroups, at least one

@@ -30,6 +30,8 @@
 namespace swfr {
 void launch2_bin(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, bool, uint32_t);
 void launch2_rows(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, bool, bool);
+bool rows_wide_instance(uint32_t, bool);
+void launch2_rows_ahead(hipStream_t, const Frame2*, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
 void launch2_rows_slow(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, uint32_t, bool);
 void launch2_tiles(hipStream_t, const Frame2*, uint32_t, uint32_t, uint32_t, int, uint32_t*);
 void launch2_linear_pieces(hipStream_t, const Frame2*, uint32_t, uint32_t);
@@ -193,7 +195,8 @@ struct swfr_renderer {
         FrameDims dims;                           // what the sizes of a frame's kernel-written buffers follow from (frame_layout.hpp)
         LaunchPlan bounds{};                      // the grids' bounds of a frame of the scene (plan_bounds); plan_of adds what a launch chooses
         Frame2 proto{};                           // the scene fields and sizes of a frame descriptor (per-frame buffers not filled in)
-        Frame2* frames_dev = nullptr;            // one descriptor per frame set (contiguous, in the arena)
+        Frame2* frames_dev = nullptr;            // one descriptor per frame set (contiguous, in the arena): parity 0, what every route launches with
+        Frame2* frames_ahead = nullptr;          // ... and the sets' parity-1 descriptors, when the upload made them (upload2): k2_bin's buffers a second time, the rest shared
         uint32_t slow_passes = SLOW_PASSES;      // passes of the slow-row kernels the scene needs (known after a frame of a resident scene)
         bool slow_verified = false;              // slow_state / slow_passes come from this scene's own counters, not from the previous scene
         int slow_state = 0;                      // 0: unknown (both slow-row kernels are launched), 1: the scene has no queued rows, 2: none with > 64 edges
@@ -205,6 +208,7 @@ struct swfr_renderer {
         hipStream_t stream = nullptr;
         DevBuf<uint8_t> work, cls;               // the kernel-written buffers of one frame, carved like a batch group's (place_frame)
         DevBuf<uint32_t> strip_cost;             // ... but the strip costs, which stay where they are from scene to scene (upload2)
+        DevBuf<uint32_t> strip_cost_ahead;       // ... and parity 1's
         uint32_t* counters = nullptr;            // this set's COUNTER_WORDS of swfr_renderer::d_counters (one buffer: one copy brings all sets' back)
         DevBuf<uint32_t> d_fb;
         // the kernels of one frame of the resident scene on this set, captured once per uploaded scene: a frame is then ONE
@@ -227,7 +231,7 @@ struct swfr_renderer {
 #endif
     DevBuf<DevBitmap> d_bitmap_table;
     DevBuf<uint32_t> d_tmp;
-    DevBuf<uint32_t> d_counters;            // 4 x COUNTER_WORDS: the frame sets' counters, contiguous
+    DevBuf<uint32_t> d_counters;            // 8 x COUNTER_WORDS: the frame sets' counters, contiguous, and behind them those of the sets' parity-1 descriptors
     int in_flight = 4;
     bool scene_from_builder = false;        // the scene in slot 0 is the frame builder's last frame (its arrays are still there)
     uint32_t sets_ready = 0;                // frame sets whose descriptors belong to the scene in slot 0 (swfr_render prepares one, swfr_upload_edges all)
@@ -261,6 +265,9 @@ struct swfr_renderer {
     int tiles_grid = 0;                     // SWFR_TILES_GRID: persistent k2_tiles wavefronts per frame (0 = default)
     int bin_threads = 0;                    // SWFR_BIN_THREADS: 256 or 1024 forces that instance of k2_bin (0 = the launch plan's rule; tests and sweeps)
     uint32_t last_bin_threads = 0;          // the instance of the last launch chain (swfr_debug_copy, what = 2)
+    int bin_ahead = 1;                      // SWFR_BIN_AHEAD=0: every frame of swfr_render_resident is bin -> rows -> tiles; 1: where the call allows it, the next frame
+                                            // of a frame set is binned in the row launch of the one before (render_resident)
+    uint32_t last_ahead_launches = 0;       // k2_rows_ahead_b launches of the last swfr_render_resident call (swfr_debug_copy, what = 3)
     int tiles_shaders = 0;                  // SWFR_TILES_SHADERS: the lowest k2_tiles instance a frame runs (0 solid, 1 bitmap, 2 shaded, 3 blend operators, 4 isolated groups, 5 masked groups, 6 faded groups, 7 erase and alpha operators; test knob)
     bool rows_wide = false;                 // SWFR_ROWS_WIDE=1: every frame with tor paths runs k2_rows_wide (test knob; aliased frames keep k2_rows_mono)
     // swfr_render_batch: groups of frames rendered by ONE launch per kernel (blockIdx.y = frame); two groups alternate,
@@ -300,7 +307,7 @@ struct swfr_renderer {
             if (read_done) (void)hipEventDestroy(read_done);
             for (int k = 0; k < 4; ++k) {
                 FrameSet& x = fs[k];
-                x.work.release(); x.cls.release(); x.strip_cost.release(); x.d_fb.release();
+                x.work.release(); x.cls.release(); x.strip_cost.release(); x.strip_cost_ahead.release(); x.d_fb.release();
                 if (x.graph_exec) (void)hipGraphExecDestroy(x.graph_exec);
                 if (x.graph) (void)hipGraphDestroy(x.graph);
                 if (k > 0 && x.stream) (void)hipStreamDestroy(x.stream);
@@ -1283,6 +1290,12 @@ void place_frame(Frame2& f, const FrameDims& d, size_t tiles_x, uint8_t*& w, uin
     set_cls_region(f, d, tiles_x, c);
     c += pad256(cls_region_bytes(d, tiles_x));
 }
+// ... and the frame's parity-1 descriptor (a copy of the parity-0 one) at buffers of its own for what k2_bin writes (frame_layout.hpp)
+void place_frame_ahead(Frame2& f, const FrameDims& d, size_t tiles_x, uint8_t*& w, uint8_t*& c) {
+    w = carve_frame_ahead(f, d, w);
+    set_cls_region(f, d, tiles_x, c);
+    c += pad256(cls_region_bytes(d, tiles_x));
+}
 
 // Uploads a scene -- the raw edge list, the paths and the styles, plus the layout above -- and sizes the buffers the
 // kernels write.
@@ -1318,7 +1331,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, SceneView sv, uint32_t* fb_
     const FrameDims dims = sc.dims = FrameDims::of_layout(L, a.n_edges, a.n_paths);
     sc.bounds = plan_bounds(L, a.n_edges, a.n_paths);
     SceneArena& A = sc.arena;
-    A.begin(scene_arena_bytes(L, a) + SceneArena::padded(4 * sizeof(Frame2)) + 4096);
+    A.begin(scene_arena_bytes(L, a) + SceneArena::padded(8 * sizeof(Frame2)) + 4096);
     Frame2 proto;
     std::memset(&proto, 0, sizeof proto);
     push_scene(A, L, a, proto);
@@ -1329,7 +1342,11 @@ int upload2(swfr_renderer* r, int si, bool all_sets, SceneView sv, uint32_t* fb_
     // ---- per-frame (kernel-written) buffers: two grow-only allocations per frame set, carved by the list in frame_layout.hpp, and the sets' descriptors
     const size_t cls_bytes = cls_region_bytes(dims, tiles_x);
     const int n_sets = std::max(1, std::min(r->in_flight, 4));
-    Frame2 fr[4];
+    // A scene uploaded into every frame set (swfr_upload_edges, or several resident frames of the builder's scene) gets two descriptors
+    // per set, parity 0 and 1: a copy each of what k2_bin writes or clears, the rest shared, so that render_resident can bin a set's next
+    // frame beside the row pass of the one before.  Every other route launches with parity 0, which lies where it always did.
+    const bool ahead = all_sets && r->bin_ahead && !r->mono && r->cfg.band_count <= 1;
+    Frame2 fr[8];                                                     // [0, 4): the sets' parity-0 descriptors, [4, 8): their parity-1 ones
     std::memset(fr, 0, sizeof fr);
     for (int k = 0; k < 4; ++k) {
         if (all_sets ? k >= n_sets : k != si) continue;
@@ -1337,7 +1354,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, SceneView sv, uint32_t* fb_
         Frame2& f = fr[k];
         f = proto;
         if (!x.stream) HIP_CHECK(hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
-        x.work.reserve(frame_work_bytes(dims)); x.cls.reserve(cls_bytes);
+        x.work.reserve(frame_work_bytes(dims) + (ahead ? frame_ahead_bytes(dims) : 0)); x.cls.reserve(ahead ? pad256(cls_bytes) + cls_bytes : cls_bytes);
         uint8_t *w = x.work.ptr, *c = x.cls.ptr;
         place_frame(f, dims, tiles_x, w, c);
         // two buffers keep places of their own instead of the carved ones.  The strip costs: the next scene's sizes would move them, and
@@ -1347,17 +1364,28 @@ int upload2(swfr_renderer* r, int si, bool all_sets, SceneView sv, uint32_t* fb_
         x.strip_cost.reserve(dims.strip_cost_count());
         if (x.strip_cost.ptr != cost_before) HIP_CHECK(hipMemsetAsync(x.strip_cost.ptr, 0, x.strip_cost.cap * sizeof(uint32_t), up_stream));
         f.strip_cost = x.strip_cost.ptr;
-        r->d_counters.reserve(4 * COUNTER_WORDS);
+        r->d_counters.reserve(8 * COUNTER_WORDS);
         f.counters = x.counters = r->d_counters.ptr + size_t(k) * COUNTER_WORDS;
-        // class bytes outside the paths' rectangles are never written by a kernel: cleared once per uploaded scene
-        HIP_CHECK(hipMemsetAsync(x.cls.ptr, 0, cls_bytes, up_stream));
+        // class bytes outside the paths' rectangles are never written by a kernel: cleared once per uploaded scene (both parities' at once)
+        HIP_CHECK(hipMemsetAsync(x.cls.ptr, 0, ahead ? pad256(cls_bytes) + cls_bytes : cls_bytes, up_stream));
         if (!x.d_fb.ptr && !r->n_targets) {                                             // (a handle with caller targets never renders into a buffer of its own)
             x.d_fb.reserve(size_t(r->width) * r->height);
             HIP_CHECK(hipMemsetAsync(x.d_fb.ptr, 0, size_t(r->width) * r->height * 4, up_stream));
         }
         f.fb = (fb_override && k == si) ? fb_override : (r->n_targets ? r->targets[uint32_t(k) % r->n_targets] : x.d_fb.ptr);
+        if (ahead) {
+            Frame2& f1 = fr[4 + k];
+            f1 = f;                                                                      // (the shared buffers, the framebuffer)
+            place_frame_ahead(f1, dims, tiles_x, w, c);
+            const uint32_t* cost1_before = x.strip_cost_ahead.ptr;
+            x.strip_cost_ahead.reserve(dims.strip_cost_count());
+            if (x.strip_cost_ahead.ptr != cost1_before) HIP_CHECK(hipMemsetAsync(x.strip_cost_ahead.ptr, 0, x.strip_cost_ahead.cap * sizeof(uint32_t), up_stream));
+            f1.strip_cost = x.strip_cost_ahead.ptr;
+            f1.counters = r->d_counters.ptr + size_t(4 + k) * COUNTER_WORDS;
+        }
     }
     sc.frames_dev = static_cast<Frame2*>(A.push(fr, sizeof fr));
+    sc.frames_ahead = ahead ? sc.frames_dev + 4 : nullptr;
     A.flush(up_stream, si == 0);
     if (all_sets) {
         // the copy and the memsets above ran on set `si`'s stream: the other sets' streams start their frames behind them
@@ -1633,13 +1661,41 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
     const bool batched = rb > 1 && frames >= 2;
     uint32_t last_set = (frames - 1) % n_sets;
     int64_t last_on[4] = {-1, -1, -1, -1};                 // per frame set's stream: the last launch of this call it carries (none: -1)
+    uint32_t last_parity[4] = {0, 0, 0, 0};                // per frame set: the descriptor its last frame of this call ran with (its counters are that one's)
+    r->last_ahead_launches = 0;
     if (batched) {
         const uint32_t groups = n_sets / rb;
         const LaunchPlan plan = plan_of(r, sc);                // (as a frame of its own, with the tile pass in its default shape unless SWFR_TILES_GRID caps it)
+        // Two launches a frame instead of three ("k2_bin of the next frame in the row launch"): a group's first launch of
+        // the call is k2_bin on parity 0; then iteration k runs with the descriptors of parity k & 1 and its row launch bins the group's
+        // next frames into the other parity's (k2_rows_ahead_b) -- but for the group's last launch of the call, whose row pass is plain
+        // k2_rows_b: nothing is binned that no row pass reads, so each strip_cost copy sees exactly one row pass between two clears,
+        // across calls and across the routes that use parity 0 alone.  Only what the fused kernel was built for: a verified scene
+        // without queued rows, the narrow antialiased row kernel, no pixman-linear pieces, the plan's own k2_bin instance, no graphs.
+        const bool ahead = r->bin_ahead && sc.frames_ahead && sc.slow_verified && !plan.run_slow && !plan.linear_grid && !r->mono && !r->bin_threads &&
+                           !r->use_graphs && !rows_wide_instance(plan.max_path_edges, plan.rows_wide);     // (a frame of box paths alone: the row launch is the bin workgroups)
+        const uint32_t launches = (frames + rb - 1) / rb;
         uint32_t gi = 0;
         for (uint32_t f = 0; f < frames; f += rb, ++gi) {
             const uint32_t g = gi % groups, cnt = std::min(rb, frames - f);
-            launch_chain(r, r->fs[g * rb].stream, sc.frames_dev + g * rb, cnt, plan, nullptr, nullptr);
+            const hipStream_t st = r->fs[g * rb].stream;
+            if (!ahead) launch_chain(r, st, sc.frames_dev + g * rb, cnt, plan, nullptr, nullptr);
+            else {
+                const uint32_t parity = (gi / groups) & 1u;
+                const Frame2* cur = (parity ? sc.frames_ahead : sc.frames_dev) + g * rb;
+                const Frame2* next = (parity ? sc.frames_dev : sc.frames_ahead) + g * rb;
+                if (gi < groups) {                                 // the prologue
+                    r->last_bin_threads = plan.bin_threads;
+                    launch2_bin(st, cur, cnt, plan.max_edges, plan.max_paths, plan.max_bands, 0u, false, plan.bin_threads);
+                }
+                if (gi + groups < launches) {
+                    const uint32_t next_cnt = std::min(rb, frames - (f + groups * rb));
+                    launch2_rows_ahead(st, cur, next, cnt, next_cnt, plan.max_edges, plan.max_paths, plan.max_bands, plan.max_chunks);
+                    ++r->last_ahead_launches;
+                } else launch2_rows(st, cur, cnt, plan.max_chunks, plan.max_path_edges, false, false);
+                launch2_tiles(st, cur, cnt, plan.max_strips, plan.tiles_grid, plan.shader_level, nullptr);
+                for (uint32_t k = 0; k < cnt; ++k) last_parity[g * rb + k] = parity;
+            }
             last_set = g * rb + cnt - 1;
             last_on[g * rb] = int64_t(gi);
         }
@@ -1659,9 +1715,11 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
     HIP_CHECK(hipEventRecord(ev_end, r->stream));
     HIP_CHECK(hipGetLastError());
     // the counters of every set come back through pinned memory behind the last kernel: one synchronisation for everything
-    if (!r->h_counters) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r->h_counters), 4 * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+    if (!r->h_counters) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r->h_counters), 8 * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
     const uint32_t used_sets = std::min(frames, n_sets);               // (a set that rendered no frame of this call holds an older frame's counters)
-    HIP_CHECK(hipMemcpyAsync(r->h_counters, r->d_counters.ptr, size_t(used_sets) * COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    // (a set whose last frame ran with its parity-1 descriptor left that frame's counters four sets further on: all eight come back)
+    const bool any_ahead = r->last_ahead_launches != 0;
+    HIP_CHECK(hipMemcpyAsync(r->h_counters, r->d_counters.ptr, size_t(any_ahead ? 8 : used_sets) * COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
     // The other sets' streams are waited for too, in the order their last frames finish: the runtime then knows them idle, and a
     // hipDeviceSynchronize behind this call (torch.cuda.synchronize()) costs 3 us instead of 47 (it drains every stream it has not seen
     // idle, 12 us apiece).  All but the last of these waits return while the GPU is still at the call's last frames.
@@ -1685,6 +1743,8 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
         setup_ms += a; rows_ms += b; tiles_ms += c;
     }
     HIP_CHECK(hipEventElapsedTime(&total_ms, ev_begin, ev_end));
+    for (uint32_t k = 0; k < used_sets; ++k)                // per set, the counters of the last frame it rendered: error flags, queued rows, queue passes, records
+        if (last_parity[k]) std::memcpy(r->h_counters + k * COUNTER_WORDS, r->h_counters + (4 + k) * COUNTER_WORDS, COUNTER_WORDS * sizeof(uint32_t));
     std::memcpy(counters, r->h_counters, sizeof counters);
     for (uint32_t k = 1; k < used_sets; ++k)               // (set 0's counts, every set's error and limit flags)
         for (uint32_t w : {uint32_t(C2_ERROR), uint32_t(C2_TIE_PAIRTEST_SKIPPED), uint32_t(C2_TIE_SORT_OVERFLOW), uint32_t(C2_TIE_DEPTH)})
@@ -2152,6 +2212,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
     r->use_graphs = 0;                                              // (the emulator's runtime has no graphs)
 #endif
     if (const char* rb = std::getenv("SWFR_RESIDENT_BATCH")) r->resident_batch = std::atoi(rb);
+    if (const char* ba = std::getenv("SWFR_BIN_AHEAD")) r->bin_ahead = std::atoi(ba) != 0;
     if (const char* cm = std::getenv("SWFR_CXFORM_CACHE_MB")) r->cx_budget = size_t(std::max(0, std::atoi(cm))) << 20;
     if (r->cfg.device == SWFR_DEVICE_HOST_ONLY) {
         *out = r.release();
@@ -2170,7 +2231,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
         for (int i = 0; i < 4 * 32 + 5; ++i) { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreate(&e)); raw->ev.push_back(e); }   // (so that no render call has to create its timing events inside somebody's timed region)
         raw->fs[0].d_fb.reserve(size_t(width) * height);
         HIP_CHECK(hipMemsetAsync(raw->fs[0].d_fb.ptr, 0, size_t(width) * height * 4, raw->stream));
-        raw->d_counters.reserve(4 * COUNTER_WORDS);
+        raw->d_counters.reserve(8 * COUNTER_WORDS);
         raw->fs[0].counters = raw->d_counters.ptr;
         HIP_CHECK(hipStreamSynchronize(raw->stream));
         return int(SWFR_OK);
@@ -2770,7 +2831,7 @@ int swfr_wait(swfr_renderer* r) {
     if (!r) return SWFR_ERR_INVALID;
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle");
     return guarded(r, [&]() {
-        if (!r->h_counters) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r->h_counters), 4 * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+        if (!r->h_counters) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r->h_counters), 8 * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
         int rc = SWFR_OK;
         for (uint32_t k = 0; k < 4; ++k) {
             if (!r->fs[k].stream || !r->fs[k].counters) continue;
@@ -2791,6 +2852,11 @@ long swfr_debug_copy(swfr_renderer* r, int what, void* dst, size_t bytes) {
     if (what == 2) {                                       // (no device buffer: what the last launch chain chose)
         if (bytes < sizeof(uint32_t)) return 0;
         std::memcpy(dst, &r->last_bin_threads, sizeof(uint32_t));
+        return long(sizeof(uint32_t));
+    }
+    if (what == 3) {                                       // (nor here: the row launches of the last resident call that binned the next frame)
+        if (bytes < sizeof(uint32_t)) return 0;
+        std::memcpy(dst, &r->last_ahead_launches, sizeof(uint32_t));
         return long(sizeof(uint32_t));
     }
     if (!r->fs[0].work.ptr) return 0;
