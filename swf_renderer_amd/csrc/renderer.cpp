@@ -13,6 +13,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <functional>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -362,6 +364,17 @@ int guarded(swfr_renderer* r, F&& f) {
 SceneView builder_view(const swfr_renderer* r) {
     const auto& e = r->builder->edges(); const auto& p = r->builder->paths(); const auto& s = r->builder->styles();
     return SceneView{e.data(), e.size(), p.data(), p.size(), s.data(), s.size()};
+}
+
+// the frame sets a handle rotates its frames over (SWFR_FRAMES_IN_FLIGHT, 1..4): what an upload into every set prepares
+uint32_t sets_wanted(const swfr_renderer* r) { return uint32_t(std::max(1, std::min(r->in_flight, 4))); }
+// ... and how many of them hold descriptors and buffers of the resident scene: what a call may rotate over now.  (upload2 gives every
+// set below sets_ready its stream, its work buffer and -- on a handle without caller targets -- its framebuffer, and swfr_set_targets
+// asks for a new upload: the buffer test only ever ends the count where sets_ready does)
+uint32_t sets_of_scene(const swfr_renderer* r) {
+    uint32_t n = 1;
+    while (n < sets_wanted(r) && n < r->sets_ready && r->fs[n].stream && r->fs[n].work.ptr) ++n;
+    return n;
 }
 
 // the handle's share of the frame's tile-rows: local tile-row l is frame tile-row first + l * stride, l < count; `padded` = the
@@ -1284,15 +1297,10 @@ void merge_bounds(LaunchPlan& p, const LaunchPlan& q) {
     p.max_chunks = std::max(p.max_chunks, q.max_chunks); p.max_path_edges = std::max(p.max_path_edges, q.max_path_edges); p.rows_wide = p.rows_wide || q.rows_wide;
     p.linear_grid = std::max(p.linear_grid, q.linear_grid); p.max_strips = std::max(p.max_strips, q.max_strips); p.shader_level = std::max(p.shader_level, q.shader_level);
 }
-// Points a frame's descriptor at its share of a work and a cls allocation (frame_layout.hpp) and moves w and c on to the next frame's
-void place_frame(Frame2& f, const FrameDims& d, size_t tiles_x, uint8_t*& w, uint8_t*& c) {
-    w = carve_frame(f, d, w);
-    set_cls_region(f, d, tiles_x, c);
-    c += pad256(cls_region_bytes(d, tiles_x));
-}
-// ... and the frame's parity-1 descriptor (a copy of the parity-0 one) at buffers of its own for what k2_bin writes (frame_layout.hpp)
-void place_frame_ahead(Frame2& f, const FrameDims& d, size_t tiles_x, uint8_t*& w, uint8_t*& c) {
-    w = carve_frame_ahead(f, d, w);
+// Points a frame's descriptor at its share of a work and a cls allocation (frame_layout.hpp) and moves w and c on to the next frame's;
+// ahead: f is the frame's parity-1 descriptor (a copy of the parity-0 one), which gets buffers of its own for what k2_bin writes
+void place_frame(Frame2& f, const FrameDims& d, size_t tiles_x, uint8_t*& w, uint8_t*& c, bool ahead = false) {
+    w = ahead ? carve_frame_ahead(f, d, w) : carve_frame(f, d, w);
     set_cls_region(f, d, tiles_x, c);
     c += pad256(cls_region_bytes(d, tiles_x));
 }
@@ -1341,7 +1349,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, SceneView sv, uint32_t* fb_
     sc.proto = proto;
     // ---- per-frame (kernel-written) buffers: two grow-only allocations per frame set, carved by the list in frame_layout.hpp, and the sets' descriptors
     const size_t cls_bytes = cls_region_bytes(dims, tiles_x);
-    const int n_sets = std::max(1, std::min(r->in_flight, 4));
+    const int n_sets = int(sets_wanted(r));
     // A scene uploaded into every frame set (swfr_upload_edges, or several resident frames of the builder's scene) gets two descriptors
     // per set, parity 0 and 1: a copy each of what k2_bin writes or clears, the rest shared, so that render_resident can bin a set's next
     // frame beside the row pass of the one before.  Every other route launches with parity 0, which lies where it always did.
@@ -1376,7 +1384,7 @@ int upload2(swfr_renderer* r, int si, bool all_sets, SceneView sv, uint32_t* fb_
         if (ahead) {
             Frame2& f1 = fr[4 + k];
             f1 = f;                                                                      // (the shared buffers, the framebuffer)
-            place_frame_ahead(f1, dims, tiles_x, w, c);
+            place_frame(f1, dims, tiles_x, w, c, true);
             const uint32_t* cost1_before = x.strip_cost_ahead.ptr;
             x.strip_cost_ahead.reserve(dims.strip_cost_count());
             if (x.strip_cost_ahead.ptr != cost1_before) HIP_CHECK(hipMemsetAsync(x.strip_cost_ahead.ptr, 0, x.strip_cost_ahead.cap * sizeof(uint32_t), up_stream));
@@ -1449,18 +1457,31 @@ void validate_upload(const swfr_renderer* r, const SceneView& sv) {
     validate_scene(r, sv);
 }
 
-// THE launch chain: bin -> rows -> queued rows -> linear pieces -> tiles.  events (optional): four, recorded around the three passes.
+// The frames of one launch chain: `n` descriptors from `cur` on (blockIdx.y = frame).  binned: an earlier row launch has run their k2_bin,
+// the chain starts at the row pass.  next: the row launch also bins these `n_next` frames, the same frame sets' other parity
+// (k2_rows_ahead_b) -- only under a plan that bins_ahead() admits.
+struct ChainFrames { const Frame2* cur; uint32_t n; bool binned = false; const Frame2* next = nullptr; uint32_t n_next = 0; };
+
+// THE launch chain: bin -> rows -> queued rows -> linear pieces -> tiles, or in its fused form (bin ->) rows + the next frames' bin ->
+// tiles.  events (optional): four, recorded around the three passes.
 // fb_to: the one frame's own target instead of its descriptor's (swfr_render_resident_async_to), else nullptr.
-void launch_chain(swfr_renderer* r, hipStream_t st, const Frame2* frames, uint32_t n_frames, const LaunchPlan& p, hipEvent_t* events, uint32_t* fb_to) {
+void launch_chain(swfr_renderer* r, hipStream_t st, const ChainFrames& f, const LaunchPlan& p, hipEvent_t* events, uint32_t* fb_to) {
     if (events) HIP_CHECK(hipEventRecord(events[0], st));
-    r->last_bin_threads = p.bin_threads;
-    launch2_bin(st, frames, n_frames, p.max_edges, p.max_paths, p.max_bands, p.slow_kernels, r->mono, p.bin_threads);
+    if (!f.binned) {
+        r->last_bin_threads = p.bin_threads;
+        launch2_bin(st, f.cur, f.n, p.max_edges, p.max_paths, p.max_bands, p.slow_kernels, r->mono, p.bin_threads);
+    }
     if (events) HIP_CHECK(hipEventRecord(events[1], st));
-    launch2_rows(st, frames, n_frames, p.max_chunks, p.max_path_edges, p.rows_wide, r->mono);
-    if (p.run_slow) launch2_rows_slow(st, frames, n_frames, p.grid_slow, p.grid_huge, p.slow_passes, r->mono);
-    launch2_linear_pieces(st, frames, n_frames, p.linear_grid);    // (pixman-linear tor paths: where libcairo starts each row's ramps; timed with the row pass)
+    if (f.next) {
+        launch2_rows_ahead(st, f.cur, f.next, f.n, f.n_next, p.max_edges, p.max_paths, p.max_bands, p.max_chunks);
+        ++r->last_ahead_launches;
+    } else {
+        launch2_rows(st, f.cur, f.n, p.max_chunks, p.max_path_edges, p.rows_wide, r->mono);
+        if (p.run_slow) launch2_rows_slow(st, f.cur, f.n, p.grid_slow, p.grid_huge, p.slow_passes, r->mono);
+        launch2_linear_pieces(st, f.cur, f.n, p.linear_grid);      // (pixman-linear tor paths: where libcairo starts each row's ramps; timed with the row pass)
+    }
     if (events) HIP_CHECK(hipEventRecord(events[2], st));
-    launch2_tiles(st, frames, n_frames, p.max_strips, p.tiles_grid, p.shader_level, fb_to);
+    launch2_tiles(st, f.cur, f.n, p.max_strips, p.tiles_grid, p.shader_level, fb_to);
     if (events) HIP_CHECK(hipEventRecord(events[3], st));
 }
 // k2_bin's instance for a launch whose frames have up to max_paths paths: SWFR_BIN_THREADS when set, else the small one where no frame
@@ -1492,7 +1513,7 @@ void launch_frame(swfr_renderer* r, const swfr_renderer::Scene& sc, swfr_rendere
     if (r->tiles_grid <= 0 && !overlapped) plan.tiles_grid = 0x7fffffffu;      // (a frame alone: one wavefront per strip)
     plan.bin_threads = bin_threads_of(r, plan.max_paths, overlapped);
     // the frame's descriptor (scene arrays, this set's buffers, the framebuffer) was uploaded with the scene
-    launch_chain(r, F.stream, sc.frames_dev + (&F - r->fs), 1, plan, e, fb);   // (fb: this frame's own target, else the descriptor's)
+    launch_chain(r, F.stream, {sc.frames_dev + (&F - r->fs), 1}, plan, e, fb);   // (fb: this frame's own target, else the descriptor's)
 }
 
 int check_counters(swfr_renderer* r, const uint32_t* counters) {
@@ -1522,6 +1543,32 @@ int check_counters(swfr_renderer* r, const uint32_t* counters) {
     }
     return SWFR_OK;
 }
+// The read-back of frames' counters, in two halves with the wait for `st` between them.  queue_counters: the copy of n frames'
+// counters to (pinned) host memory, queued on the frames' stream behind their kernels -- n contiguous ones from `dev` on in one
+// copy, or one copy each for the n descriptors of a launch.
+void queue_counters(hipStream_t st, uint32_t* host, const uint32_t* dev, uint32_t n = 1) {
+    HIP_CHECK(hipMemcpyAsync(host, dev, size_t(n) * COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+}
+void queue_counters(hipStream_t st, uint32_t* host, const Frame2* fr, uint32_t n) {
+    for (uint32_t k = 0; k < n; ++k) queue_counters(st, host + size_t(k) * COUNTER_WORDS, fr[k].counters);
+}
+// check_frames: check_counters over the n frames in order (swfr_stats accumulates in it), stopping at the first failure; rc: an earlier
+// failure, which stands with nothing more checked.  launched_for: the frames ran with only the queued-row kernels that scene is known
+// to need -- a frame that queued rows for the others is not valid, and is refused before its counters are checked.
+int check_frames(swfr_renderer* r, const uint32_t* host, uint32_t n, int rc = SWFR_OK, const swfr_renderer::Scene* launched_for = nullptr) {
+    for (uint32_t k = 0; k < n && rc == SWFR_OK; ++k) {
+        const uint32_t* c = host + size_t(k) * COUNTER_WORDS;
+        if (launched_for && ((launched_for->slow_state == 1 && c[C2_SLOW]) || (launched_for->slow_state == 2 && c[C2_HUGE])))
+            rc = fail(r, SWFR_ERR_DEVICE, "queued rows without their kernels in a batched launch");
+        if (rc == SWFR_OK) rc = check_counters(r, c);
+    }
+    return rc;
+}
+// the handle's pinned copy of d_counters: eight frames' worth
+uint32_t* pinned_counters(swfr_renderer* r) {
+    if (!r->h_counters) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r->h_counters), 8 * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+    return r->h_counters;
+}
 
 // One frame of the resident scene on frame set F as a graph launch: the set's kernels (with the queued-row kernels the scene is
 // known to need) are captured from the set's own stream the first time and replayed afterwards; a new upload, or a change in what
@@ -1545,10 +1592,6 @@ void ensure_frame_graph(swfr_renderer* r, const swfr_renderer::Scene& sc, swfr_r
         HIP_CHECK(hipGraphInstantiate(&F.graph_exec, F.graph, nullptr, nullptr, 0));
         F.graph_key = key;
     }
-}
-void launch_frame_graph(swfr_renderer* r, const swfr_renderer::Scene& sc, swfr_renderer::FrameSet& F) {
-    ensure_frame_graph(r, sc, F);
-    HIP_CHECK(hipGraphLaunch(F.graph_exec, F.stream));
 }
 
 // A mapped read-back that nobody has waited for yet (swfr_read_image_async) reads the last frame's framebuffer -- or its
@@ -1603,11 +1646,166 @@ void release_bitmap_slot(swfr_renderer* r, uint32_t id, DeviceBitmap& slot) {
     }
 }
 
+// ---- swfr_render_resident: frames of the resident scene, queued back to back over the frame sets and waited for.  What a call's steps share:
+struct ResidentCall {
+    uint32_t frames, n_sets, used_sets;           // used_sets: the sets that render a frame of this call (the others hold an older frame's counters)
+    uint32_t stride, first_timed, n_timed;        // per-kernel events on every stride-th frame from first_timed on: n_timed frames
+    uint32_t rb; bool batched;                    // frames per launch; more than one, so no frame is timed
+    uint32_t last_set;                            // the set of the call's last frame
+    int64_t last_on[4] = {-1, -1, -1, -1};        // per frame set's stream: the last launch of this call it carries (none: -1)
+    uint32_t last_parity[4] = {0, 0, 0, 0};       // per frame set: the descriptor its last frame of this call ran with (its counters are that one's)
+    hipEvent_t begin, end, *join;                 // behind the timed frames' events in swfr_renderer::ev
+};
+// Whether a call of several frames per launch takes the fused chain, two launches a frame (ChainFrames::next; DESIGN.md 6.1, "k2_bin of
+// the next frame in the row launch") -- only what k2_rows_ahead_b was built for; every other call keeps the three-launch chain.
+bool bins_ahead(const swfr_renderer* r, const swfr_renderer::Scene& sc, const LaunchPlan& plan) {
+    return r->bin_ahead                                               // not under SWFR_BIN_AHEAD=0
+        && sc.frames_ahead                                            // the upload made parity-1 descriptors: into every set, antialiased, not one band of several (upload2)
+        && sc.slow_verified                                           // not the scene's first call: what it needs of the queued-row kernels is not known yet
+        && !plan.run_slow                                             // not a scene with queued rows
+        && !plan.linear_grid                                          // not one with pixman-linear pieces
+        && !r->mono                                                   // not an aliased handle
+        && !r->bin_threads                                            // not under SWFR_BIN_THREADS: the fused kernel has the plan's own k2_bin instance alone
+        && !r->use_graphs                                             // not under SWFR_GRAPHS
+        && !rows_wide_instance(plan.max_path_edges, plan.rows_wide);  // not a path of more than 32 edges, nor SWFR_ROWS_WIDE: the narrow row kernel alone
+}
+// 1. the frame sets, the timed frames and their events, the frames per launch
+ResidentCall plan_resident_call(swfr_renderer* r, uint32_t frames) {
+    ResidentCall C{};
+    C.frames = frames; C.n_sets = frames > 1 ? sets_of_scene(r) : 1u; C.used_sets = std::min(frames, C.n_sets);
+    C.stride = r->event_stride < 1 ? 1u : uint32_t(r->event_stride);
+    if (frames < 64 && !r->event_stride_given) C.stride = std::min(C.stride, 8u);   // (a short run still gets two or three frames with per-kernel times, unless SWFR_EVENT_STRIDE says otherwise)
+    C.first_timed = std::min(C.stride / 2, frames - 1);               // (not frame 0: the first frames run before the pipeline is full)
+    C.n_timed = (frames - C.first_timed + C.stride - 1) / C.stride;
+    // events: four per timed frame (indexed by the timed frame's ordinal), then begin, end and the joins; created once, never inside
+    // a later call's timed region unless it times more frames than any call before
+    for (hipEvent_t e = nullptr; r->ev.size() < size_t(C.n_timed) * 4 + 5; r->ev.push_back(e)) HIP_CHECK(hipEventCreate(&e));
+    C.begin = r->ev[size_t(C.n_timed) * 4]; C.end = r->ev[size_t(C.n_timed) * 4 + 1]; C.join = &r->ev[size_t(C.n_timed) * 4 + 2];
+    // Frames per launch: the frame sets are cut into groups of `rb` (their descriptors are contiguous), a group's frames are one launch
+    // per kernel (blockIdx.y = frame) on the group's first stream, and the groups alternate -- a third of the host's launches per
+    // frame (three launches take the host about as long as a frame takes the GPU) and the GPU still has two streams to overlap.
+    // Only without per-kernel events (a timed frame is launched alone).
+    C.rb = (r->resident_batch >= 2 && C.stride > frames) ? uint32_t(r->resident_batch) : 1u;
+    while (C.rb > 1 && (C.rb > C.n_sets || C.n_sets % C.rb != 0)) --C.rb;
+    C.batched = C.rb > 1 && frames >= 2;
+    C.last_set = (frames - 1) % C.n_sets;
+    return C;
+}
+// 2. all frames are queued back to back, rotating over the frame sets; events bracket every kernel on the stream a timed frame runs on
+void queue_resident_frames(swfr_renderer* r, const swfr_renderer::Scene& sc, ResidentCall& C) {
+    const uint32_t frames = C.frames, n_sets = C.n_sets, rb = C.rb;
+    // (no clearing of the counters here: k2_bin zeroes its frame's counters itself)
+    // every frame set's graph exists before the first launch: a call never captures one between two frames (a short first call --
+    // a warm-up of a few frames -- would otherwise leave the capture of the sets it launched with events to the next call)
+    const bool graphs = frames > 1 && r->use_graphs && sc.slow_verified;
+    if (graphs && !(r->resident_batch >= 2 && C.stride > frames))
+        for (uint32_t k = 0; k < n_sets; ++k) ensure_frame_graph(r, sc, r->fs[k]);
+    HIP_CHECK(hipEventRecord(C.begin, r->stream));
+    order_frames_behind_pending_read(r);
+#ifdef SWFR_BEGIN_WAIT
+    for (uint32_t k = 1; k < n_sets; ++k) HIP_CHECK(hipStreamWaitEvent(r->fs[k].stream, C.begin, 0));
+#endif
+    // (the other sets' streams are not ordered behind the begin event: every call ends with all streams joined and waited for, an upload
+    //  orders them behind its copy, and three more API calls before the first launch cost a short call a microsecond per frame)
+    r->last_ahead_launches = 0;
+    if (C.batched) {
+        const uint32_t groups = n_sets / rb, launches = (frames + rb - 1) / rb;
+        const LaunchPlan plan = plan_of(r, sc);                // (as a frame of its own, with the tile pass in its default shape unless SWFR_TILES_GRID caps it)
+        // The fused chain: a group's launch k of the call runs with the descriptors of parity k & 1 (k2_bin first when k == 0) and its row
+        // launch bins the group's next frames into the other parity's -- but for the group's last launch of the call: nothing is binned that
+        // no row pass reads, so each strip_cost copy sees one row pass between two clears, across calls and the routes that use parity 0 alone.
+        const bool ahead = bins_ahead(r, sc, plan);
+        uint32_t gi = 0;
+        for (uint32_t f = 0; f < frames; f += rb, ++gi) {
+            const uint32_t g = gi % groups, cnt = std::min(rb, frames - f);
+            ChainFrames cf{sc.frames_dev + g * rb, cnt};
+            if (ahead) {
+                const uint32_t parity = (gi / groups) & 1u;
+                if (parity) cf.cur = sc.frames_ahead + g * rb;
+                cf.binned = gi >= groups;                       // (all but the prologue: the group's launch before this one binned these frames)
+                if (gi + groups < launches) { cf.next = (parity ? sc.frames_dev : sc.frames_ahead) + g * rb; cf.n_next = std::min(rb, frames - (f + groups * rb)); }
+                for (uint32_t k = 0; k < cnt; ++k) C.last_parity[g * rb + k] = parity;
+            }
+            launch_chain(r, r->fs[g * rb].stream, cf, plan, nullptr, nullptr);
+            C.last_set = g * rb + cnt - 1;
+            C.last_on[g * rb] = int64_t(gi);
+        }
+    } else for (uint32_t f = 0; f < frames; ++f) {
+        swfr_renderer::FrameSet& F = r->fs[f % n_sets];
+        const bool timed = f >= C.first_timed && (f - C.first_timed) % C.stride == 0;   // per-kernel events on every stride-th frame (each costs a queue packet)
+        if (!timed && graphs) { ensure_frame_graph(r, sc, F); HIP_CHECK(hipGraphLaunch(F.graph_exec, F.stream)); }
+        else launch_frame(r, sc, F, nullptr, timed ? &r->ev[size_t((f - C.first_timed) / C.stride) * 4] : nullptr, n_sets > 1 && frames > 1);
+        C.last_on[f % n_sets] = int64_t(f);
+    }
+}
+// 3. the other streams join the handle's, the counters are copied behind the last kernel, and every stream is waited for
+void join_resident_streams(swfr_renderer* r, ResidentCall& C) {
+    for (uint32_t k = 1; k < C.n_sets; ++k) {              // (only the streams that carried something join)
+        if (C.last_on[k] < 0) continue;
+        HIP_CHECK(hipEventRecord(C.join[k - 1], r->fs[k].stream));
+        HIP_CHECK(hipStreamWaitEvent(r->stream, C.join[k - 1], 0));
+    }
+    HIP_CHECK(hipEventRecord(C.end, r->stream));
+    HIP_CHECK(hipGetLastError());
+    // the counters of every set come back through pinned memory behind the last kernel: one synchronisation for everything
+    // (a set whose last frame ran with its parity-1 descriptor left that frame's counters four sets further on: all eight come back)
+    queue_counters(r->stream, pinned_counters(r), r->d_counters.ptr, r->last_ahead_launches ? 8u : C.used_sets);
+    // The other sets' streams are waited for too, in the order their last frames finish: the runtime then knows them idle, and a
+    // hipDeviceSynchronize behind this call (torch.cuda.synchronize()) costs 3 us instead of 47 (it drains every stream it has not seen
+    // idle, 12 us apiece).  All but the last of these waits return while the GPU is still at the call's last frames.
+    for (;;) {
+        int pick = -1;
+        for (uint32_t k = 1; k < C.n_sets; ++k)
+            if (C.last_on[k] >= 0 && (pick < 0 || C.last_on[k] < C.last_on[pick])) pick = int(k);
+        if (pick < 0) break;
+        if (r->fs[pick].stream) HIP_CHECK(hipStreamSynchronize(r->fs[pick].stream));
+        C.last_on[pick] = -1;
+    }
+    HIP_CHECK(hipStreamSynchronize(r->stream));
+}
+// ... and the call's times: swfr_last_timing but for n_records
+void read_resident_times(swfr_renderer* r, const swfr_renderer::Scene& sc, const ResidentCall& C) {
+    float setup_ms = 0, rows_ms = 0, tiles_ms = 0, total_ms = 0;
+    uint32_t timed_frames = 0;
+    for (uint32_t f = C.batched ? C.frames : C.first_timed; f < C.frames; f += C.stride, ++timed_frames) {      // (frames per launch: no per-kernel events)
+        hipEvent_t* e = &r->ev[size_t(timed_frames) * 4];
+        float a = 0, b = 0, c = 0;
+        HIP_CHECK(hipEventElapsedTime(&a, e[0], e[1]));
+        HIP_CHECK(hipEventElapsedTime(&b, e[1], e[2]));
+        HIP_CHECK(hipEventElapsedTime(&c, e[2], e[3]));
+        setup_ms += a; rows_ms += b; tiles_ms += c;
+    }
+    HIP_CHECK(hipEventElapsedTime(&total_ms, C.begin, C.end));
+    r->timing = swfr_timing{total_ms, setup_ms, rows_ms, tiles_ms, C.frames, sc.dims.n_edges, sc.dims.n_paths, sc.dims.n_rows, 0, timed_frames};
+}
+// 4. set k's counters of its last frame of the call: error flags, queued rows, queue passes, records
+const uint32_t* set_counters(const swfr_renderer* r, const ResidentCall& C, uint32_t k) {
+    return r->h_counters + size_t(C.last_parity[k] ? 4 + k : k) * COUNTER_WORDS;
+}
+// 5. what the scene needs of the queued-row kernels, from the frames' own counters: kept for its next frames and as the next scene's guess.
+// False: the launches were not enough for that guess -- rows were left in a queue nobody read, and the scene is set to launch everything
+bool learn_queued_rows(swfr_renderer* r, const ResidentCall& C) {
+    swfr_renderer::Scene& sc = r->scn[0];
+    uint32_t slow = 0, huge = 0, passes = 1;
+    for (uint32_t k = 0; k < C.used_sets; ++k) {
+        const uint32_t* c = set_counters(r, C, k);
+        slow |= c[C2_SLOW]; huge |= c[C2_HUGE];
+        for (uint32_t q = 1; q < SLOW_PASSES; ++q)
+            if (c[C2_SLOWQ + q] | c[C2_HUGEQ + q]) { passes = std::max(passes, q + 1); huge |= c[C2_HUGEQ + q]; }
+    }
+    const bool short_launch = (sc.slow_state == 1 && slow) || (sc.slow_state == 2 && huge) || passes > sc.slow_passes;
+    sc.slow_state = slow == 0 ? 1 : (huge == 0 ? 2 : 0); sc.slow_passes = passes;     // what the next frames of this resident scene can skip
+    r->hint_slow_state = sc.slow_state; r->hint_slow_passes = passes;
+    sc.slow_verified = !short_launch;
+    if (short_launch) { sc.slow_state = 0; sc.slow_passes = SLOW_PASSES; }
+    return !short_launch;
+}
+
 int render_resident(swfr_renderer* r, uint32_t frames) {
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
     if (!r->scene_ready) return fail(r, SWFR_ERR_INVALID, "no scene uploaded");
     if (frames == 0) frames = 1;
-    if (frames > 1 && r->scene_from_builder && r->sets_ready < uint32_t(std::max(1, std::min(r->in_flight, 4)))) {
+    if (frames > 1 && r->scene_from_builder && r->sets_ready < sets_wanted(r)) {
         // swfr_render prepared one frame set for its one frame; several frames of the same scene rotate over all of them
         const int rc = upload2(r, 0, true, builder_view(r), nullptr, true);
         if (rc != SWFR_OK) return rc;
@@ -1619,161 +1817,21 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
         if (rc != SWFR_OK) return rc;
         --frames;
     }
-    const swfr_renderer::Scene& sc = r->scn[0];
-    float setup_ms = 0, rows_ms = 0, tiles_ms = 0, total_ms = 0;
-    uint32_t counters[COUNTER_WORDS] = {};
     if (frames > 4096) frames = 4096;
-    // all frames are queued back to back, rotating over the frame sets; events bracket every kernel on the stream the frame runs on
-    uint32_t n_sets = 1;
-    if (frames > 1)
-        while (n_sets < uint32_t(std::min(r->in_flight, 4)) && n_sets < r->sets_ready && r->fs[n_sets].stream && (r->n_targets || r->fs[n_sets].d_fb.ptr)) ++n_sets;
-    uint32_t stride = r->event_stride < 1 ? 1u : uint32_t(r->event_stride);
-    if (frames < 64 && !r->event_stride_given) stride = std::min(stride, 8u);   // (a short run still gets two or three frames with per-kernel times, unless SWFR_EVENT_STRIDE says otherwise)
-    const uint32_t first_timed = std::min(stride / 2, frames - 1);      // (not frame 0: the first frames run before the pipeline is full)
-    const uint32_t n_timed = (frames - first_timed + stride - 1) / stride;
-    // events: four per timed frame (indexed by the timed frame's ordinal), then begin, end and the joins; created once, never inside
-    // a later call's timed region unless it times more frames than any call before
-    while (r->ev.size() < size_t(n_timed) * 4 + 5) {
-        hipEvent_t e = nullptr;
-        HIP_CHECK(hipEventCreate(&e));
-        r->ev.push_back(e);
-    }
-    hipEvent_t ev_begin = r->ev[size_t(n_timed) * 4], ev_end = r->ev[size_t(n_timed) * 4 + 1];
-    hipEvent_t* ev_join = &r->ev[size_t(n_timed) * 4 + 2];
-    // (no clearing of the counters here: k2_bin zeroes its frame's counters itself)
-    // every frame set's graph exists before the first launch: a call never captures one between two frames (a short first call --
-    // a warm-up of a few frames -- would otherwise leave the capture of the sets it launched with events to the next call)
-    if (frames > 1 && r->use_graphs && sc.slow_verified && !(r->resident_batch >= 2 && stride > frames))
-        for (uint32_t k = 0; k < n_sets; ++k) ensure_frame_graph(r, sc, r->fs[k]);
-    HIP_CHECK(hipEventRecord(ev_begin, r->stream));
-    order_frames_behind_pending_read(r);
-#ifdef SWFR_BEGIN_WAIT
-    for (uint32_t k = 1; k < n_sets; ++k) HIP_CHECK(hipStreamWaitEvent(r->fs[k].stream, ev_begin, 0));
-#endif
-    // (the other sets' streams are not ordered behind ev_begin: every call ends with all streams joined and waited for, an upload orders
-    //  them behind its copy, and three more API calls before the first launch cost a short call a microsecond per frame)
-    // Frames per launch: the frame sets are cut into groups of `rb` (their descriptors are contiguous), a group's frames are one launch
-    // per kernel (blockIdx.y = frame) on the group's first stream, and the groups alternate -- a third of the host's launches per
-    // frame (three launches take the host about as long as a frame takes the GPU) and the GPU still has two streams to overlap.
-    // Only without per-kernel events (a timed frame is launched alone).
-    uint32_t rb = (r->resident_batch >= 2 && stride > frames) ? uint32_t(r->resident_batch) : 1u;
-    while (rb > 1 && (rb > n_sets || n_sets % rb != 0)) --rb;
-    const bool batched = rb > 1 && frames >= 2;
-    uint32_t last_set = (frames - 1) % n_sets;
-    int64_t last_on[4] = {-1, -1, -1, -1};                 // per frame set's stream: the last launch of this call it carries (none: -1)
-    uint32_t last_parity[4] = {0, 0, 0, 0};                // per frame set: the descriptor its last frame of this call ran with (its counters are that one's)
-    r->last_ahead_launches = 0;
-    if (batched) {
-        const uint32_t groups = n_sets / rb;
-        const LaunchPlan plan = plan_of(r, sc);                // (as a frame of its own, with the tile pass in its default shape unless SWFR_TILES_GRID caps it)
-        // Two launches a frame instead of three ("k2_bin of the next frame in the row launch"): a group's first launch of
-        // the call is k2_bin on parity 0; then iteration k runs with the descriptors of parity k & 1 and its row launch bins the group's
-        // next frames into the other parity's (k2_rows_ahead_b) -- but for the group's last launch of the call, whose row pass is plain
-        // k2_rows_b: nothing is binned that no row pass reads, so each strip_cost copy sees exactly one row pass between two clears,
-        // across calls and across the routes that use parity 0 alone.  Only what the fused kernel was built for: a verified scene
-        // without queued rows, the narrow antialiased row kernel, no pixman-linear pieces, the plan's own k2_bin instance, no graphs.
-        const bool ahead = r->bin_ahead && sc.frames_ahead && sc.slow_verified && !plan.run_slow && !plan.linear_grid && !r->mono && !r->bin_threads &&
-                           !r->use_graphs && !rows_wide_instance(plan.max_path_edges, plan.rows_wide);     // (a frame of box paths alone: the row launch is the bin workgroups)
-        const uint32_t launches = (frames + rb - 1) / rb;
-        uint32_t gi = 0;
-        for (uint32_t f = 0; f < frames; f += rb, ++gi) {
-            const uint32_t g = gi % groups, cnt = std::min(rb, frames - f);
-            const hipStream_t st = r->fs[g * rb].stream;
-            if (!ahead) launch_chain(r, st, sc.frames_dev + g * rb, cnt, plan, nullptr, nullptr);
-            else {
-                const uint32_t parity = (gi / groups) & 1u;
-                const Frame2* cur = (parity ? sc.frames_ahead : sc.frames_dev) + g * rb;
-                const Frame2* next = (parity ? sc.frames_dev : sc.frames_ahead) + g * rb;
-                if (gi < groups) {                                 // the prologue
-                    r->last_bin_threads = plan.bin_threads;
-                    launch2_bin(st, cur, cnt, plan.max_edges, plan.max_paths, plan.max_bands, 0u, false, plan.bin_threads);
-                }
-                if (gi + groups < launches) {
-                    const uint32_t next_cnt = std::min(rb, frames - (f + groups * rb));
-                    launch2_rows_ahead(st, cur, next, cnt, next_cnt, plan.max_edges, plan.max_paths, plan.max_bands, plan.max_chunks);
-                    ++r->last_ahead_launches;
-                } else launch2_rows(st, cur, cnt, plan.max_chunks, plan.max_path_edges, false, false);
-                launch2_tiles(st, cur, cnt, plan.max_strips, plan.tiles_grid, plan.shader_level, nullptr);
-                for (uint32_t k = 0; k < cnt; ++k) last_parity[g * rb + k] = parity;
-            }
-            last_set = g * rb + cnt - 1;
-            last_on[g * rb] = int64_t(gi);
-        }
-    }
-    for (uint32_t f = 0; f < frames && !batched; ++f) {
-        swfr_renderer::FrameSet& F = r->fs[f % n_sets];
-        const bool timed = f >= first_timed && (f - first_timed) % stride == 0;   // per-kernel events on every stride-th frame (each costs a queue packet)
-        if (!timed && frames > 1 && r->use_graphs && sc.slow_verified) launch_frame_graph(r, sc, F);
-        else launch_frame(r, sc, F, nullptr, timed ? &r->ev[size_t((f - first_timed) / stride) * 4] : nullptr, n_sets > 1 && frames > 1);
-        last_on[f % n_sets] = int64_t(f);
-    }
-    for (uint32_t k = 1; k < n_sets; ++k) {                // (only the streams that carried something join)
-        if (last_on[k] < 0) continue;
-        HIP_CHECK(hipEventRecord(ev_join[k - 1], r->fs[k].stream));
-        HIP_CHECK(hipStreamWaitEvent(r->stream, ev_join[k - 1], 0));
-    }
-    HIP_CHECK(hipEventRecord(ev_end, r->stream));
-    HIP_CHECK(hipGetLastError());
-    // the counters of every set come back through pinned memory behind the last kernel: one synchronisation for everything
-    if (!r->h_counters) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r->h_counters), 8 * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
-    const uint32_t used_sets = std::min(frames, n_sets);               // (a set that rendered no frame of this call holds an older frame's counters)
-    // (a set whose last frame ran with its parity-1 descriptor left that frame's counters four sets further on: all eight come back)
-    const bool any_ahead = r->last_ahead_launches != 0;
-    HIP_CHECK(hipMemcpyAsync(r->h_counters, r->d_counters.ptr, size_t(any_ahead ? 8 : used_sets) * COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-    // The other sets' streams are waited for too, in the order their last frames finish: the runtime then knows them idle, and a
-    // hipDeviceSynchronize behind this call (torch.cuda.synchronize()) costs 3 us instead of 47 (it drains every stream it has not seen
-    // idle, 12 us apiece).  All but the last of these waits return while the GPU is still at the call's last frames.
-    for (;;) {
-        int pick = -1;
-        for (uint32_t k = 1; k < n_sets; ++k)
-            if (last_on[k] >= 0 && (pick < 0 || last_on[k] < last_on[pick])) pick = int(k);
-        if (pick < 0) break;
-        if (r->fs[pick].stream) HIP_CHECK(hipStreamSynchronize(r->fs[pick].stream));
-        last_on[pick] = -1;
-    }
-    HIP_CHECK(hipStreamSynchronize(r->stream));
-    r->fb_cur = r->n_targets ? r->targets[last_set % r->n_targets] : r->fs[last_set].d_fb.ptr;
-    uint32_t timed_frames = 0;
-    for (uint32_t f = batched ? frames : first_timed; f < frames; f += stride, ++timed_frames) {      // (frames per launch: no per-kernel events)
-        hipEvent_t* e = &r->ev[size_t(timed_frames) * 4];
-        float a = 0, b = 0, c = 0;
-        HIP_CHECK(hipEventElapsedTime(&a, e[0], e[1]));
-        HIP_CHECK(hipEventElapsedTime(&b, e[1], e[2]));
-        HIP_CHECK(hipEventElapsedTime(&c, e[2], e[3]));
-        setup_ms += a; rows_ms += b; tiles_ms += c;
-    }
-    HIP_CHECK(hipEventElapsedTime(&total_ms, ev_begin, ev_end));
-    for (uint32_t k = 0; k < used_sets; ++k)                // per set, the counters of the last frame it rendered: error flags, queued rows, queue passes, records
-        if (last_parity[k]) std::memcpy(r->h_counters + k * COUNTER_WORDS, r->h_counters + (4 + k) * COUNTER_WORDS, COUNTER_WORDS * sizeof(uint32_t));
-    std::memcpy(counters, r->h_counters, sizeof counters);
-    for (uint32_t k = 1; k < used_sets; ++k)               // (set 0's counts, every set's error and limit flags)
+    const swfr_renderer::Scene& sc = r->scn[0];
+    ResidentCall C = plan_resident_call(r, frames);
+    queue_resident_frames(r, sc, C);
+    join_resident_streams(r, C);
+    r->fb_cur = r->n_targets ? r->targets[C.last_set % r->n_targets] : r->fs[C.last_set].d_fb.ptr;
+    read_resident_times(r, sc, C);
+    uint32_t counters[COUNTER_WORDS];
+    std::memcpy(counters, set_counters(r, C, 0), sizeof counters);
+    for (uint32_t k = 1; k < C.used_sets; ++k)             // (set 0's counts, every set's error and limit flags)
         for (uint32_t w : {uint32_t(C2_ERROR), uint32_t(C2_TIE_PAIRTEST_SKIPPED), uint32_t(C2_TIE_SORT_OVERFLOW), uint32_t(C2_TIE_DEPTH)})
-            counters[w] |= r->h_counters[k * COUNTER_WORDS + w];
-    r->timing = swfr_timing{total_ms, setup_ms, rows_ms, tiles_ms, frames, sc.dims.n_edges, sc.dims.n_paths, sc.dims.n_rows, 0, timed_frames};
-    r->fb_valid = true;
-    {
-        uint32_t slow = 0, huge = 0;
-        for (uint32_t k = 0; k < used_sets; ++k) { slow |= r->h_counters[k * COUNTER_WORDS + C2_SLOW]; huge |= r->h_counters[k * COUNTER_WORDS + C2_HUGE]; }
-        uint32_t passes = 1;
-        for (uint32_t k = 0; k < used_sets; ++k)
-            for (uint32_t q = 1; q < SLOW_PASSES; ++q) {
-                const uint32_t* c = r->h_counters + k * COUNTER_WORDS;
-                if (c[C2_SLOWQ + q] | c[C2_HUGEQ + q]) { passes = std::max(passes, q + 1); huge |= c[C2_HUGEQ + q]; }
-            }
-        // were the launches enough?  (a resident scene starts with everything, or with the previous scene's needs as a guess)
-        const bool short_launch = (sc.slow_state == 1 && slow) || (sc.slow_state == 2 && huge) || passes > sc.slow_passes;
-        r->scn[0].slow_state = slow == 0 ? 1 : (huge == 0 ? 2 : 0);     // what the next frames of this resident scene can skip
-        r->scn[0].slow_passes = passes;
-        r->hint_slow_state = r->scn[0].slow_state; r->hint_slow_passes = passes;
-        r->scn[0].slow_verified = !short_launch;
-        if (short_launch) {                                    // rows were left in a queue nobody read: the frames are not valid
-            r->scn[0].slow_state = 0; r->scn[0].slow_passes = SLOW_PASSES;
-            r->fb_valid = false;
-            return render_resident(r, frames);
-        }
-        r->timing.n_records = 0;
-        for (uint32_t h = 0; h < C2_HEADS; ++h) r->timing.n_records += counters[C2_HEAD + h];     // cells of the last frame of set 0
-    }
+            counters[w] |= set_counters(r, C, k)[w];
+    r->fb_valid = learn_queued_rows(r, C);
+    if (!r->fb_valid) return render_resident(r, frames);   // (a short launch: the frames are not valid, and are rendered again with everything)
+    for (uint32_t h = 0; h < C2_HEADS; ++h) r->timing.n_records += counters[C2_HEAD + h];     // cells of the last frame of set 0
     return check_counters(r, counters);
 }
 
@@ -1894,16 +1952,15 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
     int rc = SWFR_OK;
     double device_ms = 0;                                   // kernels only, summed over the groups (they do not overlap each other much)
     uint32_t gi = 0;
-    struct Pending { uint32_t first, count; };
-    Pending pend[2] = {{0, 0}, {0, 0}};
+    uint32_t pend[2] = {0, 0};                              // per group: the frames of its launch whose counters have not been checked
     auto finish_group = [&](int g) {                        // waits for a group's launches and checks its frames' counters
         auto& G = r->groups[g];
-        if (!pend[g].count) return;
+        if (!pend[g]) return;
         HIP_CHECK(hipStreamSynchronize(G.stream));
         float ms = 0;
         if (hipEventElapsedTime(&ms, G.ev_begin, G.ev_end) == hipSuccess) device_ms += ms;
-        for (uint32_t k = 0; k < pend[g].count && rc == SWFR_OK; ++k) rc = check_counters(r, G.h_counters + size_t(k) * COUNTER_WORDS);
-        pend[g].count = 0;
+        rc = check_frames(r, G.h_counters, pend[g], rc);
+        pend[g] = 0;
     };
     try {
         for (uint32_t first = 0; first < n && rc == SWFR_OK; first += B, ++gi) {
@@ -1966,12 +2023,11 @@ int render_batch2(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* 
             t_stage += ms_since(t0); t0 = clk::now();
             if (!G.ev_begin) { HIP_CHECK(hipEventCreate(&G.ev_begin)); HIP_CHECK(hipEventCreate(&G.ev_end)); }
             HIP_CHECK(hipEventRecord(G.ev_begin, G.stream));
-            launch_chain(r, G.stream, frames_dev, cnt, plan, nullptr, nullptr);
+            launch_chain(r, G.stream, {frames_dev, cnt}, plan, nullptr, nullptr);
             HIP_CHECK(hipEventRecord(G.ev_end, G.stream));
-            for (uint32_t k = 0; k < cnt; ++k)
-                HIP_CHECK(hipMemcpyAsync(G.h_counters + size_t(k) * COUNTER_WORDS, fr[k].counters, COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, G.stream));
+            queue_counters(G.stream, G.h_counters, fr.data(), cnt);
             HIP_CHECK(hipGetLastError());
-            pend[g] = Pending{first, cnt};
+            pend[g] = cnt;
             r->fb_cur = fr[cnt - 1].fb;
             t_launch += ms_since(t0);
         }
@@ -2037,28 +2093,20 @@ int render_resident_batched(swfr_renderer* r, uint32_t per_launch, uint32_t laun
     LaunchPlan plan = plan_of(r, sc);
     plan.grid_slow = 256u; plan.grid_huge = sc.slow_state == 2 ? 0u : 64u; plan.tiles_grid = ~0u;
     plan.bin_threads = bin_threads_of(r, plan.max_paths, B > 1);
-    launch_chain(r, st, r->rb_frames.ptr, B, plan, nullptr, nullptr);      // warm-up: leaves a cost history for the strip order
+    launch_chain(r, st, {r->rb_frames.ptr, B}, plan, nullptr, nullptr);    // warm-up: leaves a cost history for the strip order
     HIP_CHECK(hipEventRecord(r->rb_ev[0], st));
-    for (uint32_t l = 0; l < launches; ++l) launch_chain(r, st, r->rb_frames.ptr, B, plan, nullptr, nullptr);
+    for (uint32_t l = 0; l < launches; ++l) launch_chain(r, st, {r->rb_frames.ptr, B}, plan, nullptr, nullptr);
     HIP_CHECK(hipEventRecord(r->rb_ev[1], st));
     HIP_CHECK(hipGetLastError());
     std::vector<uint32_t> hc(size_t(B) * COUNTER_WORDS);
-    for (uint32_t k = 0; k < B; ++k)
-        HIP_CHECK(hipMemcpyAsync(hc.data() + size_t(k) * COUNTER_WORDS, fr[k].counters, COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    queue_counters(st, hc.data(), fr.data(), B);
     HIP_CHECK(hipStreamSynchronize(st));
     float ms = 0;
     HIP_CHECK(hipEventElapsedTime(&ms, r->rb_ev[0], r->rb_ev[1]));
     if (ms_out) *ms_out = ms;
     r->fb_cur = fr[B - 1].fb;
     r->fb_valid = true;
-    int rc = SWFR_OK;
-    for (uint32_t k = 0; k < B && rc == SWFR_OK; ++k) {
-        const uint32_t* c = hc.data() + size_t(k) * COUNTER_WORDS;
-        // a frame that queued rows for kernels this call did not launch is not valid
-        if ((sc.slow_state == 1 && c[C2_SLOW]) || (sc.slow_state == 2 && c[C2_HUGE])) rc = fail(r, SWFR_ERR_DEVICE, "queued rows without their kernels in a batched launch");
-        if (rc == SWFR_OK) rc = check_counters(r, c);
-    }
-    return rc;
+    return check_frames(r, hc.data(), B, SWFR_OK, &sc);       // (a frame that queued rows for kernels this call did not launch is not valid)
 }
 
 int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* device_dst, size_t frame_stride) {
@@ -2067,7 +2115,7 @@ int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* d
     if (device_dst && frame_stride < size_t(r->width) * r->height * 4) return fail(r, SWFR_ERR_INVALID, "frame stride smaller than a frame");
     if (device_dst && r->batch_frames > 1) return render_batch2(r, stages, n, device_dst, frame_stride);
     order_frames_behind_pending_read(r);                       // (frames without a device_dst land in the frame sets' own framebuffers)
-    const uint32_t n_sets = uint32_t(std::max(1, std::min(r->in_flight, 4)));
+    const uint32_t n_sets = sets_wanted(r);
     uint32_t* hc = nullptr;
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hc), size_t(n) * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
     int rc = SWFR_OK;
@@ -2086,7 +2134,7 @@ int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* d
             swfr_renderer::FrameSet& F = r->fs[k];
             if (k > 0 && i < n_sets) HIP_CHECK(hipStreamSynchronize(r->stream));   // first use of the set: bitmap table etc. are in place
             launch_frame(r, r->scn[k], F, nullptr, nullptr, n_sets > 1 && n > 1);     // (the descriptor carries the frame's target)
-            HIP_CHECK(hipMemcpyAsync(hc + size_t(i) * COUNTER_WORDS, F.counters, COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, F.stream));
+            queue_counters(F.stream, hc + size_t(i) * COUNTER_WORDS, F.counters);
             r->fb_cur = fb_dst ? fb_dst : F.d_fb.ptr;
         }
         HIP_CHECK(hipGetLastError());
@@ -2105,8 +2153,7 @@ int render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n, void* d
     }
     r->scene_ready = false;                 // scene 0 now holds some frame of the batch, not a scene the caller uploaded
     r->fb_valid = true;
-    if (rc == SWFR_OK)
-        for (uint32_t i = 0; i < n && rc == SWFR_OK; ++i) rc = check_counters(r, hc + size_t(i) * COUNTER_WORDS);
+    rc = check_frames(r, hc, n, rc);
     (void)hipHostFree(hc);
     return rc;
 }
@@ -2151,8 +2198,7 @@ int render_resident_async(swfr_renderer* r, void* block_target, uint32_t* out_se
     const BandShare bs = band_share(r);
     if (block_target && bs.stride != 1) return fail(r, SWFR_ERR_INVALID, "a block target needs a handle that owns one contiguous block of tile-rows");
     return guarded(r, [&]() {
-        uint32_t n_sets = 1;
-        while (n_sets < uint32_t(std::min(r->in_flight, 4)) && n_sets < r->sets_ready && r->fs[n_sets].stream && r->fs[n_sets].work.ptr) ++n_sets;
+        const uint32_t n_sets = sets_of_scene(r);
         const uint32_t k = r->async_next++ % n_sets;
         r->async_used |= 1u << k;
         if (!r->scn[0].slow_verified) { r->scn[0].slow_state = 0; r->scn[0].slow_passes = SLOW_PASSES; }   // (nothing checks an async frame's queues: launch everything unless a blocking frame of this scene has shown what it needs)
@@ -2167,6 +2213,39 @@ int render_resident_async(swfr_renderer* r, void* block_target, uint32_t* out_se
         if (out_set) *out_set = k;
         return int(SWFR_OK);
     });
+}
+
+// The skeleton of the swfr_debug_time_* probes, on the handle's stream: the device buffers are allocated (and set to their fill byte),
+// the events created, `warm_up` run once; then each phase's launch is queued `reps` times between two events, the last event waited
+// for, and *ms of each phase is the time of one of its launches.  The buffers and events are freed behind a wait for the stream,
+// whether or not something threw.
+struct ProbeBuffer { uint32_t** ptr; size_t bytes; int fill; };      // *ptr: nullptr on entry; fill < 0: left as allocated
+struct ProbePhase { std::function<void()> launch; float* ms; };
+int time_phases(swfr_renderer* r, uint32_t reps, std::initializer_list<ProbeBuffer> buffers, const std::function<void()>& warm_up, std::initializer_list<ProbePhase> phases) {
+    std::vector<hipEvent_t> e(phases.size() + 1, nullptr);
+    std::exception_ptr failure;
+    try {
+        for (const ProbeBuffer& b : buffers) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(b.ptr), b.bytes));
+        for (const ProbeBuffer& b : buffers) if (b.fill >= 0) HIP_CHECK(hipMemsetAsync(*b.ptr, b.fill, b.bytes, r->stream));
+        for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
+        warm_up();
+        HIP_CHECK(hipEventRecord(e[0], r->stream));
+        for (size_t k = 0; k < phases.size(); ++k) {
+            for (uint32_t i = 0; i < reps; ++i) phases.begin()[k].launch();
+            HIP_CHECK(hipEventRecord(e[k + 1], r->stream));
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventSynchronize(e.back()));
+        for (size_t k = 0; k < phases.size(); ++k) HIP_CHECK(hipEventElapsedTime(phases.begin()[k].ms, e[k], e[k + 1]));
+        for (const ProbePhase& ph : phases) *ph.ms /= float(reps);
+    } catch (...) {
+        failure = std::current_exception();
+    }
+    (void)hipStreamSynchronize(r->stream);
+    for (const ProbeBuffer& b : buffers) if (*b.ptr) (void)hipFree(*b.ptr);
+    for (auto& x : e) if (x) (void)hipEventDestroy(x);
+    if (failure) std::rethrow_exception(failure);
+    return SWFR_OK;
 }
 
 // (swfr_last_error(NULL): why this thread's last swfr_create refused a flag combination, if it did)
@@ -2227,7 +2306,7 @@ int swfr_create(uint32_t width, uint32_t height, const swfr_config* cfg, swfr_re
         HIP_CHECK(hipStreamCreateWithFlags(&raw->stream, hipStreamNonBlocking));
         raw->fs[0].stream = raw->stream;
         // the frame sets' streams first: HIP deals streams onto a few hardware queues in creation order, and the sets must not share one
-        for (int k = 1; k < std::max(1, std::min(raw->in_flight, 4)); ++k) HIP_CHECK(hipStreamCreateWithFlags(&raw->fs[k].stream, hipStreamNonBlocking));
+        for (uint32_t k = 1; k < sets_wanted(raw); ++k) HIP_CHECK(hipStreamCreateWithFlags(&raw->fs[k].stream, hipStreamNonBlocking));
         for (int i = 0; i < 4 * 32 + 5; ++i) { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreate(&e)); raw->ev.push_back(e); }   // (so that no render call has to create its timing events inside somebody's timed region)
         raw->fs[0].d_fb.reserve(size_t(width) * height);
         HIP_CHECK(hipMemsetAsync(raw->fs[0].d_fb.ptr, 0, size_t(width) * height * 4, raw->stream));
@@ -2351,35 +2430,14 @@ int swfr_debug_time_cxform(swfr_renderer* r, uint32_t bitmap_id, const swfr_colo
             for (int k = 0; k < 4; ++k) w |= uint32_t(std::clamp(((c * ct->mult[k]) >> 8) + ct->add[k], 0, 255)) << (8 * k);
             chain[c] = w;
         }
-        uint32_t* out = nullptr;
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        std::exception_ptr failure;
-        try {
-            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&out), bytes + CX_TABLE_BYTES));
+        uint32_t* out = nullptr;                                                                    // the texels, and behind them the table
+        const auto pass = [&]() { launch_cxform_texels(r->stream, bm.d_straight, out, n, out + n); };
+        const auto copy = [&]() { HIP_CHECK(hipMemcpyAsync(out, bm.d_straight, bytes, hipMemcpyDeviceToDevice, r->stream)); };
+        return time_phases(r, reps, {{&out, bytes + CX_TABLE_BYTES, -1}}, [&]() {
             HIP_CHECK(hipMemcpyAsync(out + n, chain, CX_TABLE_BYTES, hipMemcpyHostToDevice, r->stream));
             HIP_CHECK(hipStreamSynchronize(r->stream));                                             // (`chain` is a local)
-            for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
-            launch_cxform_texels(r->stream, bm.d_straight, out, n, out + n);                       // (warm-up)
-            HIP_CHECK(hipMemcpyAsync(out, bm.d_straight, bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_CHECK(hipEventRecord(e[0], r->stream));
-            for (uint32_t i = 0; i < reps; ++i) launch_cxform_texels(r->stream, bm.d_straight, out, n, out + n);
-            HIP_CHECK(hipEventRecord(e[1], r->stream));
-            for (uint32_t i = 0; i < reps; ++i) HIP_CHECK(hipMemcpyAsync(out, bm.d_straight, bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_CHECK(hipEventRecord(e[2], r->stream));
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventSynchronize(e[2]));
-            HIP_CHECK(hipEventElapsedTime(pass_ms, e[0], e[1]));
-            HIP_CHECK(hipEventElapsedTime(copy_ms, e[1], e[2]));
-            *pass_ms /= float(reps);
-            *copy_ms /= float(reps);
-        } catch (...) {
-            failure = std::current_exception();
-        }
-        (void)hipStreamSynchronize(r->stream);
-        if (out) (void)hipFree(out);
-        for (auto& x : e) if (x) (void)hipEventDestroy(x);
-        if (failure) std::rethrow_exception(failure);
-        return int(SWFR_OK);
+            pass(); copy();                                                                         // (warm-up)
+        }, {{pass, pass_ms}, {copy, copy_ms}});
     });
 }
 
@@ -2538,43 +2596,16 @@ int swfr_debug_time_shadow(swfr_renderer* r, uint32_t width, uint32_t height, in
     return guarded(r, [&]() {
         const size_t n = size_t(width) * height, bytes = n * 4;
         uint32_t *a = nullptr, *b = nullptr, *c = nullptr;
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        std::exception_ptr failure;
-        try {
-            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&a), bytes));
-            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b), bytes));
-            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c), bytes));
-            HIP_CHECK(hipMemsetAsync(a, 0x5a, bytes, r->stream));
-            HIP_CHECK(hipMemsetAsync(c, 0x5a, bytes, r->stream));
-            for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
-            const uint32_t cp = 0x80402010u;
-            launch_shadow_alpha(r->stream, a, b, width, height, dx, dy);                           // (warm-up of both kernels and the copy)
+        const uint32_t cp = 0x80402010u;
+        const auto alpha = [&]() { launch_shadow_alpha(r->stream, a, b, width, height, dx, dy); };
+        // (in place over the alpha words, as swfr_render runs it: a result's alpha byte is the next repetition's input, whatever it is)
+        const auto finish = [&]() { launch_shadow_finish(r->stream, b, c, true, b, n, cp, 1u, 0u); };
+        const auto copy = [&]() { HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream)); };
+        return time_phases(r, reps, {{&a, bytes, 0x5a}, {&b, bytes, -1}, {&c, bytes, 0x5a}}, [&]() {   // (warm-up of both kernels and the copy)
+            alpha();
             launch_shadow_finish(r->stream, b, a, true, b, n, cp, 1u, 0u);
-            HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_CHECK(hipEventRecord(e[0], r->stream));
-            for (uint32_t i = 0; i < reps; ++i) launch_shadow_alpha(r->stream, a, b, width, height, dx, dy);
-            HIP_CHECK(hipEventRecord(e[1], r->stream));
-            // (in place over the alpha words, as swfr_render runs it: a result's alpha byte is the next repetition's input, whatever it is)
-            for (uint32_t i = 0; i < reps; ++i) launch_shadow_finish(r->stream, b, c, true, b, n, cp, 1u, 0u);
-            HIP_CHECK(hipEventRecord(e[2], r->stream));
-            for (uint32_t i = 0; i < reps; ++i) HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_CHECK(hipEventRecord(e[3], r->stream));
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventSynchronize(e[3]));
-            HIP_CHECK(hipEventElapsedTime(alpha_ms, e[0], e[1]));
-            HIP_CHECK(hipEventElapsedTime(finish_ms, e[1], e[2]));
-            HIP_CHECK(hipEventElapsedTime(copy_ms, e[2], e[3]));
-            *alpha_ms /= float(reps); *finish_ms /= float(reps); *copy_ms /= float(reps);
-        } catch (...) {
-            failure = std::current_exception();
-        }
-        (void)hipStreamSynchronize(r->stream);
-        if (a) (void)hipFree(a);
-        if (b) (void)hipFree(b);
-        if (c) (void)hipFree(c);
-        for (auto& x : e) if (x) (void)hipEventDestroy(x);
-        if (failure) std::rethrow_exception(failure);
-        return int(SWFR_OK);
+            copy();
+        }, {{alpha, alpha_ms}, {finish, finish_ms}, {copy, copy_ms}});
     });
 }
 
@@ -2585,38 +2616,11 @@ int swfr_debug_time_blur(swfr_renderer* r, uint32_t width, uint32_t height, uint
     return guarded(r, [&]() {
         const size_t bytes = size_t(width) * height * 4;
         uint32_t *a = nullptr, *b = nullptr;
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        std::exception_ptr failure;
-        try {
-            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&a), bytes));
-            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b), bytes));
-            HIP_CHECK(hipMemsetAsync(a, 0x5a, bytes, r->stream));
-            for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
-            launch_blur_pass(r->stream, a, b, width, height, w, false);                            // (warm-up of both kernels and the copy)
-            launch_blur_pass(r->stream, a, b, width, height, w, true);
-            HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_CHECK(hipEventRecord(e[0], r->stream));
-            for (uint32_t i = 0; i < reps; ++i) launch_blur_pass(r->stream, a, b, width, height, w, false);
-            HIP_CHECK(hipEventRecord(e[1], r->stream));
-            for (uint32_t i = 0; i < reps; ++i) launch_blur_pass(r->stream, a, b, width, height, w, true);
-            HIP_CHECK(hipEventRecord(e[2], r->stream));
-            for (uint32_t i = 0; i < reps; ++i) HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_CHECK(hipEventRecord(e[3], r->stream));
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventSynchronize(e[3]));
-            HIP_CHECK(hipEventElapsedTime(h_ms, e[0], e[1]));
-            HIP_CHECK(hipEventElapsedTime(v_ms, e[1], e[2]));
-            HIP_CHECK(hipEventElapsedTime(copy_ms, e[2], e[3]));
-            *h_ms /= float(reps); *v_ms /= float(reps); *copy_ms /= float(reps);
-        } catch (...) {
-            failure = std::current_exception();
-        }
-        (void)hipStreamSynchronize(r->stream);
-        if (a) (void)hipFree(a);
-        if (b) (void)hipFree(b);
-        for (auto& x : e) if (x) (void)hipEventDestroy(x);
-        if (failure) std::rethrow_exception(failure);
-        return int(SWFR_OK);
+        const auto across = [&]() { launch_blur_pass(r->stream, a, b, width, height, w, false); };
+        const auto down = [&]() { launch_blur_pass(r->stream, a, b, width, height, w, true); };
+        const auto copy = [&]() { HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream)); };
+        return time_phases(r, reps, {{&a, bytes, 0x5a}, {&b, bytes, -1}}, [&]() { across(); down(); copy(); },   // (warm-up of both kernels and the copy)
+                           {{across, h_ms}, {down, v_ms}, {copy, copy_ms}});
     });
 }
 
@@ -2831,14 +2835,13 @@ int swfr_wait(swfr_renderer* r) {
     if (!r) return SWFR_ERR_INVALID;
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle");
     return guarded(r, [&]() {
-        if (!r->h_counters) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&r->h_counters), 8 * COUNTER_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+        uint32_t* const host = pinned_counters(r);
         int rc = SWFR_OK;
         for (uint32_t k = 0; k < 4; ++k) {
             if (!r->fs[k].stream || !r->fs[k].counters) continue;
-            if (!(r->async_used >> k & 1u)) { HIP_CHECK(hipStreamSynchronize(r->fs[k].stream)); continue; }
-            HIP_CHECK(hipMemcpyAsync(r->h_counters + k * COUNTER_WORDS, r->fs[k].counters, COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, r->fs[k].stream));
+            if (r->async_used >> k & 1u) queue_counters(r->fs[k].stream, host + k * COUNTER_WORDS, r->fs[k].counters);
             HIP_CHECK(hipStreamSynchronize(r->fs[k].stream));
-            if (rc == SWFR_OK) rc = check_counters(r, r->h_counters + k * COUNTER_WORDS);
+            if (r->async_used >> k & 1u) rc = check_frames(r, host + k * COUNTER_WORDS, 1, rc);
         }
         r->async_used = 0;
         r->fb_valid = rc == SWFR_OK;
@@ -2849,14 +2852,9 @@ int swfr_wait(swfr_renderer* r) {
 long swfr_debug_copy(swfr_renderer* r, int what, void* dst, size_t bytes) {
     if (!r || !dst) return -long(SWFR_ERR_INVALID);
     if (!r->has_device) return -long(SWFR_ERR_NO_DEVICE);
-    if (what == 2) {                                       // (no device buffer: what the last launch chain chose)
+    if (what == 2 || what == 3) {      // (no device buffer: what the last launch chain chose; the row launches of the last resident call that binned the next frame)
         if (bytes < sizeof(uint32_t)) return 0;
-        std::memcpy(dst, &r->last_bin_threads, sizeof(uint32_t));
-        return long(sizeof(uint32_t));
-    }
-    if (what == 3) {                                       // (nor here: the row launches of the last resident call that binned the next frame)
-        if (bytes < sizeof(uint32_t)) return 0;
-        std::memcpy(dst, &r->last_ahead_launches, sizeof(uint32_t));
+        std::memcpy(dst, what == 2 ? &r->last_bin_threads : &r->last_ahead_launches, sizeof(uint32_t));
         return long(sizeof(uint32_t));
     }
     if (!r->fs[0].work.ptr) return 0;

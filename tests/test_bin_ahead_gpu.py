@@ -318,3 +318,34 @@ def test_the_fused_chain_from_the_second_call():
         assert st["queued_rows"] == 0 and st["crowded_rows"] == 0, st
     finally:
         r.close()
+
+
+def test_counters_of_a_parity_1_frame(monkeypatch):
+    """four frame sets, two frames per launch, eight frames: every set's last frame of the call ran with its parity-1 descriptor, whose
+    counters lie four sets further on.  What the call reports of them -- the records of set 0's last frame, and what every set's
+    frame adds to swfr_stats -- is what the same call reports under the three-launch chain."""
+    import swf_renderer_amd as S
+    sc, want = _main_case()
+    monkeypatch.setenv("SWFR_FRAMES_IN_FLIGHT", "4")
+    monkeypatch.setenv("SWFR_RESIDENT_BATCH", "2")
+
+    def call():
+        r = S.Renderer(W, H)
+        try:
+            r.upload_edges(*build_on_host(sc))
+            r.render_resident(1)
+            before = r.stats()
+            r.render_resident(8)
+            after = r.stats()
+            assert diff_stats(r.read_image(premultiplied=True), want) == (0, 0)
+            return _ahead_launches(r), r.timing()["n_records"], {k: after[k] - before[k] for k in after}
+        finally:
+            r.close()
+
+    fused, records, delta = call()
+    monkeypatch.setenv("SWFR_BIN_AHEAD", "0")
+    fused0, records0, delta0 = call()
+    print("ahead launches %d / %d, n_records %d / %d, stats %r / %r" % (fused, fused0, records, records0, delta, delta0))
+    assert fused > 0 and fused0 == 0, (fused, fused0)
+    assert records == records0, (records, records0)
+    assert delta == delta0, (delta, delta0)
