@@ -145,7 +145,7 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
        SWFR_OBJECT_COLOR_TRANSFORM = 3   /* a container (matrix + children) whose `id` names a colour-transform slot (swfr_set_color_transform):
                                             the slot's value at the time of the render call applies to everything below it.  Beyond the
                                             reference, whose display objects carry a matrix and a ratio only */,
-       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10, 12, 14, 15, 17, 18 and 20 and above) */
+       /* 4 is not a display-object type: SWFR_ERR_INVALID, "UnexpectedDisplayObjectType" (as are 6, 7, 9, 10, 12, 14, 15, 17, 18, 20 and 22 and above) */
        SWFR_OBJECT_BLEND_MODE = 5,       /* a container (matrix + children) whose `id` is an SWF blend-mode number (SWFR_BLEND_*): every path
                                             drawn below it is composited, each on its own, with the mode's Cairo operator -- what
                                             CanvasRenderer would do if it set ctx.globalCompositeOperation before drawing the object.  It
@@ -217,9 +217,25 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
                                             swfr_built_layer_shadow), one box path in the parent naming texture SWFR_BLUR_BASE + k, at most
                                             SWFR_MAX_BLUR_LAYERS of both kinds in a frame ("BlurLayers"), neither kind below either
                                             ("NestedBlur"), drawn by swfr_render only ("NotImplementedBlurRoute", "NotImplementedBlurBands").
-                                            DESIGN.md, "Shadowed layers" */ };
+                                            DESIGN.md, "Shadowed layers" */,
+       /* 20 is not a display-object type */
+       SWFR_OBJECT_FILTERED_LAYER = 21   /* a layer with an ordered filter list: a container (matrix + children) whose children are drawn
+                                            onto a transparent surface of the frame's size, as a blurred layer's are; the list's entries
+                                            (swfr_filter, below: box blurs and shadows, 1..SWFR_MAX_FILTERS of them) are applied to that
+                                            surface one after the other, each to the result of the one before it -- a shadow later in the
+                                            list shadows the earlier filters' output, earlier shadows included --, and the last result is
+                                            composited onto the parent as ONE layer.  `id` is mode | slot << 8: the mode an SWF blend-mode
+                                            number, accepted exactly as SWFR_OBJECT_LAYER accepts it; the slot (< 65536) one set with
+                                            swfr_set_filters, whose list at the scene walk is the list, checked again there -- an unset
+                                            slot: SWFR_ERR_NOT_FOUND, "FiltersNotFound".  A list of one entry is the blurred or shadowed
+                                            layer of that entry, byte for byte.  Built, numbered, limited and refused together with
+                                            blurred and shadowed layers: a sub-frame of its own (swfr_built_layer, swfr_built_layer_filters),
+                                            one box path in the parent naming texture SWFR_BLUR_BASE + k, at most SWFR_MAX_BLUR_LAYERS of
+                                            the three kinds in a frame whatever the lists' lengths ("BlurLayers"), none of the three below
+                                            any of the three ("NestedBlur"), drawn by swfr_render only ("NotImplementedBlurRoute",
+                                            "NotImplementedBlurBands").  DESIGN.md, "Filter lists" */ };
 #define SWFR_MAX_LAYER_DEPTH 4
-#define SWFR_MAX_BLUR_LAYERS 8           /* blurred and shadowed layers in one frame, together */
+#define SWFR_MAX_BLUR_LAYERS 8           /* blurred, shadowed and filtered layers in one frame, together */
 #define SWFR_BLUR_BASE 131072            /* swfr_style::bitmap of the k-th blurred layer of a frame: SWFR_BLUR_BASE + k */
 
 /* SWF blend-mode numbers (PlaceObject3, swf-tree BlendMode).  0, 1: OVER.  3..8, 13, 14: the Cairo operator of the same name
@@ -286,6 +302,24 @@ typedef struct { uint32_t blur_x, blur_y, passes; int32_t dx, dy; swfr_rgba8 col
 /* Sets shadow slot `slot` (< 65536) of the handle, or clears it (shadow == NULL), as swfr_set_color_transform does for its slots.  A
    value out of range: SWFR_ERR_INVALID, "InvalidShadow".  SWFR_OBJECT_SHADOWED_LAYER names a slot. */
 int swfr_set_shadow(swfr_renderer *r, uint32_t slot, const swfr_shadow *shadow);
+
+/* ---- filter lists ("Filter lists") --------------------------------------------------------------------------------
+   An ordered list of 1..SWFR_MAX_FILTERS filters of a group surface R_0 (premultiplied, of the frame's size), entry i made of R_(i-1):
+     SWFR_FILTER_BLUR    R_i = R_(i-1) box-blurred as swfr_blur_bitmap blurs, on all four channels.  The entry uses shadow.blur_x,
+                         shadow.blur_y (0..255) and shadow.passes (1..15); every other field of `shadow` must be zero.
+     SWFR_FILTER_SHADOW  R_i = the final surface R of swfr_shadow, above, with G := R_(i-1): what is shadowed is the earlier filters'
+                         output, earlier shadows included.  The entry's `shadow` is checked as swfr_set_shadow checks one.
+   Not Flash Player's filter list: these two kinds only (no inner shadow, bevel, gradient glow, colour matrix or convolution), four
+   entries at most, and every caveat of swfr_blur_bitmap's box and of swfr_shadow holds for each entry.
+   An unknown kind or a value out of range: SWFR_ERR_INVALID, "InvalidFilter". */
+#define SWFR_MAX_FILTERS 4
+enum { SWFR_FILTER_BLUR = 0, SWFR_FILTER_SHADOW = 1 };
+typedef struct { uint32_t kind; swfr_shadow shadow; } swfr_filter;
+/* Sets filter-list slot `slot` (< 65536) of the handle to the `count` entries at `filters`, or clears it (filters == NULL or count == 0),
+   as swfr_set_shadow does for its slots.  A slot above 65535, an unknown kind or a value out of range: SWFR_ERR_INVALID,
+   "InvalidFilter"; count > SWFR_MAX_FILTERS: SWFR_ERR_CAPACITY, "FilterListLength".  A refused call leaves the slot as it was.
+   SWFR_OBJECT_FILTERED_LAYER names a slot. */
+int swfr_set_filters(swfr_renderer *r, uint32_t slot, const swfr_filter *filters, uint32_t count);
 
 /* ---- configuration ------------------------------------------------------------------------ */
 #define SWFR_DEVICE_HOST_ONLY (-1)       /* decode + geometry only; swfr_render fails with NO_DEVICE */
@@ -476,9 +510,10 @@ int  swfr_build_frame(swfr_renderer *r, const swfr_stage *stage,
                       const swfr_path **paths, size_t *n_paths,
                       const swfr_style **styles, size_t *n_styles);
 
-/* The sub-frames of the blurred layers (SWFR_OBJECT_BLURRED_LAYER) of the frame the handle's last scene walk built: how many, and the
-   k-th one's arrays -- what swfr_render renders, captures and blurs into texture SWFR_BLUR_BASE + k before the parent frame -- with its
-   blur.  Owned by the handle until its next walk; any out-parameter may be NULL.  k out of range: SWFR_ERR_NOT_FOUND. */
+/* The sub-frames of the blurred, shadowed and filtered layers (SWFR_OBJECT_BLURRED_LAYER, _SHADOWED_LAYER, _FILTERED_LAYER) of the frame
+   the handle's last scene walk built: how many, and the k-th one's arrays -- what swfr_render renders, captures and filters into texture
+   SWFR_BLUR_BASE + k before the parent frame -- with its blur: a shadowed layer's shadow's box, a filtered layer's first entry's box.
+   Owned by the handle until its next walk; any out-parameter may be NULL.  k out of range: SWFR_ERR_NOT_FOUND. */
 uint32_t swfr_built_layers(const swfr_renderer *r);
 int  swfr_built_layer(swfr_renderer *r, uint32_t k,
                       const swfr_edge **edges, size_t *n_edges,
@@ -486,8 +521,14 @@ int  swfr_built_layer(swfr_renderer *r, uint32_t k,
                       const swfr_style **styles, size_t *n_styles,
                       uint32_t *blur_x, uint32_t *blur_y, uint32_t *passes);
 /* Whether the k-th sub-frame is a shadowed layer's (SWFR_OBJECT_SHADOWED_LAYER) and, if so, its shadow as the scene walk read it from
-   the slot; swfr_built_layer reports that shadow's box.  Either out-parameter may be NULL.  k out of range: SWFR_ERR_NOT_FOUND. */
+   the slot; swfr_built_layer reports that shadow's box.  A filtered layer's sub-frame (SWFR_OBJECT_FILTERED_LAYER) answers
+   has_shadow = 0, whatever its list holds: swfr_built_layer_filters reports lists.  Either out-parameter may be NULL.  k out of range:
+   SWFR_ERR_NOT_FOUND. */
 int  swfr_built_layer_shadow(swfr_renderer *r, uint32_t k, int *has_shadow, swfr_shadow *out);
+/* The filter list of the k-th sub-frame as the scene walk read it: `count` entries (1..SWFR_MAX_FILTERS) at `out`, which has room for
+   SWFR_MAX_FILTERS.  A blurred layer's sub-frame reports its one blur entry, a shadowed layer's its one shadow entry.  Either
+   out-parameter may be NULL.  k out of range: SWFR_ERR_NOT_FOUND. */
+int  swfr_built_layer_filters(swfr_renderer *r, uint32_t k, uint32_t *count, swfr_filter *out);
 
 /* Decoded paths of a registered (morph) shape as JSON text in the format of the reference's
    decode goldens (tests/<set>/<name>/shape.ts.json).  String owned by the handle. */

@@ -39,6 +39,7 @@ EXPORTS = [
     "swfr_set_color_transform", "swfr_debug_time_cxform",
     "swfr_capture_bitmap", "swfr_blur_bitmap", "swfr_built_layers", "swfr_built_layer", "swfr_debug_time_blur",
     "swfr_set_shadow", "swfr_shadow_bitmap", "swfr_built_layer_shadow", "swfr_debug_time_shadow",
+    "swfr_set_filters", "swfr_built_layer_filters",
 ]
 OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
 OBJECT_BLEND_MODE = 5
@@ -48,8 +49,11 @@ OBJECT_FADED_LAYER = 13                 # a layer with an opacity (swfr.h SWFR_O
 OBJECT_BLURRED_LAYER = 16               # a blurred layer (swfr.h SWFR_OBJECT_BLURRED_LAYER): `id` is the blend mode | blur_x << 8 | blur_y << 16 | passes << 24
 OBJECT_SHADOWED_LAYER = 19              # a shadowed layer (swfr.h SWFR_OBJECT_SHADOWED_LAYER): `id` is the blend mode | shadow slot << 8
 SHADOW_HIDE_OBJECT, SHADOW_KNOCKOUT = 1, 2
+OBJECT_FILTERED_LAYER = 21              # a layer with an ordered filter list (swfr.h SWFR_OBJECT_FILTERED_LAYER): `id` is the blend mode | filter-list slot << 8
+MAX_FILTERS = 4                         # entries in one filter list
+FILTER_BLUR, FILTER_SHADOW = 0, 1       # swfr_filter::kind
 MAX_LAYER_DEPTH = 4                     # (a masked layer takes two levels)
-MAX_BLUR_LAYERS = 8                     # blurred and shadowed layers in one frame
+MAX_BLUR_LAYERS = 8                     # blurred, shadowed and filtered layers in one frame
 BLUR_BASE = 131072                      # a bitmap style's `bitmap` at or above it names the texture of a blurred layer of the frame
 PATH_TOR, PATH_BOXES, PATH_GROUP_BEGIN, PATH_GROUP_END, PATH_GROUP_MASK = 0, 1, 2, 3, 4
 # SWF blend-mode numbers under swf-tree's names (BlendMode); what the library does with each is swfr.h's SWFR_BLEND_* comment
@@ -115,6 +119,42 @@ def shadow_values(shadow):
 
 def _shadow_struct(v):
     return Shadow(v[0], v[1], v[2], v[3], v[4], Rgba8(*v[5:9]), v[9], v[10])
+
+
+def filter_values(filters):
+    """the ((kind, values), ...) of a "filters" value: a list of entries, each a dict with exactly one key -- {"blur": a "blur" value}
+    (blur_values) or {"shadow": a "shadow" value} (shadow_values).  Anything else is InvalidFilter; a list too long for the library still
+    goes there, to be refused by name."""
+    if not isinstance(filters, (list, tuple)):
+        raise SwfrError(ERR_INVALID, "InvalidFilter: %r" % (filters,))
+    out = []
+    for entry in filters:
+        if not isinstance(entry, dict) or len(entry) != 1 or next(iter(entry)) not in ("blur", "shadow"):
+            raise SwfrError(ERR_INVALID, "InvalidFilter: %r" % (entry,))
+        if "blur" in entry:
+            out.append((FILTER_BLUR, blur_values(entry["blur"])))
+        else:
+            out.append((FILTER_SHADOW, shadow_values(entry["shadow"])))
+    return tuple(out)
+
+
+def _filter_structs(values):
+    """the Filter array of filter_values' result"""
+    arr = (Filter * max(len(values), 1))()
+    for f, (kind, v) in zip(arr, values):
+        f.kind = kind
+        if kind == FILTER_BLUR:
+            f.shadow.blur_x, f.shadow.blur_y, f.shadow.passes = v
+        else:
+            f.shadow = _shadow_struct(v)
+    return arr
+
+
+def _shadow_dict(sh):
+    """a Shadow as a "shadow" value with every key"""
+    return {"color": (sh.color.r, sh.color.g, sh.color.b, sh.color.a), "dx": sh.dx, "dy": sh.dy, "x": sh.blur_x, "y": sh.blur_y,
+            "passes": sh.passes, "strength": sh.strength, "hide_object": bool(sh.flags & SHADOW_HIDE_OBJECT),
+            "knockout": bool(sh.flags & SHADOW_KNOCKOUT)}
 
 
 def layer_mode_number(layer) -> int:
@@ -195,6 +235,11 @@ class Shadow(C.Structure):
     """swfr_shadow"""
     _fields_ = [("blur_x", C.c_uint32), ("blur_y", C.c_uint32), ("passes", C.c_uint32), ("dx", C.c_int32), ("dy", C.c_int32), ("color", Rgba8),
                 ("strength", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class Filter(C.Structure):
+    """swfr_filter"""
+    _fields_ = [("kind", C.c_uint32), ("shadow", Shadow)]
 
 
 class Stage(C.Structure):
@@ -347,6 +392,10 @@ def load_library():
     L.swfr_shadow_bitmap.argtypes = [P, U, U, C.POINTER(Shadow)]
     L.swfr_built_layer_shadow.restype = I
     L.swfr_built_layer_shadow.argtypes = [P, U, C.POINTER(I), C.POINTER(Shadow)]
+    L.swfr_set_filters.restype = I
+    L.swfr_set_filters.argtypes = [P, U, C.POINTER(Filter), U]
+    L.swfr_built_layer_filters.restype = I
+    L.swfr_built_layer_filters.argtypes = [P, U, C.POINTER(U), C.POINTER(Filter)]
     L.swfr_debug_time_shadow.restype = I
     L.swfr_debug_time_shadow.argtypes = [P, U, U, C.c_int32, C.c_int32, U, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.swfr_debug_time_blur.restype = I
@@ -397,6 +446,7 @@ class _Arena:
         self.keep = []
         self.cxforms = {}     # the eight values -> slot: one slot per distinct transform of the call (all of its stages)
         self.shadows = {}     # shadow_values -> slot, likewise
+        self.filters = {}     # filter_values -> slot, likewise
 
     def array(self, ctype, items):
         arr = (ctype * max(len(items), 1))(*items)
@@ -639,7 +689,8 @@ class Renderer:
     def built_layers(self):
         """The sub-frames of the blurred and shadowed layers of the frame the last scene walk built (build_frame, render): a list of
         (edges, paths, styles, (x, y, passes)), in painter's order -- what render() draws, captures and blurs before the frame.  A
-        shadowed layer's tuple has a fifth member, its shadow as a dict with every key of a "shadow" value."""
+        shadowed layer's tuple has a fifth member, its shadow as a dict with every key of a "shadow" value.  A filtered layer ("filters")
+        has the four-member tuple with its first entry's box; built_filters() gives the lists."""
         out = []
         for k in range(self.L.swfr_built_layers(self.h)):
             pe, pp, ps = C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -651,11 +702,30 @@ class Renderer:
             has, sh = C.c_int(), Shadow()
             self._check(self.L.swfr_built_layer_shadow(self.h, k, C.byref(has), C.byref(sh)))
             if has.value:
-                layer += ({"color": (sh.color.r, sh.color.g, sh.color.b, sh.color.a), "dx": sh.dx, "dy": sh.dy, "x": sh.blur_x, "y": sh.blur_y,
-                           "passes": sh.passes, "strength": sh.strength, "hide_object": bool(sh.flags & SHADOW_HIDE_OBJECT),
-                           "knockout": bool(sh.flags & SHADOW_KNOCKOUT)},)
+                layer += (_shadow_dict(sh),)
             out.append(layer)
         return out
+
+    def built_filters(self):
+        """The filter lists of the sub-frames of the last scene walk, in built_layers()' order, as the walk read them: each a list of
+        {"blur": {"x", "y", "passes"}} / {"shadow": a "shadow" value with every key}.  A blurred or shadowed layer reports its one entry."""
+        out = []
+        for k in range(self.L.swfr_built_layers(self.h)):
+            n, arr = C.c_uint32(), (Filter * MAX_FILTERS)()
+            self._check(self.L.swfr_built_layer_filters(self.h, k, C.byref(n), arr))
+            out.append([{"blur": {"x": f.shadow.blur_x, "y": f.shadow.blur_y, "passes": f.shadow.passes}} if f.kind == FILTER_BLUR
+                        else {"shadow": _shadow_dict(f.shadow)} for f in arr[:n.value]])
+        return out
+
+    def set_filters(self, slot, filters):
+        """swfr_set_filters: `filters` a "filters" value (filter_values), or None (or an empty list) to clear the slot.  (render() and the
+        other stage calls assign slots 0.. to the lists of their own stages and set them; this is for callers that build type-21 display
+        objects themselves.)"""
+        if filters is None:
+            self._check(self.L.swfr_set_filters(self.h, slot, None, 0))
+            return
+        v = filter_values(filters)
+        self._check(self.L.swfr_set_filters(self.h, slot, _filter_structs(v), len(v)))
 
     def set_shadow(self, slot, shadow):
         """swfr_set_shadow: `shadow` a "shadow" value (shadow_values), or None to clear the slot.  (render() and the other stage calls
@@ -707,12 +777,14 @@ class Renderer:
 
     def _apply_cxforms(self, arena):
         """Sets the handle's colour-transform slots to this call's transforms (slots 0..n-1, by first appearance), and its shadow slots
-        to this call's shadows in the same way."""
+        to this call's shadows and its filter-list slots to this call's lists in the same way."""
         for v, slot in arena.cxforms.items():
             ct = ColorTransform((C.c_int32 * 4)(*v[:4]), (C.c_int32 * 4)(*v[4:]))
             self._check(self.L.swfr_set_color_transform(self.h, slot, C.byref(ct)))
         for v, slot in arena.shadows.items():
             self._check(self.L.swfr_set_shadow(self.h, slot, C.byref(_shadow_struct(v))))
+        for v, slot in arena.filters.items():
+            self._check(self.L.swfr_set_filters(self.h, slot, _filter_structs(v), len(v)))
 
     def _object(self, arena, obj):
         d = DisplayObject()
@@ -745,6 +817,26 @@ class Renderer:
             inner = {k: v for k, v in obj.items() if k not in ("mask", "layer")}
             kids = arena.array(DisplayObject, [self._object(arena, {"type": "container", "children": list(obj["mask"])}), self._object(arena, inner)])
             w.n_children, w.children = 2, C.cast(kids, C.POINTER(DisplayObject))
+            return w
+        if obj.get("filters") is not None:
+            # an ordered filter list: the object inside a type-21 wrapper, where the type-16 wrapper would sit, and composited like it; the
+            # list goes to a slot of this call's (as a shadow does).  An empty list is no filter at all.  The single keys beside the list
+            # have no place in its order: refused
+            if obj.get("blur") is not None or obj.get("shadow") is not None:
+                raise SwfrError(ERR_NOT_IMPLEMENTED, "NotImplementedFilterChain")
+            v = filter_values(obj["filters"])
+            inner = {k: x for k, x in obj.items() if k != "filters"}
+            if not v:
+                return self._object(arena, inner)
+            w = DisplayObject()
+            layer = obj.get("layer")
+            mode = BLEND_MODES["normal"] if layer is None or layer is False else layer_mode_number(layer)
+            if not 0 <= mode <= 255:
+                raise SwfrError(ERR_INVALID, "InvalidBlendMode: %r" % (layer,))
+            w.type, w.id = OBJECT_FILTERED_LAYER, mode | arena.filters.setdefault(v, len(arena.filters)) << 8
+            inner.pop("layer", None)
+            kids = arena.array(DisplayObject, [self._object(arena, inner)])
+            w.n_children, w.children = 1, C.cast(kids, C.POINTER(DisplayObject))
             return w
         if obj.get("shadow") is not None:
             # the object inside a type-19 wrapper, where the type-16 wrapper would sit, and composited like it; the shadow's values go to a

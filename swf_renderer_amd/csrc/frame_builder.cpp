@@ -81,6 +81,13 @@ bool shadow_valid(const swfr_shadow& s) {
            s.flags != (SWFR_SHADOW_HIDE_OBJECT | SWFR_SHADOW_KNOCKOUT);
 }
 uint32_t shadow_color_pixel(const swfr_rgba8& c) { return premultiplied_pixel(Css{c.r, c.g, c.b, c.a}); }
+bool filter_valid(const swfr_filter& f) {
+    if (f.kind == SWFR_FILTER_SHADOW) return shadow_valid(f.shadow);
+    if (f.kind != SWFR_FILTER_BLUR) return false;
+    const swfr_shadow& s = f.shadow;
+    return s.blur_x <= 255u && s.blur_y <= 255u && s.passes >= 1u && s.passes <= 15u && s.dx == 0 && s.dy == 0 && s.color.r == 0 && s.color.g == 0 &&
+           s.color.b == 0 && s.color.a == 0 && s.strength == 0u && s.flags == 0u;
+}
 
 bool color_transform_valid(const swfr_color_transform& ct) {
     for (int k = 0; k < 4; ++k)
@@ -405,10 +412,9 @@ void FrameBuilder::draw(const swfr_display_object& obj, int depth) {
             draw_masked_layer(obj, depth);
             break;
         case SWFR_OBJECT_BLURRED_LAYER:
-            draw_blurred_layer(obj, depth);
-            break;
         case SWFR_OBJECT_SHADOWED_LAYER:
-            draw_shadowed_layer(obj, depth);
+        case SWFR_OBJECT_FILTERED_LAYER:
+            draw_filtered_layer(obj, depth);
             break;
         case SWFR_OBJECT_SHAPE: {
             const DecodedShape* sh = shape(obj.id, false);
@@ -569,37 +575,48 @@ void FrameBuilder::draw_masked_layer(const swfr_display_object& obj, int depth) 
     paths_.push_back(m);
 }
 
-// A blurred layer: the `id` unpacked and checked; draw_filtered_layer does the rest
-void FrameBuilder::draw_blurred_layer(const swfr_display_object& obj, int depth) {
-    const uint32_t mode = obj.id & 0xffu, blur_x = (obj.id >> 8) & 0xffu, blur_y = (obj.id >> 16) & 0xffu, passes = obj.id >> 24;
-    layer_operator(mode, alpha_modes_);                      // (a refused mode is reported before a bad blur)
-    if (passes == 0u || passes > 15u) throw StatusError{SWFR_ERR_INVALID, "InvalidBlur"};
-    draw_filtered_layer(obj, depth, mode, blur_x, blur_y, passes, nullptr);
-}
-
-// A shadowed layer ("Shadowed layers"): a blurred layer's sub-frame and box path, with the slot's shadow stored beside the
-// sub-frame -- swfr_render makes the final surface (the group with its shadow) in texture BLUR_BASE + k, so the parent's path is the same.
-void FrameBuilder::draw_shadowed_layer(const swfr_display_object& obj, int depth) {
-    const uint32_t mode = obj.id & 0xffu, slot = obj.id >> 8;
-    layer_operator(mode, alpha_modes_);
-    if (slot > 65535u) throw StatusError{SWFR_ERR_INVALID, "InvalidShadow"};
-    const auto& slots = store()->shadows_;
-    const auto it = slots.find(slot);
-    if (it == slots.end()) throw StatusError{SWFR_ERR_NOT_FOUND, "ShadowNotFound"};
-    const swfr_shadow sh = it->second;
-    if (!shadow_valid(sh)) throw StatusError{SWFR_ERR_INVALID, "InvalidShadow"};
-    draw_filtered_layer(obj, depth, mode, sh.blur_x, sh.blur_y, sh.passes, &sh);
-}
-
-// A blurred or shadowed layer ("Blurred layers"): cairo_push_group; the children; cairo_pop_group; the blur on the group's surface;
-// cairo_set_source; cairo_set_operator; cairo_paint.  The children are built -- under the matrix, colour-transform chain and blend
-// mode in force -- into a sub-frame of their own: a surface of the frame's size that starts clear, with its own layer depth.  In the
-// parent the object is one box path over the whole frame whose bitmap style names the sub-frame's blurred texture, BLUR_BASE + k: a
-// nearest fetch at 1:1 under full coverage, composited with the operator, is the group paint.  The parent surface counts as drawn on
-// behind it (the blurred surface is dirty to Cairo whatever it holds).  ALPHA is a group's operator only in the tile pass: the path
-// then sits in a group of its own over the whole frame, which the END composites with it.  `shadow` (a shadowed layer's, or null) is kept with the sub-frame for swfr_render.
-void FrameBuilder::draw_filtered_layer(const swfr_display_object& obj, int depth, uint32_t mode, uint32_t blur_x, uint32_t blur_y, uint32_t passes, const swfr_shadow* shadow) {
-    const uint32_t op = layer_operator(mode, alpha_modes_);
+// A blurred, shadowed or filtered layer ("Blurred layers", "Shadowed layers", "Filter lists"): cairo_push_group; the children;
+// cairo_pop_group; the filters, in order, on the group's surface; cairo_set_source; cairo_set_operator; cairo_paint.  The three types
+// differ in where the list comes from: a blurred layer's `id` carries its one blur, a shadowed layer's names a shadow slot, a filtered
+// layer's a filter-list slot -- the slots' values at this walk, checked again here.  The children are built -- under the matrix,
+// colour-transform chain and blend mode in force -- into a sub-frame of their own: a surface of the frame's size that starts clear,
+// with its own layer depth; the list is kept with it for swfr_render.  In the parent the object is one box path over the whole frame
+// whose bitmap style names the sub-frame's filtered texture, BLUR_BASE + k: a nearest fetch at 1:1 under full coverage, composited
+// with the operator, is the group paint.  The parent surface counts as drawn on behind it (the filtered surface is dirty to Cairo
+// whatever it holds).  ALPHA is a group's operator only in the tile pass: the path then sits in a group of its own over the whole
+// frame, which the END composites with it.
+void FrameBuilder::draw_filtered_layer(const swfr_display_object& obj, int depth) {
+    const uint32_t mode = obj.id & 0xffu;
+    const uint32_t op = layer_operator(mode, alpha_modes_);      // (a refused mode is reported before a bad filter)
+    swfr_filter list[SWFR_MAX_FILTERS];
+    uint32_t n_list = 1;
+    std::memset(list, 0, sizeof list);
+    if (obj.type == SWFR_OBJECT_BLURRED_LAYER) {
+        list[0].kind = SWFR_FILTER_BLUR;
+        list[0].shadow.blur_x = (obj.id >> 8) & 0xffu; list[0].shadow.blur_y = (obj.id >> 16) & 0xffu; list[0].shadow.passes = obj.id >> 24;
+        if (!filter_valid(list[0])) throw StatusError{SWFR_ERR_INVALID, "InvalidBlur"};
+    } else if (obj.type == SWFR_OBJECT_SHADOWED_LAYER) {
+        const uint32_t slot = obj.id >> 8;
+        if (slot > 65535u) throw StatusError{SWFR_ERR_INVALID, "InvalidShadow"};
+        const auto& slots = store()->shadows_;
+        const auto it = slots.find(slot);
+        if (it == slots.end()) throw StatusError{SWFR_ERR_NOT_FOUND, "ShadowNotFound"};
+        list[0].kind = SWFR_FILTER_SHADOW;
+        list[0].shadow = it->second;
+        if (!filter_valid(list[0])) throw StatusError{SWFR_ERR_INVALID, "InvalidShadow"};
+    } else {
+        const uint32_t slot = obj.id >> 8;
+        if (slot > 65535u) throw StatusError{SWFR_ERR_INVALID, "InvalidFilter"};
+        const auto& slots = store()->filters_;
+        const auto it = slots.find(slot);
+        if (it == slots.end() || it->second.empty()) throw StatusError{SWFR_ERR_NOT_FOUND, "FiltersNotFound"};
+        if (it->second.size() > SWFR_MAX_FILTERS) throw StatusError{SWFR_ERR_CAPACITY, "FilterListLength"};
+        n_list = uint32_t(it->second.size());
+        for (uint32_t i = 0; i < n_list; ++i) {
+            list[i] = it->second[i];
+            if (!filter_valid(list[i])) throw StatusError{SWFR_ERR_INVALID, "InvalidFilter"};
+        }
+    }
     if (in_blur_) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NestedBlur"};
     if (parent_) throw StatusError{BLUR_IN_PIECE, "blurred layer in a build piece"};
     if (layers_.size() >= SWFR_MAX_BLUR_LAYERS) throw StatusError{SWFR_ERR_CAPACITY, "BlurLayers"};
@@ -615,8 +632,8 @@ void FrameBuilder::draw_filtered_layer(const swfr_display_object& obj, int depth
     layers_.emplace_back();
     BlurLayer& L = layers_.back();
     L.edges.swap(edges_); L.paths.swap(paths_); L.styles.swap(styles_);
-    L.blur_x = blur_x; L.blur_y = blur_y; L.passes = passes;
-    if (shadow) { L.has_shadow = true; L.shadow = *shadow; L.shadow_pixel = shadow_color_pixel(shadow->color); }
+    L.type = obj.type; L.n_filters = n_list;
+    std::memcpy(L.filters, list, sizeof list);
     edges_.swap(parent_edges); paths_.swap(parent_paths); styles_.swap(parent_styles);
     drawn_ = parent_drawn; group_depth_ = parent_depth; in_blur_ = false;
     // ---- the parent's path

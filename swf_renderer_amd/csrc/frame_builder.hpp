@@ -24,18 +24,18 @@ struct BitmapInfo {
     bool captured = false;                           // made on the device (swfr_capture_bitmap, swfr_blur_bitmap): no straight texels to transform
 };
 
-// The sub-frame of a blurred layer (SWFR_OBJECT_BLURRED_LAYER) or a shadowed one (SWFR_OBJECT_SHADOWED_LAYER): what its children build
-// as a frame of their own, and its blur.  The parent frame samples the rendered, filtered sub-frame as texture BLUR_BASE + k, k the layer's index in FrameBuilder::layers().
+// The sub-frame of a blurred layer (SWFR_OBJECT_BLURRED_LAYER), a shadowed one (SWFR_OBJECT_SHADOWED_LAYER) or a filtered one
+// (SWFR_OBJECT_FILTERED_LAYER): what its children build as a frame of their own, and its filter list.  The parent frame samples the
+// rendered, filtered sub-frame as texture BLUR_BASE + k, k the layer's index in FrameBuilder::layers().
 struct BlurLayer {
     std::vector<swfr_edge> edges;
     std::vector<swfr_path> paths;
     std::vector<swfr_style> styles;
-    uint32_t blur_x = 0, blur_y = 0, passes = 0;
-    // a shadowed layer's (SWFR_OBJECT_SHADOWED_LAYER): the slot's value at the walk -- blur_x, blur_y and passes above are its box --
-    // and its colour's premultiplied pixel (shadow_color_pixel)
-    bool has_shadow = false;
-    swfr_shadow shadow{};
-    uint32_t shadow_pixel = 0;
+    // the ordered filters, as the walk read them: a blurred layer's one blur entry made of its `id`, a shadowed layer's one shadow
+    // entry (its slot's value), a filtered layer's slot's list
+    uint32_t type = 0;                                // the display-object type the layer came from
+    uint32_t n_filters = 0;                           // 1..SWFR_MAX_FILTERS
+    swfr_filter filters[SWFR_MAX_FILTERS]{};
 };
 constexpr uint32_t BLUR_BASE = SWFR_BLUR_BASE;
 
@@ -72,6 +72,9 @@ bool color_transform_valid(const swfr_color_transform& ct);
 bool shadow_valid(const swfr_shadow& s);
 // the premultiplied ARGB pixel of cairo_set_source_rgba(r / 255, g / 255, b / 255, a / 255), from the bytes directly
 uint32_t shadow_color_pixel(const swfr_rgba8& c);
+// swfr_set_filters' check of one entry (swfr.h, swfr_filter): a known kind; a blur entry's box and passes in range and its other fields
+// zero; a shadow entry as shadow_valid has it
+bool filter_valid(const swfr_filter& f);
 
 // Frames with many top-level display objects are built by several threads: the children are cut into contiguous ranges, every range
 // is walked by a worker builder of its own (same code, its own output arrays), and the pieces are joined in painter's order.  The one
@@ -90,6 +93,7 @@ public:
     void add_bitmap(uint32_t id, BitmapInfo info) { bitmaps_[id] = info; }
     void set_color_transform(uint32_t slot, const swfr_color_transform* ct) { if (ct) cxforms_[slot] = *ct; else cxforms_.erase(slot); }
     void set_shadow(uint32_t slot, const swfr_shadow* sh) { if (sh) shadows_[slot] = *sh; else shadows_.erase(slot); }
+    void set_filters(uint32_t slot, const swfr_filter* f, uint32_t count) { if (f && count) filters_[slot].assign(f, f + count); else filters_.erase(slot); }
     const DecodedShape* shape(uint32_t id, bool morph) const;
 
     // Throws StatusError.  Results stay valid until the next build().
@@ -113,9 +117,7 @@ private:
     void draw(const swfr_display_object& obj, int depth);
     void draw_layer(const swfr_display_object& obj, int depth, uint32_t mode, uint32_t opacity);
     void draw_masked_layer(const swfr_display_object& obj, int depth);
-    void draw_blurred_layer(const swfr_display_object& obj, int depth);
-    void draw_shadowed_layer(const swfr_display_object& obj, int depth);
-    void draw_filtered_layer(const swfr_display_object& obj, int depth, uint32_t mode, uint32_t blur_x, uint32_t blur_y, uint32_t passes, const swfr_shadow* shadow);
+    void draw_filtered_layer(const swfr_display_object& obj, int depth);
     void group_rectangle(swfr_path& b, size_t begin, size_t end, uint32_t op);   // the markers' rectangle of the group paths_[begin .. end)
     void emit_clearing_group();                                // an ALPHA layer with a transparent source: the surface drawn so far becomes clear
     void draw_path(const StyledPath& p, bool morph, double ratio);
@@ -168,6 +170,7 @@ private:
     // textures its bitmap styles ask for (deduplicated by (bitmap, chain))
     std::map<uint32_t, swfr_color_transform> cxforms_;
     std::map<uint32_t, swfr_shadow> shadows_;   // the shadow slots (set on the handle's builder)
+    std::map<uint32_t, std::vector<swfr_filter>> filters_;   // the filter-list slots, likewise
     std::vector<ColorLut> luts_;
     std::map<std::string, int32_t> lut_index_;                 // table bytes -> index into luts_
     std::map<std::pair<int32_t, std::string>, int32_t> compose_memo_;   // (outer chain, inner transform bytes) -> chain

@@ -252,7 +252,7 @@ struct swfr_renderer {
     // frame's size each, valid until the handle's next scene walk -- and the scratch texture the passes alternate with
     DevBuf<uint32_t> blur_tex[SWFR_MAX_BLUR_LAYERS];
     DevBuf<uint32_t> blur_scratch;
-    DevBuf<uint32_t> shadow_scratch;       // swfr_shadow_bitmap: the alpha surface, which alternates with blur_scratch
+    DevBuf<uint32_t> shadow_scratch;       // swfr_shadow_bitmap, and a shadow behind another filter: the alpha surface, which alternates with blur_scratch
     std::vector<DevBitmap> blur_table;
     bool bitmap_table_dirty = false, bitmap_table_dirty_copied = false;
     bool scene_ready = false, fb_valid = false;
@@ -1835,12 +1835,18 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
     return check_counters(r, counters);
 }
 
-// The blurred layers of the frame the builder has just built, before the frame itself (swfr_render): sub-frame k is validated, uploaded
-// and rendered as an ordinary frame, its framebuffer captured as ARGB texels and blurred into texture k of the pool.  The capture goes
-// to the texture or to the scratch, whichever makes the last pass land in the texture.  Everything runs on the handle's stream, behind
-// the sub-frame's kernels (render_resident returns with every stream idle), and is waited for: the builder's arrays and the
-// framebuffer are free for the next sub-frame, and for the parent.  A shadowed layer's sub-frame ("Shadowed layers") takes the
-// same way with the alpha pass in the capture's place and the finish pass behind the blur.
+// The blurred, shadowed and filtered layers of the frame the builder has just built, before the frame itself (swfr_render): sub-frame k
+// is validated, uploaded and rendered as an ordinary frame, once, and its filter list (a blurred or shadowed layer's has one entry) is
+// run over it into texture k of the pool -- DESIGN.md, "Filter lists".  Three buffers take part: 0 the texture, 1 blur_scratch, 2
+// shadow_scratch.  The first entry reads the framebuffer: a blur through the capture, a shadow through the alpha pass and, behind
+// its box passes, the finish pass with the framebuffer as the group.  Every later entry reads the result before it as ARGB texels: a
+// blur's box passes alternate between that buffer and the other of 0 and 1; a shadow keeps its group where it is, its alpha surface
+// goes to the other of 0 and 1 and alternates with buffer 2, and its finish pass runs in place over the group.  So an entry ends
+// where it began, or -- a blur of an odd number of box passes -- in the other of 0 and 1: planned from the last entry, which ends
+// in the texture, backwards, every entry knows where to end, and the first one where to put its capture or alpha pass.  No copy, no
+// wait between entries.  Everything runs on the handle's stream, behind the sub-frame's kernels (render_resident returns with every
+// stream idle), and is waited for once per layer: the builder's arrays and the framebuffer are free for the next sub-frame, and for
+// the parent.
 int render_blur_layers(swfr_renderer* r) {
     const auto& layers = r->builder->layers();
     if (r->cfg.band_count > 1) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlurBands"};
@@ -1862,22 +1868,45 @@ int render_blur_layers(swfr_renderer* r) {
             int rc = upload2(r, 0, false, sv, nullptr, true);
             if (rc == SWFR_OK) rc = render_resident(r, 1);
             if (rc != SWFR_OK) return rc;
-            const uint32_t steps = blur_steps(B.blur_x, B.blur_y, B.passes);
-            if (steps) r->blur_scratch.reserve(n);                 // (a box of 1 x 1 runs no pass: the capture is the texture)
-            uint32_t* const tmp = r->blur_scratch.ptr;
-            const bool odd = (steps & 1u) != 0u;
-            const uint32_t* const fb = r->fb_cur ? r->fb_cur : r->fs[0].d_fb.ptr;
-            if (B.has_shadow) {
-                // the group's alpha, shifted, instead of the capture; behind the box passes, which leave it in the texture, the finish
-                // pass in place: the sub-frame's framebuffer is still the group
-                launch_shadow_alpha(r->stream, fb, odd ? tmp : tex, r->width, r->height, B.shadow.dx, B.shadow.dy);
-                blur_image(r->stream, odd ? tmp : tex, odd ? tex : tmp, r->width, r->height, B.blur_x, B.blur_y, B.passes);
-                launch_shadow_finish(r->stream, tex, fb, true, tex, n, B.shadow_pixel, B.shadow.strength, B.shadow.flags);
-                HIP_CHECK(hipGetLastError());
-            } else {
-                launch_blur_capture(r->stream, fb, odd ? tmp : tex, n);
-                blur_image(r->stream, odd ? tmp : tex, odd ? tex : tmp, r->width, r->height, B.blur_x, B.blur_y, B.passes);
+            // where every entry ends (0 or 1), from the last one backwards, and which scratch buffers the chain touches
+            uint32_t steps[SWFR_MAX_FILTERS];
+            int end[SWFR_MAX_FILTERS];
+            bool scratch1 = false, scratch2 = false;
+            for (uint32_t i = B.n_filters, at = 0; i-- > 0;) {
+                const swfr_filter& F = B.filters[i];
+                steps[i] = blur_steps(F.shadow.blur_x, F.shadow.blur_y, F.shadow.passes);
+                end[i] = int(at);
+                if (i ? (F.kind == SWFR_FILTER_SHADOW || steps[i] != 0u) : steps[i] != 0u) scratch1 = true;
+                if (i && F.kind == SWFR_FILTER_SHADOW && steps[i] != 0u) scratch2 = true;
+                if (i && F.kind == SWFR_FILTER_BLUR && (steps[i] & 1u)) at ^= 1u;          // (its input lies in the other buffer)
+                if (at) scratch1 = true;
             }
+            if (scratch1) r->blur_scratch.reserve(n);                 // (a lone box of 1 x 1 runs no pass: the capture is the texture)
+            if (scratch2) r->shadow_scratch.reserve(n);
+            uint32_t* const buf[3] = {tex, r->blur_scratch.ptr, r->shadow_scratch.ptr};
+            const uint32_t* const fb = r->fb_cur ? r->fb_cur : r->fs[0].d_fb.ptr;
+            for (uint32_t i = 0; i < B.n_filters; ++i) {
+                const swfr_filter& F = B.filters[i];
+                const swfr_shadow& S = F.shadow;
+                if (i == 0) {
+                    // the capture or the alpha pass goes where the box passes, alternating between 0 and 1, end in end[0]
+                    const int first = (steps[0] & 1u) ? end[0] ^ 1 : end[0];
+                    if (F.kind == SWFR_FILTER_SHADOW) launch_shadow_alpha(r->stream, fb, buf[first], r->width, r->height, S.dx, S.dy);
+                    else launch_blur_capture(r->stream, fb, buf[first], n);
+                    blur_image(r->stream, buf[first], buf[first ^ 1], r->width, r->height, S.blur_x, S.blur_y, S.passes);
+                    // (the finish pass in place over the blurred alpha: the sub-frame's framebuffer is still the group)
+                    if (F.kind == SWFR_FILTER_SHADOW)
+                        launch_shadow_finish(r->stream, buf[end[0]], fb, true, buf[end[0]], n, shadow_color_pixel(S.color), S.strength, S.flags);
+                } else if (F.kind == SWFR_FILTER_SHADOW) {
+                    uint32_t* const group = buf[end[i]];                 // (== end[i - 1]: a shadow ends where it began)
+                    launch_shadow_alpha(r->stream, group, buf[end[i] ^ 1], r->width, r->height, S.dx, S.dy);
+                    const uint32_t* const alpha = blur_image(r->stream, buf[end[i] ^ 1], buf[2], r->width, r->height, S.blur_x, S.blur_y, S.passes);
+                    launch_shadow_finish(r->stream, alpha, group, false, group, n, shadow_color_pixel(S.color), S.strength, S.flags);
+                } else {
+                    blur_image(r->stream, buf[end[i - 1]], buf[end[i - 1] ^ 1], r->width, r->height, S.blur_x, S.blur_y, S.passes);
+                }
+            }
+            HIP_CHECK(hipGetLastError());
         }
         HIP_CHECK(hipStreamSynchronize(r->stream));
         r->blur_table[k] = DevBitmap{tex, r->width, r->height};
@@ -2414,6 +2443,16 @@ int swfr_set_shadow(swfr_renderer* r, uint32_t slot, const swfr_shadow* shadow) 
     return SWFR_OK;
 }
 
+int swfr_set_filters(swfr_renderer* r, uint32_t slot, const swfr_filter* filters, uint32_t count) {
+    if (!r) return SWFR_ERR_INVALID;
+    if (slot > 65535) return fail(r, SWFR_ERR_INVALID, "InvalidFilter");
+    if (filters && count > SWFR_MAX_FILTERS) return fail(r, SWFR_ERR_CAPACITY, "FilterListLength");
+    for (uint32_t i = 0; filters && i < count; ++i)
+        if (!filter_valid(filters[i])) return fail(r, SWFR_ERR_INVALID, "InvalidFilter");
+    r->builder->set_filters(slot, filters, count);
+    return SWFR_OK;
+}
+
 int swfr_debug_time_cxform(swfr_renderer* r, uint32_t bitmap_id, const swfr_color_transform* ct, uint32_t reps, float* pass_ms, float* copy_ms) {
     if (!r || !ct || !pass_ms || !copy_ms || reps == 0) return fail(r, SWFR_ERR_INVALID, "null argument");
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
@@ -2472,9 +2511,9 @@ int swfr_built_layer(swfr_renderer* r, uint32_t k, const swfr_edge** edges, size
     if (n_paths) *n_paths = B.paths.size();
     if (styles) *styles = B.styles.data();
     if (n_styles) *n_styles = B.styles.size();
-    if (blur_x) *blur_x = B.blur_x;
-    if (blur_y) *blur_y = B.blur_y;
-    if (passes) *passes = B.passes;
+    if (blur_x) *blur_x = B.filters[0].shadow.blur_x;
+    if (blur_y) *blur_y = B.filters[0].shadow.blur_y;
+    if (passes) *passes = B.filters[0].shadow.passes;
     return SWFR_OK;
 }
 
@@ -2482,8 +2521,18 @@ int swfr_built_layer_shadow(swfr_renderer* r, uint32_t k, int* has_shadow, swfr_
     if (!r) return SWFR_ERR_INVALID;
     const auto& layers = r->builder->layers();
     if (k >= layers.size()) return fail(r, SWFR_ERR_NOT_FOUND, "no such blurred layer in the last built frame");
-    if (has_shadow) *has_shadow = layers[k].has_shadow ? 1 : 0;
-    if (out && layers[k].has_shadow) *out = layers[k].shadow;
+    const bool shadowed = layers[k].type == SWFR_OBJECT_SHADOWED_LAYER;
+    if (has_shadow) *has_shadow = shadowed ? 1 : 0;
+    if (out && shadowed) *out = layers[k].filters[0].shadow;
+    return SWFR_OK;
+}
+
+int swfr_built_layer_filters(swfr_renderer* r, uint32_t k, uint32_t* count, swfr_filter* out) {
+    if (!r) return SWFR_ERR_INVALID;
+    const auto& layers = r->builder->layers();
+    if (k >= layers.size()) return fail(r, SWFR_ERR_NOT_FOUND, "no such blurred layer in the last built frame");
+    if (count) *count = layers[k].n_filters;
+    if (out) std::copy(layers[k].filters, layers[k].filters + layers[k].n_filters, out);
     return SWFR_OK;
 }
 
