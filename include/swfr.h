@@ -290,14 +290,27 @@ int swfr_set_color_transform(swfr_renderer *r, uint32_t slot, const swfr_color_t
          premultiplied pixel as Cairo makes it (each of a, r * a, g * a, b * a in doubles, * 65535 + 0.5 to 16 bits, >> 8);
      R   SWFR_SHADOW_HIDE_OBJECT: Tc.  SWFR_SHADOW_KNOCKOUT: CAIRO_OPERATOR_DEST_OUT paint of G, R = mul_un8(Tc, 255 - Ga).  Neither:
          OVER paint of G, R = G + mul_un8(Tc, 255 - Ga), saturating.  Both: invalid.
+   An inner shadow (SWFR_SHADOW_INNER) is made of the inverse of the group's alpha and composited inside the group; S and R change,
+   the blur, T and Tc do not:
+     S'  clear; cairo_set_source_rgba(0, 0, 0, 1); cairo_paint; CAIRO_OPERATOR_DEST_OUT; cairo_mask_surface(G, dx, dy):
+         S(x, y) = (255 - Ga(x - dx, y - dy)) << 24, and 255 << 24 where that pixel lies outside the frame (it counts as empty);
+     R'  SWFR_SHADOW_INNER alone: CAIRO_OPERATOR_ATOP paint of Tc onto G, R = mul_un8(Tc, Ga) + mul_un8(G, 255 - Tca) per channel,
+         saturating; R's alpha is G's.  With SWFR_SHADOW_KNOCKOUT: CAIRO_OPERATOR_DEST_IN paint of G onto Tc, R = mul_un8(Tc, Ga) --
+         only the shadow, only inside the object.  With SWFR_SHADOW_HIDE_OBJECT: invalid -- inside the object "hide the object" and
+         "knock out" are the same picture, and it is offered once, as the knockout.
+   An inner glow is an inner shadow with dx = dy = 0.  The blur reads 0 beyond the frame, so an object that runs off the frame gets no
+   inner shadow along the frame's edge (right for an object that continues there; a Flash bitmap ends at the object's bounds); an
+   offset that shifts the whole group out of the frame gives a uniformly tinted object.
    A glow is a shadow with dx = dy = 0.  Not Flash Player's DropShadowFilter / GlowFilter: the box and the offset are whole device
    pixels that no matrix scales (a caller rounds distance * (cos, sin)(angle) itself), the strength is whole (Flash: 8.8 fixed), there
-   is no inner shadow and no quality beyond `passes`, the surface is cut to the frame before the shadow is made, an even box sits
+   is no quality beyond `passes`, the surface is cut to the frame before the shadow is made, an even box sits
    where pixman puts it, and a colour transform around the object recolours what is drawn inside, not the shadow.
-   Ranges: blur_x, blur_y 0..255; passes 1..15; dx, dy -32768..32767; strength 1..255; flags of the two below, not both; anything
-   else is SWFR_ERR_INVALID, "InvalidShadow". */
+   Ranges: blur_x, blur_y 0..255; passes 1..15; dx, dy -32768..32767; strength 1..255; flags 0, 1, 2, 8 or 10 (HIDE_OBJECT, KNOCKOUT, INNER,
+   INNER | KNOCKOUT); anything else is SWFR_ERR_INVALID, "InvalidShadow".  Bit 2 (value 4) is skipped on purpose: flags 4 and 5 have been
+   refused by name since shadows exist, the tests of the shadow and filter-list features hold them so, and they stay refused. */
 #define SWFR_SHADOW_HIDE_OBJECT 1u
 #define SWFR_SHADOW_KNOCKOUT 2u
+#define SWFR_SHADOW_INNER 8u
 typedef struct { uint32_t blur_x, blur_y, passes; int32_t dx, dy; swfr_rgba8 color; uint32_t strength, flags; } swfr_shadow;
 /* Sets shadow slot `slot` (< 65536) of the handle, or clears it (shadow == NULL), as swfr_set_color_transform does for its slots.  A
    value out of range: SWFR_ERR_INVALID, "InvalidShadow".  SWFR_OBJECT_SHADOWED_LAYER names a slot. */
@@ -309,7 +322,7 @@ int swfr_set_shadow(swfr_renderer *r, uint32_t slot, const swfr_shadow *shadow);
                          shadow.blur_y (0..255) and shadow.passes (1..15); every other field of `shadow` must be zero.
      SWFR_FILTER_SHADOW  R_i = the final surface R of swfr_shadow, above, with G := R_(i-1): what is shadowed is the earlier filters'
                          output, earlier shadows included.  The entry's `shadow` is checked as swfr_set_shadow checks one.
-   Not Flash Player's filter list: these two kinds only (no inner shadow, bevel, gradient glow, colour matrix or convolution), four
+   Not Flash Player's filter list: these two kinds only (no bevel, gradient glow, colour matrix or convolution), four
    entries at most, and every caveat of swfr_blur_bitmap's box and of swfr_shadow holds for each entry.
    An unknown kind or a value out of range: SWFR_ERR_INVALID, "InvalidFilter". */
 #define SWFR_MAX_FILTERS 4
@@ -633,6 +646,9 @@ int  swfr_debug_time_blur(swfr_renderer *r, uint32_t width, uint32_t height, uin
    with offset (dx, dy), the finish pass with a framebuffer-ordered group, in place --, `reps` times each, back to back, then `reps`
    device-to-device copies of the same bytes; HIP-event time per pass and per copy.  Touches no frame and no bitmap. */
 int  swfr_debug_time_shadow(swfr_renderer *r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float *alpha_ms, float *finish_ms, float *copy_ms);
+/* Measurement (tools/inner_bench.py): swfr_debug_time_shadow with the inner shadow's instances of the two passes -- the inverted alpha
+   pass and the inner finish pass (SWFR_SHADOW_INNER alone) --, over the same three textures in the same order. */
+int  swfr_debug_time_inner_shadow(swfr_renderer *r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float *alpha_ms, float *finish_ms, float *copy_ms);
 /* Device pointer of the premultiplied RGBA8 framebuffer (width*height*4 bytes, tight rows). */
 void *swfr_device_framebuffer(swfr_renderer *r);
 

@@ -38,7 +38,7 @@ EXPORTS = [
     "swfr_register_bitmap_tag", "swfr_decode_x_swf_bmp", "swfr_render_resident_async_to", "swfr_render_resident_group_to",
     "swfr_set_color_transform", "swfr_debug_time_cxform",
     "swfr_capture_bitmap", "swfr_blur_bitmap", "swfr_built_layers", "swfr_built_layer", "swfr_debug_time_blur",
-    "swfr_set_shadow", "swfr_shadow_bitmap", "swfr_built_layer_shadow", "swfr_debug_time_shadow",
+    "swfr_set_shadow", "swfr_shadow_bitmap", "swfr_built_layer_shadow", "swfr_debug_time_shadow", "swfr_debug_time_inner_shadow",
     "swfr_set_filters", "swfr_built_layer_filters",
 ]
 OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
@@ -49,6 +49,7 @@ OBJECT_FADED_LAYER = 13                 # a layer with an opacity (swfr.h SWFR_O
 OBJECT_BLURRED_LAYER = 16               # a blurred layer (swfr.h SWFR_OBJECT_BLURRED_LAYER): `id` is the blend mode | blur_x << 8 | blur_y << 16 | passes << 24
 OBJECT_SHADOWED_LAYER = 19              # a shadowed layer (swfr.h SWFR_OBJECT_SHADOWED_LAYER): `id` is the blend mode | shadow slot << 8
 SHADOW_HIDE_OBJECT, SHADOW_KNOCKOUT = 1, 2
+SHADOW_INNER = 8                        # (bit 2 is skipped: swfr.h)
 OBJECT_FILTERED_LAYER = 21              # a layer with an ordered filter list (swfr.h SWFR_OBJECT_FILTERED_LAYER): `id` is the blend mode | filter-list slot << 8
 MAX_FILTERS = 4                         # entries in one filter list
 FILTER_BLUR, FILTER_SHADOW = 0, 1       # swfr_filter::kind
@@ -95,9 +96,9 @@ def blur_values(blur):
 def shadow_values(shadow):
     """the (x, y, passes, dx, dy, r, g, b, a, strength, flags) of a "shadow" value: a dict with "color" ((r, g, b, a), straight bytes) and the
     integers "dx", "dy" (the offset in device pixels), "x", "y" (the box; all four absent: 0), "passes", "strength" (absent: 1) and the
-    booleans "hide_object", "knockout".  A value out of the library's range still goes there, to be refused by name, when it fits the struct."""
+    booleans "hide_object", "knockout", "inner".  A value out of the library's range still goes there, to be refused by name, when it fits the struct."""
     bad = SwfrError(ERR_INVALID, "InvalidShadow: %r" % (shadow,))
-    if not isinstance(shadow, dict) or set(shadow) - {"color", "dx", "dy", "x", "y", "passes", "strength", "hide_object", "knockout"}:
+    if not isinstance(shadow, dict) or set(shadow) - {"color", "dx", "dy", "x", "y", "passes", "strength", "hide_object", "knockout", "inner"}:
         raise bad
     color = shadow.get("color")
     if not isinstance(color, (tuple, list)) or len(color) != 4:
@@ -110,7 +111,7 @@ def shadow_values(shadow):
             raise bad
         v.append(int(n))
     flags = 0
-    for key, bit in (("hide_object", SHADOW_HIDE_OBJECT), ("knockout", SHADOW_KNOCKOUT)):
+    for key, bit in (("hide_object", SHADOW_HIDE_OBJECT), ("knockout", SHADOW_KNOCKOUT), ("inner", SHADOW_INNER)):
         if not isinstance(shadow.get(key, False), (bool, np.bool_)):
             raise bad
         flags |= bit if shadow.get(key, False) else 0
@@ -151,10 +152,13 @@ def _filter_structs(values):
 
 
 def _shadow_dict(sh):
-    """a Shadow as a "shadow" value with every key"""
-    return {"color": (sh.color.r, sh.color.g, sh.color.b, sh.color.a), "dx": sh.dx, "dy": sh.dy, "x": sh.blur_x, "y": sh.blur_y,
-            "passes": sh.passes, "strength": sh.strength, "hide_object": bool(sh.flags & SHADOW_HIDE_OBJECT),
-            "knockout": bool(sh.flags & SHADOW_KNOCKOUT)}
+    """a Shadow as a "shadow" value with every key; "inner" only where it is set"""
+    d = {"color": (sh.color.r, sh.color.g, sh.color.b, sh.color.a), "dx": sh.dx, "dy": sh.dy, "x": sh.blur_x, "y": sh.blur_y,
+         "passes": sh.passes, "strength": sh.strength, "hide_object": bool(sh.flags & SHADOW_HIDE_OBJECT),
+         "knockout": bool(sh.flags & SHADOW_KNOCKOUT)}
+    if sh.flags & SHADOW_INNER:
+        d["inner"] = True
+    return d
 
 
 def layer_mode_number(layer) -> int:
@@ -398,6 +402,8 @@ def load_library():
     L.swfr_built_layer_filters.argtypes = [P, U, C.POINTER(U), C.POINTER(Filter)]
     L.swfr_debug_time_shadow.restype = I
     L.swfr_debug_time_shadow.argtypes = [P, U, U, C.c_int32, C.c_int32, U, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.swfr_debug_time_inner_shadow.restype = I
+    L.swfr_debug_time_inner_shadow.argtypes = L.swfr_debug_time_shadow.argtypes
     L.swfr_debug_time_blur.restype = I
     L.swfr_debug_time_blur.argtypes = [P, U, U, U, U, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     if L.swfr_abi_version() != 1:
@@ -745,6 +751,13 @@ class Renderer:
         """swfr_debug_time_shadow: HIP-event milliseconds of one alpha pass, one finish pass and one device-to-device copy."""
         a, f, c = C.c_float(), C.c_float(), C.c_float()
         self._check(self.L.swfr_debug_time_shadow(self.h, width, height, dx, dy, reps, C.byref(a), C.byref(f), C.byref(c)))
+        return a.value, f.value, c.value
+
+    def debug_time_inner_shadow(self, width, height, dx=0, dy=0, reps=20):
+        """swfr_debug_time_inner_shadow: HIP-event milliseconds of one inverted alpha pass, one inner finish pass and one device-to-device
+        copy."""
+        a, f, c = C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.swfr_debug_time_inner_shadow(self.h, width, height, dx, dy, reps, C.byref(a), C.byref(f), C.byref(c)))
         return a.value, f.value, c.value
 
     def debug_time_blur(self, width, height, w, reps=20):

@@ -77,8 +77,8 @@ constexpr int BLUR_IN_PIECE = -16;
 
 bool shadow_valid(const swfr_shadow& s) {
     return s.blur_x <= 255u && s.blur_y <= 255u && s.passes >= 1u && s.passes <= 15u && s.dx >= -32768 && s.dx <= 32767 && s.dy >= -32768 &&
-           s.dy <= 32767 && s.strength >= 1u && s.strength <= 255u && (s.flags & ~(SWFR_SHADOW_HIDE_OBJECT | SWFR_SHADOW_KNOCKOUT)) == 0u &&
-           s.flags != (SWFR_SHADOW_HIDE_OBJECT | SWFR_SHADOW_KNOCKOUT);
+           s.dy <= 32767 && s.strength >= 1u && s.strength <= 255u &&
+           (s.flags <= SWFR_SHADOW_KNOCKOUT || s.flags == SWFR_SHADOW_INNER || s.flags == (SWFR_SHADOW_INNER | SWFR_SHADOW_KNOCKOUT));   // 0, 1, 2, 8, 10
 }
 uint32_t shadow_color_pixel(const swfr_rgba8& c) { return premultiplied_pixel(Css{c.r, c.g, c.b, c.a}); }
 bool filter_valid(const swfr_filter& f) {

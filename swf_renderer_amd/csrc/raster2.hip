@@ -1,5 +1,5 @@
-// raster2.hip -- the kernels of the hot path (raw edge list -> RGBA8 framebuffer in HBM), CDNA4 / gfx950.  The build's only device
-// translation unit; raster_common.hip (included below) holds the exact-arithmetic helpers, the replay of Cairo's edge-list order
+// raster2.hip -- the kernels of the hot path (raw edge list -> RGBA8 framebuffer in HBM), CDNA4 / gfx950.  The build's device
+// translation unit (but for shadow_inner.hip, the inner shadow's three kernels); raster_common.hip (included below) holds the exact-arithmetic helpers, the replay of Cairo's edge-list order
 // and the shaders the kernels share.  Arithmetic: Cairo 1.16 "tor" scan conversion + pixman sampling.
 //
 // One frame = four launches on one stream (DESIGN.md section 3 has the data layout and the bytes):

@@ -502,31 +502,13 @@ __device__ __forceinline__ uint32_t mul8x2_7f(uint32_t a, uint32_t b) {
     uint32_t t = (a & 0xff00ffu) * b + 0x7f007fu;
     return ((t + ((t >> 8) & 0xff00ffu)) >> 8) & 0xff00ffu;
 }
-__device__ __forceinline__ uint32_t add8x2_sat(uint32_t a, uint32_t b) {
-    uint32_t t = a + b;
-    t |= 0x1000100u - ((t >> 8) & 0xff00ffu);
-    return t & 0xff00ffu;
-}
+#include "pixman_ops.hip"                 // add8x2_sat, mul_un8, over_pixel: shared with shadow_inner.hip
 // Cairo's span lerp for SOURCE with 8-bit coverage (0x7f rounding)
 __device__ __forceinline__ uint32_t lerp_pixel(uint32_t src, uint32_t a, uint32_t dst) {
     // Cairo adds the two products with a saturating add; they cannot exceed 255 per channel (a + (255 - a) = 255 and both
     // products round down from src*a/255 + 1/2), so a plain add gives the same bits
     const uint32_t ia = 255u - a;
     return (mul8x2_7f(src, a) + mul8x2_7f(dst, ia)) | ((mul8x2_7f(src >> 8, a) + mul8x2_7f(dst >> 8, ia)) << 8);
-}
-// pixman UN8x4_MUL_UN8 (0x80 rounding) and OVER
-__device__ __forceinline__ uint32_t mul_un8(uint32_t x, uint32_t a) {
-    uint32_t rb = (x & 0xff00ffu) * a + 0x800080u;
-    rb = ((rb + ((rb >> 8) & 0xff00ffu)) >> 8) & 0xff00ffu;
-    uint32_t ag = ((x >> 8) & 0xff00ffu) * a + 0x800080u;
-    ag = ((ag + ((ag >> 8) & 0xff00ffu)) >> 8) & 0xff00ffu;
-    return rb | (ag << 8);
-}
-__device__ __forceinline__ uint32_t over_pixel(uint32_t src, uint32_t dst) {
-    const uint32_t m = mul_un8(dst, 255u - (src >> 24));
-    const uint32_t rb = add8x2_sat(m & 0xff00ffu, src & 0xff00ffu);
-    const uint32_t ag = add8x2_sat((m >> 8) & 0xff00ffu, (src >> 8) & 0xff00ffu);
-    return rb | (ag << 8);
 }
 
 __device__ uint32_t gradient_color(const swfr_style& s, double t) {

@@ -42,7 +42,7 @@ void launch_pack_band(hipStream_t, const uint32_t*, uint32_t*, int, int, uint32_
 void launch_cxform_texels(hipStream_t, const uint8_t*, uint32_t*, size_t, const uint32_t*);
 void launch_blur_capture(hipStream_t, const uint32_t*, uint32_t*, size_t);
 void launch_blur_pass(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, bool);
-void launch_shadow_alpha(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, int32_t, int32_t);
+void launch_shadow_alpha(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, int32_t, int32_t, bool);
 void launch_shadow_finish(hipStream_t, const uint32_t*, const uint32_t*, bool, uint32_t*, size_t, uint32_t, uint32_t, uint32_t);
 }  // namespace swfr
 
@@ -1891,7 +1891,7 @@ int render_blur_layers(swfr_renderer* r) {
                 if (i == 0) {
                     // the capture or the alpha pass goes where the box passes, alternating between 0 and 1, end in end[0]
                     const int first = (steps[0] & 1u) ? end[0] ^ 1 : end[0];
-                    if (F.kind == SWFR_FILTER_SHADOW) launch_shadow_alpha(r->stream, fb, buf[first], r->width, r->height, S.dx, S.dy);
+                    if (F.kind == SWFR_FILTER_SHADOW) launch_shadow_alpha(r->stream, fb, buf[first], r->width, r->height, S.dx, S.dy, (S.flags & SWFR_SHADOW_INNER) != 0u);
                     else launch_blur_capture(r->stream, fb, buf[first], n);
                     blur_image(r->stream, buf[first], buf[first ^ 1], r->width, r->height, S.blur_x, S.blur_y, S.passes);
                     // (the finish pass in place over the blurred alpha: the sub-frame's framebuffer is still the group)
@@ -1899,7 +1899,7 @@ int render_blur_layers(swfr_renderer* r) {
                         launch_shadow_finish(r->stream, buf[end[0]], fb, true, buf[end[0]], n, shadow_color_pixel(S.color), S.strength, S.flags);
                 } else if (F.kind == SWFR_FILTER_SHADOW) {
                     uint32_t* const group = buf[end[i]];                 // (== end[i - 1]: a shadow ends where it began)
-                    launch_shadow_alpha(r->stream, group, buf[end[i] ^ 1], r->width, r->height, S.dx, S.dy);
+                    launch_shadow_alpha(r->stream, group, buf[end[i] ^ 1], r->width, r->height, S.dx, S.dy, (S.flags & SWFR_SHADOW_INNER) != 0u);
                     const uint32_t* const alpha = blur_image(r->stream, buf[end[i] ^ 1], buf[2], r->width, r->height, S.blur_x, S.blur_y, S.passes);
                     launch_shadow_finish(r->stream, alpha, group, false, group, n, shadow_color_pixel(S.color), S.strength, S.flags);
                 } else {
@@ -2611,7 +2611,7 @@ int swfr_shadow_bitmap(swfr_renderer* r, uint32_t dst_id, uint32_t src_id, const
         if (dst_id != src_id) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fresh), std::max<size_t>(n, 1) * 4));
         const uint32_t* const group = sit->second.pixels;
         uint32_t* const out = fresh ? fresh : sit->second.pixels;
-        launch_shadow_alpha(r->stream, group, r->shadow_scratch.ptr, w, h, shadow->dx, shadow->dy);
+        launch_shadow_alpha(r->stream, group, r->shadow_scratch.ptr, w, h, shadow->dx, shadow->dy, (shadow->flags & SWFR_SHADOW_INNER) != 0u);
         const uint32_t* at = blur_image(r->stream, r->shadow_scratch.ptr, r->blur_scratch.ptr, w, h, shadow->blur_x, shadow->blur_y, shadow->passes);
         launch_shadow_finish(r->stream, at, group, false, out, n, shadow_color_pixel(shadow->color), shadow->strength, shadow->flags);
         const hipError_t launched = hipGetLastError(), done = hipStreamSynchronize(r->stream);
@@ -2646,13 +2646,34 @@ int swfr_debug_time_shadow(swfr_renderer* r, uint32_t width, uint32_t height, in
         const size_t n = size_t(width) * height, bytes = n * 4;
         uint32_t *a = nullptr, *b = nullptr, *c = nullptr;
         const uint32_t cp = 0x80402010u;
-        const auto alpha = [&]() { launch_shadow_alpha(r->stream, a, b, width, height, dx, dy); };
+        const auto alpha = [&]() { launch_shadow_alpha(r->stream, a, b, width, height, dx, dy, false); };
         // (in place over the alpha words, as swfr_render runs it: a result's alpha byte is the next repetition's input, whatever it is)
         const auto finish = [&]() { launch_shadow_finish(r->stream, b, c, true, b, n, cp, 1u, 0u); };
         const auto copy = [&]() { HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream)); };
         return time_phases(r, reps, {{&a, bytes, 0x5a}, {&b, bytes, -1}, {&c, bytes, 0x5a}}, [&]() {   // (warm-up of both kernels and the copy)
             alpha();
             launch_shadow_finish(r->stream, b, a, true, b, n, cp, 1u, 0u);
+            copy();
+        }, {{alpha, alpha_ms}, {finish, finish_ms}, {copy, copy_ms}});
+    });
+}
+
+int swfr_debug_time_inner_shadow(swfr_renderer* r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float* alpha_ms, float* finish_ms, float* copy_ms) {
+    if (!r || !alpha_ms || !finish_ms || !copy_ms || reps == 0 || width == 0 || height == 0 || width > 32768 || height > 32768 || dx < -32768 ||
+        dx > 32767 || dy < -32768 || dy > 32767)
+        return fail(r, SWFR_ERR_INVALID, "bad argument");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    return guarded(r, [&]() {
+        const size_t n = size_t(width) * height, bytes = n * 4;
+        uint32_t *a = nullptr, *b = nullptr, *c = nullptr;
+        const uint32_t cp = 0x80402010u;
+        // (swfr_debug_time_shadow with the inner instances: the same buffers, the same order)
+        const auto alpha = [&]() { launch_shadow_alpha(r->stream, a, b, width, height, dx, dy, true); };
+        const auto finish = [&]() { launch_shadow_finish(r->stream, b, c, true, b, n, cp, 1u, SWFR_SHADOW_INNER); };
+        const auto copy = [&]() { HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream)); };
+        return time_phases(r, reps, {{&a, bytes, 0x5a}, {&b, bytes, -1}, {&c, bytes, 0x5a}}, [&]() {
+            alpha();
+            launch_shadow_finish(r->stream, b, a, true, b, n, cp, 1u, SWFR_SHADOW_INNER);
             copy();
         }, {{alpha, alpha_ms}, {finish, finish_ms}, {copy, copy_ms}});
     });

@@ -1,6 +1,7 @@
 """The compiler's resource remarks of every kernel in csrc/raster2.hip (gfx950; needs hipcc, no GPU): SGPRs, VGPRs, scratch,
 spills, LDS, occupancy -- one line per kernel.  A pull request that must leave existing kernels alone compares this listing before
-and after (profiles/blend_kernel_resources.txt).
+and after (profiles/blend_kernel_resources.txt).  listing() is raster2.hip's, the unit the budget tests hold; listing(unit) is that
+of another device translation unit of the build (shadow_inner.hip), and the command line lists them all, raster2.hip first.
 
 usage: python tools/kernel_resources.py [-o listing.txt] [--diff older_listing.txt]
 """
@@ -15,19 +16,23 @@ sys.path.insert(0, ROOT)
 FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
 
 
-_LISTING = None                                                        # (one compile per process, however many callers)
+_LISTING = {}                                                          # (one compile per unit and process, however many callers)
 
 
-def listing():
-    global _LISTING
-    if _LISTING is None:
-        _LISTING = _compile_listing()
-    return list(_LISTING)
-
-
-def _compile_listing():
+def device_units():
     from swf_renderer_amd import build as b
-    src = os.path.join(b.CSRC, "raster2.hip")
+    return [s for s in b.SOURCES if s.endswith(".hip")]
+
+
+def listing(unit="raster2.hip"):
+    if unit not in _LISTING:
+        _LISTING[unit] = _compile_listing(unit)
+    return list(_LISTING[unit])
+
+
+def _compile_listing(unit):
+    from swf_renderer_amd import build as b
+    src = os.path.join(b.CSRC, unit)
     with tempfile.TemporaryDirectory() as tmp:
         cmd = [b.hipcc(), "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-DSWFR_BUILD",
                "--cuda-device-only", "-c", src, "-o", os.path.join(tmp, "dev.o"), "-Rpass-analysis=kernel-resource-usage"]
@@ -46,7 +51,7 @@ def _compile_listing():
 
 
 def main():
-    lines = listing()
+    lines = [l for unit in device_units() for l in listing(unit)]
     text = "\n".join(lines) + "\n"
     if "-o" in sys.argv:
         open(sys.argv[sys.argv.index("-o") + 1], "w").write(text)
