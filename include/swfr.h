@@ -551,7 +551,7 @@ int  swfr_shape_json(swfr_renderer *r, uint32_t id, int morph, const char **json
    ts/src/test/node-canvas-renderer.spec.ts:86-113; rs/src/lib.rs:116-130).  With a device destination the frames are rendered
    in groups of up to SWFR_BATCH_FRAMES (default 64) by ONE launch per kernel and group, two groups alternating so that the host
    builds one while the GPU renders the other; frame i lands, premultiplied RGBA8 with tight rows, at device_dst + i * frame_stride
-   (DEVICE memory, e.g. a torch tensor).  With device_dst == NULL the frames are rendered one after the other and only the last is
+   (DEVICE memory, e.g. a torch tensor; both multiples of 4 bytes, else SWFR_ERR_INVALID "MisalignedTarget", see swfr_set_targets).  With device_dst == NULL the frames are rendered one after the other and only the last is
    kept for swfr_read_image.  Blocking: returns when every frame is finished.
    A refused frame (e.g. SWFR_ERR_NOT_FOUND for an unknown shape or bitmap) ends the batch with its error code, returned only after
    everything the call queued has finished: no frame is still being written.  The frames before it are complete, except that with
@@ -614,7 +614,11 @@ int  swfr_copy_band_slab(swfr_renderer *r, void *device_dst);
    some tile-rows writes only those rows.  swfr_render_resident_async queues one frame on the next frame set without waiting and
    reports which set (and so which target and which stream) it used; swfr_stream_handle gives that set's hipStream_t so that the
    caller's own streams can be ordered behind / before it with events; swfr_wait blocks until everything queued has finished and
-   reports the kernels' error state like swfr_render_resident does. */
+   reports the kernels' error state like swfr_render_resident does.
+   Alignment: every target, block target and batch destination is written as 32-bit words, so its address -- and the frame_stride
+   of swfr_render_batch -- must be a multiple of 4 bytes; one that is not is refused with SWFR_ERR_INVALID and the message
+   "MisalignedTarget" before anything is launched, and the handle keeps the targets it had.  Nothing more is asked: a target that
+   is only 4-, 8- or 12-byte aligned is rendered into with narrower stores, to the same bytes. */
 int  swfr_set_targets(swfr_renderer *r, void *const *device_targets, uint32_t n_targets);
 int  swfr_render_resident_async(swfr_renderer *r, uint32_t *out_set);
 /* The same, with THIS frame's pixels going to block_target: a device buffer that holds only the handle's own block of tile-rows

@@ -2280,6 +2280,10 @@ int time_phases(swfr_renderer* r, uint32_t reps, std::initializer_list<ProbeBuff
 // (swfr_last_error(NULL): why this thread's last swfr_create refused a flag combination, if it did)
 thread_local const char* create_error = nullptr;
 
+// a caller's device address or stride that every kernel takes as uint32_t words
+inline bool word_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0u; }
+inline bool word_aligned(size_t bytes) { return (bytes & 3u) == 0u; }
+
 }  // namespace
 
 extern "C" {
@@ -2773,6 +2777,7 @@ int swfr_render_sequence_readback(swfr_renderer* r, const swfr_stage* stages, ui
 int swfr_render_batch(swfr_renderer* r, const swfr_stage* stages, uint32_t n_stages, void* device_dst, size_t frame_stride) {
     if (!r || (!stages && n_stages)) return fail(r, SWFR_ERR_INVALID, "null argument");
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    if (device_dst && !(word_aligned(device_dst) && word_aligned(frame_stride))) return fail(r, SWFR_ERR_INVALID, "MisalignedTarget");
     ++r->cx_epoch;
     return guarded(r, [&]() { return render_batch(r, stages, n_stages, device_dst, frame_stride); });
 }
@@ -2866,6 +2871,8 @@ int swfr_copy_band_slab(swfr_renderer* r, void* device_dst) {
 
 int swfr_set_targets(swfr_renderer* r, void* const* device_targets, uint32_t n_targets) {
     if (!r || n_targets > 4 || (n_targets && !device_targets)) return fail(r, SWFR_ERR_INVALID, "bad targets");
+    for (uint32_t k = 0; k < n_targets; ++k)                  // (refused as a whole: the handle keeps the targets it had)
+        if (!word_aligned(device_targets[k])) return fail(r, SWFR_ERR_INVALID, "MisalignedTarget");
     r->n_targets = n_targets;
     for (uint32_t k = 0; k < n_targets; ++k) r->targets[k] = static_cast<uint32_t*>(device_targets[k]);
     r->scene_ready = false;                               // the frame descriptors carry the framebuffer address: upload again
@@ -2877,11 +2884,15 @@ int swfr_render_resident_async(swfr_renderer* r, uint32_t* out_set) {
 }
 
 int swfr_render_resident_async_to(swfr_renderer* r, void* block_target, uint32_t* out_set) {
-    return r && block_target ? render_resident_async(r, block_target, out_set) : SWFR_ERR_INVALID;
+    if (!r || !block_target) return SWFR_ERR_INVALID;
+    if (!word_aligned(block_target)) return fail(r, SWFR_ERR_INVALID, "MisalignedTarget");
+    return render_resident_async(r, block_target, out_set);
 }
 
 int swfr_render_resident_group_to(swfr_renderer* r, void* const* block_targets, uint32_t n_frames, uint32_t* sets_used) {
     if (!r || !block_targets || n_frames == 0 || n_frames > 64) return SWFR_ERR_INVALID;
+    for (uint32_t i = 0; i < n_frames; ++i)                  // (before the first launch: no frame of the group is queued)
+        if (block_targets[i] && !word_aligned(block_targets[i])) return fail(r, SWFR_ERR_INVALID, "MisalignedTarget");
     uint32_t used = 0;
     for (uint32_t i = 0; i < n_frames; ++i) {
         uint32_t k = 0;

@@ -131,6 +131,87 @@ def two_bands(W, H, contiguous, draw, aliased=False, make=None, bitmaps=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- caller-owned frames
+SENTINEL = 0xA5
+
+
+class GuardedFrames:
+    """n frames of h x w RGBA8 words in ONE allocation of device memory (a torch tensor; under the emulator, whose device memory is
+    host memory, numpy) filled with SENTINEL bytes: frame i starts at base + pad + offset + i * (h * w * 4 + gap), where `base` is
+    picked from the allocation's real address so that frame 0's address is `offset` modulo 16 -- `offset` 4, 8 or 12: a target that is
+    word aligned only; 1, 2, 3: one no kernel may be given.  Every byte of the allocation outside the frames is a guard: the front pad,
+    the gaps, the back pad.  The frames start as SENTINEL bytes too: a frame with clear pixels that equals its expected picture has
+    had every pixel written.  All of it lies inside the one allocation: a store that strays by less than `pad` bytes is seen and
+    harms nothing."""
+
+    def __init__(self, n, h, w, offset=0, gap=0, pad=256):
+        assert n >= 1 and 0 <= offset < 16 and gap >= 0 and pad >= 16
+        self.n, self.h, self.w, self.offset, self.gap = n, h, w, offset, gap
+        self.frame_bytes = h * w * 4
+        self.stride = self.frame_bytes + gap
+        size = 16 + pad + offset + (n - 1) * self.stride + self.frame_bytes + pad
+        if EMU:
+            self.a = np.full(size, SENTINEL, np.uint8)
+            address = self.a.ctypes.data
+        else:
+            import torch
+            self.t = torch.full((size,), SENTINEL, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            address = self.t.data_ptr()
+        self.first = (-(address + pad)) % 16 + pad + offset          # frame 0's place in the allocation
+        self.ptr = address + self.first
+        assert self.ptr % 16 == offset and self.first >= pad and self.first + (n - 1) * self.stride + self.frame_bytes + pad <= size
+
+    def address(self, i):
+        assert 0 <= i < self.n
+        return self.ptr + i * self.stride
+
+    def addresses(self):
+        return [self.address(i) for i in range(self.n)]
+
+    def _bytes(self, wait):
+        if EMU:
+            return self.a.copy()
+        if wait:
+            import torch
+            torch.cuda.synchronize()
+        return self.t.cpu().numpy()
+
+    def _frames_of(self, b):
+        if self.gap == 0:
+            return b[self.first:self.first + self.n * self.frame_bytes].reshape(self.n, self.h, self.w, 4)
+        return np.stack([b[self.first + i * self.stride:][:self.frame_bytes].reshape(self.h, self.w, 4) for i in range(self.n)])
+
+    def raw(self):
+        """the n frames as they are, without waiting for anything"""
+        return self._frames_of(self._bytes(False))
+
+    def frames(self):
+        """the n frames, [n, h, w, 4], once the device is idle"""
+        return self._frames_of(self._bytes(True))
+
+    def guards_intact(self):
+        """every byte outside the frames is still SENTINEL; returns the frames (read in the same copy)"""
+        b = self._bytes(True)
+        at = 0
+        for i in range(self.n + 1):
+            end = self.first + i * self.stride if i < self.n else len(b)
+            bad = np.flatnonzero(b[at:end] != SENTINEL)
+            assert bad.size == 0, "guard bytes %d..%d overwritten (%d of them; frame %d begins at byte %d)" % (
+                at + bad[0], at + bad[-1], bad.size, min(i, self.n - 1), self.first + min(i, self.n - 1) * self.stride)
+            at = end + self.frame_bytes
+        return self._frames_of(b)
+
+    def refill(self):
+        if EMU:
+            self.a[:] = SENTINEL
+        else:
+            import torch
+            torch.cuda.synchronize()
+            self.t.fill_(SENTINEL)
+            torch.cuda.synchronize()
+
+
 # ---------------------------------------------------------------------------------------------------------------- the goldens
 def golden_scenes(family, fname, route, thin=True):
     """([(name, scene)], aliased, the golden file) of one route"""

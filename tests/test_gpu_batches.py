@@ -19,6 +19,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import device_routes as dr  # noqa: E402
 import helpers  # noqa: E402
 import scenarios  # noqa: E402
 from helpers import diff_stats, oracle_render  # noqa: E402
@@ -32,7 +33,7 @@ W, H = helpers.BATCH_W, helpers.BATCH_H
 CORPUS = helpers.batch_corpus()
 KINDS = list(CORPUS)
 LINEAR = {"linear"}                          # the documented +-1 LSB extension against the oracle
-SENTINEL = 0xA5
+SENTINEL = dr.SENTINEL
 
 
 def _pairs(kinds):
@@ -124,36 +125,16 @@ def _renderer(mode="nonzero", width=W, height=H, bitmaps=None):
     return r
 
 
-class _Dest:
-    """n frames of device memory (a torch tensor; under the emulator, whose device memory is host memory, numpy), filled with
-    SENTINEL bytes.  raw() reads it as it is, without waiting for anything."""
-
-    def __init__(self, n, h=H, w=W):
-        if EMU:
-            self.a = np.full((n, h, w, 4), SENTINEL, np.uint8)
-            self.ptr = self.a.ctypes.data
-        else:
-            import torch
-            self.t = torch.full((n, h, w, 4), SENTINEL, dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            self.ptr = self.t.data_ptr()
-        self.stride = h * w * 4
-
-    def raw(self):
-        return self.a.copy() if EMU else self.t.cpu().numpy()
-
-    def numpy(self):
-        if not EMU:
-            import torch
-            torch.cuda.synchronize()
-        return self.raw()
+def _Dest(n, h=H, w=W):
+    """n frames of device memory filled with SENTINEL bytes, guard bytes before and behind them (tests/device_routes.py)"""
+    return dr.GuardedFrames(n, h, w, offset=0, gap=0)
 
 
 def _batch(r, kinds, where, mode="nonzero"):
     """render_batch of the corpus frames `kinds` into a device destination; every frame checked"""
     d = _Dest(len(kinds))
     r.render_batch([CORPUS[k]["stage"] for k in kinds], d.ptr, d.stride)
-    got = d.numpy()
+    got = d.guards_intact()
     for i, k in enumerate(kinds):
         _check(got[i], k, mode, (where, i))
 
@@ -318,7 +299,7 @@ def test_dense_4k_frames_in_groups_of_two(monkeypatch):
     try:
         d = _Dest(len(frames), 2160, 3840)
         r.render_batch([sc["stage"] for sc in frames], d.ptr, d.stride)
-        got = d.numpy()
+        got = d.guards_intact()
     finally:
         r.close()
     for i, sc in enumerate(frames):
@@ -381,6 +362,7 @@ def test_refused_frame_ends_the_batch_after_its_work(what, route, monkeypatch):
                     _check(got[i], k, "nonzero", (what, route, pos, i))
                 else:
                     assert (got[i] == SENTINEL).all(), (what, route, pos, i)
+            d.guards_intact()
             with pytest.raises(S.SwfrError) as e:
                 r.read_image(premultiplied=True)
             assert e.value.code == api.ERR_INVALID
