@@ -221,7 +221,7 @@ enum { SWFR_OBJECT_SHAPE = 0, SWFR_OBJECT_MORPH_SHAPE = 1, SWFR_OBJECT_CONTAINER
        /* 20 is not a display-object type */
        SWFR_OBJECT_FILTERED_LAYER = 21   /* a layer with an ordered filter list: a container (matrix + children) whose children are drawn
                                             onto a transparent surface of the frame's size, as a blurred layer's are; the list's entries
-                                            (swfr_filter, below: box blurs and shadows, 1..SWFR_MAX_FILTERS of them) are applied to that
+                                            (swfr_filter, below: box blurs, shadows and convolutions, 1..SWFR_MAX_FILTERS of them) are applied to that
                                             surface one after the other, each to the result of the one before it -- a shadow later in the
                                             list shadows the earlier filters' output, earlier shadows included --, and the last result is
                                             composited onto the parent as ONE layer.  `id` is mode | slot << 8: the mode an SWF blend-mode
@@ -322,17 +322,47 @@ int swfr_set_shadow(swfr_renderer *r, uint32_t slot, const swfr_shadow *shadow);
                          shadow.blur_y (0..255) and shadow.passes (1..15); every other field of `shadow` must be zero.
      SWFR_FILTER_SHADOW  R_i = the final surface R of swfr_shadow, above, with G := R_(i-1): what is shadowed is the earlier filters'
                          output, earlier shadows included.  The entry's `shadow` is checked as swfr_set_shadow checks one.
-   Not Flash Player's filter list: these two kinds only (no bevel, gradient glow, colour matrix or convolution), four
-   entries at most, and every caveat of swfr_blur_bitmap's box and of swfr_shadow holds for each entry.
-   An unknown kind or a value out of range: SWFR_ERR_INVALID, "InvalidFilter". */
+     SWFR_FILTER_CONVOLUTION
+                         R_i = R_(i-1) convolved with the kernel (swfr_kernel, below) of the slot that shadow.blur_x names (0..65535),
+                         as swfr_convolve_bitmap convolves, on all four channels.  Every other field of `shadow` must be zero.  The
+                         kernel is the slot's value at the scene walk, like a shadowed layer's shadow: an unset slot there is
+                         SWFR_ERR_NOT_FOUND, "KernelNotFound" (swfr_set_filters does not look at the slot).
+   Not Flash Player's filter list: these three kinds only (no bevel, gradient glow or colour matrix), four
+   entries at most, and every caveat of swfr_blur_bitmap's box, of swfr_shadow and of swfr_kernel holds for each entry.
+   An unknown kind or a value out of range: SWFR_ERR_INVALID, "InvalidFilter".  Kinds 2 and 3 are skipped on purpose: they, 255 and
+   2^32 - 1 have been refused by name since filter lists exist, the tests of that feature hold them so, and they stay refused. */
 #define SWFR_MAX_FILTERS 4
-enum { SWFR_FILTER_BLUR = 0, SWFR_FILTER_SHADOW = 1 };
+enum { SWFR_FILTER_BLUR = 0, SWFR_FILTER_SHADOW = 1, SWFR_FILTER_CONVOLUTION = 4 };
 typedef struct { uint32_t kind; swfr_shadow shadow; } swfr_filter;
 /* Sets filter-list slot `slot` (< 65536) of the handle to the `count` entries at `filters`, or clears it (filters == NULL or count == 0),
    as swfr_set_shadow does for its slots.  A slot above 65535, an unknown kind or a value out of range: SWFR_ERR_INVALID,
    "InvalidFilter"; count > SWFR_MAX_FILTERS: SWFR_ERR_CAPACITY, "FilterListLength".  A refused call leaves the slot as it was.
    SWFR_OBJECT_FILTERED_LAYER names a slot. */
 int swfr_set_filters(swfr_renderer *r, uint32_t slot, const swfr_filter *filters, uint32_t count);
+
+/* ---- convolution kernels ("Convolution filters") -------------------------------------------------------------------
+   A kernel of width x height taps (1..SWFR_MAX_KERNEL_DIM each way) in row-major order, each a signed 16.16 number.  For every pixel
+   (x, y) of a premultiplied image and every channel c, alpha included and treated like the colours:
+     S = sum_j sum_i taps[j * width + i] * c(x - width / 2 + i, y - height / 2 + j) + 0x8000
+     out = S < 0 ? 255 : min(255, S >> 16)
+   -- integer divisions, a tap outside the image reading 0: what pixman 0.40 computes for PIXMAN_FILTER_CONVOLUTION with these taps
+   under PIXMAN_OP_SRC from an image of EXTEND_NONE, byte for byte.  A NEGATIVE SUM GIVES 255, NOT 0: pixman 0.40 keeps the sums in
+   unsigned integers (pixman-bits-image.c, reduce_32), so a negative one is a huge one and clips at the top.  A sharpen, emboss or edge
+   kernel therefore turns the pixels it would darken below zero fully bright, alpha included; this library follows libpixman, the
+   yardstick it is held against, and does not mend it.  The window sits where a
+   box of swfr_blur_bitmap sits: an even size reaches one pixel further left and up.  The sum of the taps' absolute values is at most
+   8 388 607 (below 128.0): a kernel beyond that is refused, never wrapped.  All taps zero is legal (a clear surface); the 1 x 1 kernel
+   {65536} is the identity.  Negative taps make pixels whose colour exceeds their alpha; what follows (later entries, the composite)
+   treats them with the saturating arithmetic libcairo treats them with.
+   Not Flash Player's ConvolutionFilter: no bias, no preserveAlpha (alpha is convolved like the colours, on premultiplied pixels), no
+   clamp / color (outside the frame reads clear); dimensions up to 7; the taps are in device pixels, which no matrix scales; the
+   surface is cut to the frame first; the caller folds the divisor into the taps.
+   A dimension of 0 or above 7, or a sum beyond the bound: SWFR_ERR_INVALID, "InvalidKernel". */
+#define SWFR_MAX_KERNEL_DIM 7
+typedef struct { uint32_t width, height; int32_t taps[49]; } swfr_kernel;
+/* Sets kernel slot `slot` (< 65536) of the handle, or clears it (kernel == NULL), as swfr_set_shadow does for its slots.  A refused call
+   leaves the slot as it was.  A filter entry of kind SWFR_FILTER_CONVOLUTION names a slot. */
+int swfr_set_kernel(swfr_renderer *r, uint32_t slot, const swfr_kernel *kernel);
 
 /* ---- configuration ------------------------------------------------------------------------ */
 #define SWFR_DEVICE_HOST_ONLY (-1)       /* decode + geometry only; swfr_render fails with NO_DEVICE */
@@ -400,6 +430,11 @@ int  swfr_blur_bitmap(swfr_renderer *r, uint32_t bitmap_id, uint32_t blur_x, uin
    and the finish pass run on the device (scratch textures the handle keeps).  `shadow` out of range: SWFR_ERR_INVALID,
    "InvalidShadow"; an unknown src_id: SWFR_ERR_NOT_FOUND.  Blocking, ordered like swfr_blur_bitmap. */
 int  swfr_shadow_bitmap(swfr_renderer *r, uint32_t dst_id, uint32_t src_id, const swfr_shadow *shadow);
+/* Registered bitmap `bitmap_id` convolved with `kernel` (swfr_kernel, above) on the device: one out-of-place pass over the premultiplied
+   ARGB texels into a scratch texture the handle keeps, and the result back in the bitmap's own texture.  `kernel` NULL or out of range:
+   SWFR_ERR_INVALID, "InvalidKernel"; a host-only handle: SWFR_ERR_NO_DEVICE; an unknown id: SWFR_ERR_NOT_FOUND.  The bitmap's
+   generation is bumped and it counts as captured from then on.  Blocking, ordered like swfr_blur_bitmap. */
+int  swfr_convolve_bitmap(swfr_renderer *r, uint32_t bitmap_id, const swfr_kernel *kernel);
 int  swfr_read_image(swfr_renderer *r, uint8_t *dst, size_t dst_stride, int premultiplied);
 /* Mapped read-back in two halves (HeadlessGfxRenderer::get_image maps its staging buffer the same way:
    rs/src/headless_renderer.rs:725-868): _async queues the device-to-host copy of the last frame into the handle's PINNED staging
@@ -525,7 +560,8 @@ int  swfr_build_frame(swfr_renderer *r, const swfr_stage *stage,
 
 /* The sub-frames of the blurred, shadowed and filtered layers (SWFR_OBJECT_BLURRED_LAYER, _SHADOWED_LAYER, _FILTERED_LAYER) of the frame
    the handle's last scene walk built: how many, and the k-th one's arrays -- what swfr_render renders, captures and filters into texture
-   SWFR_BLUR_BASE + k before the parent frame -- with its blur: a shadowed layer's shadow's box, a filtered layer's first entry's box.
+   SWFR_BLUR_BASE + k before the parent frame -- with its blur: a shadowed layer's shadow's box, a filtered layer's first entry's box ((0, 0, 1) where
+   that entry is a convolution).
    Owned by the handle until its next walk; any out-parameter may be NULL.  k out of range: SWFR_ERR_NOT_FOUND. */
 uint32_t swfr_built_layers(const swfr_renderer *r);
 int  swfr_built_layer(swfr_renderer *r, uint32_t k,
@@ -542,6 +578,10 @@ int  swfr_built_layer_shadow(swfr_renderer *r, uint32_t k, int *has_shadow, swfr
    SWFR_MAX_FILTERS.  A blurred layer's sub-frame reports its one blur entry, a shadowed layer's its one shadow entry.  Either
    out-parameter may be NULL.  k out of range: SWFR_ERR_NOT_FOUND. */
 int  swfr_built_layer_filters(swfr_renderer *r, uint32_t k, uint32_t *count, swfr_filter *out);
+/* The kernel the scene walk read for entry `entry` of the k-th sub-frame's filter list (swfr_built_layer_filters reports the entry
+   itself as it was set: its kind and its slot).  k or entry out of range, or an entry that is no convolution: SWFR_ERR_NOT_FOUND.  `out`
+   may be NULL. */
+int  swfr_built_layer_kernel(swfr_renderer *r, uint32_t k, uint32_t entry, swfr_kernel *out);
 
 /* Decoded paths of a registered (morph) shape as JSON text in the format of the reference's
    decode goldens (tests/<set>/<name>/shape.ts.json).  String owned by the handle. */
@@ -653,6 +693,11 @@ int  swfr_debug_time_shadow(swfr_renderer *r, uint32_t width, uint32_t height, i
 /* Measurement (tools/inner_bench.py): swfr_debug_time_shadow with the inner shadow's instances of the two passes -- the inverted alpha
    pass and the inner finish pass (SWFR_SHADOW_INNER alone) --, over the same three textures in the same order. */
 int  swfr_debug_time_inner_shadow(swfr_renderer *r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float *alpha_ms, float *finish_ms, float *copy_ms);
+/* Measurement (tools/convolve_bench.py): one pass of `kernel` over a width x height texture of the handle's own into another, by the
+   framebuffer instance and by the texel instance of convolve.hip, `reps` times each, back to back, then `reps` capture passes
+   (k_blur_capture: one read and one write of the same bytes, the streaming roof); HIP-event time per pass.  Touches no frame and no
+   bitmap. */
+int  swfr_debug_time_convolve(swfr_renderer *r, uint32_t width, uint32_t height, const swfr_kernel *kernel, uint32_t reps, float *fb_ms, float *tex_ms, float *capture_ms);
 /* Device pointer of the premultiplied RGBA8 framebuffer (width*height*4 bytes, tight rows). */
 void *swfr_device_framebuffer(swfr_renderer *r);
 

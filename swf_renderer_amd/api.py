@@ -8,6 +8,7 @@ swf-tree JSON objects of the reference fixtures (tests/<set>/<name>/ast.json).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -40,6 +41,7 @@ EXPORTS = [
     "swfr_capture_bitmap", "swfr_blur_bitmap", "swfr_built_layers", "swfr_built_layer", "swfr_debug_time_blur",
     "swfr_set_shadow", "swfr_shadow_bitmap", "swfr_built_layer_shadow", "swfr_debug_time_shadow", "swfr_debug_time_inner_shadow",
     "swfr_set_filters", "swfr_built_layer_filters",
+    "swfr_set_kernel", "swfr_built_layer_kernel", "swfr_convolve_bitmap", "swfr_debug_time_convolve",
 ]
 OBJECT_SHAPE, OBJECT_MORPH_SHAPE, OBJECT_CONTAINER, OBJECT_COLOR_TRANSFORM = 0, 1, 2, 3
 OBJECT_BLEND_MODE = 5
@@ -53,6 +55,8 @@ SHADOW_INNER = 8                        # (bit 2 is skipped: swfr.h)
 OBJECT_FILTERED_LAYER = 21              # a layer with an ordered filter list (swfr.h SWFR_OBJECT_FILTERED_LAYER): `id` is the blend mode | filter-list slot << 8
 MAX_FILTERS = 4                         # entries in one filter list
 FILTER_BLUR, FILTER_SHADOW = 0, 1       # swfr_filter::kind
+FILTER_CONVOLUTION = 4                  # (kinds 2 and 3 are skipped: swfr.h)
+MAX_KERNEL_DIM = 7                      # taps along one side of a convolution kernel
 MAX_LAYER_DEPTH = 4                     # (a masked layer takes two levels)
 MAX_BLUR_LAYERS = 8                     # blurred, shadowed and filtered layers in one frame
 BLUR_BASE = 131072                      # a bitmap style's `bitmap` at or above it names the texture of a blurred layer of the frame
@@ -122,30 +126,79 @@ def _shadow_struct(v):
     return Shadow(v[0], v[1], v[2], v[3], v[4], Rgba8(*v[5:9]), v[9], v[10])
 
 
-def filter_values(filters):
+def kernel_values(conv):
+    """the (width, height, taps...) of a "convolution" value: a dict with exactly one of "taps" -- rows of signed 16.16 integers -- and
+    "matrix" -- rows of numbers, with an optional "divisor" (absent: 1): tap = floor(m * 65536 / divisor + 0.5).  1..MAX_KERNEL_DIM rows
+    of one length 1..MAX_KERNEL_DIM.  Ragged rows, both keys or neither, a divisor of 0 or with "taps", a non-dict: InvalidFilter.  A kernel
+    beyond the library's bound (swfr.h, swfr_kernel) still goes there, to be refused by name, when it fits the struct."""
+    bad = SwfrError(ERR_INVALID, "InvalidFilter: %r" % (conv,))
+    if not isinstance(conv, dict) or set(conv) - {"taps", "matrix", "divisor"} or ("taps" in conv) == ("matrix" in conv) or ("taps" in conv and "divisor" in conv):
+        raise bad
+    rows = conv["taps"] if "taps" in conv else conv["matrix"]
+    if not isinstance(rows, (list, tuple)) or not 1 <= len(rows) <= MAX_KERNEL_DIM or not all(isinstance(r, (list, tuple)) for r in rows):
+        raise bad
+    if not 1 <= len(rows[0]) <= MAX_KERNEL_DIM or any(len(r) != len(rows[0]) for r in rows):
+        raise bad
+    flat = [v for r in rows for v in r]
+    if "taps" in conv:
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in flat):
+            raise bad
+        taps = [int(v) for v in flat]
+    else:
+        div = conv.get("divisor", 1)
+        if any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) for v in flat + [div]) or div == 0:
+            raise bad
+        try:
+            taps = [int(math.floor(float(v) * 65536.0 / float(div) + 0.5)) for v in flat]
+        except (OverflowError, ValueError):
+            raise bad
+    if any(not -2 ** 31 <= t < 2 ** 31 for t in taps):
+        raise bad
+    return (len(rows[0]), len(rows)) + tuple(taps)
+
+
+def _kernel_struct(v):
+    k = Kernel(v[0], v[1])
+    for i, t in enumerate(v[2:]):
+        k.taps[i] = t
+    return k
+
+
+def filter_values(filters, slots=False):
     """the ((kind, values), ...) of a "filters" value: a list of entries, each a dict with exactly one key -- {"blur": a "blur" value}
-    (blur_values) or {"shadow": a "shadow" value} (shadow_values).  Anything else is InvalidFilter; a list too long for the library still
-    goes there, to be refused by name."""
+    (blur_values), {"shadow": a "shadow" value} (shadow_values) or {"convolution": a "convolution" value} (kernel_values).  Anything else
+    is InvalidFilter; a list too long for the library still goes there, to be refused by name.  slots: a convolution entry is
+    {"convolution": {"slot": n}} instead, naming a kernel slot (Renderer.set_kernel) as the library's entry does -- Renderer.set_filters."""
     if not isinstance(filters, (list, tuple)):
         raise SwfrError(ERR_INVALID, "InvalidFilter: %r" % (filters,))
     out = []
     for entry in filters:
-        if not isinstance(entry, dict) or len(entry) != 1 or next(iter(entry)) not in ("blur", "shadow"):
+        if not isinstance(entry, dict) or len(entry) != 1 or next(iter(entry)) not in ("blur", "shadow", "convolution"):
             raise SwfrError(ERR_INVALID, "InvalidFilter: %r" % (entry,))
         if "blur" in entry:
             out.append((FILTER_BLUR, blur_values(entry["blur"])))
-        else:
+        elif "shadow" in entry:
             out.append((FILTER_SHADOW, shadow_values(entry["shadow"])))
+        elif slots:
+            conv = entry["convolution"]
+            n = conv.get("slot") if isinstance(conv, dict) and set(conv) == {"slot"} else None
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n < 2 ** 32:
+                raise SwfrError(ERR_INVALID, "InvalidFilter: %r" % (entry,))
+            out.append((FILTER_CONVOLUTION, ("slot", int(n))))
+        else:
+            out.append((FILTER_CONVOLUTION, kernel_values(entry["convolution"])))
     return tuple(out)
 
 
-def _filter_structs(values):
-    """the Filter array of filter_values' result"""
+def _filter_structs(values, kernels=None):
+    """the Filter array of filter_values' result; kernels: kernel_values -> the kernel slot its convolution entries name"""
     arr = (Filter * max(len(values), 1))()
     for f, (kind, v) in zip(arr, values):
         f.kind = kind
         if kind == FILTER_BLUR:
             f.shadow.blur_x, f.shadow.blur_y, f.shadow.passes = v
+        elif kind == FILTER_CONVOLUTION:
+            f.shadow.blur_x = v[1] if v[0] == "slot" else kernels[v]
         else:
             f.shadow = _shadow_struct(v)
     return arr
@@ -244,6 +297,11 @@ class Shadow(C.Structure):
 class Filter(C.Structure):
     """swfr_filter"""
     _fields_ = [("kind", C.c_uint32), ("shadow", Shadow)]
+
+
+class Kernel(C.Structure):
+    """swfr_kernel"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("taps", C.c_int32 * 49)]
 
 
 class Stage(C.Structure):
@@ -400,6 +458,14 @@ def load_library():
     L.swfr_set_filters.argtypes = [P, U, C.POINTER(Filter), U]
     L.swfr_built_layer_filters.restype = I
     L.swfr_built_layer_filters.argtypes = [P, U, C.POINTER(U), C.POINTER(Filter)]
+    L.swfr_set_kernel.restype = I
+    L.swfr_set_kernel.argtypes = [P, U, C.POINTER(Kernel)]
+    L.swfr_built_layer_kernel.restype = I
+    L.swfr_built_layer_kernel.argtypes = [P, U, U, C.POINTER(Kernel)]
+    L.swfr_convolve_bitmap.restype = I
+    L.swfr_convolve_bitmap.argtypes = [P, U, C.POINTER(Kernel)]
+    L.swfr_debug_time_convolve.restype = I
+    L.swfr_debug_time_convolve.argtypes = [P, U, U, C.POINTER(Kernel), U, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.swfr_debug_time_shadow.restype = I
     L.swfr_debug_time_shadow.argtypes = [P, U, U, C.c_int32, C.c_int32, U, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.swfr_debug_time_inner_shadow.restype = I
@@ -453,6 +519,7 @@ class _Arena:
         self.cxforms = {}     # the eight values -> slot: one slot per distinct transform of the call (all of its stages)
         self.shadows = {}     # shadow_values -> slot, likewise
         self.filters = {}     # filter_values -> slot, likewise
+        self.kernels = {}     # kernel_values -> slot, likewise: the slots the lists' convolution entries name
 
     def array(self, ctype, items):
         arr = (ctype * max(len(items), 1))(*items)
@@ -714,14 +781,45 @@ class Renderer:
 
     def built_filters(self):
         """The filter lists of the sub-frames of the last scene walk, in built_layers()' order, as the walk read them: each a list of
-        {"blur": {"x", "y", "passes"}} / {"shadow": a "shadow" value with every key}.  A blurred or shadowed layer reports its one entry."""
+        {"blur": {"x", "y", "passes"}} / {"shadow": a "shadow" value with every key} / {"convolution": {"taps": rows of 16.16 integers}}, the
+        kernel the walk read from the entry's slot.  A blurred or shadowed layer reports its one entry."""
         out = []
         for k in range(self.L.swfr_built_layers(self.h)):
             n, arr = C.c_uint32(), (Filter * MAX_FILTERS)()
             self._check(self.L.swfr_built_layer_filters(self.h, k, C.byref(n), arr))
-            out.append([{"blur": {"x": f.shadow.blur_x, "y": f.shadow.blur_y, "passes": f.shadow.passes}} if f.kind == FILTER_BLUR
-                        else {"shadow": _shadow_dict(f.shadow)} for f in arr[:n.value]])
+            entries = []
+            for i, f in enumerate(arr[:n.value]):
+                if f.kind == FILTER_BLUR:
+                    entries.append({"blur": {"x": f.shadow.blur_x, "y": f.shadow.blur_y, "passes": f.shadow.passes}})
+                elif f.kind == FILTER_CONVOLUTION:
+                    kn = Kernel()
+                    self._check(self.L.swfr_built_layer_kernel(self.h, k, i, C.byref(kn)))
+                    entries.append({"convolution": {"taps": [[kn.taps[j * kn.width + c] for c in range(kn.width)] for j in range(kn.height)]}})
+                else:
+                    entries.append({"shadow": _shadow_dict(f.shadow)})
+            out.append(entries)
         return out
+
+    def set_kernel(self, slot, convolution):
+        """swfr_set_kernel: `convolution` a "convolution" value (kernel_values), or None to clear the slot.  (render() and the other stage
+        calls assign slots 0.. to the kernels of their own stages and set them; this is for callers that set filter lists themselves.)"""
+        if convolution is None:
+            self._check(self.L.swfr_set_kernel(self.h, slot, None))
+            return
+        self._check(self.L.swfr_set_kernel(self.h, slot, C.byref(_kernel_struct(kernel_values(convolution)))))
+
+    def convolve_bitmap(self, bitmap_id, convolution):
+        """swfr_convolve_bitmap: registered bitmap `bitmap_id` convolved with a "convolution" value on the device, as pixman's
+        convolution filter computes it; the result is the bitmap's new texels."""
+        self._check(self.L.swfr_convolve_bitmap(self.h, bitmap_id, C.byref(_kernel_struct(kernel_values(convolution)))))
+
+    def debug_time_convolve(self, width, height, convolution, reps=20):
+        """swfr_debug_time_convolve: HIP-event milliseconds of one pass of the framebuffer instance, one of the texel instance and one
+        capture pass (the streaming roof)."""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.swfr_debug_time_convolve(self.h, width, height, C.byref(_kernel_struct(kernel_values(convolution))), reps,
+                                                    C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def set_filters(self, slot, filters):
         """swfr_set_filters: `filters` a "filters" value (filter_values), or None (or an empty list) to clear the slot.  (render() and the
@@ -730,7 +828,7 @@ class Renderer:
         if filters is None:
             self._check(self.L.swfr_set_filters(self.h, slot, None, 0))
             return
-        v = filter_values(filters)
+        v = filter_values(filters, slots=True)                     # (a convolution entry names its kernel slot: {"convolution": {"slot": n}})
         self._check(self.L.swfr_set_filters(self.h, slot, _filter_structs(v), len(v)))
 
     def set_shadow(self, slot, shadow):
@@ -790,14 +888,16 @@ class Renderer:
 
     def _apply_cxforms(self, arena):
         """Sets the handle's colour-transform slots to this call's transforms (slots 0..n-1, by first appearance), and its shadow slots
-        to this call's shadows and its filter-list slots to this call's lists in the same way."""
+        to this call's shadows, its kernel slots to this call's kernels and its filter-list slots to this call's lists in the same way."""
         for v, slot in arena.cxforms.items():
             ct = ColorTransform((C.c_int32 * 4)(*v[:4]), (C.c_int32 * 4)(*v[4:]))
             self._check(self.L.swfr_set_color_transform(self.h, slot, C.byref(ct)))
         for v, slot in arena.shadows.items():
             self._check(self.L.swfr_set_shadow(self.h, slot, C.byref(_shadow_struct(v))))
+        for v, slot in arena.kernels.items():
+            self._check(self.L.swfr_set_kernel(self.h, slot, C.byref(_kernel_struct(v))))
         for v, slot in arena.filters.items():
-            self._check(self.L.swfr_set_filters(self.h, slot, _filter_structs(v), len(v)))
+            self._check(self.L.swfr_set_filters(self.h, slot, _filter_structs(v, arena.kernels), len(v)))
 
     def _object(self, arena, obj):
         d = DisplayObject()
@@ -846,6 +946,9 @@ class Renderer:
             mode = BLEND_MODES["normal"] if layer is None or layer is False else layer_mode_number(layer)
             if not 0 <= mode <= 255:
                 raise SwfrError(ERR_INVALID, "InvalidBlendMode: %r" % (layer,))
+            for kind, kv in v:                                        # (a kernel goes to a slot of this call's, as a shadow does)
+                if kind == FILTER_CONVOLUTION:
+                    arena.kernels.setdefault(kv, len(arena.kernels))
             w.type, w.id = OBJECT_FILTERED_LAYER, mode | arena.filters.setdefault(v, len(arena.filters)) << 8
             inner.pop("layer", None)
             kids = arena.array(DisplayObject, [self._object(arena, inner)])

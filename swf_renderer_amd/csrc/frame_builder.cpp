@@ -83,10 +83,17 @@ bool shadow_valid(const swfr_shadow& s) {
 uint32_t shadow_color_pixel(const swfr_rgba8& c) { return premultiplied_pixel(Css{c.r, c.g, c.b, c.a}); }
 bool filter_valid(const swfr_filter& f) {
     if (f.kind == SWFR_FILTER_SHADOW) return shadow_valid(f.shadow);
-    if (f.kind != SWFR_FILTER_BLUR) return false;
     const swfr_shadow& s = f.shadow;
-    return s.blur_x <= 255u && s.blur_y <= 255u && s.passes >= 1u && s.passes <= 15u && s.dx == 0 && s.dy == 0 && s.color.r == 0 && s.color.g == 0 &&
-           s.color.b == 0 && s.color.a == 0 && s.strength == 0u && s.flags == 0u;
+    const bool rest_zero = s.dx == 0 && s.dy == 0 && s.color.r == 0 && s.color.g == 0 && s.color.b == 0 && s.color.a == 0 && s.strength == 0u && s.flags == 0u;
+    if (f.kind == SWFR_FILTER_CONVOLUTION) return s.blur_x <= 65535u && s.blur_y == 0u && s.passes == 0u && rest_zero;   // (blur_x: the kernel slot)
+    if (f.kind != SWFR_FILTER_BLUR) return false;
+    return s.blur_x <= 255u && s.blur_y <= 255u && s.passes >= 1u && s.passes <= 15u && rest_zero;
+}
+bool kernel_valid(const swfr_kernel& k) {
+    if (k.width < 1u || k.width > SWFR_MAX_KERNEL_DIM || k.height < 1u || k.height > SWFR_MAX_KERNEL_DIM) return false;
+    int64_t sum = 0;
+    for (uint32_t i = 0; i < k.width * k.height; ++i) sum += k.taps[i] < 0 ? -int64_t(k.taps[i]) : int64_t(k.taps[i]);
+    return sum <= 8388607;
 }
 
 bool color_transform_valid(const swfr_color_transform& ct) {
@@ -589,8 +596,10 @@ void FrameBuilder::draw_filtered_layer(const swfr_display_object& obj, int depth
     const uint32_t mode = obj.id & 0xffu;
     const uint32_t op = layer_operator(mode, alpha_modes_);      // (a refused mode is reported before a bad filter)
     swfr_filter list[SWFR_MAX_FILTERS];
+    swfr_kernel kernels[SWFR_MAX_FILTERS];
     uint32_t n_list = 1;
     std::memset(list, 0, sizeof list);
+    std::memset(kernels, 0, sizeof kernels);
     if (obj.type == SWFR_OBJECT_BLURRED_LAYER) {
         list[0].kind = SWFR_FILTER_BLUR;
         list[0].shadow.blur_x = (obj.id >> 8) & 0xffu; list[0].shadow.blur_y = (obj.id >> 16) & 0xffu; list[0].shadow.passes = obj.id >> 24;
@@ -615,6 +624,11 @@ void FrameBuilder::draw_filtered_layer(const swfr_display_object& obj, int depth
         for (uint32_t i = 0; i < n_list; ++i) {
             list[i] = it->second[i];
             if (!filter_valid(list[i])) throw StatusError{SWFR_ERR_INVALID, "InvalidFilter"};
+            if (list[i].kind != SWFR_FILTER_CONVOLUTION) continue;
+            const auto kit = store()->kernels_.find(list[i].shadow.blur_x);      // the kernel is its slot's value at this walk
+            if (kit == store()->kernels_.end()) throw StatusError{SWFR_ERR_NOT_FOUND, "KernelNotFound"};
+            kernels[i] = kit->second;
+            if (!kernel_valid(kernels[i])) throw StatusError{SWFR_ERR_INVALID, "InvalidKernel"};
         }
     }
     if (in_blur_) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NestedBlur"};
@@ -634,6 +648,7 @@ void FrameBuilder::draw_filtered_layer(const swfr_display_object& obj, int depth
     L.edges.swap(edges_); L.paths.swap(paths_); L.styles.swap(styles_);
     L.type = obj.type; L.n_filters = n_list;
     std::memcpy(L.filters, list, sizeof list);
+    std::memcpy(L.kernels, kernels, sizeof kernels);
     edges_.swap(parent_edges); paths_.swap(parent_paths); styles_.swap(parent_styles);
     drawn_ = parent_drawn; group_depth_ = parent_depth; in_blur_ = false;
     // ---- the parent's path

@@ -36,6 +36,7 @@ struct BlurLayer {
     uint32_t type = 0;                                // the display-object type the layer came from
     uint32_t n_filters = 0;                           // 1..SWFR_MAX_FILTERS
     swfr_filter filters[SWFR_MAX_FILTERS]{};
+    swfr_kernel kernels[SWFR_MAX_FILTERS]{};          // entry i's kernel as the walk read it from its slot, where entry i is a convolution
 };
 constexpr uint32_t BLUR_BASE = SWFR_BLUR_BASE;
 
@@ -73,8 +74,10 @@ bool shadow_valid(const swfr_shadow& s);
 // the premultiplied ARGB pixel of cairo_set_source_rgba(r / 255, g / 255, b / 255, a / 255), from the bytes directly
 uint32_t shadow_color_pixel(const swfr_rgba8& c);
 // swfr_set_filters' check of one entry (swfr.h, swfr_filter): a known kind; a blur entry's box and passes in range and its other fields
-// zero; a shadow entry as shadow_valid has it
+// zero; a shadow entry as shadow_valid has it; a convolution entry's slot (shadow.blur_x) below 65536 and its other fields zero
 bool filter_valid(const swfr_filter& f);
+// swfr_set_kernel's and swfr_convolve_bitmap's check (swfr.h, swfr_kernel): both dimensions 1..SWFR_MAX_KERNEL_DIM, sum |tap| <= 8 388 607
+bool kernel_valid(const swfr_kernel& k);
 
 // Frames with many top-level display objects are built by several threads: the children are cut into contiguous ranges, every range
 // is walked by a worker builder of its own (same code, its own output arrays), and the pieces are joined in painter's order.  The one
@@ -94,6 +97,7 @@ public:
     void set_color_transform(uint32_t slot, const swfr_color_transform* ct) { if (ct) cxforms_[slot] = *ct; else cxforms_.erase(slot); }
     void set_shadow(uint32_t slot, const swfr_shadow* sh) { if (sh) shadows_[slot] = *sh; else shadows_.erase(slot); }
     void set_filters(uint32_t slot, const swfr_filter* f, uint32_t count) { if (f && count) filters_[slot].assign(f, f + count); else filters_.erase(slot); }
+    void set_kernel(uint32_t slot, const swfr_kernel* k) { if (k) kernels_[slot] = *k; else kernels_.erase(slot); }
     const DecodedShape* shape(uint32_t id, bool morph) const;
 
     // Throws StatusError.  Results stay valid until the next build().
@@ -171,6 +175,7 @@ private:
     std::map<uint32_t, swfr_color_transform> cxforms_;
     std::map<uint32_t, swfr_shadow> shadows_;   // the shadow slots (set on the handle's builder)
     std::map<uint32_t, std::vector<swfr_filter>> filters_;   // the filter-list slots, likewise
+    std::map<uint32_t, swfr_kernel> kernels_;   // the convolution-kernel slots, likewise
     std::vector<ColorLut> luts_;
     std::map<std::string, int32_t> lut_index_;                 // table bytes -> index into luts_
     std::map<std::pair<int32_t, std::string>, int32_t> compose_memo_;   // (outer chain, inner transform bytes) -> chain

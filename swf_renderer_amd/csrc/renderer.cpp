@@ -44,6 +44,7 @@ void launch_blur_capture(hipStream_t, const uint32_t*, uint32_t*, size_t);
 void launch_blur_pass(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, bool);
 void launch_shadow_alpha(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, int32_t, int32_t, bool);
 void launch_shadow_finish(hipStream_t, const uint32_t*, const uint32_t*, bool, uint32_t*, size_t, uint32_t, uint32_t, uint32_t);
+void launch_convolve(hipStream_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, const swfr_kernel&, bool);   // convolve.hip
 }  // namespace swfr
 
 using namespace swfr;
@@ -1839,7 +1840,9 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
 // is validated, uploaded and rendered as an ordinary frame, once, and its filter list (a blurred or shadowed layer's has one entry) is
 // run over it into texture k of the pool -- DESIGN.md, "Filter lists".  Three buffers take part: 0 the texture, 1 blur_scratch, 2
 // shadow_scratch.  The first entry reads the framebuffer: a blur through the capture, a shadow through the alpha pass and, behind
-// its box passes, the finish pass with the framebuffer as the group.  Every later entry reads the result before it as ARGB texels: a
+// its box passes, the finish pass with the framebuffer as the group, a convolution straight into the buffer it must end in (no
+// capture pass in front of it).  A later convolution is one out-of-place step from the buffer the result lies in to the other of 0
+// and 1, planned exactly as a blur of one box step.  Every later entry reads the result before it as ARGB texels: a
 // blur's box passes alternate between that buffer and the other of 0 and 1; a shadow keeps its group where it is, its alpha surface
 // goes to the other of 0 and 1 and alternates with buffer 2, and its finish pass runs in place over the group.  So an entry ends
 // where it began, or -- a blur of an odd number of box passes -- in the other of 0 and 1: planned from the last entry, which ends
@@ -1874,11 +1877,12 @@ int render_blur_layers(swfr_renderer* r) {
             bool scratch1 = false, scratch2 = false;
             for (uint32_t i = B.n_filters, at = 0; i-- > 0;) {
                 const swfr_filter& F = B.filters[i];
-                steps[i] = blur_steps(F.shadow.blur_x, F.shadow.blur_y, F.shadow.passes);
+                const bool conv = F.kind == SWFR_FILTER_CONVOLUTION;      // (one out-of-place step: planned as a blur of one box step)
+                steps[i] = conv ? 1u : blur_steps(F.shadow.blur_x, F.shadow.blur_y, F.shadow.passes);
                 end[i] = int(at);
-                if (i ? (F.kind == SWFR_FILTER_SHADOW || steps[i] != 0u) : steps[i] != 0u) scratch1 = true;
+                if (i ? (F.kind == SWFR_FILTER_SHADOW || steps[i] != 0u) : (!conv && steps[i] != 0u)) scratch1 = true;   // (a first convolution reads the framebuffer)
                 if (i && F.kind == SWFR_FILTER_SHADOW && steps[i] != 0u) scratch2 = true;
-                if (i && F.kind == SWFR_FILTER_BLUR && (steps[i] & 1u)) at ^= 1u;          // (its input lies in the other buffer)
+                if (i && F.kind != SWFR_FILTER_SHADOW && (steps[i] & 1u)) at ^= 1u;        // (its input lies in the other buffer)
                 if (at) scratch1 = true;
             }
             if (scratch1) r->blur_scratch.reserve(n);                 // (a lone box of 1 x 1 runs no pass: the capture is the texture)
@@ -1888,7 +1892,11 @@ int render_blur_layers(swfr_renderer* r) {
             for (uint32_t i = 0; i < B.n_filters; ++i) {
                 const swfr_filter& F = B.filters[i];
                 const swfr_shadow& S = F.shadow;
-                if (i == 0) {
+                if (F.kind == SWFR_FILTER_CONVOLUTION) {
+                    // the framebuffer words, or the texels of the result before it, into the buffer the entry ends in
+                    if (i == 0) launch_convolve(r->stream, fb, buf[end[0]], r->width, r->height, B.kernels[0], true);
+                    else launch_convolve(r->stream, buf[end[i] ^ 1], buf[end[i]], r->width, r->height, B.kernels[i], false);
+                } else if (i == 0) {
                     // the capture or the alpha pass goes where the box passes, alternating between 0 and 1, end in end[0]
                     const int first = (steps[0] & 1u) ? end[0] ^ 1 : end[0];
                     if (F.kind == SWFR_FILTER_SHADOW) launch_shadow_alpha(r->stream, fb, buf[first], r->width, r->height, S.dx, S.dy, (S.flags & SWFR_SHADOW_INNER) != 0u);
@@ -2447,6 +2455,14 @@ int swfr_set_shadow(swfr_renderer* r, uint32_t slot, const swfr_shadow* shadow) 
     return SWFR_OK;
 }
 
+int swfr_set_kernel(swfr_renderer* r, uint32_t slot, const swfr_kernel* kernel) {
+    if (!r) return SWFR_ERR_INVALID;
+    if (slot > 65535) return fail(r, SWFR_ERR_INVALID, "kernel slot out of range (0..65535)");
+    if (kernel && !kernel_valid(*kernel)) return fail(r, SWFR_ERR_INVALID, "InvalidKernel");
+    r->builder->set_kernel(slot, kernel);
+    return SWFR_OK;
+}
+
 int swfr_set_filters(swfr_renderer* r, uint32_t slot, const swfr_filter* filters, uint32_t count) {
     if (!r) return SWFR_ERR_INVALID;
     if (slot > 65535) return fail(r, SWFR_ERR_INVALID, "InvalidFilter");
@@ -2515,9 +2531,10 @@ int swfr_built_layer(swfr_renderer* r, uint32_t k, const swfr_edge** edges, size
     if (n_paths) *n_paths = B.paths.size();
     if (styles) *styles = B.styles.data();
     if (n_styles) *n_styles = B.styles.size();
-    if (blur_x) *blur_x = B.filters[0].shadow.blur_x;
-    if (blur_y) *blur_y = B.filters[0].shadow.blur_y;
-    if (passes) *passes = B.filters[0].shadow.passes;
+    const bool conv = B.filters[0].kind == SWFR_FILTER_CONVOLUTION;      // (no box: its blur_x names a kernel slot)
+    if (blur_x) *blur_x = conv ? 0u : B.filters[0].shadow.blur_x;
+    if (blur_y) *blur_y = conv ? 0u : B.filters[0].shadow.blur_y;
+    if (passes) *passes = conv ? 1u : B.filters[0].shadow.passes;
     return SWFR_OK;
 }
 
@@ -2537,6 +2554,15 @@ int swfr_built_layer_filters(swfr_renderer* r, uint32_t k, uint32_t* count, swfr
     if (k >= layers.size()) return fail(r, SWFR_ERR_NOT_FOUND, "no such blurred layer in the last built frame");
     if (count) *count = layers[k].n_filters;
     if (out) std::copy(layers[k].filters, layers[k].filters + layers[k].n_filters, out);
+    return SWFR_OK;
+}
+
+int swfr_built_layer_kernel(swfr_renderer* r, uint32_t k, uint32_t entry, swfr_kernel* out) {
+    if (!r) return SWFR_ERR_INVALID;
+    const auto& layers = r->builder->layers();
+    if (k >= layers.size()) return fail(r, SWFR_ERR_NOT_FOUND, "no such blurred layer in the last built frame");
+    if (entry >= layers[k].n_filters || layers[k].filters[entry].kind != SWFR_FILTER_CONVOLUTION) return fail(r, SWFR_ERR_NOT_FOUND, "no such convolution entry in the layer's filter list");
+    if (out) *out = layers[k].kernels[entry];
     return SWFR_OK;
 }
 
@@ -2582,6 +2608,35 @@ int swfr_blur_bitmap(swfr_renderer* r, uint32_t bitmap_id, uint32_t blur_x, uint
         if (blur_steps(blur_x, blur_y, passes)) r->blur_scratch.reserve(n);
         const uint32_t* at = blur_image(r->stream, bm.pixels, r->blur_scratch.ptr, bm.width, bm.height, blur_x, blur_y, passes);
         if (at != bm.pixels) HIP_CHECK(hipMemcpyAsync(bm.pixels, at, n * 4, hipMemcpyDeviceToDevice, r->stream));
+        HIP_CHECK(hipStreamSynchronize(r->stream));
+        // the texels are no longer the registered ones: a new generation (stale colour-transformed variants go), and no straight texels
+        uint32_t* const pixels = bm.pixels;
+        const uint32_t w = bm.width, h = bm.height;
+        bm.pixels = nullptr;
+        release_bitmap_slot(r, bitmap_id, bm);
+        bm.pixels = pixels; bm.width = w; bm.height = h;
+        bm.gen = ++r->bitmap_gen;
+        bm.captured = true;
+        r->builder->set_bitmap_captured(bitmap_id);
+        return int(SWFR_OK);
+    });
+}
+
+int swfr_convolve_bitmap(swfr_renderer* r, uint32_t bitmap_id, const swfr_kernel* kernel) {
+    if (!r) return SWFR_ERR_INVALID;
+    if (!kernel || !kernel_valid(*kernel)) return fail(r, SWFR_ERR_INVALID, "InvalidKernel");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle has no bitmaps on a device");
+    return guarded(r, [&]() {
+        const auto bit = r->bitmaps.find(bitmap_id);
+        if (bit == r->bitmaps.end() || !bit->second.pixels) return fail(r, SWFR_ERR_NOT_FOUND, "BitmapNotFound");
+        DeviceBitmap& bm = bit->second;
+        wait_all_streams(r);
+        const size_t n = size_t(bm.width) * bm.height;
+        // the pass is out of place: into the scratch texture, and the result back to the bitmap's own
+        r->blur_scratch.reserve(n);
+        launch_convolve(r->stream, bm.pixels, r->blur_scratch.ptr, bm.width, bm.height, *kernel, false);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(bm.pixels, r->blur_scratch.ptr, n * 4, hipMemcpyDeviceToDevice, r->stream));
         HIP_CHECK(hipStreamSynchronize(r->stream));
         // the texels are no longer the registered ones: a new generation (stale colour-transformed variants go), and no straight texels
         uint32_t* const pixels = bm.pixels;
@@ -2680,6 +2735,20 @@ int swfr_debug_time_inner_shadow(swfr_renderer* r, uint32_t width, uint32_t heig
             launch_shadow_finish(r->stream, b, a, true, b, n, cp, 1u, SWFR_SHADOW_INNER);
             copy();
         }, {{alpha, alpha_ms}, {finish, finish_ms}, {copy, copy_ms}});
+    });
+}
+
+int swfr_debug_time_convolve(swfr_renderer* r, uint32_t width, uint32_t height, const swfr_kernel* kernel, uint32_t reps, float* fb_ms, float* tex_ms, float* capture_ms) {
+    if (!r || !kernel || !kernel_valid(*kernel) || !fb_ms || !tex_ms || !capture_ms || reps == 0 || width == 0 || height == 0 || width > 32768 || height > 32768)
+        return fail(r, SWFR_ERR_INVALID, "bad argument");
+    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
+    return guarded(r, [&]() {
+        const size_t n = size_t(width) * height, bytes = n * 4;
+        uint32_t *a = nullptr, *b = nullptr;
+        const auto fb = [&]() { launch_convolve(r->stream, a, b, width, height, *kernel, true); };
+        const auto tex = [&]() { launch_convolve(r->stream, a, b, width, height, *kernel, false); };
+        const auto capture = [&]() { launch_blur_capture(r->stream, a, b, n); };     // the streaming roof: one read, one write of the same bytes
+        return time_phases(r, reps, {{&a, bytes, 0x5a}, {&b, bytes, -1}}, [&]() { fb(); tex(); capture(); }, {{fb, fb_ms}, {tex, tex_ms}, {capture, capture_ms}});
     });
 }
 
