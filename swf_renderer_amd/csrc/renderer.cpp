@@ -25,6 +25,7 @@
 #include "../../include/swfr.h"
 #include "device_types.hpp"
 #include "frame_layout.hpp"
+#include "filter_plan.hpp"
 #include "frame_builder.hpp"
 #include "shape_decoder.hpp"
 #include "bitmap_decode.hpp"
@@ -1615,10 +1616,9 @@ void wait_all_streams(swfr_renderer* r) {
     for (auto& x : r->fs) if (x.stream) HIP_CHECK(hipStreamSynchronize(x.stream));
     for (auto& g : r->groups) if (g.stream) HIP_CHECK(hipStreamSynchronize(g.stream));
 }
-// the box passes of a blur that do something: a width of 0 or 1 leaves its axis alone
-uint32_t blur_steps(uint32_t blur_x, uint32_t blur_y, uint32_t passes) { return passes * ((blur_x > 1u ? 1u : 0u) + (blur_y > 1u ? 1u : 0u)); }
 // The blur (blur_x, blur_y, passes) of the width x height image at `a`, the passes alternating between `a` and `b`, queued on `st`:
-// returns where the result lies -- `a` after an even number of steps (blur_steps), `b` after an odd one
+// returns where the result lies -- `a` after an even number of steps (blur_steps), `b` after an odd one.  swfr_shadow_bitmap's box
+// passes only: every other route plans its passes (filter_plan.hpp) and runs them through run_filter_plan
 uint32_t* blur_image(hipStream_t st, uint32_t* a, uint32_t* b, uint32_t width, uint32_t height, uint32_t blur_x, uint32_t blur_y, uint32_t passes) {
     for (uint32_t p = 0; p < passes; ++p)
         for (int vertical = 0; vertical < 2; ++vertical) {
@@ -1629,6 +1629,28 @@ uint32_t* blur_image(hipStream_t st, uint32_t* a, uint32_t* b, uint32_t width, u
         }
     HIP_CHECK(hipGetLastError());
     return a;
+}
+// Queues a plan's steps (filter_plan.hpp) on `st`, in order: the one place that maps a step to a launch.  bufs: the width x height
+// buffers the plan names, indexed by Buffer (those it does not use may be null); list, kernels: the entries the plan was made of and,
+// per convolution entry, its kernel
+void run_filter_plan(hipStream_t st, const FilterPlan& plan, const swfr_filter* list, const swfr_kernel* kernels, uint32_t* const bufs[4], uint32_t width, uint32_t height) {
+    const size_t n = size_t(width) * height;
+    for (uint32_t k = 0; k < plan.n; ++k) {
+        const FilterStep& s = plan.steps[k];
+        const swfr_shadow& S = list[s.entry].shadow;
+        const uint32_t* const src = bufs[s.src];
+        uint32_t* const dst = bufs[s.dst];
+        switch (s.op) {
+        case Op::CAPTURE: launch_blur_capture(st, src, dst, n); break;
+        case Op::BOX_H: launch_blur_pass(st, src, dst, width, height, S.blur_x, false); break;
+        case Op::BOX_V: launch_blur_pass(st, src, dst, width, height, S.blur_y, true); break;
+        case Op::SHADOW_ALPHA: launch_shadow_alpha(st, src, dst, width, height, S.dx, S.dy, (S.flags & SWFR_SHADOW_INNER) != 0u); break;
+        case Op::SHADOW_FINISH: launch_shadow_finish(st, src, bufs[s.group], s.group == FB, dst, n, shadow_color_pixel(S.color), S.strength, S.flags); break;
+        case Op::CONVOLVE: launch_convolve(st, src, dst, width, height, kernels[s.entry], s.src == FB); break;
+        case Op::COPY: HIP_CHECK(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, st)); break;
+        }
+    }
+    HIP_CHECK(hipGetLastError());
 }
 // drops what a bitmap slot holds before it gets new texels: its device memory, and the colour-transformed textures made from it
 void release_bitmap_slot(swfr_renderer* r, uint32_t id, DeviceBitmap& slot) {
@@ -1645,6 +1667,41 @@ void release_bitmap_slot(swfr_renderer* r, uint32_t id, DeviceBitmap& slot) {
             it = r->cx_cache.erase(it);
         } else ++it;
     }
+}
+// Slot `id` holds the w x h texels at `pixels`, made on the device (the slot's own, written in place, or a fresh allocation the slot
+// takes over): a new generation -- stale colour-transformed variants go --, no straight texels.  in_place: a registered bitmap keeps
+// its texture and size, and the builder only learns that it is captured; otherwise it is registered (again) and the table follows
+void bitmap_slot_has_new_texels(swfr_renderer* r, uint32_t id, uint32_t* pixels, uint32_t w, uint32_t h, bool in_place) {
+    DeviceBitmap& bm = r->bitmaps[id];
+    if (bm.pixels == pixels) bm.pixels = nullptr;                // (kept: release_bitmap_slot frees what the slot holds)
+    release_bitmap_slot(r, id, bm);
+    bm.pixels = pixels; bm.width = w; bm.height = h;
+    bm.gen = ++r->bitmap_gen;
+    bm.captured = true;
+    if (in_place) { r->builder->set_bitmap_captured(id); return; }
+    BitmapInfo info{w, h};
+    info.captured = true;
+    r->builder->add_bitmap(id, info);
+    if (r->bitmap_table.size() <= id) r->bitmap_table.resize(id + 1, DevBitmap{nullptr, 0, 0});
+    r->bitmap_table[id] = DevBitmap{pixels, w, h};
+    r->bitmap_table_dirty = true;
+}
+// A one-entry filter list over the texels of a registered bitmap, in place (swfr_blur_bitmap, swfr_convolve_bitmap): planned from
+// texels (filter_plan.hpp), run behind everything queued on the handle and waited for
+int filter_bitmap(swfr_renderer* r, uint32_t bitmap_id, const swfr_filter& entry, const swfr_kernel* kernel) {
+    return guarded(r, [&]() {
+        const auto bit = r->bitmaps.find(bitmap_id);
+        if (bit == r->bitmaps.end() || !bit->second.pixels) return fail(r, SWFR_ERR_NOT_FOUND, "BitmapNotFound");
+        const DeviceBitmap& bm = bit->second;
+        wait_all_streams(r);
+        const FilterPlan plan = plan_filters(&entry, 1, Source::Texels);
+        if (plan.uses[T1]) r->blur_scratch.reserve(size_t(bm.width) * bm.height);
+        uint32_t* const bufs[4] = {nullptr, bm.pixels, r->blur_scratch.ptr, nullptr};
+        run_filter_plan(r->stream, plan, &entry, kernel, bufs, bm.width, bm.height);
+        HIP_CHECK(hipStreamSynchronize(r->stream));
+        bitmap_slot_has_new_texels(r, bitmap_id, bm.pixels, bm.width, bm.height, true);
+        return int(SWFR_OK);
+    });
 }
 
 // ---- swfr_render_resident: frames of the resident scene, queued back to back over the frame sets and waited for.  What a call's steps share:
@@ -1838,18 +1895,9 @@ int render_resident(swfr_renderer* r, uint32_t frames) {
 
 // The blurred, shadowed and filtered layers of the frame the builder has just built, before the frame itself (swfr_render): sub-frame k
 // is validated, uploaded and rendered as an ordinary frame, once, and its filter list (a blurred or shadowed layer's has one entry) is
-// run over it into texture k of the pool -- DESIGN.md, "Filter lists".  Three buffers take part: 0 the texture, 1 blur_scratch, 2
-// shadow_scratch.  The first entry reads the framebuffer: a blur through the capture, a shadow through the alpha pass and, behind
-// its box passes, the finish pass with the framebuffer as the group, a convolution straight into the buffer it must end in (no
-// capture pass in front of it).  A later convolution is one out-of-place step from the buffer the result lies in to the other of 0
-// and 1, planned exactly as a blur of one box step.  Every later entry reads the result before it as ARGB texels: a
-// blur's box passes alternate between that buffer and the other of 0 and 1; a shadow keeps its group where it is, its alpha surface
-// goes to the other of 0 and 1 and alternates with buffer 2, and its finish pass runs in place over the group.  So an entry ends
-// where it began, or -- a blur of an odd number of box passes -- in the other of 0 and 1: planned from the last entry, which ends
-// in the texture, backwards, every entry knows where to end, and the first one where to put its capture or alpha pass.  No copy, no
-// wait between entries.  Everything runs on the handle's stream, behind the sub-frame's kernels (render_resident returns with every
-// stream idle), and is waited for once per layer: the builder's arrays and the framebuffer are free for the next sub-frame, and for
-// the parent.
+// planned from the framebuffer into texture k of the pool (filter_plan.hpp; DESIGN.md, "Filter lists") and run.  Everything runs on
+// the handle's stream, behind the sub-frame's kernels (render_resident returns with every stream idle), and is waited for once per
+// layer: the builder's arrays and the framebuffer are free for the next sub-frame, and for the parent.
 int render_blur_layers(swfr_renderer* r) {
     const auto& layers = r->builder->layers();
     if (r->cfg.band_count > 1) throw StatusError{SWFR_ERR_NOT_IMPLEMENTED, "NotImplementedBlurBands"};
@@ -1871,50 +1919,11 @@ int render_blur_layers(swfr_renderer* r) {
             int rc = upload2(r, 0, false, sv, nullptr, true);
             if (rc == SWFR_OK) rc = render_resident(r, 1);
             if (rc != SWFR_OK) return rc;
-            // where every entry ends (0 or 1), from the last one backwards, and which scratch buffers the chain touches
-            uint32_t steps[SWFR_MAX_FILTERS];
-            int end[SWFR_MAX_FILTERS];
-            bool scratch1 = false, scratch2 = false;
-            for (uint32_t i = B.n_filters, at = 0; i-- > 0;) {
-                const swfr_filter& F = B.filters[i];
-                const bool conv = F.kind == SWFR_FILTER_CONVOLUTION;      // (one out-of-place step: planned as a blur of one box step)
-                steps[i] = conv ? 1u : blur_steps(F.shadow.blur_x, F.shadow.blur_y, F.shadow.passes);
-                end[i] = int(at);
-                if (i ? (F.kind == SWFR_FILTER_SHADOW || steps[i] != 0u) : (!conv && steps[i] != 0u)) scratch1 = true;   // (a first convolution reads the framebuffer)
-                if (i && F.kind == SWFR_FILTER_SHADOW && steps[i] != 0u) scratch2 = true;
-                if (i && F.kind != SWFR_FILTER_SHADOW && (steps[i] & 1u)) at ^= 1u;        // (its input lies in the other buffer)
-                if (at) scratch1 = true;
-            }
-            if (scratch1) r->blur_scratch.reserve(n);                 // (a lone box of 1 x 1 runs no pass: the capture is the texture)
-            if (scratch2) r->shadow_scratch.reserve(n);
-            uint32_t* const buf[3] = {tex, r->blur_scratch.ptr, r->shadow_scratch.ptr};
-            const uint32_t* const fb = r->fb_cur ? r->fb_cur : r->fs[0].d_fb.ptr;
-            for (uint32_t i = 0; i < B.n_filters; ++i) {
-                const swfr_filter& F = B.filters[i];
-                const swfr_shadow& S = F.shadow;
-                if (F.kind == SWFR_FILTER_CONVOLUTION) {
-                    // the framebuffer words, or the texels of the result before it, into the buffer the entry ends in
-                    if (i == 0) launch_convolve(r->stream, fb, buf[end[0]], r->width, r->height, B.kernels[0], true);
-                    else launch_convolve(r->stream, buf[end[i] ^ 1], buf[end[i]], r->width, r->height, B.kernels[i], false);
-                } else if (i == 0) {
-                    // the capture or the alpha pass goes where the box passes, alternating between 0 and 1, end in end[0]
-                    const int first = (steps[0] & 1u) ? end[0] ^ 1 : end[0];
-                    if (F.kind == SWFR_FILTER_SHADOW) launch_shadow_alpha(r->stream, fb, buf[first], r->width, r->height, S.dx, S.dy, (S.flags & SWFR_SHADOW_INNER) != 0u);
-                    else launch_blur_capture(r->stream, fb, buf[first], n);
-                    blur_image(r->stream, buf[first], buf[first ^ 1], r->width, r->height, S.blur_x, S.blur_y, S.passes);
-                    // (the finish pass in place over the blurred alpha: the sub-frame's framebuffer is still the group)
-                    if (F.kind == SWFR_FILTER_SHADOW)
-                        launch_shadow_finish(r->stream, buf[end[0]], fb, true, buf[end[0]], n, shadow_color_pixel(S.color), S.strength, S.flags);
-                } else if (F.kind == SWFR_FILTER_SHADOW) {
-                    uint32_t* const group = buf[end[i]];                 // (== end[i - 1]: a shadow ends where it began)
-                    launch_shadow_alpha(r->stream, group, buf[end[i] ^ 1], r->width, r->height, S.dx, S.dy, (S.flags & SWFR_SHADOW_INNER) != 0u);
-                    const uint32_t* const alpha = blur_image(r->stream, buf[end[i] ^ 1], buf[2], r->width, r->height, S.blur_x, S.blur_y, S.passes);
-                    launch_shadow_finish(r->stream, alpha, group, false, group, n, shadow_color_pixel(S.color), S.strength, S.flags);
-                } else {
-                    blur_image(r->stream, buf[end[i - 1]], buf[end[i - 1] ^ 1], r->width, r->height, S.blur_x, S.blur_y, S.passes);
-                }
-            }
-            HIP_CHECK(hipGetLastError());
+            const FilterPlan plan = plan_filters(B.filters, B.n_filters, Source::Framebuffer);
+            if (plan.uses[T1]) r->blur_scratch.reserve(n);            // (a lone box of 1 x 1 runs no pass: the capture is the texture)
+            if (plan.uses[T2]) r->shadow_scratch.reserve(n);
+            uint32_t* const bufs[4] = {r->fb_cur ? r->fb_cur : r->fs[0].d_fb.ptr, tex, r->blur_scratch.ptr, r->shadow_scratch.ptr};
+            run_filter_plan(r->stream, plan, B.filters, B.kernels, bufs, r->width, r->height);
         }
         HIP_CHECK(hipStreamSynchronize(r->stream));
         r->blur_table[k] = DevBitmap{tex, r->width, r->height};
@@ -2599,56 +2608,18 @@ int swfr_blur_bitmap(swfr_renderer* r, uint32_t bitmap_id, uint32_t blur_x, uint
     if (!r) return SWFR_ERR_INVALID;
     if (blur_x > 255u || blur_y > 255u || passes == 0u || passes > 15u) return fail(r, SWFR_ERR_INVALID, "InvalidBlur");
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle has no bitmaps on a device");
-    return guarded(r, [&]() {
-        const auto bit = r->bitmaps.find(bitmap_id);
-        if (bit == r->bitmaps.end() || !bit->second.pixels) return fail(r, SWFR_ERR_NOT_FOUND, "BitmapNotFound");
-        DeviceBitmap& bm = bit->second;
-        wait_all_streams(r);
-        const size_t n = size_t(bm.width) * bm.height;
-        if (blur_steps(blur_x, blur_y, passes)) r->blur_scratch.reserve(n);
-        const uint32_t* at = blur_image(r->stream, bm.pixels, r->blur_scratch.ptr, bm.width, bm.height, blur_x, blur_y, passes);
-        if (at != bm.pixels) HIP_CHECK(hipMemcpyAsync(bm.pixels, at, n * 4, hipMemcpyDeviceToDevice, r->stream));
-        HIP_CHECK(hipStreamSynchronize(r->stream));
-        // the texels are no longer the registered ones: a new generation (stale colour-transformed variants go), and no straight texels
-        uint32_t* const pixels = bm.pixels;
-        const uint32_t w = bm.width, h = bm.height;
-        bm.pixels = nullptr;
-        release_bitmap_slot(r, bitmap_id, bm);
-        bm.pixels = pixels; bm.width = w; bm.height = h;
-        bm.gen = ++r->bitmap_gen;
-        bm.captured = true;
-        r->builder->set_bitmap_captured(bitmap_id);
-        return int(SWFR_OK);
-    });
+    swfr_filter entry{};
+    entry.kind = SWFR_FILTER_BLUR; entry.shadow.blur_x = blur_x; entry.shadow.blur_y = blur_y; entry.shadow.passes = passes;
+    return filter_bitmap(r, bitmap_id, entry, nullptr);
 }
 
 int swfr_convolve_bitmap(swfr_renderer* r, uint32_t bitmap_id, const swfr_kernel* kernel) {
     if (!r) return SWFR_ERR_INVALID;
     if (!kernel || !kernel_valid(*kernel)) return fail(r, SWFR_ERR_INVALID, "InvalidKernel");
     if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle has no bitmaps on a device");
-    return guarded(r, [&]() {
-        const auto bit = r->bitmaps.find(bitmap_id);
-        if (bit == r->bitmaps.end() || !bit->second.pixels) return fail(r, SWFR_ERR_NOT_FOUND, "BitmapNotFound");
-        DeviceBitmap& bm = bit->second;
-        wait_all_streams(r);
-        const size_t n = size_t(bm.width) * bm.height;
-        // the pass is out of place: into the scratch texture, and the result back to the bitmap's own
-        r->blur_scratch.reserve(n);
-        launch_convolve(r->stream, bm.pixels, r->blur_scratch.ptr, bm.width, bm.height, *kernel, false);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(bm.pixels, r->blur_scratch.ptr, n * 4, hipMemcpyDeviceToDevice, r->stream));
-        HIP_CHECK(hipStreamSynchronize(r->stream));
-        // the texels are no longer the registered ones: a new generation (stale colour-transformed variants go), and no straight texels
-        uint32_t* const pixels = bm.pixels;
-        const uint32_t w = bm.width, h = bm.height;
-        bm.pixels = nullptr;
-        release_bitmap_slot(r, bitmap_id, bm);
-        bm.pixels = pixels; bm.width = w; bm.height = h;
-        bm.gen = ++r->bitmap_gen;
-        bm.captured = true;
-        r->builder->set_bitmap_captured(bitmap_id);
-        return int(SWFR_OK);
-    });
+    swfr_filter entry{};
+    entry.kind = SWFR_FILTER_CONVOLUTION;
+    return filter_bitmap(r, bitmap_id, entry, kernel);
 }
 
 int swfr_shadow_bitmap(swfr_renderer* r, uint32_t dst_id, uint32_t src_id, const swfr_shadow* shadow) {
@@ -2679,24 +2650,13 @@ int swfr_shadow_bitmap(swfr_renderer* r, uint32_t dst_id, uint32_t src_id, const
             HIP_CHECK(launched);
             HIP_CHECK(done);
         }
-        // the destination's texels are new: a new generation (stale colour-transformed variants go), and no straight texels
-        DeviceBitmap& bm = r->bitmaps[dst_id];                  // (src_id's own slot when the two are one)
-        if (!fresh) bm.pixels = nullptr;                        // (kept: release_bitmap_slot frees what the slot holds)
-        release_bitmap_slot(r, dst_id, bm);
-        bm.pixels = out; bm.width = w; bm.height = h;
-        bm.gen = ++r->bitmap_gen;
-        bm.captured = true;
-        BitmapInfo info{w, h};
-        info.captured = true;
-        r->builder->add_bitmap(dst_id, info);
-        if (r->bitmap_table.size() <= dst_id) r->bitmap_table.resize(dst_id + 1, DevBitmap{nullptr, 0, 0});
-        r->bitmap_table[dst_id] = DevBitmap{bm.pixels, w, h};
-        r->bitmap_table_dirty = true;
+        bitmap_slot_has_new_texels(r, dst_id, out, w, h, false);     // (src_id's own slot and texels when the two are one)
         return int(SWFR_OK);
     });
 }
 
-int swfr_debug_time_shadow(swfr_renderer* r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float* alpha_ms, float* finish_ms, float* copy_ms) {
+// swfr_debug_time_shadow and swfr_debug_time_inner_shadow: the outer or the inner instances, the same buffers, the same order
+static int time_shadow(swfr_renderer* r, bool inner, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float* alpha_ms, float* finish_ms, float* copy_ms) {
     if (!r || !alpha_ms || !finish_ms || !copy_ms || reps == 0 || width == 0 || height == 0 || width > 32768 || height > 32768 || dx < -32768 ||
         dx > 32767 || dy < -32768 || dy > 32767)
         return fail(r, SWFR_ERR_INVALID, "bad argument");
@@ -2704,38 +2664,23 @@ int swfr_debug_time_shadow(swfr_renderer* r, uint32_t width, uint32_t height, in
     return guarded(r, [&]() {
         const size_t n = size_t(width) * height, bytes = n * 4;
         uint32_t *a = nullptr, *b = nullptr, *c = nullptr;
-        const uint32_t cp = 0x80402010u;
-        const auto alpha = [&]() { launch_shadow_alpha(r->stream, a, b, width, height, dx, dy, false); };
+        const uint32_t cp = 0x80402010u, flags = inner ? SWFR_SHADOW_INNER : 0u;
+        const auto alpha = [&]() { launch_shadow_alpha(r->stream, a, b, width, height, dx, dy, inner); };
         // (in place over the alpha words, as swfr_render runs it: a result's alpha byte is the next repetition's input, whatever it is)
-        const auto finish = [&]() { launch_shadow_finish(r->stream, b, c, true, b, n, cp, 1u, 0u); };
+        const auto finish = [&]() { launch_shadow_finish(r->stream, b, c, true, b, n, cp, 1u, flags); };
         const auto copy = [&]() { HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream)); };
         return time_phases(r, reps, {{&a, bytes, 0x5a}, {&b, bytes, -1}, {&c, bytes, 0x5a}}, [&]() {   // (warm-up of both kernels and the copy)
             alpha();
-            launch_shadow_finish(r->stream, b, a, true, b, n, cp, 1u, 0u);
+            launch_shadow_finish(r->stream, b, a, true, b, n, cp, 1u, flags);
             copy();
         }, {{alpha, alpha_ms}, {finish, finish_ms}, {copy, copy_ms}});
     });
 }
-
+int swfr_debug_time_shadow(swfr_renderer* r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float* alpha_ms, float* finish_ms, float* copy_ms) {
+    return time_shadow(r, false, width, height, dx, dy, reps, alpha_ms, finish_ms, copy_ms);
+}
 int swfr_debug_time_inner_shadow(swfr_renderer* r, uint32_t width, uint32_t height, int32_t dx, int32_t dy, uint32_t reps, float* alpha_ms, float* finish_ms, float* copy_ms) {
-    if (!r || !alpha_ms || !finish_ms || !copy_ms || reps == 0 || width == 0 || height == 0 || width > 32768 || height > 32768 || dx < -32768 ||
-        dx > 32767 || dy < -32768 || dy > 32767)
-        return fail(r, SWFR_ERR_INVALID, "bad argument");
-    if (!r->has_device) return fail(r, SWFR_ERR_NO_DEVICE, "host-only handle cannot rasterize");
-    return guarded(r, [&]() {
-        const size_t n = size_t(width) * height, bytes = n * 4;
-        uint32_t *a = nullptr, *b = nullptr, *c = nullptr;
-        const uint32_t cp = 0x80402010u;
-        // (swfr_debug_time_shadow with the inner instances: the same buffers, the same order)
-        const auto alpha = [&]() { launch_shadow_alpha(r->stream, a, b, width, height, dx, dy, true); };
-        const auto finish = [&]() { launch_shadow_finish(r->stream, b, c, true, b, n, cp, 1u, SWFR_SHADOW_INNER); };
-        const auto copy = [&]() { HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, r->stream)); };
-        return time_phases(r, reps, {{&a, bytes, 0x5a}, {&b, bytes, -1}, {&c, bytes, 0x5a}}, [&]() {
-            alpha();
-            launch_shadow_finish(r->stream, b, a, true, b, n, cp, 1u, SWFR_SHADOW_INNER);
-            copy();
-        }, {{alpha, alpha_ms}, {finish, finish_ms}, {copy, copy_ms}});
-    });
+    return time_shadow(r, true, width, height, dx, dy, reps, alpha_ms, finish_ms, copy_ms);
 }
 
 int swfr_debug_time_convolve(swfr_renderer* r, uint32_t width, uint32_t height, const swfr_kernel* kernel, uint32_t reps, float* fb_ms, float* tex_ms, float* capture_ms) {

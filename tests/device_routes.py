@@ -1,5 +1,7 @@
-"""What the device tests of the compositing features share (tests/test_{blend,layer,mask,fade}_gpu.py, tests/test_composite_fuzz_gpu.py):
-handles, the routes a frame can take to the device, the comparisons, and every libcairo golden of a family through every route.
+"""What the device tests of the compositing and filter features share (tests/test_{blend,layer,mask,fade}_gpu.py,
+tests/test_composite_fuzz_gpu.py, tests/test_{blur,shadow,inner,filters,convolution}_gpu.py): handles, the routes a frame can take to
+the device, the comparisons, every libcairo golden of a compositing family through every route, and what the filter families' tests
+have in common ("the filter families", below).
 
 A family is one row of FAMILIES: its scenes module (files(), golden_path(), LINEAR_BOUND), the SWFR_TILES_SHADERS value of its
 k2_tiles instance, and what differs between the families' golden runs.  A new compositing feature adds a scenes module and a row.
@@ -21,11 +23,18 @@ import numpy as np
 import pytest
 
 import blend_scenes
+import blur_scenes
+import convolution_scenes
 import fade_scenes
+import filter_scenes
 import frame_model
 import helpers
+import inner_scenes
 import layer_scenes
 import mask_scenes
+import scenarios
+import shadow_model
+import shadow_scenes
 from helpers import diff_stats, oracle_render
 from host_frames import build_on_host
 
@@ -37,7 +46,12 @@ REFUSALS = ("pairtest_limit", "start_group_limit", "history_limit")
 # layouts: the band layouts of route 2 (contiguous_bands of swfr_create)
 Family = namedtuple("Family", "name scenes instance forced_render layouts")
 FAMILIES = {f.name: f for f in (Family("blend", blend_scenes, "3", False, (True,)), Family("layer", layer_scenes, "4", False, (True, False)),
-                                Family("mask", mask_scenes, "5", True, (True, False)), Family("fade", fade_scenes, "6", True, (True, False)))}
+                                Family("mask", mask_scenes, "5", True, (True, False)), Family("fade", fade_scenes, "6", True, (True, False)),
+                                # the filter families: the instance is the layers' (a filtered layer is composited as one bitmap path),
+                                # never forced; no band layouts (filtered layers are refused on band handles)
+                                Family("blur", blur_scenes, "4", False, ()), Family("shadow", shadow_scenes, "4", False, ()),
+                                Family("inner", inner_scenes, "4", False, ()), Family("filters", filter_scenes, "4", False, ()),
+                                Family("convolution", convolution_scenes, "4", False, ()))}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -420,6 +434,136 @@ def s1_4k_known_answer_through_instance(family, monkeypatch):
         assert hashlib.sha256(r.read_image(premultiplied=True).tobytes()).hexdigest() == synth.S1_SHA256_PREMUL
         r.render_resident(3)                                         # (overlapped frames: the tile pass in its paired launch shape)
         assert hashlib.sha256(r.read_image(premultiplied=True).tobytes()).hexdigest() == synth.S1_SHA256_PREMUL
+    finally:
+        r.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- the filter families
+# What tests/test_{blur,shadow,inner,filters,convolution}_gpu.py share: a filtered layer is rendered as a sub-frame and composited as
+# one bitmap path, so its goldens take render and the resident parent frame, and every other route refuses it by name.
+#
+# The image sizes at which the passes can go wrong.  blur.hip: the horizontal pass works on 1024 x 4 pixels a workgroup, the vertical
+# one on 256 x 64 -- 2100 x 150 spans three segments of both on both axes and is a multiple of none.  shadow.hip: a lane takes four
+# words -- 257 x 3 and 3 x 257 leave one and three words behind the groups of four and put a row's end inside a group; 2048 workgroups
+# of 256 lanes stride over the image, 2 097 152 words a stride -- 2051 x 1029 is 2 110 479 words: both kernels' loops over groups of
+# four run a second, partial time (3 331 groups), and three words are left for the word loop (which takes more than three only in a
+# buffer that is not 16-byte aligned: none of the handle's own is).  On the emulator 2051 x 1029 is a matter of minutes and left out
+SIZES = ((13, 11), (257, 3), (3, 257), (2100, 150))
+LOOPS_TWICE = (2051, 1029)
+SIZES_AND_LOOPS_TWICE = SIZES + (() if EMU else (LOOPS_TWICE,))
+
+
+def content(w, h):
+    """translucent and opaque shapes all over a w x h frame, some across its edges, clear pixels between them"""
+    rng = np.random.default_rng(w * 1000 + h)
+    kids = []
+    for i in range(16):
+        cx, cy = rng.uniform(-0.1, 1.1) * w, rng.uniform(-0.1, 1.1) * h
+        pts = [(cx + rng.uniform(-0.25, 0.25) * w, cy + rng.uniform(-0.5, 0.5) * h) for _ in range(3)]
+        a = 255 if i % 5 == 0 else int(rng.integers(30, 250))
+        kids.append(blur_scenes._shape(pts, (int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 256)), a)))
+    kids.append(blur_scenes._rect(0, 0, 1, h / 2, (255, 255, 255, 255)))       # opaque white against the left edge
+    return kids
+
+
+def whole_frame_bitmap(w, h, bitmap_id):
+    """the bitmap drawn 1:1 over a w x h frame with a nearest fill: the frame is the bitmap's texels"""
+    fill = {"type": "bitmap", "bitmap_id": bitmap_id, "repeating": False, "smoothed": False, "filter": "nearest",
+            "matrix": scenarios._m(20, 20, 0, 0)}
+    return {"type": "shape", "definition": scenarios._poly_shape([(0, 0), (w * 20, 0), (w * 20, h * 20), (0, h * 20)], fill)}
+
+
+def goldens_through_render_and_resident(family, fname):
+    """every scene of a libcairo + pixman golden file through render, zero differing bytes; the textures stay: the resident parent
+    frame renders again to the same pixels"""
+    items, aliased, gold = golden_scenes(family, fname, 4, thin=False)
+    for name, sc in items:
+        r = renderer_for(sc, aliased)
+        try:
+            r.render(sc["stage"])
+            not_refused(r, name)
+            zero(r.read_image(premultiplied=True), gold[name], (family.name, fname, name, "render"))
+            r.render_resident(1)
+            zero(r.read_image(premultiplied=True), gold[name], (family.name, fname, name, "resident"))
+        finally:
+            r.close()
+
+
+def alpha_and_erase(family, golden_file, clear_name, opaque_name):
+    """On a flagged handle the filtered surface is the source of DEST_OUT / DEST_IN (ERASE is the path's operator; ALPHA, a group's
+    operator only, puts the path in a group of its own): against the frame model of the composite -- the surface from the goldens'
+    normal scene over clear, where the frame IS that surface, applied to the ground of the scene over opaque"""
+    final = np.load(family.scenes.golden_path(golden_file))[clear_name].astype(np.int64)
+    sc = family.scenes.operator_scenes()[opaque_name]
+    ground = through_render(dict(sc, stage={"children": sc["stage"]["children"][:-1]})).astype(np.int64)
+    for mode, factor in (("erase", 255 - final[..., 3:]), ("alpha", final[..., 3:])):
+        want = shadow_model.mul_un8(ground, factor).astype(np.uint8)
+        assert (want != ground).any()
+        kids = sc["stage"]["children"][:-1] + [dict(sc["stage"]["children"][-1], layer=mode)]
+        zero(through_render(dict(sc, stage={"children": kids}), alpha_modes=True), want, (family.name, mode))
+
+
+def refused_routes(family, sc, plain, want, want_plain):
+    """the routes that do not draw filtered layers refuse `sc` by name, and the handle renders `plain` (sc without its filters)
+    correctly afterwards; want, want_plain: the two frames"""
+    from swf_renderer_amd import api
+    r = renderer_for(sc, False)
+    try:
+        def refused(call, code, name):
+            with pytest.raises(api.SwfrError) as e:
+                call()
+            assert e.value.code == code and name in str(e.value), (code, name, str(e.value))
+            r.render(plain["stage"])
+            zero(r.read_image(premultiplied=True), want_plain, (family.name, name, "the plain frame afterwards"))
+        refused(lambda: r.render_batch([plain["stage"], sc["stage"], plain["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
+        refused(lambda: r.render_sequence([plain["stage"], sc["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
+        refused(lambda: r.render_sequence_readback([sc["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
+        if not EMU:
+            import torch
+            dst = torch.zeros((3, sc["height"], sc["width"], 4), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            refused(lambda: r.render_batch([plain["stage"], sc["stage"], plain["stage"]], dst.data_ptr(), dst.stride(0)),
+                    api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
+        # the layer's texture named in a caller's scene: not found -- also right behind a render that made one
+        r.render(sc["stage"])
+        zero(r.read_image(premultiplied=True), want, (family.name, "render"))
+        edges, paths, styles = r.build_frame(sc["stage"])
+        assert any(s.kind == api.STYLE_BITMAP and s.bitmap == api.BLUR_BASE for s in styles)
+        refused(lambda: r.upload_edges(edges, paths, styles), api.ERR_NOT_FOUND, "BitmapNotFound")
+        r.render(sc["stage"])
+        zero(r.read_image(premultiplied=True), want, (family.name, "render again"))
+    finally:
+        r.close()
+    for contiguous in (False, True):
+        b = renderer_for(sc, False, band_index=0, band_count=2, contiguous_bands=contiguous)
+        try:
+            with pytest.raises(api.SwfrError) as e:
+                b.render(sc["stage"])
+            assert e.value.code == api.ERR_NOT_IMPLEMENTED and "NotImplementedBlurBands" in str(e.value)
+            b.render(plain["stage"])
+        finally:
+            b.close()
+
+
+def plain_frame_after(family, names, golden_file):
+    """a frame without filters behind a filtered one (the scenes `names` of the golden file) is the frame a fresh handle renders, also
+    as resident frames; and the other way round: the filtered frame behind the plain one, then resident, is its golden"""
+    scenes = family.scenes.files()[golden_file][0]()
+    plain_sc = layer_scenes.overlap_scenes()["multiply_translucent"]
+    assert (plain_sc["width"], plain_sc["height"]) == (family.scenes.W, family.scenes.H)
+    fresh = through_render(plain_sc)
+    gold = np.load(family.scenes.golden_path(golden_file))
+    r = renderer_for(plain_sc, False)
+    try:
+        for name in names:
+            r.render(scenes[name]["stage"])
+            r.render(plain_sc["stage"])
+            zero(r.read_image(premultiplied=True), fresh, (family.name, name))
+            r.render_resident(3)
+            zero(r.read_image(premultiplied=True), fresh, (family.name, name, "resident"))
+            r.render(scenes[name]["stage"])
+            r.render_resident(2)
+            zero(r.read_image(premultiplied=True), gold[name], (family.name, name, "behind the plain one"))
     finally:
         r.close()
 

@@ -15,16 +15,14 @@ import blur_model as bm
 import blur_scenes as bl
 import device_routes as dr
 import layer_scenes as ls
-import scenarios
 from device_routes import need_gpu  # noqa: F401 (the module's autouse fixture)
 from helpers import diff_stats
 from swf_renderer_amd import api
 
 pytestmark = pytest.mark.gpu
 
-# the last size spans three segments of both kernels on both axes (blur.hip: the horizontal pass works on 1024 x 4 pixels a workgroup,
-# the vertical one on 256 x 64) and is a multiple of none
-SIZES = ((13, 11), (257, 3), (3, 257), (2100, 150))
+FAMILY = dr.FAMILIES["blur"]
+SIZES = dr.SIZES
 # every width of 1, 2, 3, 4, 64, 255 on either axis
 BOX_PAIRS = ((1, 2), (2, 1), (3, 4), (4, 3), (64, 255), (255, 64))
 PASSES = (1, 3)
@@ -32,7 +30,8 @@ BITMAP = 7
 
 
 def _content(w, h):
-    """translucent and opaque shapes all over a w x h frame, some across its edges"""
+    """translucent and opaque shapes all over a w x h frame, some across its edges (more and larger ones than device_routes.content: the
+    blur's own recipe, which leaves few clear pixels)"""
     rng = np.random.default_rng(w * 1000 + h)
     kids = []
     for i in range(24):
@@ -44,10 +43,7 @@ def _content(w, h):
     return kids
 
 
-def _whole_frame_bitmap(w, h, bitmap_id):
-    fill = {"type": "bitmap", "bitmap_id": bitmap_id, "repeating": False, "smoothed": False, "filter": "nearest",
-            "matrix": scenarios._m(20, 20, 0, 0)}
-    return {"type": "shape", "definition": scenarios._poly_shape([(0, 0), (w * 20, 0), (w * 20, h * 20), (0, h * 20)], fill)}
+_whole_frame_bitmap = dr.whole_frame_bitmap
 
 
 # ---- 1. the kernels alone
@@ -145,80 +141,21 @@ def test_a_1x1_box_is_the_plain_layer_sources(mode):
 # ---- 3. the goldens of libcairo + pixman
 @pytest.mark.parametrize("fname", sorted(bl.files()))
 def test_goldens_through_render(fname):
-    make, aliased = bl.files()[fname]
-    gold = np.load(bl.golden_path(fname))
-    scenes = make()
-    assert sorted(scenes) == sorted(gold.files)
-    for name, sc in sorted(scenes.items()):
-        r = dr.renderer_for(sc, aliased)
-        try:
-            r.render(sc["stage"])
-            dr.not_refused(r, name)
-            got = r.read_image(premultiplied=True)
-            n, mx = diff_stats(got, gold[name])
-            print(fname, name, "differing pixels", n, "max", mx)
-            assert (n, mx) == (0, 0), (fname, name)
-            # the textures stay: the resident parent frame renders again to the same pixels
-            r.render_resident(1)
-            assert diff_stats(r.read_image(premultiplied=True), gold[name]) == (0, 0), (fname, name, "resident")
-        finally:
-            r.close()
+    dr.goldens_through_render_and_resident(FAMILY, fname)
 
 
 def test_alpha_and_erase_blurred_layers():
-    """ERASE is the path's operator; ALPHA, a group's operator only, puts the path in a group of its own: both against the frame model
-    of the composite -- the blurred group from the goldens' normal scene over clear, DEST_OUT / DEST_IN on the ground"""
-    gold = np.load(bl.golden_path("cairo_blur_operators"))
-    group = gold["normal_clear"].astype(np.int64)                     # over a clear ground the frame IS the blurred group
-    sc = bl.operator_scenes()["normal_opaque"]
-    ground = dr.through_render(dict(sc, stage={"children": sc["stage"]["children"][:-1]})).astype(np.int64)
-    for mode, factor in (("erase", 255 - group[..., 3:]), ("alpha", group[..., 3:])):
-        t = ground * factor + 0x80
-        want = ((t + (t >> 8)) >> 8).astype(np.uint8)                 # pixman's mul_un8
-        kids = sc["stage"]["children"][:-1] + [dict(sc["stage"]["children"][-1], layer=mode)]
-        got = dr.through_render(dict(sc, stage={"children": kids}), alpha_modes=True)
-        assert diff_stats(got, want) == (0, 0), mode
+    dr.alpha_and_erase(FAMILY, "cairo_blur_operators", "normal_clear", "normal_opaque")
 
 
 # ---- 4. the routes not taken refuse by name
 def test_refused_routes_and_the_handle_afterwards():
     sc = bl.operator_scenes()["multiply_opaque"]
     plain = dict(sc, stage={"children": bl.without_blur(sc["stage"]["children"])})
-    want_plain = dr.through_render(plain)
-    want_blur = np.load(bl.golden_path("cairo_blur_operators"))["multiply_opaque"]
-    r = dr.renderer_for(sc, False)
-    try:
-        def refused(call, code, name):
-            with pytest.raises(api.SwfrError) as e:
-                call()
-            assert e.value.code == code and name in str(e.value), (code, name, str(e.value))
-            r.render(plain["stage"])                                  # the handle renders an unblurred frame correctly afterwards
-            assert diff_stats(r.read_image(premultiplied=True), want_plain) == (0, 0), name
-        refused(lambda: r.render_batch([plain["stage"], sc["stage"], plain["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        refused(lambda: r.render_sequence([plain["stage"], sc["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        refused(lambda: r.render_sequence_readback([sc["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        if not dr.EMU:
-            import torch
-            dst = torch.zeros((3, sc["height"], sc["width"], 4), dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            refused(lambda: r.render_batch([plain["stage"], sc["stage"], plain["stage"]], dst.data_ptr(), dst.stride(0)),
-                    api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        # a blur texture named in a caller's scene: not found -- also right behind a render that made one
-        r.render(sc["stage"])
-        assert diff_stats(r.read_image(premultiplied=True), want_blur) == (0, 0)
-        edges, paths, styles = r.build_frame(sc["stage"])
-        assert any(s.kind == api.STYLE_BITMAP and s.bitmap == api.BLUR_BASE for s in styles)
-        refused(lambda: r.upload_edges(edges, paths, styles), api.ERR_NOT_FOUND, "BitmapNotFound")
-        r.render(sc["stage"])
-        assert diff_stats(r.read_image(premultiplied=True), want_blur) == (0, 0)
-    finally:
-        r.close()
-    for contiguous in (False, True):
+    dr.refused_routes(FAMILY, sc, plain, np.load(bl.golden_path("cairo_blur_operators"))["multiply_opaque"], dr.through_render(plain))
+    for contiguous in (False, True):                                  # a band handle captures no bitmap either
         b = dr.renderer_for(sc, False, band_index=0, band_count=2, contiguous_bands=contiguous)
         try:
-            with pytest.raises(api.SwfrError) as e:
-                b.render(sc["stage"])
-            assert e.value.code == api.ERR_NOT_IMPLEMENTED and "NotImplementedBlurBands" in str(e.value)
             b.render(plain["stage"])
             with pytest.raises(api.SwfrError) as e:
                 b.capture_bitmap(BITMAP)
@@ -229,20 +166,7 @@ def test_refused_routes_and_the_handle_afterwards():
 
 # ---- 5. nothing of a blurred frame stays behind
 def test_a_plain_frame_after_a_blurred_one_is_a_fresh_handles_frame():
-    scenes = bl.box_scenes()
-    plain_sc = ls.overlap_scenes()["multiply_translucent"]
-    assert (plain_sc["width"], plain_sc["height"]) == (bl.W, bl.H)
-    fresh = dr.through_render(plain_sc)
-    r = dr.renderer_for(plain_sc, False)
-    try:
-        for name in ("two_layers", "box_wider_than_frame", "blur_mask_opacity"):
-            r.render(scenes[name]["stage"])
-            r.render(plain_sc["stage"])
-            assert diff_stats(r.read_image(premultiplied=True), fresh) == (0, 0), name
-            r.render_resident(3)
-            assert diff_stats(r.read_image(premultiplied=True), fresh) == (0, 0), name
-    finally:
-        r.close()
+    dr.plain_frame_after(FAMILY, ("two_layers", "box_wider_than_frame", "blur_mask_opacity"), "cairo_blur_boxes")
 
 
 def _many(n=300):

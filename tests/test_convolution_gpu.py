@@ -16,13 +16,11 @@ import itertools
 import numpy as np
 import pytest
 
-import blur_scenes as bl
 import convolution_model as cm
 import convolution_scenes as csc
 import device_routes as dr
 import filter_model as fm
 import filter_scenes as fsc
-import scenarios
 from device_routes import GuardedFrames, need_gpu  # noqa: F401 (need_gpu: the module's autouse fixture)
 from helpers import diff_stats
 from shadow_scenes import DROP, GLOW
@@ -35,26 +33,11 @@ ALL_SIZES_AT = (13, 11)
 IMAGE_SIZES = ((1, 1), (3, 2), ALL_SIZES_AT, (T_W - 1, T_H + 1), (2 * T_W + 1, T_H - 1), (257, 3), (3, 257))
 CHAIN_SIZES = ((13, 11), (257, 3), (2 * T_W + 1, T_H + 1))
 BITMAP = 7
+FAMILY = dr.FAMILIES["convolution"]
 Cv = cm.convolution
 
 
-def _content(w, h):
-    """translucent and opaque shapes all over a w x h frame, some across its edges, clear pixels between them (tests/test_filters_gpu.py's
-    recipe)"""
-    rng = np.random.default_rng(w * 1000 + h)
-    kids = []
-    for i in range(16):
-        cx, cy = rng.uniform(-0.1, 1.1) * w, rng.uniform(-0.1, 1.1) * h
-        pts = [(cx + rng.uniform(-0.25, 0.25) * w, cy + rng.uniform(-0.5, 0.5) * h) for _ in range(3)]
-        a = 255 if i % 5 == 0 else int(rng.integers(30, 250))
-        kids.append(bl._shape(pts, (int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 256)), a)))
-    kids.append(bl._rect(0, 0, 1, h / 2, (255, 255, 255, 255)))                  # opaque white against the left edge
-    return kids
-
-
-def _whole_frame_bitmap(w, h, bitmap_id):
-    fill = {"type": "bitmap", "bitmap_id": bitmap_id, "repeating": False, "smoothed": False, "filter": "nearest", "matrix": scenarios._m(20, 20, 0, 0)}
-    return {"type": "shape", "definition": scenarios._poly_shape([(0, 0), (w * 20, 0), (w * 20, h * 20), (0, h * 20)], fill)}
+_content, _whole_frame_bitmap = dr.content, dr.whole_frame_bitmap
 
 
 def _six_kernels(w, h):
@@ -188,24 +171,8 @@ def test_the_chain_inside_render_against_the_model(size):
 # ---- 3. the goldens of libcairo + pixman
 @pytest.mark.parametrize("fname", sorted(csc.files()))
 def test_goldens_through_render(fname):
-    make, aliased = csc.files()[fname]
-    gold = np.load(csc.golden_path(fname))
-    scenes = make()
-    assert sorted(scenes) == sorted(gold.files)
-    for name, sc in sorted(scenes.items()):
-        assert sc["width"] <= 96 and sc["height"] <= 64
-        r = dr.renderer_for(sc, aliased)
-        try:
-            r.render(sc["stage"])
-            dr.not_refused(r, name)
-            n, mx = diff_stats(r.read_image(premultiplied=True), gold[name])
-            print(fname, name, "differing pixels", n, "max", mx)
-            assert (n, mx) == (0, 0), (fname, name)
-            # the textures stay: the resident parent frame renders again to the same pixels
-            r.render_resident(1)
-            assert diff_stats(r.read_image(premultiplied=True), gold[name]) == (0, 0), (fname, name, "resident")
-        finally:
-            r.close()
+    assert all(sc["width"] <= 96 and sc["height"] <= 64 for sc in csc.files()[fname][0]().values())
+    dr.goldens_through_render_and_resident(FAMILY, fname)
 
 
 # ---- 4. a caller-owned target that is word aligned only
@@ -242,32 +209,7 @@ def test_first_entry_on_a_handle_with_an_unaligned_target(offset):
 def test_refused_routes_and_the_handle_afterwards():
     sc = csc.structure_scenes()["multiply_opaque_ground"]
     plain = dict(sc, stage={"children": csc.without_filters(sc["stage"]["children"])})
-    want_plain = dr.through_render(plain)
-    want = np.load(csc.golden_path("cairo_convolution_structure"))["multiply_opaque_ground"]
-    r = dr.renderer_for(sc, False)
-    try:
-        def refused(call, code, name):
-            with pytest.raises(api.SwfrError) as e:
-                call()
-            assert e.value.code == code and name in str(e.value), (code, name, str(e.value))
-            r.render(plain["stage"])                                  # the handle renders a frame without filters correctly afterwards
-            assert diff_stats(r.read_image(premultiplied=True), want_plain) == (0, 0), name
-        refused(lambda: r.render_batch([plain["stage"], sc["stage"], plain["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        refused(lambda: r.render_sequence([plain["stage"], sc["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        refused(lambda: r.render_sequence_readback([sc["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        r.render(sc["stage"])
-        assert diff_stats(r.read_image(premultiplied=True), want) == (0, 0)
-    finally:
-        r.close()
-    for contiguous in (False, True):
-        b = dr.renderer_for(sc, False, band_index=0, band_count=2, contiguous_bands=contiguous)
-        try:
-            with pytest.raises(api.SwfrError) as e:
-                b.render(sc["stage"])
-            assert e.value.code == api.ERR_NOT_IMPLEMENTED and "NotImplementedBlurBands" in str(e.value)
-            b.render(plain["stage"])
-        finally:
-            b.close()
+    dr.refused_routes(FAMILY, sc, plain, np.load(csc.golden_path("cairo_convolution_structure"))["multiply_opaque_ground"], dr.through_render(plain))
 
 
 # ---- 6. the slot is read at the walk

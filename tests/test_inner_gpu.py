@@ -21,47 +21,17 @@ import device_routes as dr
 import filter_model as fm
 import inner_model as im
 import inner_scenes as isc
-import layer_scenes as ls
-import scenarios
-import shadow_model as sm
 from device_routes import need_gpu  # noqa: F401 (the module's autouse fixture)
 from helpers import diff_stats
 from shadow_model import COLORS, STRENGTHS, offsets
 
 pytestmark = pytest.mark.gpu
 
-# this file's row of tests/device_routes.py's table: the scenes module; the instance is the layers' (a filtered layer is composited as one
-# bitmap path), never forced here; no band layouts (filtered layers are refused on band handles)
-FAMILY = dr.Family("inner", isc, "4", False, ())
-
-# shadow.hip: a lane takes four words, 2048 workgroups of 256 lanes stride over the image -- 2 097 152 words a stride.  2051 x 1029 is
-# 2 110 479 words: both kernels' loops over groups of four words run a second, partial time (3 331 groups), and three words are left for
-# the word loop.  257 x 3 and 3 x 257 leave one and three words behind the groups of four and put a row's end inside a group; 2100 x 150
-# takes more than one workgroup and spans three segments of the box passes between the two kernels.  On the emulator 2051 x 1029 is a
-# matter of minutes and left out
-LOOPS_TWICE = (2051, 1029)
-SIZES = ((13, 11), (257, 3), (3, 257), (2100, 150)) + (() if dr.EMU else (LOOPS_TWICE,))
+FAMILY = dr.FAMILIES["inner"]
+SIZES = dr.SIZES_AND_LOOPS_TWICE
 FLAGS = {"atop": {"inner": True}, "knockout": {"inner": True, "knockout": True}}
 SRC, DST = 7, 9
-
-
-def _content(w, h):
-    """translucent and opaque shapes all over a w x h frame, some across its edges, clear pixels between them (as tests/test_shadow_gpu.py)"""
-    rng = np.random.default_rng(w * 1000 + h)
-    kids = []
-    for i in range(16):
-        cx, cy = rng.uniform(-0.1, 1.1) * w, rng.uniform(-0.1, 1.1) * h
-        pts = [(cx + rng.uniform(-0.25, 0.25) * w, cy + rng.uniform(-0.5, 0.5) * h) for _ in range(3)]
-        a = 255 if i % 5 == 0 else int(rng.integers(30, 250))
-        kids.append(bl._shape(pts, (int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 256)), a)))
-    kids.append(bl._rect(0, 0, 1, h / 2, (255, 255, 255, 255)))                  # opaque white against the left edge
-    return kids
-
-
-def _whole_frame_bitmap(w, h, bitmap_id):
-    fill = {"type": "bitmap", "bitmap_id": bitmap_id, "repeating": False, "smoothed": False, "filter": "nearest",
-            "matrix": scenarios._m(20, 20, 0, 0)}
-    return {"type": "shape", "definition": scenarios._poly_shape([(0, 0), (w * 20, 0), (w * 20, h * 20), (0, h * 20)], fill)}
+_content, _whole_frame_bitmap = dr.content, dr.whole_frame_bitmap
 
 
 def _cases(w, h):
@@ -157,35 +127,12 @@ def test_the_chain_inside_render_against_the_model(size):
 # ---- 3. the goldens of libcairo + pixman
 @pytest.mark.parametrize("fname", sorted(isc.files()))
 def test_goldens_through_render_and_render_resident(fname):
-    items, aliased, gold = dr.golden_scenes(FAMILY, fname, 4, thin=False)
-    assert [n for n, _ in items] == sorted(gold.files)
-    for name, sc in items:
-        r = dr.renderer_for(sc, aliased)
-        try:
-            r.render(sc["stage"])
-            dr.not_refused(r, name)
-            dr.check(FAMILY, r.read_image(premultiplied=True), gold[name], sc, (fname, name, "render"))
-            # the textures stay: the resident parent frame renders again to the same pixels
-            r.render_resident(1)
-            dr.check(FAMILY, r.read_image(premultiplied=True), gold[name], sc, (fname, name, "resident"))
-        finally:
-            r.close()
+    dr.goldens_through_render_and_resident(FAMILY, fname)
 
 
 # ---- 4. ALPHA and ERASE
 def test_alpha_and_erase_inner_shadowed_layers():
-    """on a flagged handle the final surface is the source of DEST_OUT / DEST_IN: against the frame model of the composite -- the final
-    surface from the goldens' normal scene over clear, where the frame IS that surface"""
-    gold = np.load(isc.golden_path("cairo_inner_operators"))
-    final = gold["shadow_normal_clear"].astype(np.int64)
-    sc = isc.operator_scenes()["shadow_normal_opaque"]
-    ground = dr.through_render(dict(sc, stage={"children": sc["stage"]["children"][:-1]})).astype(np.int64)
-    for mode, factor in (("erase", 255 - final[..., 3:]), ("alpha", final[..., 3:])):
-        want = sm.mul_un8(ground, factor).astype(np.uint8)
-        assert (want != ground).any()
-        kids = sc["stage"]["children"][:-1] + [dict(sc["stage"]["children"][-1], layer=mode)]
-        got = dr.through_render(dict(sc, stage={"children": kids}), alpha_modes=True)
-        dr.zero(got, want, mode)
+    dr.alpha_and_erase(FAMILY, "cairo_inner_operators", "shadow_normal_clear", "shadow_normal_opaque")
 
 
 # ---- 5. an empty group
@@ -205,22 +152,4 @@ def test_an_empty_group_with_an_inner_shadow_is_the_frame_without_it():
 
 # ---- 6. nothing of an inner-shadowed frame stays behind
 def test_a_plain_frame_after_an_inner_shadowed_one_is_a_fresh_handles_frame():
-    scenes = isc.structure_scenes()
-    plain_sc = ls.overlap_scenes()["multiply_translucent"]
-    assert (plain_sc["width"], plain_sc["height"]) == (isc.W, isc.H)
-    fresh = dr.through_render(plain_sc)
-    gold = np.load(isc.golden_path("cairo_inner_structure"))
-    r = dr.renderer_for(plain_sc, False)
-    try:
-        for name in ("two_inner_and_an_outer", "list_chain_of_four", "list_and_mask_opacity"):
-            r.render(scenes[name]["stage"])
-            r.render(plain_sc["stage"])
-            dr.zero(r.read_image(premultiplied=True), fresh, name)
-            r.render_resident(3)
-            dr.zero(r.read_image(premultiplied=True), fresh, (name, "resident"))
-            # and the other way round: the inner-shadowed frame behind the plain one, then resident
-            r.render(scenes[name]["stage"])
-            r.render_resident(2)
-            dr.zero(r.read_image(premultiplied=True), gold[name], (name, "behind the plain one"))
-    finally:
-        r.close()
+    dr.plain_frame_after(FAMILY, ("two_inner_and_an_outer", "list_chain_of_four", "list_and_mask_opacity"), "cairo_inner_structure")

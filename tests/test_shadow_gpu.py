@@ -15,10 +15,8 @@ import itertools
 import numpy as np
 import pytest
 
-import blur_scenes as bl
 import device_routes as dr
 import layer_scenes as ls
-import scenarios
 import shadow_model as sm
 import shadow_scenes as ss
 from device_routes import need_gpu  # noqa: F401 (the module's autouse fixture)
@@ -28,33 +26,10 @@ from shadow_model import COLORS, FLAGS, STRENGTHS, offsets
 
 pytestmark = pytest.mark.gpu
 
-# shadow.hip: a lane takes four words, 2048 workgroups of 256 lanes stride over the image -- 2 097 152 words a stride.  2051 x 1029 is
-# 2 110 479 words: both kernels' loops over groups of four words run a second, partial time (3 331 groups), and three words are left for
-# the word loop (which takes more than three only in a buffer that is not 16-byte aligned: none of the handle's own is).  The blur passes
-# between them have their own sizes (tests/test_blur_gpu.py): 2100 x 150 spans three segments of both.  On the emulator 2051 x 1029 is a
-# matter of minutes and left out
-LOOPS_TWICE = (2051, 1029)
-SIZES = ((13, 11), (257, 3), (3, 257), (2100, 150)) + (() if dr.EMU else (LOOPS_TWICE,))
+FAMILY = dr.FAMILIES["shadow"]
+SIZES = dr.SIZES_AND_LOOPS_TWICE                  # (the blur passes between shadow.hip's two kernels have their own sizes: tests/test_blur_gpu.py)
 SRC, DST = 7, 9
-
-
-def _content(w, h):
-    """translucent and opaque shapes all over a w x h frame, some across its edges, clear pixels between them"""
-    rng = np.random.default_rng(w * 1000 + h)
-    kids = []
-    for i in range(16):
-        cx, cy = rng.uniform(-0.1, 1.1) * w, rng.uniform(-0.1, 1.1) * h
-        pts = [(cx + rng.uniform(-0.25, 0.25) * w, cy + rng.uniform(-0.5, 0.5) * h) for _ in range(3)]
-        a = 255 if i % 5 == 0 else int(rng.integers(30, 250))
-        kids.append(bl._shape(pts, (int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 256)), a)))
-    kids.append(bl._rect(0, 0, 1, h / 2, (255, 255, 255, 255)))                  # opaque white against the left edge
-    return kids
-
-
-def _whole_frame_bitmap(w, h, bitmap_id):
-    fill = {"type": "bitmap", "bitmap_id": bitmap_id, "repeating": False, "smoothed": False, "filter": "nearest",
-            "matrix": scenarios._m(20, 20, 0, 0)}
-    return {"type": "shape", "definition": scenarios._poly_shape([(0, 0), (w * 20, 0), (w * 20, h * 20), (0, h * 20)], fill)}
+_content, _whole_frame_bitmap = dr.content, dr.whole_frame_bitmap
 
 
 def _cases(w, h):
@@ -176,105 +151,23 @@ def test_a_shadow_that_adds_nothing_is_the_plain_layer_sources(mode):
 # ---- 3. the goldens of libcairo + pixman
 @pytest.mark.parametrize("fname", sorted(ss.files()))
 def test_goldens_through_render(fname):
-    make, aliased = ss.files()[fname]
-    gold = np.load(ss.golden_path(fname))
-    scenes = make()
-    assert sorted(scenes) == sorted(gold.files)
-    for name, sc in sorted(scenes.items()):
-        r = dr.renderer_for(sc, aliased)
-        try:
-            r.render(sc["stage"])
-            dr.not_refused(r, name)
-            got = r.read_image(premultiplied=True)
-            n, mx = diff_stats(got, gold[name])
-            print(fname, name, "differing pixels", n, "max", mx)
-            assert (n, mx) == (0, 0), (fname, name)
-            # the textures stay: the resident parent frame renders again to the same pixels
-            r.render_resident(1)
-            assert diff_stats(r.read_image(premultiplied=True), gold[name]) == (0, 0), (fname, name, "resident")
-        finally:
-            r.close()
+    dr.goldens_through_render_and_resident(FAMILY, fname)
 
 
 def test_alpha_and_erase_shadowed_layers():
-    """on a flagged handle the final surface is the source of DEST_OUT / DEST_IN: against the frame model of the composite -- the final
-    surface from the goldens' normal scene over clear, where the frame IS that surface"""
-    gold = np.load(ss.golden_path("cairo_shadow_operators"))
-    final = gold["drop_normal_clear"].astype(np.int64)
-    sc = ss.operator_scenes()["drop_normal_opaque"]
-    ground = dr.through_render(dict(sc, stage={"children": sc["stage"]["children"][:-1]})).astype(np.int64)
-    for mode, factor in (("erase", 255 - final[..., 3:]), ("alpha", final[..., 3:])):
-        want = sm.mul_un8(ground, factor).astype(np.uint8)
-        kids = sc["stage"]["children"][:-1] + [dict(sc["stage"]["children"][-1], layer=mode)]
-        got = dr.through_render(dict(sc, stage={"children": kids}), alpha_modes=True)
-        assert diff_stats(got, want) == (0, 0), mode
+    dr.alpha_and_erase(FAMILY, "cairo_shadow_operators", "drop_normal_clear", "drop_normal_opaque")
 
 
 # ---- 4. the routes not taken refuse by name
 def test_refused_routes_and_the_handle_afterwards():
     sc = ss.operator_scenes()["glow_multiply_opaque"]
     plain = dict(sc, stage={"children": ss.without_shadow(sc["stage"]["children"])})
-    want_plain = dr.through_render(plain)
-    want_shadow = np.load(ss.golden_path("cairo_shadow_operators"))["glow_multiply_opaque"]
-    r = dr.renderer_for(sc, False)
-    try:
-        def refused(call, code, name):
-            with pytest.raises(api.SwfrError) as e:
-                call()
-            assert e.value.code == code and name in str(e.value), (code, name, str(e.value))
-            r.render(plain["stage"])                                  # the handle renders a frame without shadows correctly afterwards
-            assert diff_stats(r.read_image(premultiplied=True), want_plain) == (0, 0), name
-        refused(lambda: r.render_batch([plain["stage"], sc["stage"], plain["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        refused(lambda: r.render_sequence([plain["stage"], sc["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        refused(lambda: r.render_sequence_readback([sc["stage"]]), api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        if not dr.EMU:
-            import torch
-            dst = torch.zeros((3, sc["height"], sc["width"], 4), dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            refused(lambda: r.render_batch([plain["stage"], sc["stage"], plain["stage"]], dst.data_ptr(), dst.stride(0)),
-                    api.ERR_NOT_IMPLEMENTED, "NotImplementedBlurRoute")
-        # the shadow's texture named in a caller's scene: not found -- also right behind a render that made one
-        r.render(sc["stage"])
-        assert diff_stats(r.read_image(premultiplied=True), want_shadow) == (0, 0)
-        edges, paths, styles = r.build_frame(sc["stage"])
-        assert any(s.kind == api.STYLE_BITMAP and s.bitmap == api.BLUR_BASE for s in styles)
-        refused(lambda: r.upload_edges(edges, paths, styles), api.ERR_NOT_FOUND, "BitmapNotFound")
-        r.render(sc["stage"])
-        assert diff_stats(r.read_image(premultiplied=True), want_shadow) == (0, 0)
-    finally:
-        r.close()
-    for contiguous in (False, True):
-        b = dr.renderer_for(sc, False, band_index=0, band_count=2, contiguous_bands=contiguous)
-        try:
-            with pytest.raises(api.SwfrError) as e:
-                b.render(sc["stage"])
-            assert e.value.code == api.ERR_NOT_IMPLEMENTED and "NotImplementedBlurBands" in str(e.value)
-            b.render(plain["stage"])
-        finally:
-            b.close()
+    dr.refused_routes(FAMILY, sc, plain, np.load(ss.golden_path("cairo_shadow_operators"))["glow_multiply_opaque"], dr.through_render(plain))
 
 
 # ---- 5. nothing of a shadowed frame stays behind
 def test_a_plain_frame_after_a_shadowed_one_is_a_fresh_handles_frame():
-    scenes = ss.structure_scenes()
-    plain_sc = ls.overlap_scenes()["multiply_translucent"]
-    assert (plain_sc["width"], plain_sc["height"]) == (ss.W, ss.H)
-    fresh = dr.through_render(plain_sc)
-    gold = np.load(ss.golden_path("cairo_shadow_structure"))
-    r = dr.renderer_for(plain_sc, False)
-    try:
-        for name in ("two_shadows_and_a_blur", "shadow_wider_than_frame", "shadow_mask_opacity"):
-            r.render(scenes[name]["stage"])
-            r.render(plain_sc["stage"])
-            assert diff_stats(r.read_image(premultiplied=True), fresh) == (0, 0), name
-            r.render_resident(3)
-            assert diff_stats(r.read_image(premultiplied=True), fresh) == (0, 0), name
-            # and the other way round: the shadowed frame behind the plain one, then resident
-            r.render(scenes[name]["stage"])
-            r.render_resident(2)
-            assert diff_stats(r.read_image(premultiplied=True), gold[name]) == (0, 0), name
-    finally:
-        r.close()
+    dr.plain_frame_after(FAMILY, ("two_shadows_and_a_blur", "shadow_wider_than_frame", "shadow_mask_opacity"), "cairo_shadow_structure")
 
 
 def test_the_slots_value_at_the_walk_is_the_shadow():
